@@ -1,8 +1,17 @@
 #!/usr/bin/env python3
 """bench.py -- pivots/s of the HIP PIP engine on BASELINE.json's workloads.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does only what the headline figure needs: it sets the lanes up (the pre-pass below), warms up, times ONE
+region of --steps steps, writes the outputs of the last timed step if --dump-outputs is given, and prints the line.
+`--full` adds everything else, as described below: three timed regions (the median is the line's value), the 96-step
+steady state, the per-launch roofline, the row-skipping-off leg, `pipeline1_value`, `other_configs`, the parametric leg,
+the CPU baseline, the other scaling mode (--gpus N > 1) and the engine's own screening of every batch against the
+oracle's list (`--no-dense`, `--no-others`, `--no-cpu` leave legs of it out).
+`--dump-outputs DIR`: what pipamd_batch_results gave the caller for the last timed step (rank 0's lane that ran it:
+status, pivot and cut counts, solution numerators and denominators) as DIR/<name>.npy in float64 (dump_outputs).
 
 Headline workload (BASELINE.json configs[2], the one the metric is quoted on): per GPU a batch of
 10,000 synthetic 64x128 int64 tableaux (nvar = 127 unknowns, 64 inequality rows, constant
@@ -13,7 +22,7 @@ pivot and cut counts and the solutions into the caller's arrays); inputs are res
 Steps are pipelined: up to --pipeline (default 14) batches are in flight on separate HIP streams,
 each lane with its own engine and workspace (each step is a complete load + solve + results of its
 batch), all driven by ONE host thread through the asynchronous C ABI (pipamd_batch_solve_async /
-pipamd_batch_poll; `--threads` = round 2's one-host-thread-per-lane driver).  The timed region is run three times; ms_per_step is
+pipamd_batch_poll; `--threads` = round 2's one-host-thread-per-lane driver).  With --full the timed region is run three times; ms_per_step is
 the median region / steps and all three are printed (`regions_ms`).  `pipeline1_value` is the same
 workload with one batch at a time.  `other_configs` carries BASELINE configs[1] and configs[4]
 measured the same way (shorter runs).
@@ -28,7 +37,8 @@ weak-scaling figure (10k tableaux per GPU and batch) is measured as well and rep
 What is timed is checked: which tableaux are left out of a batch (slow-converging cuts) comes from a committed list
 made by the CPU oracle (tests/golden/bench_screen.json), the engine must agree with it, the pivots of the pre-pass
 must be the oracle's, and after every timed region the status / pivot arrays the lanes fetched are reduced on the
-device and compared with the pre-pass (`regions_checked`).  A mismatch voids the line (exit code 3).
+device and compared with the pre-pass (`regions_checked`).  A mismatch voids the line (exit code 3).  (A plain run
+takes the oracle's list of slow tableaux as it stands; --full also has the engine find them and compares.)
 
 Prints ONE JSON line (rank 0).
 """
@@ -249,6 +259,7 @@ class Lanes:
         self.want = []          # per lane batch: what the oracle says about it (None: no record)
         self.next_step = 0  # steps handed out so far (the batches take turns across timed regions)
         self.last_of_lane = {}  # lane -> the batch its arrays hold (set by the runners)
+        self.last_lane = None   # the lane that ran the last step handed out (its arrays hold that step's results)
         self.checked_passes = 0
         # Few launch sequences in flight, or a run so short that every sequence has a lane to itself: nothing runs beside a
         # sequence's middle launch for long, so the engines run in their lone-batches mode (pipamd_engine_set_lone_batches).
@@ -259,7 +270,9 @@ class Lanes:
         # launch read them where they are instead of a copy pass (--copy-rows switches that off)
         stay = 0 if getattr(args, "copy_rows", False) else eng.T_ROWS_STAY
         tf = (eng.T_INT if cfg["integer"] else 0) | stay
-        screen_engine = eng.Engine(local)
+        # the engine's own screening is a check of the oracle's list (bench.py --full); without a list it is the screening
+        check_screen = getattr(args, "full", True)
+        screen_engine = []
         records = screen_records(cfg["screen"]) if cfg.get("screen") else {}
         full_batch = cfg["batch"]
         lo, hi = shard if shard else (0, full_batch)
@@ -279,14 +292,18 @@ class Lanes:
             rec = records.get(str(g)) if rows.shape[0] == full_batch else None
             want = None
             if cfg["integer"] and rows.shape[0] > 1:
-                mine = torch.as_tensor(rows[lo:hi], dtype=torch.int64).to(dev).contiguous()
                 ncuts = cfg.get("screen_cuts", SCREEN_CUTS)
-                bad = [b_ + lo for b_ in eng.slow_converging(screen_engine, mine, cfg["nvar"], cut_rows=ncuts,
-                                                            entier_bits=cfg["ebits"])]
-                del mine
+                bad = None
+                if rec is None or check_screen:
+                    if not screen_engine:
+                        screen_engine.append(eng.Engine(local))
+                    mine = torch.as_tensor(rows[lo:hi], dtype=torch.int64).to(dev).contiguous()
+                    bad = [b_ + lo for b_ in eng.slow_converging(screen_engine[0], mine, cfg["nvar"], cut_rows=ncuts,
+                                                                entier_bits=cfg["ebits"])]
+                    del mine
                 if rec is not None:
                     slow = sorted(rec["slow"])
-                    if bad != [b_ for b_ in slow if lo <= b_ < hi]:
+                    if bad is not None and bad != [b_ for b_ in slow if lo <= b_ < hi]:
                         raise VoidLine(f"{cfg['key']} batch {g}: the engine leaves tableaux {bad} at PIPAMD_ST_CAPACITY under a budget "
                                        f"of {ncuts} cuts, the oracle's list (tests/golden/bench_screen.json) says {slow}")
                     src = "tests/golden/bench_screen.json (CPU oracle)"
@@ -423,6 +440,7 @@ class Lanes:
             if k is None:
                 return
             _, bi, st = self.lanes[i]
+            self.last_lane = i
             bi.load_parts(self.batches[k], st.cuda_stream)
             bi.solve_async(st.cuda_stream)
             active[i] = k
@@ -451,6 +469,8 @@ class Lanes:
                     while True:
                         with lock:
                             k = next(it, None)
+                            if k is not None:
+                                self.last_lane = i
                         if k is None:
                             break
                         bi.load_parts(self.batches[k], st.cuda_stream)
@@ -662,6 +682,26 @@ def kernel_ms_of(b, parts=None, reps=2):
     return sum(ms) / len(ms)
 
 
+DUMP_BYTES = 64 << 20
+DUMP_ARRAYS = ("status", "pivots", "cuts", "sol_num", "sol_den")
+
+
+def dump_outputs(arrays, outdir):
+    """--dump-outputs: `arrays` (name -> host array, one row per tableau: what pipamd_batch_results gave a caller of the
+    timed path) as outdir/<name>.npy, float64.  When they would exceed DUMP_BYTES a fixed, seeded sample of the
+    tableaux is written instead, and the indices chosen as tableau_index.npy."""
+    import numpy as np
+    n = arrays["status"].shape[0]
+    per = 8 * sum(a[0].size for a in arrays.values())  # float64 bytes of one tableau's results
+    if n * per > DUMP_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(n, DUMP_BYTES // (per + 8), replace=False))
+        arrays = {k: a[keep] for k, a in arrays.items()}
+        arrays["tableau_index"] = keep
+    os.makedirs(outdir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(outdir, k + ".npy"), a.astype(np.float64))
+
+
 def free_port():
     import socket
     with socket.socket() as sk:
@@ -723,6 +763,12 @@ def main():
     ap.add_argument("--no-dense", action="store_true", help="skip the row-skipping-off measurement")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--no-others", action="store_true", help="skip other_configs and pipeline1_value")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: three timed regions (median), steady state, roofline, the "
+                         "row-skipping-off leg, other configurations, parametric leg, CPU baseline, the other scaling "
+                         "mode, the engine's own screening (--no-dense / --no-others / --no-cpu leave legs out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the results of the last timed step (rank 0) as DIR/<name>.npy, float64")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be at least 1")
@@ -813,14 +859,19 @@ def main():
     fuse = lanes.fuse
     e, b, _ = lanes.lanes[0]
 
-    # three timed regions of --steps steps each; the median is the line's value, all three are printed
+    # one timed region of --steps steps (--full: three, the median is the line's value, all three are printed)
     try:
-        regions = timed_regions(lanes, args.steps, args.warmup, barrier, args.stagger)
+        regions = timed_regions(lanes, args.steps, args.warmup, barrier, args.stagger, n=3 if args.full else 1)
     except VoidLine as ex:
         print(json.dumps({"error": "void: " + str(ex), "metric": "pivots/sec", "value": None}), flush=True)
         raise SystemExit(3)
+    if args.dump_outputs and rank == 0:
+        # every region times the same steps: the last one handed out ran last on lanes.last_lane
+        torch.cuda.synchronize(dev)
+        last = lanes.lanes[lanes.last_lane][1]
+        dump_outputs({k: getattr(last, k).cpu().numpy() for k in DUMP_ARRAYS}, args.dump_outputs)
     regions_checked_passes = lanes.checked_passes
-    dt, share = regions[1]
+    dt, share = regions[len(regions) // 2]
     steps_done = len(share) * fuse   # == --steps unless shards are fused (whole passes of `fuse` steps)
     progress(f"regions {[round(r[0] * 1e3, 2) for r in regions]} ms")
     tot = lanes.totals(share)
@@ -831,7 +882,7 @@ def main():
     # the same lanes over a longer run: the driver's 20 steps are one round of 16 batches that start together plus four
     # stragglers (pipeline fill and drain); 96 steps show the rate of a steady stream of batches
     steady = None
-    if args.steps < 96:
+    if args.full and args.steps < 96:
         try:
             sdt, sshare = timed(lanes, 96, 0, barrier)
             sgt, sdt_max = pdist.gather_totals(lanes.totals(sshare), sdt, dev)
@@ -841,12 +892,12 @@ def main():
 
     # the advance kernel's own launch durations (HIP events on its stream), un-overlapped
     parts0 = lanes.batches[0]
-    k_ms = kernel_ms_of(b, parts0)
+    k_ms = kernel_ms_of(b, parts0) if args.full else None
     torch.cuda.synchronize(dev)
     gt, dt_max = pdist.gather_totals(tot, dt, dev)
 
     other = None
-    if world > 1:  # the other scaling mode, same steps (every rank takes part)
+    if args.full and world > 1:  # the other scaling mode, same steps (every rank takes part)
         mode2 = "weak" if args.scaling == "strong" else "strong"
         lanes.close()
         del lanes
@@ -934,6 +985,10 @@ def main():
     if steady:
         out["steady_state_value"] = steady.get("value")
         out["steady_state"] = steady
+    if not args.full:
+        print(json.dumps(out), flush=True)
+        pdist.finish()
+        return
     traffic, traffic_src = None, None
     t, src = profile_json("r04_pmc_hbm.json", "r03_pmc_hbm.json", "r02_pmc_hbm.json")
     step_traffic = None

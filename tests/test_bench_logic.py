@@ -67,3 +67,31 @@ def test_batch_rows_are_the_seeded_batches():
     assert np.array_equal(bench.batch_rows(cfg, 3), synth.lexmin_batch(1000 + 7919 * 3, 50, 127, 64))
     w = bench.batch_rows(bench.OTHERS[1], 0)
     assert w.shape == (1000, 128, 256) and np.array_equal(w, bench.batch_rows(bench.OTHERS[1], 5))
+
+
+def test_dump_outputs_float64_whole_or_a_seeded_sample_under_the_cap(tmp_path):
+    """--dump-outputs: the headline batch's results are written whole (float64, about 20 MB); a larger batch is cut
+    to a fixed, seeded sample of tableaux within the 64 MB cap, the same sample every run"""
+    import numpy as np
+
+    def results(n):
+        g = np.random.default_rng(n)
+        return {"status": np.ones(n, np.int32), "pivots": g.integers(0, 500, n).astype(np.int32),
+                "cuts": g.integers(0, 50, n).astype(np.int32), "sol_num": g.integers(-9, 9, (n, 127, 1)),
+                "sol_den": g.integers(1, 9, (n, 127))}
+    small = results(10000)
+    bench.dump_outputs(small, str(tmp_path / "a"))
+    for k, a in small.items():
+        got = np.load(tmp_path / "a" / (k + ".npy"))
+        assert got.dtype == np.float64 and np.array_equal(got, a)
+    assert not (tmp_path / "a" / "tableau_index.npy").exists()
+    big = results(40000)
+    for d in ("b", "c"):
+        bench.dump_outputs(big, str(tmp_path / d))
+    files = sorted(p.name for p in (tmp_path / "b").iterdir())
+    assert files == sorted([k + ".npy" for k in big] + ["tableau_index.npy"])
+    assert sum((tmp_path / "b" / f).stat().st_size for f in files) <= bench.DUMP_BYTES + 4096 * len(files)
+    keep = np.load(tmp_path / "b" / "tableau_index.npy").astype(np.int64)
+    assert len(set(keep)) == len(keep) > 10000 and np.array_equal(keep, np.load(tmp_path / "c" / "tableau_index.npy"))
+    for k, a in big.items():
+        assert np.array_equal(np.load(tmp_path / "b" / (k + ".npy")), a[keep])

@@ -131,8 +131,8 @@ def test_bench_gpus_2_starts_its_own_ranks():
         env.pop(k, None)
     if torch.cuda.device_count() < 2:
         env["PIPAMD_BENCH_BACKEND"] = "gloo"
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--no-cpu",
-                        "--no-others", "--no-dense"], env=env, capture_output=True, timeout=850)
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2", "--full",
+                        "--no-cpu", "--no-others", "--no-dense"], env=env, capture_output=True, timeout=850)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     lines = [ln for ln in p.stdout.decode().splitlines() if ln.startswith("{")]
     assert len(lines) == 1, lines
