@@ -40,8 +40,10 @@ extern "C" {
  * 300: round 3 -- pipamd_batch_solve_async / _wait / _poll, pipamd_batch_load_part, unbounded row growth in the
  * batch layer (no PIPAMD_ST_CAPACITY short of the engine's 16,000-row limit), pipamd_solve_tableaux128,
  * pipamd_engine_set_max_rows.  400: round 4 -- pipamd_solve_tableaux_lockstep128, pipamd_engine_set_lean64; the 128-bit
- * entries try the device-resident traiter() first (pipamd_last_device_tree answers for them too); nothing removed. */
-#define PIPAMD_VERSION 400
+ * entries try the device-resident traiter() first (pipamd_last_device_tree answers for them too); nothing removed.
+ * 500: the device-resident traiter() takes problems of 65 ... 128 columns too (two column blocks per wave);
+ * pipamd_device_tree_fits tells whether a shape is in its box; nothing removed. */
+#define PIPAMD_VERSION 500
 
 /* ---- error codes (return values) ---- */
 #define PIPAMD_OK 0
@@ -267,8 +269,8 @@ int pipamd_traiter(pipamd_engine *e, int nvar, int nparm, int ni, int nc, int bi
  * with a wider Entier (include/piplib/piplib.h:42-88): device tableaux, context, parametric cuts
  * and tape all carry __int128 here; the input rows are int64, the cells' parameters come back as
  * (low, high) int64 pairs.  Tableaux must fit a workgroup's LDS (about 1,600 rows of <= 128
- * columns).  Small problems run their whole decision tree on the device in this flavour too (the 128-bit instantiation
- * of csrc/pip_quast.hip), many problems go through pipamd_solve_tableaux128 / pipamd_solve_tableaux_lockstep128. */
+ * columns).  Small problems run their whole decision tree on the device in this flavour too (the 128-bit instantiations
+ * of csrc/pip_quast.hip, up to 128 columns: the box at pipamd_engine_set_device_tree), many problems go through pipamd_solve_tableaux128 / pipamd_solve_tableaux_lockstep128. */
 typedef struct pipamd_sol_cell128 {
   int32_t kind, reserved;
   int64_t param1_lo, param1_hi, param2_lo, param2_hi;
@@ -318,12 +320,17 @@ int pipamd_solve_tableaux_lockstep(pipamd_engine *e, int n, const pipamd_problem
                                    int *statuses, int64_t *pivots);
 /* The lock-step scheduler of the overflow-safe flavour (piplib.h:42-88, funcall.h:37-41: the flavour is a type choice):
  * device tableaux, contexts, parametric cuts and tape cells are 128-bit, one launch sequence per step serves the whole
- * batch; no device-resident traiter() in front of it (that kernel is 64-bit); rare paths go to a TreeT<__int128>. */
+ * batch; the 128-bit instantiation of the device-resident traiter() runs in front of it (the problems in its box, see
+ * pipamd_device_tree_fits), rare paths go to a TreeT<__int128>. */
 int pipamd_solve_tableaux_lockstep128(pipamd_engine *e, int n, const pipamd_problem *problems, int simplify,
                                       int deepest_cut, pipamd_sol_cell128 **cells, size_t *n_cells, int *rcs,
                                       int *statuses, int64_t *pivots);
-/* Small problems (at most 64 columns, spare room for new parameters included, and 104 inequalities -- 128 real rows with
- * the cuts; round 4: in both entry widths) are first given to the device-resident traiter() (csrc/pip_quast.hip): one wave per
+/* Small problems are first given to the device-resident traiter() (csrc/pip_quast.hip), in both entry widths: at most 128
+ * columns (a lane per column up to 64, two columns per lane beyond; the spare columns for new parameters -- up to 10 -- stay
+ * within that width, so a problem of 127 or 128 columns that needs a new parameter is handed back), at most 104
+ * inequalities (128 real rows with the cuts), a context of at most 64 columns with its spare ones, and an LDS image that fits
+ * the limit of its width (up to 64 columns: 96 KB in 64 bits, 150 KB in 128 bits; beyond: 160 KB, a workgroup's LDS --
+ * so the widest, tallest 128-bit shapes go to the host schedulers).  pipamd_device_tree_fits answers for one shape.  One wave per
  * problem runs the whole call tree -- pivots, compa_test sub-problems (traiter.c:162-243), forks of the
  * quast (traiter.c:695-759), cuts with new parameters (integrer.c:156-291) -- and writes the tape, with
  * no host round trip.  A problem in which a 64-bit operation would overflow, or that outgrows its
@@ -336,6 +343,11 @@ int pipamd_solve_tableaux_lockstep128(pipamd_engine *e, int n, const pipamd_prob
  * pipamd_last_device_tree reports how many problems of the last lock-step call each side served. */
 int pipamd_engine_set_device_tree(pipamd_engine *e, int on);
 int pipamd_last_device_tree(const pipamd_engine *e, int *served, int *handed_back);
+/* 1 if the device-resident traiter() takes a problem of this shape in the flavour of `entier_bits` (64 or 128) -- it may
+ * still hand it back at run time (overflow, rows, tape, stack) --, 0 if the shape goes straight to the host schedulers,
+ * PIPAMD_E_INVALID for bad arguments.  Host only: needs neither an engine nor a GPU.  The same decision the solve entries
+ * make (interface version 500). */
+int pipamd_device_tree_fits(const pipamd_problem *p, int entier_bits);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,5 @@
 // piplib_amd/csrc/pip_quast.hip -- traiter() with its quast decision tree on the device, for SMALL
-// parametric problems (at most 64 columns and 128 real rows), in both entry widths.
+// parametric problems (at most 128 columns and 128 real rows), in both entry widths.
 //
 // One wave64 per problem runs the whole call tree of traiter() (traiter.c:628-791) without a host
 // round trip: the dual simplex with lexicographic pivoting (pivoter, traiter.c:345-548), exam_coef
@@ -7,8 +7,10 @@
 // (traiter.c:162-243), the forks of the quast (traiter.c:695-759; the "else" state waits on a stack in
 // HBM while the "then" branch runs), Gomory cuts with new parameters (integrer.c:156-291,305-534)
 // and the solution tape (sol.c:104-209).  The tableaux live in LDS.  Column work (pivot-column tournament, cut
-// vectors, tape cells) has a lane per column; row work (multipliers, elimination, row gcd, exact division,
-// sign tests, the selection sort of tab_sort_rows) has a lane per row.
+// vectors, tape cells) has a lane per column -- in one block of 64 columns, or in two (lane l holds columns l and
+// l + 64: pip_quast_kernel<QI, 2>, for tableaux of 65 ... 128 columns); row work (multipliers, elimination, row gcd,
+// exact division, sign tests, the selection sort of tab_sort_rows) has a lane per row and walks the row's columns.
+// The compa_test sub-problems are as wide as the context (at most 64 columns) and run one block in either kernel.
 //
 // The kernel computes on true integers: every product and sum is checked, and a problem in which a
 // 64-bit operation overflows (where the reference's `long long` build wraps or exits with "Integer
@@ -129,24 +131,41 @@ enum { MAXDET = 4 };  // tab.h:67
 #define LDS __attribute__((address_space(3)))
 typedef LDS int lint;
 
-// The kernel's functions as static members of a class template over the entry type: inside it `i64` IS the entry type
-// (and `uE` its unsigned twin), so the code below reads as it did when there was one flavour.
+// one tableau in LDS: logical rows (unit row on column `ref`, or real row in slot `ref`)
 template <class QI>
+struct QTab {
+  LDS QI *den;   // [rows]
+  LDS QI *val;   // [slots][W]
+  lint *flag;  // [rows]
+  lint *ref;   // [rows]
+  lint *ldet;  // -> number of determinant limbs in use
+  LDS QI *det;   // -> MAXDET limbs
+  int W, rows_cap, slots_cap;
+};
+
+// scalars of the main tableau that travel with a stack frame
+template <class QI>
+struct QStateT {
+  int nvar, nparm, ni, nc, pivi, ldet, ni0, pad1;
+  QI det[MAXDET];
+  // Compute_dual: tab_sort_rows' `pos` of the traiter() call in progress (traiter.c:567-620): logical row of each of
+  // the call's ni0 inequalities after its sort.  Part of the image, so a fork's frame keeps the caller's.
+  unsigned short pos[64];
+};
+
+// The kernel's functions as static members of a class template over the entry type and the number of column blocks: inside
+// it `i64` IS the entry type (and `uE` its unsigned twin), so the code below reads as it did when there was one flavour.
+// NB = 1: a lane per column, at most 64 columns.  NB = 2: lane l holds columns l and l + 64 (at most 128 columns), and a
+// mask over columns is two words.  Tableaux and their rows are the same either way (Tab, QState); the compa_test
+// sub-problems are as wide as the context (at most 64 columns) and always run as QK<QI, 1>.
+template <class QI, int NB>
 struct QK {
 typedef QI i64;
 typedef typename QT<QI>::U uE;
 typedef LDS i64 li64;
-
-// one tableau in LDS: logical rows (unit row on column `ref`, or real row in slot `ref`)
-struct Tab {
-  li64 *den;   // [rows]
-  li64 *val;   // [slots][W]
-  lint *flag;  // [rows]
-  lint *ref;   // [rows]
-  lint *ldet;  // -> number of determinant limbs in use
-  li64 *det;   // -> MAXDET limbs
-  int W, rows_cap, slots_cap;
-};
+typedef QTab<QI> Tab;
+typedef QStateT<QI> QState;
+static_assert(NB == 1 || NB == 2, "one or two column blocks");
 
 struct Wv {
   int lane;
@@ -155,20 +174,77 @@ struct Wv {
   int deepest;
 };
 
-// scalars of the main tableau that travel with a stack frame
-struct QState {
-  int nvar, nparm, ni, nc, pivi, ldet, ni0, pad1;
-  i64 det[MAXDET];
-  // Compute_dual: tab_sort_rows' `pos` of the traiter() call in progress (traiter.c:567-620): logical row of each of
-  // the call's ni0 inequalities after its sort.  Part of the image, so a fork's frame keeps the caller's.
-  unsigned short pos[64];
-};
-
 #define BAD(w) (__any((w).bad) != 0)
 static __device__ __forceinline__ void wsync() { __syncthreads(); }  // one wave per workgroup: orders its LDS traffic
 static __device__ __forceinline__ i64 bcast(i64 x, int src) { return qshfl(x, src); }
 static __device__ __forceinline__ int popc64(u64 m) { return __popcll(m); }
 static __device__ __forceinline__ int first64(u64 m) { return __ffsll((long long)m) - 1; }
+
+// ---- column work over NB blocks of 64: lane l holds column l + 64 h of block h.  With NB = 1 each helper is the
+// one-word expression it stands for.
+// x of block h (h uniform or per lane), without indexing the register array
+template <class T>
+static __device__ __forceinline__ T blk(const T (&x)[NB], int h) {
+  T r = x[0];
+#pragma unroll
+  for (int b = 1; b < NB; b++)
+    if (h == b) r = x[b];
+  return r;
+}
+// the value held for column j (uniform): bcast of its block's register from its lane
+static __device__ __forceinline__ i64 bcast_col(const i64 (&x)[NB], int j) { return bcast(blk(x, j >> 6), j & 63); }
+// lowest column of a non-empty mask
+static __device__ __forceinline__ int first_col(const u64 (&m)[NB]) {
+#pragma unroll
+  for (int b = 0; b < NB - 1; b++)
+    if (m[b]) return 64 * b + first64(m[b]);
+  return 64 * (NB - 1) + first64(m[NB - 1]);
+}
+static __device__ __forceinline__ bool any_col(const u64 (&m)[NB]) {
+  u64 a = m[0];
+#pragma unroll
+  for (int b = 1; b < NB; b++) a |= m[b];
+  return a != 0;
+}
+static __device__ __forceinline__ int popc_cols(const u64 (&m)[NB]) {
+  int n = popc64(m[0]);
+#pragma unroll
+  for (int b = 1; b < NB; b++) n += popc64(m[b]);
+  return n;
+}
+static __device__ __forceinline__ bool has_col(const u64 (&m)[NB], int j) {
+  if constexpr (NB == 1) return (m[0] >> j) & 1;
+  return (blk(m, j >> 6) >> (j & 63)) & 1;
+}
+static __device__ __forceinline__ void drop_col(u64 (&m)[NB], int j) {
+  if constexpr (NB == 1) {
+    m[0] &= ~(1ull << j);
+  } else {
+#pragma unroll
+    for (int b = 0; b < NB; b++)
+      if ((j >> 6) == b) m[b] &= ~(1ull << (j & 63));
+  }
+}
+static __device__ __forceinline__ void only_col(u64 (&m)[NB], int j) {
+  if constexpr (NB == 1) {
+    m[0] = 1ull << j;
+  } else {
+#pragma unroll
+    for (int b = 0; b < NB; b++) m[b] = (j >> 6) == b ? 1ull << (j & 63) : 0ull;
+  }
+}
+// lane j < nparm: column nvar + 1 + j (a row's parameter part; nvar + 1 + nparm <= 64 NB)
+static __device__ __forceinline__ i64 parm_part(const i64 (&v)[NB], int nvar, int lane) {
+  if constexpr (NB == 1) return qshfl(v[0], (lane + nvar + 1) & 63);
+  const int src = lane + nvar + 1;
+  i64 r = 0;
+#pragma unroll
+  for (int b = 0; b < NB; b++) {
+    const i64 x = qshfl(v[b], src & 63);
+    if ((src >> 6) == b) r = x;
+  }
+  return r;
+}
 
 static __device__ __forceinline__ i64 cmul(i64 a, i64 b, int &bad) {
   i64 r;
@@ -252,11 +328,11 @@ static __device__ __forceinline__ float wave_min_f(float x) {
   return x;
 }
 
-// value of logical row k in column `lane` (traiter.c:246-252 valeur); 0 beyond ncol
-static __device__ __forceinline__ i64 row_at(const Tab &t, int k, int lane, int ncol) {
+// value of logical row k in column `col` (traiter.c:246-252 valeur); 0 beyond ncol
+static __device__ __forceinline__ i64 row_at(const Tab &t, int k, int col, int ncol) {
   const int fl = t.flag[k], rf = t.ref[k];
-  if (fl & F_UNIT) return rf == lane ? t.den[k] : 0;
-  return lane < ncol ? t.val[rf * t.W + lane] : 0;
+  if (fl & F_UNIT) return rf == col ? t.den[k] : 0;
+  return col < ncol ? t.val[rf * t.W + col] : 0;
 }
 
 // traiter.c:39-44 chercher: first row among 0..n-1 whose flag meets `mask`, n if none
@@ -527,44 +603,64 @@ static __device__ __noinline__ int pivot_step(Tab t, int pivi, int nvar, int nco
   const int W = t.W;
   int bad = 0;
   const int pslot = t.ref[pivi];
-  const i64 p = lane < ncol ? t.val[pslot * W + lane] : 0;
-  u64 tied = __ballot(lane < nvar && p > 0);
-  if (!tied) return -1;
-  for (int k = 0; k < nligne && popc64(tied) > 1; k++) {
+  i64 p[NB];
+  u64 tied[NB];
+#pragma unroll
+  for (int h = 0; h < NB; h++) {
+    const int j = lane + 64 * h;
+    p[h] = j < ncol ? t.val[pslot * W + j] : 0;
+    tied[h] = __ballot(j < nvar && p[h] > 0);
+  }
+  if (!any_col(tied)) return -1;
+  for (int k = 0; k < nligne && popc_cols(tied) > 1; k++) {
     const int fl = t.flag[k], rf = t.ref[k];
     if (fl & F_UNIT) {  // its own column has the only positive ratio there: every other tied column is smaller
-      tied &= ~(1ull << rf);
+      drop_col(tied, rf);
       continue;
     }
-    const i64 v = lane < ncol ? t.val[rf * W + lane] : 0;
-    const bool in = (tied >> lane) & 1;
-    if (!__ballot(in && v != 0)) continue;
-    int c = first64(tied);
-    // each round moves to a strictly smaller ratio, so at most 64 rounds on true integers; products that
+    i64 v[NB];
+    bool in[NB];
+    u64 nz = 0;
+#pragma unroll
+    for (int h = 0; h < NB; h++) {
+      const int j = lane + 64 * h;
+      v[h] = j < ncol ? t.val[rf * W + j] : 0;
+      in[h] = (tied[h] >> lane) & 1;
+      nz |= __ballot(in[h] && v[h] != 0);
+    }
+    if (!nz) continue;
+    int c = first_col(tied);
+    // each round moves to a strictly smaller ratio, so at most 64 NB rounds on true integers; products that
     // overflowed compare as garbage and could go round in circles: the problem is handed back then
     for (int round = 0;; round++) {
-      const i64 pc = bcast(p, c), vc = bcast(v, c);
-      const i64 x = csub(cmul(pc, v, bad), cmul(vc, p, bad), bad);
-      const u64 less = __ballot(in && x < 0);
-      if (!less) {
-        tied = __ballot(in && x == 0);
+      const i64 pc = bcast_col(p, c), vc = bcast_col(v, c);
+      i64 x[NB];
+      u64 less[NB];
+#pragma unroll
+      for (int h = 0; h < NB; h++) {
+        x[h] = csub(cmul(pc, v[h], bad), cmul(vc, p[h], bad), bad);
+        less[h] = __ballot(in[h] && x[h] < 0);
+      }
+      if (!any_col(less)) {
+#pragma unroll
+        for (int h = 0; h < NB; h++) tied[h] = __ballot(in[h] && x[h] == 0);
         break;
       }
-      if (round >= 64 || __any(bad)) {
+      if (round >= 64 * NB || __any(bad)) {
         bad |= Q_WHY_OVERFLOW;
-        tied = 1ull << c;
+        only_col(tied, c);
         break;
       }
-      c = first64(less);
+      c = first_col(less);  // (the lowest column among the smaller ratios: ties end on the lowest index, as choisir_piv's)
     }
-    if (!tied) {  // (only with garbage from an overflow)
+    if (!any_col(tied)) {  // (only with garbage from an overflow)
       bad |= Q_WHY_OVERFLOW;
-      tied = 1ull << c;
+      only_col(tied, c);
     }
   }
   if (__any(bad)) return bad;
-  const int pivj = first64(tied);
-  const i64 pivot = bcast(p, pivj), dpiv = t.den[pivi];
+  const int pivj = first_col(tied);
+  const i64 pivot = bcast_col(p, pivj), dpiv = t.den[pivi];
   // the determinant in limbs, traiter.c:412-446 (uniform values; lane 0 publishes them).  A pivot of 1
   // over a denominator of 1 multiplies a limb that still has room by 1: nothing to do.
   constexpr int EBW = 8 * (int)sizeof(i64);  // bits of an Entier (traiter.c:430: lllog2(limb) + lllog2(pivot) < 8 * sizeof(Entier))
@@ -692,7 +788,11 @@ static __device__ __noinline__ int pivot_step(Tab t, int pivi, int nvar, int nco
     return bad | Q_WHY_OTHER;
   }
   // swap roles, traiter.c:503-516: the unit row of pivj becomes real (in the pivot row's slot)
-  if (lane < ncol) t.val[pslot * W + lane] = lane == pivj ? dpiv : cneg(p, bad);
+#pragma unroll
+  for (int h = 0; h < NB; h++) {
+    const int j = lane + 64 * h;
+    if (j < ncol) t.val[pslot * W + j] = j == pivj ? dpiv : cneg(p[h], bad);
+  }
   if (lane == 0) {
     t.flag[ku] = F_PLUS;
     t.ref[ku] = pslot;
@@ -723,30 +823,37 @@ static __device__ __forceinline__ i64 bezout(i64 x, i64 y, i64 delta, int &bad) 
   return pmod(cmul(c, x, bad), delta);
 }
 
-// the cut of row i (integrer.c:342-400), one column per lane
+// the cut of row i (integrer.c:342-400), one column per lane and block
 struct Cut {
-  i64 c;
+  i64 c[NB];
   bool ok_var, ok_const, ok_parm;
 };
 static __device__ __forceinline__ Cut make_cut(const Tab &t, int i, int nvar, int ncol, int bigparm, int lane) {
   Cut q;
   const i64 D = t.den[i];
-  const i64 v = lane < ncol ? t.val[t.ref[i] * t.W + lane] : 0;
-  i64 c = 0;
-  if (lane < nvar)
-    c = pmod(v, D);
-  else if (lane < ncol && lane != bigparm)  // the big parameter is a multiple of everything
-    c = -pmod(-v, D);
-  q.c = c;
-  q.ok_var = __ballot(lane < nvar && c > 0) != 0;
-  q.ok_const = bcast(c, nvar) != 0;
-  q.ok_parm = __ballot(lane > nvar && lane < ncol && c != 0) != 0;
+  u64 var = 0, parm = 0;
+#pragma unroll
+  for (int h = 0; h < NB; h++) {
+    const int j = lane + 64 * h;
+    const i64 v = j < ncol ? t.val[t.ref[i] * t.W + j] : 0;
+    i64 c = 0;
+    if (j < nvar)
+      c = pmod(v, D);
+    else if (j < ncol && j != bigparm)  // the big parameter is a multiple of everything
+      c = -pmod(-v, D);
+    q.c[h] = c;
+    var |= __ballot(j < nvar && c > 0);
+    parm |= __ballot(j > nvar && j < ncol && c != 0);
+  }
+  q.ok_var = var != 0;
+  q.ok_const = bcast_col(q.c, nvar) != 0;
+  q.ok_parm = parm != 0;
   return q;
 }
 
-// deepest cut, integrer.c:417-438 (constant cuts only)
-static __device__ __forceinline__ i64 deepen(i64 c, i64 D, int nvar, int lane, int &bad) {
-  const i64 cst = bcast(c, nvar);
+// deepest cut, integrer.c:417-438 (constant cuts only), in place
+static __device__ __forceinline__ void deepen(i64 (&cv)[NB], i64 D, int nvar, int lane, int &bad) {
+  const i64 cst = bcast_col(cv, nvar);
   i64 tt = -cst;
   const i64 delta = gcd64(tt, D), tau = quo(tt, delta), dd = quo(D, delta);
   tt = dd - 1;
@@ -757,15 +864,23 @@ static __device__ __forceinline__ i64 deepen(i64 c, i64 D, int nvar, int lane, i
     tt = gcd64(lambda, D);
   }
   if (tt != 1) bad |= Q_WHY_OTHER;
-  if (lane < nvar) return pmod(cmul(lambda, c, bad), D);
-  if (lane == nvar) return -(D - pmod(cmul(c, lambda, bad), D));
-  return c;
+#pragma unroll
+  for (int h = 0; h < NB; h++) {
+    const int j = lane + 64 * h;
+    const i64 c = cv[h];
+    if (j < nvar)
+      cv[h] = pmod(cmul(lambda, c, bad), D);
+    else if (j == nvar)
+      cv[h] = -(D - pmod(cmul(c, lambda, bad), D));
+  }
 }
 
 // append a cut as logical row nligne in slot ni (flag Minus, denominator D); false: no room
-static __device__ __forceinline__ bool append_row(Tab &t, int nligne, int ni, i64 c, i64 D, int lane) {
+static __device__ __forceinline__ bool append_row(Tab &t, int nligne, int ni, const i64 (&c)[NB], i64 D, int lane) {
   if (nligne >= t.rows_cap || ni >= t.slots_cap) return false;
-  if (lane < t.W) t.val[ni * t.W + lane] = c;
+#pragma unroll
+  for (int h = 0; h < NB; h++)
+    if (lane + 64 * h < t.W) t.val[ni * t.W + lane + 64 * h] = c[h];
   if (lane == 0) {
     t.flag[nligne] = F_MINUS;
     t.ref[nligne] = ni;
@@ -790,9 +905,14 @@ static __device__ __noinline__ int solve_plain(Tab t, int nvar, int ni, int lane
       // integrer.c:305-534 with constant cuts only
       int i;
       bool nil = false;
-      const u64 frac = __ballot(lane < nvar && !(t.flag[lane] & F_UNIT) && t.den[lane] != 1);  // rows that may be fractional
-      for (i = frac ? first64(frac) : nvar; i < nvar; i++) {
-        if (!((frac >> i) & 1)) continue;
+      u64 frac[NB];  // rows that may be fractional
+#pragma unroll
+      for (int h = 0; h < NB; h++) {
+        const int r = lane + 64 * h;
+        frac[h] = __ballot(r < nvar && !(t.flag[r] & F_UNIT) && t.den[r] != 1);
+      }
+      for (i = any_col(frac) ? first_col(frac) : nvar; i < nvar; i++) {
+        if (!has_col(frac, i)) continue;
         Cut q = make_cut(t, i, nvar, ncol, -1, lane);
         if (!q.ok_const) continue;  // integral row
         if (!q.ok_var) {            // constant fractional, nothing to cut with
@@ -800,10 +920,11 @@ static __device__ __noinline__ int solve_plain(Tab t, int nvar, int ni, int lane
           break;
         }
         const i64 D = t.den[i];
-        i64 c = q.c;
-        if (deepest) c = deepen(c, D, nvar, lane, bad);
-        if (lane >= ncol) c = 0;
-        if (!append_row(t, nligne, ni, c, D, lane)) bad |= Q_WHY_ROWS | 512;
+        if (deepest) deepen(q.c, D, nvar, lane, bad);
+#pragma unroll
+        for (int h = 0; h < NB; h++)
+          if (lane + 64 * h >= ncol) q.c[h] = 0;
+        if (!append_row(t, nligne, ni, q.c, D, lane)) bad |= Q_WHY_ROWS | 512;
         pivi = nligne;
         ni++;
         break;
@@ -906,6 +1027,12 @@ static __device__ __forceinline__ void run(const QProb *probs, const w64 *input,
   const int pi = blockIdx.x;
   if (pi >= nprob) return;
   const QProb P = probs[pi];
+  if constexpr (NB > 1) {  // the host's box, checked once more: every column within the blocks, the context within one
+    if (cap.W > 64 * NB || cap.CW > 64 || P.nvar + P.nparm + 1 > cap.W || P.nparm + 1 > cap.CW) {
+      if (threadIdx.x < Q_OUT) out[Q_OUT * pi + threadIdx.x] = threadIdx.x == 0 ? Q_FALLBACK : (threadIdx.x == 3 ? Q_WHY_OTHER : 0);
+      return;
+    }
+  }
   const long long t_start = wall_clock64();
   // No problem keeps its wave for more than Q_PIVOT_BUDGET pivots (its own and those of its compa_test sub-problems;
   // about two seconds of one wave): whatever is still running then is handed back to the host schedulers.  Every loop
@@ -981,7 +1108,9 @@ static __device__ __forceinline__ void run(const QProb *probs, const w64 *input,
     const int ncol = nvar + nparm + 1;
     const w64 *in = input + P.in_off;
     for (int r = 0; r < ni; r++)
-      if (lane < ncol) M.val[r * W + lane] = in[(size_t)r * ncol + lane];
+#pragma unroll
+      for (int h = 0; h < NB; h++)
+        if (lane + 64 * h < ncol) M.val[r * W + lane + 64 * h] = in[(size_t)r * ncol + lane + 64 * h];
     const w64 *cin = in + (size_t)ni * ncol;
     for (int r = 0; r < nc; r++)
       if (lane <= nparm) ctx[r * CW + lane] = cin[(size_t)r * (nparm + 1) + lane];
@@ -1032,7 +1161,7 @@ static __device__ __forceinline__ void run(const QProb *probs, const w64 *input,
     if (sni < 0)
       w.bad |= Q_WHY_ROWS | 1024;
     else {
-      const int r = solve_plain(S, nparm, sni, lane, w.deepest, Q_PIVOT_BUDGET - w.pivots);
+      const int r = QK<QI, 1>::solve_plain(S, nparm, sni, lane, w.deepest, Q_PIVOT_BUDGET - w.pivots);
       w.bad |= (r >> 1) & 0x7fff;
       w.pivots += r >> 16;
       if (!(r & 1) && !BAD(w)) result = Q_VOID;
@@ -1065,11 +1194,18 @@ static __device__ __forceinline__ void run(const QProb *probs, const w64 *input,
           for (int i = first_flagged(M, F_CRITIC | F_UNKNOWN, nligne, lane); i < nligne && !BAD(w); i++) {
             const int fl = M.flag[i];
             if (!(fl & (F_CRITIC | F_UNKNOWN))) continue;
-            const i64 v = lane < ncol ? M.val[M.ref[i] * W + lane] : 0;
-            const bool critic = __ballot(lane < nvar && v > 0) == 0;
+            i64 v[NB];
+            u64 pos = 0;
+#pragma unroll
+            for (int h = 0; h < NB; h++) {
+              const int j = lane + 64 * h;
+              v[h] = j < ncol ? M.val[M.ref[i] * W + j] : 0;
+              pos |= __ballot(j < nvar && v[h] > 0);
+            }
+            const bool critic = pos == 0;
             // lane j <= nparm of the new context row: parameters, then the constant
-            const i64 vc = bcast(v, nvar);
-            const i64 vp = qshfl(v, (lane + nvar + 1) & 63);  // lane j < nparm: column nvar+1+j
+            const i64 vc = bcast_col(v, nvar);
+            const i64 vp = parm_part(v, nvar, lane);  // lane j < nparm: column nvar+1+j
             i64 ex = lane < nparm ? vp : (lane == nparm ? (critic ? vc : csub(vc, 1, w.bad)) : 0);
             int sni = build_sub(S, ctx, CW, nparm, nc, true, ex, lane);
             if (sni < 0) {
@@ -1083,7 +1219,7 @@ static __device__ __forceinline__ void run(const QProb *probs, const w64 *input,
                 ex = lane < nparm ? cneg(vp, w.bad) : (lane == nparm ? csub(cneg(vc, w.bad), 1, w.bad) : 0);
                 sni = build_sub(S, ctx, CW, nparm, nc, true, ex, lane);
               }
-              const int r = solve_plain(S, nparm, sni, lane, w.deepest, Q_PIVOT_BUDGET - w.pivots);
+              const int r = QK<QI, 1>::solve_plain(S, nparm, sni, lane, w.deepest, Q_PIVOT_BUDGET - w.pivots);
               w.bad |= (r >> 1) & 0x7fff;
               w.pivots += r >> 16;
               can[sg] = r & 1;
@@ -1114,9 +1250,11 @@ static __device__ __forceinline__ void run(const QProb *probs, const w64 *input,
               w.bad |= sp >= cap.depth ? Q_WHY_STACK : (nc >= cap.CR ? (Q_WHY_ROWS | 4096) : (nparm >= PIPAMD_MAXPARM ? Q_WHY_OTHER : Q_WHY_TAPE));
               break;
             }
-            const i64 v = lane < ncol ? M.val[M.ref[pivi] * W + lane] : 0;
-            const i64 vc = bcast(v, nvar);
-            const i64 vp = qshfl(v, (lane + nvar + 1) & 63);
+            i64 v[NB];
+#pragma unroll
+            for (int h = 0; h < NB; h++) v[h] = lane + 64 * h < ncol ? M.val[M.ref[pivi] * W + lane + 64 * h] : 0;
+            const i64 vc = bcast_col(v, nvar);
+            const i64 vp = parm_part(v, nvar, lane);
             i64 g = 0;
             for (int j = 0; j < nparm; j++) g = gcd64(g, bcast(vp, j));
             if (!integer) g = gcd64(g, vc);
@@ -1164,25 +1302,35 @@ static __device__ __forceinline__ void run(const QProb *probs, const w64 *input,
           if (integer) {
             // integrer.c:305-534
             int i;
-            const u64 frac = __ballot(lane < nvar && !(M.flag[lane] & F_UNIT) && M.den[lane] != 1);  // rows that may be fractional
-            for (i = frac ? first64(frac) : nvar; i < nvar; i++) {
-              if (!((frac >> i) & 1)) continue;
+            u64 frac[NB];  // rows that may be fractional
+#pragma unroll
+            for (int h = 0; h < NB; h++) {
+              const int r = lane + 64 * h;
+              frac[h] = __ballot(r < nvar && !(M.flag[r] & F_UNIT) && M.den[r] != 1);
+            }
+            for (i = any_col(frac) ? first_col(frac) : nvar; i < nvar; i++) {
+              if (!has_col(frac, i)) continue;
               Cut qc = make_cut(M, i, nvar, ncol, bigparm, lane);
               if (!qc.ok_parm && !qc.ok_const) continue;  // integral row
               const i64 D = M.den[i];
-              i64 c = qc.c;
               if (!qc.ok_parm) {
                 if (!qc.ok_var) {  // constant fractional, nothing to cut with
                   nil = true;
                   break;
                 }
-                if (w.deepest) c = deepen(c, D, nvar, lane, w.bad);
-                if (lane >= ncol) c = 0;
-                if (!append_row(M, nligne, ni, c, D, lane)) w.bad |= Q_WHY_ROWS | 2048;
+                if (w.deepest) deepen(qc.c, D, nvar, lane, w.bad);
+#pragma unroll
+                for (int h = 0; h < NB; h++)
+                  if (lane + 64 * h >= ncol) qc.c[h] = 0;
+                if (!append_row(M, nligne, ni, qc.c, D, lane)) w.bad |= Q_WHY_ROWS | 2048;
                 break;
               }
               // parametric cut, integrer.c:487-520; cutv = constant | parameters | divisor
-              if (lane >= nvar && lane < ncol) cutv[lane - nvar] = c;
+#pragma unroll
+              for (int h = 0; h < NB; h++) {
+                const int j = lane + 64 * h;
+                if (j >= nvar && j < ncol) cutv[j - nvar] = qc.c[h];
+              }
               if (lane == 0) cutv[1 + nparm] = D;
               wsync();
               int parm = find_quotient(ctx, CW, nc, nparm, cutv, lane, w.bad);
@@ -1237,9 +1385,13 @@ static __device__ __forceinline__ void run(const QProb *probs, const w64 *input,
                 break;
               }
               // the cut row: the first ncol columns of the cut, the divisor added in the quotient's column
-              if (lane >= ncol) c = 0;
-              if (lane == nvar + 1 + parm) c = cadd(c, D, w.bad);
-              if (!append_row(M, nligne, ni, c, D, lane)) w.bad |= Q_WHY_ROWS | 2048;
+#pragma unroll
+              for (int h = 0; h < NB; h++) {
+                const int j = lane + 64 * h;
+                if (j >= ncol) qc.c[h] = 0;
+                if (j == nvar + 1 + parm) qc.c[h] = cadd(qc.c[h], D, w.bad);
+              }
+              if (!append_row(M, nligne, ni, qc.c, D, lane)) w.bad |= Q_WHY_ROWS | 2048;
               break;
             }
             if (BAD(w)) break;
@@ -1271,10 +1423,14 @@ static __device__ __forceinline__ void run(const QProb *probs, const w64 *input,
             for (int i = 0; i < nvar; i++) {
               const int at = tape.n + 1 + i * (nparm + 2);
               const i64 d = M.den[i];
-              const i64 v = row_at(M, i, lane, nc1);
               if (lane == 0) tape_put(tape, at, C_FORM, nparm + 1, 0);
-              if (lane > nvar && lane < nc1) tape_put(tape, at + (lane - nvar), C_VAL, v, d);
-              if (lane == nvar) tape_put(tape, at + nparm + 1, C_VAL, v, d);
+#pragma unroll
+              for (int h = 0; h < NB; h++) {
+                const int j = lane + 64 * h;
+                const i64 v = row_at(M, i, j, nc1);
+                if (j > nvar && j < nc1) tape_put(tape, at + (j - nvar), C_VAL, v, d);
+                if (j == nvar) tape_put(tape, at + nparm + 1, C_VAL, v, d);
+              }
             }
             tape.n += need;
             if (dual) {
@@ -1352,10 +1508,10 @@ static __device__ __forceinline__ void run(const QProb *probs, const w64 *input,
 
 };  // struct QK
 
-template <class QI>
+template <class QI, int NB>
 __global__ __launch_bounds__(64) void pip_quast_kernel(const QProb *probs, const w64 *input, QI *stack, QI *cells, int *out,
                                                         int nprob, QCaps cap) {
-  QK<QI>::run(probs, input, stack, cells, out, nprob, cap);
+  QK<QI, NB>::run(probs, input, stack, cells, out, nprob, cap);
 }
 
 // cells of every finished problem, packed back to back: off[i] .. off[i+1] (a cell is `cw` raw words: three entries)
@@ -1369,7 +1525,7 @@ __global__ void pip_quast_pack_kernel(const w64 *cells, const w64 *off, w64 *pac
 }  // namespace
 
 // LDS image and stack frame of a launch, by entry width (ebits 64 or 128): EB bytes an entry
-static size_t quast_state_bytes(int ebits) { return ebits == 128 ? sizeof(QK<w128>::QState) : sizeof(QK<w64>::QState); }
+static size_t quast_state_bytes(int ebits) { return ebits == 128 ? sizeof(QStateT<w128>) : sizeof(QStateT<w64>); }
 extern "C" size_t pipk_quast_lds_bytes(const QCaps *c, int ebits) {
   const size_t EB = ebits == 128 ? 16 : 8;
   size_t b = EB * (size_t)c->R + EB * (size_t)c->S * c->W + EB * (size_t)c->CR * c->CW + 8 * (size_t)c->R + quast_state_bytes(ebits);
@@ -1383,30 +1539,38 @@ extern "C" size_t pipk_quast_frame_words(const QCaps *c, int ebits) {
   return (EB * (size_t)c->R + EB * (size_t)c->S * c->W + EB * (size_t)c->CR * c->CW + 8 * (size_t)c->R + quast_state_bytes(ebits)) / EB;
 }
 
-static int g_quast_lds[2][64];  // per flavour and device: dynamic LDS the kernel has been allowed
+static int g_quast_lds[4][64];  // per instantiation (flavour x column blocks) and device: dynamic LDS it has been allowed
 
-// stack, cells: entries of `ebits` bits (frame_words x depth and 3 x cells of them per problem); input: long longs
-extern "C" hipError_t pipk_launch_quast(const QProb *probs, const long long *input, void *stack, void *cells, int *out,
-                                        int nprob, const QCaps *cap, int ebits, hipStream_t stream) {
-  if (nprob <= 0) return hipSuccess;
-  const size_t shm = pipk_quast_lds_bytes(cap, ebits);
-  const int fl = ebits == 128 ? 1 : 0;
-  const void *fn = fl ? (const void *)pip_quast_kernel<w128> : (const void *)pip_quast_kernel<w64>;
+template <class QI, int NB>
+static hipError_t launch_quast(int slot, const QProb *probs, const long long *input, void *stack, void *cells, int *out, int nprob,
+                               const QCaps *cap, size_t shm, hipStream_t stream) {
+  const void *fn = (const void *)pip_quast_kernel<QI, NB>;
   int dev = 0;
   hipError_t e = hipGetDevice(&dev);
   if (e != hipSuccess) return e;
-  if (dev < 0 || dev >= 64 || (size_t)g_quast_lds[fl][dev] < shm) {  // opt in to more dynamic LDS, once per device and size
+  if (dev < 0 || dev >= 64 || (size_t)g_quast_lds[slot][dev] < shm) {  // opt in to more dynamic LDS, once per device and size
     e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
     if (e != hipSuccess) return e;
-    if (dev >= 0 && dev < 64) g_quast_lds[fl][dev] = (int)shm;
+    if (dev >= 0 && dev < 64) g_quast_lds[slot][dev] = (int)shm;
   }
-  if (fl)
-    hipLaunchKernelGGL(pip_quast_kernel<w128>, dim3(nprob), dim3(64), shm, stream, probs, input, (w128 *)stack, (w128 *)cells, out,
-                       nprob, *cap);
-  else
-    hipLaunchKernelGGL(pip_quast_kernel<w64>, dim3(nprob), dim3(64), shm, stream, probs, input, (w64 *)stack, (w64 *)cells, out, nprob,
-                       *cap);
+  hipLaunchKernelGGL((pip_quast_kernel<QI, NB>), dim3(nprob), dim3(64), shm, stream, probs, input, (QI *)stack, (QI *)cells, out,
+                     nprob, *cap);
   return hipGetLastError();
+}
+
+// stack, cells: entries of `ebits` bits (frame_words x depth and 3 x cells of them per problem); input: long longs.  The
+// instantiation follows the launch's width: one column block up to 64 columns, two up to 128.
+extern "C" hipError_t pipk_launch_quast(const QProb *probs, const long long *input, void *stack, void *cells, int *out,
+                                        int nprob, const QCaps *cap, int ebits, hipStream_t stream) {
+  if (nprob <= 0) return hipSuccess;
+  if (cap->W > 128 || cap->CW > 64) return hipErrorInvalidValue;
+  const size_t shm = pipk_quast_lds_bytes(cap, ebits);
+  const bool wide = cap->W > 64;
+  if (ebits == 128)
+    return wide ? launch_quast<w128, 2>(3, probs, input, stack, cells, out, nprob, cap, shm, stream)
+                : launch_quast<w128, 1>(1, probs, input, stack, cells, out, nprob, cap, shm, stream);
+  return wide ? launch_quast<w64, 2>(2, probs, input, stack, cells, out, nprob, cap, shm, stream)
+              : launch_quast<w64, 1>(0, probs, input, stack, cells, out, nprob, cap, shm, stream);
 }
 extern "C" hipError_t pipk_launch_quast_pack(const long long *cells, const long long *off, long long *packed, int nprob,
                                              int cells_cap, int ebits, hipStream_t stream) {

@@ -1877,14 +1877,19 @@ bool quast_caps(const pipamd_problem &p, QCaps &c) {
   const int ncol = p.nvar + p.nparm + 1;
   if (p.nvar < 0 || p.nparm < 0 || p.ni < 0 || p.nc < 0 || (p.ni && !p.ineq) || (p.nc && !p.ctx)) return false;
   if (p.bigparm >= ncol || (p.bigparm >= 0 && p.bigparm <= p.nvar)) return false;
-  // at most 64 columns (a lane per column) and 104 inequalities: up to 128 real rows with the cuts (tab_sort_rows has a
-  // lane per row up to 64 rows and two rows per lane beyond -- not with Compute_dual, whose `pos` table has 64 entries)
-  if (ncol > 64 || p.ni > 104 || p.ni + p.nvar == 0) return false;
+  // at most 128 columns (a lane per column in one block of 64, or two blocks beyond: pip_quast_kernel<E, 2>) and 104
+  // inequalities: up to 128 real rows with the cuts (tab_sort_rows has a lane per row up to 64 rows and two rows per lane
+  // beyond -- not with Compute_dual, whose `pos` table has 64 entries)
+  if (ncol > 128 || p.ni > 104 || p.ni + p.nvar == 0) return false;
   // Room for 10 quotients of parametric cuts, 24 cut rows and 24 nested forks.  (Smaller reserves -- 4 / 8 / 8:
   // 11 KB of LDS instead of 26 KB, twice the problems per CU -- made the launch of 10k problems 27 % shorter,
-  // but every problem that then runs out of room costs the host schedulers milliseconds.)
-  const int newp = p.nparm ? std::min(10, 64 - ncol) : 0;
+  // but every problem that then runs out of room costs the host schedulers milliseconds.)  The spare columns stay
+  // within the problem's block count: a tableau of <= 64 columns never becomes a two-block one.
+  const int blocks = ncol > 64 ? 2 : 1;
+  const int newp = p.nparm ? std::min(10, 64 * blocks - ncol) : 0;
   const int depth = p.nparm ? 24 : 0;
+  // the compa_test sub-problems are as wide as the context and keep one block
+  if (p.nparm + newp + 1 > 64) return false;
   c.W = ncol + newp;
   c.S = p.ni <= 56 ? std::min(64, p.ni + 24) : std::min(128, p.ni + 24);
   c.R = (p.nvar + c.S + 1) & ~1;  // (even: the LDS image and the stack frames are whole 16-byte units in either flavour)
@@ -1896,6 +1901,20 @@ bool quast_caps(const pipamd_problem &p, QCaps &c) {
   c.depth = depth;
   c.cells = 4096;  // SOL_SIZE, type.h:33
   return true;
+}
+// LDS a problem's image may take.  One column block: 96 KB in 64 bits (the tall shapes of up to 128 real rows; the usual
+// ones are a quarter of that); the 128-bit flavour, whose image is twice the size, may have 150 KB.  Two blocks (65 ... 128
+// columns): a workgroup's whole LDS, 160 KB, in either flavour.
+size_t quast_lds_limit(const QCaps &c, int ebits) {
+  if (c.W > 64) return (size_t)160 * 1024;
+  return ebits == 128 ? (size_t)150 * 1024 : (size_t)96 * 1024;
+}
+// The device tree's box: true when a problem of this shape is given to the device-resident traiter() in the flavour of
+// `ebits` (64 or 128) -- capacities in c.  The one decision of device_tree() and pipamd_device_tree_fits.
+bool device_tree_caps(const pipamd_problem &p, int ebits, QCaps &c) {
+  memset(&c, 0, sizeof c);
+  if (!quast_caps(p, c)) return false;
+  return pipk_quast_lds_bytes(&c, ebits) <= quast_lds_limit(c, ebits);
 }
 void quast_caps_max(QCaps &a, const QCaps &b) {
   a.R = std::max(a.R, b.R);
@@ -2006,9 +2025,6 @@ template <class E>
 void device_tree(pipamd_engine *e, int n, const pipamd_problem *probs, int simplify, int deepest_cut, std::vector<FResultT<E>> &res,
                  int *served, int *handed_back, int qflags = 0) {
   constexpr int EBITS = 64 * (int)(sizeof(E) / 8);
-  // LDS a problem's image may take: 96 KB in 64 bits (the tall shapes of up to 128 real rows; the usual ones are a quarter
-  // of that); the 128-bit flavour, whose image is twice the size, may have a CU's worth
-  const size_t lds_limit = EBITS == 128 ? (size_t)150 * 1024 : (size_t)96 * 1024;
   struct Hold {  // the engine's device-tree buffers serve one call at a time
     pthread_mutex_t *m;
     explicit Hold(pthread_mutex_t *mm) : m(mm) { pthread_mutex_lock(m); }
@@ -2034,16 +2050,13 @@ void device_tree(pipamd_engine *e, int n, const pipamd_problem *probs, int simpl
   };
   // Problems of similar size share a launch: every problem of a launch gets the LDS image of the largest, so a
   // batch of tiny problems with one large one among them would run at the large one's occupancy.  Size classes
-  // of 8 KB of LDS, smallest first.
+  // of 8 KB of LDS, smallest first; the one-block shapes before the two-block ones (a launch runs one instantiation).
   std::vector<std::pair<int, int>> order;  // (size class, problem)
   order.reserve(n);
   for (int i = 0; i < n; i++) {
     QCaps c;
-    memset(&c, 0, sizeof c);
-    if (!quast_caps(probs[i], c)) continue;
-    const size_t lds = pipk_quast_lds_bytes(&c, EBITS);
-    if (lds > lds_limit) continue;
-    order.emplace_back((int)(lds / 8192), i);
+    if (!device_tree_caps(probs[i], EBITS, c)) continue;
+    order.emplace_back((c.W > 64 ? 1 << 20 : 0) + (int)(pipk_quast_lds_bytes(&c, EBITS) / 8192), i);
   }
   std::stable_sort(order.begin(), order.end(), [](const std::pair<int, int> &a, const std::pair<int, int> &b) { return a.first < b.first; });
   int cls = -1;
@@ -2058,7 +2071,7 @@ void device_tree(pipamd_engine *e, int n, const pipamd_problem *probs, int simpl
     }
     QCaps m = cap;
     quast_caps_max(m, c);
-    if (pipk_quast_lds_bytes(&m, EBITS) > lds_limit) {  // (the maxima of several shapes of one class together)
+    if (pipk_quast_lds_bytes(&m, EBITS) > quast_lds_limit(m, EBITS)) {  // (the maxima of several shapes of one class together)
       flush();
       m = c;
     }
@@ -2073,6 +2086,13 @@ void device_tree(pipamd_engine *e, int n, const pipamd_problem *probs, int simpl
   flush();
 }
 }  // namespace
+
+extern "C" int pipamd_device_tree_fits(const pipamd_problem *p, int entier_bits) {
+  if (!p || (entier_bits != 64 && entier_bits != 128)) return PIPAMD_E_INVALID;
+  if (p->nvar < 0 || p->nparm < 0 || p->ni < 0 || p->nc < 0 || (p->ni && !p->ineq) || (p->nc && !p->ctx)) return PIPAMD_E_INVALID;
+  QCaps c;
+  return device_tree_caps(*p, entier_bits, c) ? 1 : 0;
+}
 
 template <class E>
 static bool device_tree_one(pipamd_engine *e, const pipamd_problem &p, int simplify, int deepest_cut, int qflags,

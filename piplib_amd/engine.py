@@ -21,7 +21,7 @@ class BatchDesc(C.Structure):
                 ("batch", "nvar", "nparm", "ni", "bigparm", "tflags", "cap_cuts", "cap_newparm", "entier_bits")]
 
 
-ABI_VERSION = 400  # include/piplib_amd.h PIPAMD_VERSION
+ABI_VERSION = 500  # include/piplib_amd.h PIPAMD_VERSION
 _lib = None
 
 
@@ -473,6 +473,17 @@ class PreparedProblems:
             t = tape_text(_take_cells(self.cells[i], self.ncell[i])) if self.rcs[i] == 0 else None
             out.append((t, self.rcs[i], self.sts[i], self.piv[i]))
         return out
+
+
+def device_tree_fits(problem, bits=64):
+    """pipamd_device_tree_fits: 1 if the device-resident traiter() takes a problem of this shape in the `bits` (64 or 128)
+    flavour (it may still hand it back at run time), 0 if the shape goes straight to the host schedulers.  No engine, no GPU."""
+    prep = PreparedProblems([problem])
+    L = lib()
+    L.pipamd_device_tree_fits.argtypes = [C.c_void_p, C.c_int]
+    rc = L.pipamd_device_tree_fits(prep.arr, int(bits))
+    _check(min(rc, 0))
+    return rc
 
 
 def solve_tableaux128(engine, problems, simplify=True, deepest_cut=False, nthreads=8):

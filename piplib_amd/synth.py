@@ -92,3 +92,28 @@ def dense_batch(seed, batch, nvar, ni, cmax=40, x0max=9, pzero=0.3):
     T[:, :, :nvar] = A
     T[:, :, nvar] = slack - np.einsum("bij,bj->bi", A, x0)
     return T
+
+
+def sparse_parametric_problems(seed, count, nvar, nparm, ni, nc, nq, nnz=2, cmax=2, pp=0.3, pmax=2):
+    """Wide, sparse parametric problems, the shape polyhedral callers produce: many unknowns, few parameters.
+
+    The unknowns' part of each problem is lexmin_rows (sparse rows around a hidden integer point, so the problem without
+    parameters is feasible); each parameter coefficient is drawn in [-pmax, pmax] and kept with probability pp.  Context:
+    row i < nparm is p_i >= 0, row i >= nparm is -p_(i mod nparm) + 12 >= 0.  (random_problems is dense: at 64 columns
+    and more nearly all of its problems overflow 64 bits.)"""
+    rng = np.random.default_rng(seed)
+    out = []
+    for _ in range(count):
+        R = lexmin_rows(rng, nvar, ni, nnz=nnz, cmax=cmax)  # unknowns | constant
+        P = rng.integers(-pmax, pmax + 1, size=(ni, nparm)).astype(np.int64)
+        P[rng.random((ni, nparm)) > pp] = 0
+        T = np.concatenate([R, P], axis=1).astype(np.int64)
+        C = np.zeros((nc, nparm + 1), dtype=np.int64)
+        for i in range(nc):
+            if i < nparm:
+                C[i, i] = 1
+            else:
+                C[i, i % nparm] = -1
+                C[i, nparm] = 12
+        out.append(Problem(nvar, nparm, ni, nc, -1, nq, T, C))
+    return out
