@@ -118,7 +118,7 @@ int pipamd_engine_set_tail_waves(pipamd_engine *e, int waves);
  * tail launches instead (a lone 10k batch: 4.7 ms instead of 6.3 ms; 14 batches in flight: 10 % fewer pivots/s). */
 int pipamd_engine_set_lone_batches(pipamd_engine *e, int on);
 /* 128-bit batches without parameters of 129 ... 256 columns (at least 128 tableaux): 1 = the first launch of
- * pipamd_batch_solve is the lean kernel of csrc/pip_lean64.h -- one wave per tableau, rows held as long longs while every
+ * pipamd_batch_solve is pip_lean64_kernel (csrc/pip_lean.h, long long rows) -- one wave per tableau, rows held as long longs while every
  * entry fits 63 bits (half the traffic and registers), tableaux with a wider entry handed over to the 128-bit kernel.
  * Default 0: on BASELINE's configs[4] it is no faster than the four-waves-per-tableau 128-bit kernel. */
 int pipamd_engine_set_lean64(pipamd_engine *e, int on);

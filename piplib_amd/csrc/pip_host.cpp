@@ -384,7 +384,7 @@ struct BatchRun {
     const int KA = !integer ? 0 : (e->round_rows > 0 ? e->round_rows : 48);
     tail_waves = e->waves_per_job ? e->waves_per_job : (e->tail_waves ? e->tail_waves : 4);
     upper = lay.batch;
-    // The 128-bit flavour on rows of 129 ... 256 columns without parameters can start with the lean kernel of pip_lean64.h,
+    // The 128-bit flavour on rows of 129 ... 256 columns without parameters can start with pip_lean64_kernel (pip_lean.h),
     // one wave per tableau over the whole batch: it finishes the tableaux whose stored entries stay below 2^63 (two in
     // three of BASELINE's configs[4]) and leaves the others to the launches below.  Opt-in (pipamd_engine_set_lean64):
     // measured on that batch it is no faster than pip_advance_kernel's four waves per tableau.
@@ -600,7 +600,7 @@ extern "C" int pipamd_debug_lean(pipamd_engine *e, int on) {
   return PIPAMD_OK;
 }
 
-// The lean kernel of the 128-bit flavour (csrc/pip_lean64.h) as the first launch of pipamd_batch_solve on batches it can
+// The lean kernel of the 128-bit flavour (pip_lean64_kernel, csrc/pip_lean.h) as the first launch of pipamd_batch_solve on batches it can
 // take (no parameters, 129 ... 256 columns, at least 128 tableaux); default off.
 extern "C" int pipamd_engine_set_lean64(pipamd_engine *e, int on) {
   if (!e) return PIPAMD_E_INVALID;

@@ -20,7 +20,7 @@ struct pipamd_engine {
   int single_launch; /* debug: stop after one launch */
   int lone_batches;  /* 1: no general one-wave launch between the lean launch and the tail (pipamd_engine_set_lone_batches) */
   int no_lean;       /* 1: bulk launches without the lean kernel (pip_lean.h) */
-  int lean64;        /* 1: 128-bit batches of 129 ... 256 columns start with the lean kernel of pip_lean64.h (pipamd_engine_set_lean64) */
+  int lean64;        /* 1: 128-bit batches of 129 ... 256 columns start with pip_lean64_kernel (pip_lean.h; pipamd_engine_set_lean64) */
   int no_lean2;      /* 1: the second one-wave bulk launch is the general kernel even where the lean kernel could resume */
   int *h_run;        /* pinned: {jobs still running, their largest row count | PIPAMD_Q_CAPFLAG, how many of them are out of rows} */
   int *d_q;          /* launch-list control words (a pool, see pipamd_batch_solve) and the two job lists */

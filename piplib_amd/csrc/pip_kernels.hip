@@ -5,7 +5,6 @@
 // holds the determinant replay, the batch load / results / counters kernels, expanser for the batch layer, the
 // helpers of the lock-step scheduler and every launcher.
 #include "pip_lean.h"
-#include "pip_lean64.h"
 
 // the instantiations of the pivot kernel's launcher live in pip_adv_*.hip
 #define PIP_ADV_EXTERN(...) extern template hipError_t launch_advance_t<__VA_ARGS__>(const AdvanceLaunch &);
@@ -582,6 +581,42 @@ extern "C" int pipk_lean_class(int smax) {
   const int s = (smax + 3) & ~3;
   return s <= 64 ? 64 : (s <= 96 ? 96 : (s <= 112 ? 112 : (s <= 128 ? 128 : (s <= 160 ? 160 : 0))));
 }
+// the lean kernel of the 128-bit flavour: pip_lean.h's loop on long long rows, row capacity at run time
+__global__ __launch_bounds__(64, PIP_LEAN64_WAVES) void pip_lean64_kernel(PipJob *jobs, i64 *arena, int njobs, int Smax, int Lmax,
+                                                                          int iter_limit, PipQueue q PIP_LEAN_PROF_PARAM) {
+  typedef LeanLongRows F;
+  constexpr bool FULL = false;
+#define PIP_LEAN_LOOP
+#include "pip_lean.h"
+#undef PIP_LEAN_LOOP
+}
+// the launch of pip_lean64_kernel: a.Smax / a.Lmax = the row capacity of the LDS image (the caller sizes it with
+// lean64_lds_bytes); an image above 48 KB needs the dynamic-LDS limit raised, once per device
+static hipError_t launch_lean64(const AdvanceLaunch &a) {
+  const int grid = a.grid > 0 && a.grid < a.njobs ? a.grid : a.njobs;
+  const size_t shm = lean64_lds_bytes(a.Smax, a.Lmax);
+  const void *fn = (const void *)pip_lean64_kernel;
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return e;
+  if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
+  if (shm > 48 * 1024) {
+    static std::atomic<unsigned long long> raised{0};
+    if (!((raised.load(std::memory_order_acquire) >> dev) & 1)) {
+      e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, PIPAMD_LDS_BUDGET);
+      if (e != hipSuccess) return e;
+      raised.fetch_or(1ull << dev, std::memory_order_release);
+    }
+  }
+#ifdef PIP_PROFILE
+  hipLaunchKernelGGL(pip_lean64_kernel, dim3(grid), dim3(64), shm, a.stream, a.jobs, a.arena, a.njobs, a.Smax, a.Lmax, a.iter_limit,
+                     a.q, (u64 *)a.prof);
+#else
+  hipLaunchKernelGGL(pip_lean64_kernel, dim3(grid), dim3(64), shm, a.stream, a.jobs, a.arena, a.njobs, a.Smax, a.Lmax, a.iter_limit,
+                     a.q);
+#endif
+  return hipGetLastError();
+}
 extern "C" size_t pipk_lean64_lds_bytes(int Smax, int Lmax) { return lean64_lds_bytes((Smax + 3) & ~3, (Lmax + 3) & ~3); }
 // the lean bulk kernel over a launch list; the caller has checked pipk_lean_class(a.Smax) != 0
 static hipError_t launch_lean_class(AdvanceLaunch a) {
@@ -648,7 +683,7 @@ static hipError_t launch_by_shape(const AdvanceLaunch &a, bool one, int wp, int 
 // can (no parameters, entries below 2^15) and leaves the others PIPAMD_ST_RUN on the output list for a launch without
 // this bit.  Bit 2: no determinant replay behind the launch (see pipk_launch_replay_all).  Bit 3 (one wave per job, 128-bit
 // entries, 129 ... 256 columns, pipk_lean64_lds_bytes(Smax, Lmax) within the LDS budget, else refused) = the lean kernel of
-// pip_lean64.h: it runs the jobs it can (no parameters, entries below 2^63) and leaves the others on the output list.
+// pip_lean.h on long long rows: it runs the jobs it can (no parameters, entries below 2^63) and leaves the others on the output list.
 extern "C" hipError_t pipk_launch_advance_q(PipJob *jobs, i64 *arena, int njobs, int Lmax, int Smax, int Wmax,
                                             int iter_limit, int waves_per_job, int ebits, void *const *q5, int grid,
                                             void **big, int hints, unsigned long long *prof, hipStream_t stream) {
@@ -713,7 +748,7 @@ extern "C" hipError_t pipk_launch_advance_q(PipJob *jobs, i64 *arena, int njobs,
   if (hints & 2) {
     if (!one || ebits != 64 || wp != 128 || a.gimg || !pipk_lean_class(a.Smax)) return hipErrorInvalidValue;
     le = launch_lean_class(a);
-  } else if (hints & 8) {  // the lean kernel of the 128-bit flavour (pip_lean64.h): 129 ... 256 columns, one wave per job
+  } else if (hints & 8) {  // the lean kernel of the 128-bit flavour (pip_lean.h on long long rows): 129 ... 256 columns, one wave per job
     if (!one || ebits != 128 || wp != 256 || pipk_lean64_lds_bytes(a.Smax, a.Lmax) > PIPAMD_LDS_BUDGET) return hipErrorInvalidValue;
     le = launch_lean64(a);
   } else {

@@ -1,170 +1,421 @@
-// piplib_amd/csrc/pip_lean.h -- the lean bulk kernel: pip_advance_kernel's pivot loop specialised for the regime the
-// headline workload lives in.
+// piplib_amd/csrc/pip_lean.h -- the lean bulk kernels: pip_advance_kernel's pivot loop specialised for the regimes the
+// batches live in, written once (the text under PIP_LEAN_LOOP at the end of this file) against a "row flavour", compiled
+// for the two flavours below.
 //
-// One wave per tableau, at most 127 unknowns + constant in rows of W <= 128 columns (FULL: exactly 127 + 1, compile-time
-// column counts), no parameters, no big parameter, 64-bit Entier, compile-time row capacity SC, rows skipped, plain
-// cuts -- and EVERY entry of EVERY row below 2^31 in magnitude, i.e. an int.  Under that invariant
-//   * rows live in HBM as int32 (4 W bytes per row, in the first half of the row's slot of W long longs): half the
-//     traffic of the reference's long long rows, half the working set; a row is two 32-bit registers per lane;
-//   * while the rows involved are in magnitude class 0 (entries below 2^15; pivot row's denominator too) every product of
-//     a pivot fits 31 bits: the elimination is 24-bit multiplies, the row gcd float-reciprocal remainders, the exact
-//     division, the summaries, choisir_piv's cross products (24-bit) and the cuts 32-bit arithmetic (the "small" path,
-//     96 % of the headline's pivots);
-//   * a row of class 1 (an entry between 2^15 and 2^31), or a pivot row of class 1, takes the "mid" path (round 4): the same
-//     int rows, products in 64-bit registers (v_mad_i64_i32; below 2^62 each, so nothing wraps), the row gcd and the
-//     division through row_reduce<i64> -- the code pip_advance_kernel runs on such a row, on the same values -- and
-//     choisir_piv's cross products in 64 bits.  The result is an int row again, almost always;
+// A lean kernel is one wave per tableau, no parameters, no big parameter, rows skipped, plain cuts -- and EVERY entry of
+// EVERY row stored at HALF the width of the flavour's Entier T (the packed element E).  Under that invariant
+//   * rows live in HBM packed (the first half of the row's slot of W entries of T): half the traffic of the reference's
+//     rows, half the working set, half the registers;
+//   * while the rows involved are in magnitude class 0 (entries below 2^CLS0_BITS; pivot row's denominator too) every
+//     product of a pivot fits E: the "small" path;
+//   * a row of class 1 (an entry beyond that, still an E), or a pivot row of class 1, takes the "mid" path: the same
+//     packed rows, products in T (nothing wraps), the row gcd and the division through row_reduce<T> -- the code
+//     pip_advance_kernel runs on such a row, on the same values -- and choisir_piv's cross products in T.  The result
+//     is a packed row again, almost always;
 //   * none of the general kernel's other paths (wide tournament, parameters, deepest cuts, row tables in HBM) is
-//     compiled in, the pivot row stays in registers, the LDS image is smaller (lean_lds_bytes): 64 VGPRs, no
-//     scratch, eight waves per SIMD.
-// A rewritten row that does NOT fit ints any more is stored in the general format (W long longs, the whole slot) and
+//     compiled in, the pivot row stays in registers, the LDS image is smaller (lean_image_bytes).
+// A rewritten row that does NOT fit E any more is stored in the general format (W entries of T, the whole slot) and
 // summarised with pip_advance_kernel's magnitude classes (2, 3); the pivot is finished -- no row is read twice in a pivot
 // -- and the running maximum of the classes, checked between pivots, then ends the lean run.  A tableau that leaves --
-// or anything else this kernel does not do: entries beyond ints at entry, a cut under a denominator of 2^31 or more,
-// PIPAMD_T_NOSKIP / _DEEPEST, a paused job -- is handed over in the general format (int rows widened to int64 in
-// place, the same row tables and saved summaries as a paused job of pip_advance_kernel) and stays PIPAMD_ST_RUN on the
-// launch list: pipamd_batch_solve's next launches (pip_advance_kernel) take it from there.  Same algorithm, same
-// statuses, same bits as pip_advance_kernel -- the reference's traiter()/pivoter()/choisir_piv()/exam_coef()/integrer()/tab_sort_rows
-// (traiter.c:101-159, 297-548, 556-623, 628-791; integrer.c:305-486) -- which the parity tests check tableau by tableau
-// (tests/test_gpu_parity.py: test_lean_kernel_paths, test_lean_kernel_other_widths, and every batch test of the suite).
-#ifndef PIP_LEAN_H
+// or anything else these kernels do not do: entries beyond E at entry, a cut under too large a denominator,
+// PIPAMD_T_NOSKIP / _DEEPEST, a paused job -- is handed over in the general format (packed rows widened in place, the
+// same row tables and saved summaries as a paused job of pip_advance_kernel) and stays PIPAMD_ST_RUN on the launch
+// list: pipamd_batch_solve's next launches (pip_advance_kernel) take it from there.  Same algorithm, same statuses,
+// same bits as pip_advance_kernel -- the reference's traiter()/pivoter()/choisir_piv()/exam_coef()/integrer()/tab_sort_rows
+// (traiter.c:101-159, 297-548, 556-623, 628-791; integrer.c:305-486) -- which the parity tests check tableau by tableau.
+//
+// LeanIntRows, pip_lean_kernel<SC, FULL>: the regime the headline workload lives in.  64-bit Entier, int rows, at most
+//   127 unknowns + constant in rows of W <= 128 columns (FULL: exactly 127 + 1, compile-time column counts),
+//   compile-time row capacity SC.  A row is two 32-bit registers per lane (columns 2l, 2l + 1).  Small path (96 % of the
+//   headline's pivots): 24-bit multiplies, the row gcd by float-reciprocal remainders, 32-bit summaries and cuts; mid
+//   path (round 4): v_mad_i64_i32 products below 2^62.  64 VGPRs, no scratch, eight waves per SIMD.
+//   (tests/test_gpu_parity.py: test_lean_kernel_paths, test_lean_kernel_other_widths, and every batch test of the suite.)
+// LeanLongRows, pip_lean64_kernel: the same one width up.  128-bit Entier, long long rows, 129 ... 256 columns, run-time
+//   row capacity; lane l holds columns l, 64 + l, 128 + l, 192 + l (the geometry of pip_advance_kernel<__int128, 4>, so
+//   that the saved summaries of a paused job mean the same to both kernels).  The overflow-safe flavour (piplib.h:42-88)
+//   exists for the tableaux on which 64-bit arithmetic overflows -- but what outgrows 64 bits there are the determinant
+//   limbs and the products of a row update, seldom the rows themselves: of the 1,000 tableaux of BASELINE's configs[4]
+//   (the batch pinned by tests/golden/gmp/wide128.json) the reference's GMP build forms a value beyond 2^63 on 587, yet on
+//   two in three every STORED entry stays below 2^63 from the first pivot to the last (657 of the 1,000 finish in this
+//   kernel, 325 leave on a row beyond 2^63).  Small path: 64-bit arithmetic; mid path: 64 x 64 -> 128-bit products (four
+//   32-bit multiply-adds each, not ten), reduce_by_inverse picks the narrowest width that holds them.  OPT-IN
+//   (pipamd_engine_set_lean64): measured on that batch it is no faster than the four-wave pip_advance_kernel<__int128>
+//   (16 registers a row, 128 VGPRs, 400 bytes of scratch per lane, three waves in four waiting during choisir_piv),
+//   DESIGN.md section 3.  (tests/test_gpu_parity.py: test_lean64_kernel_paths, test_full_size_int128_config, against the
+//   128-bit oracle and the reference's GMP build.)
+#if !defined(PIP_LEAN_LOOP) && !defined(PIP_LEAN_H)
 #define PIP_LEAN_H
 #include "pip_advance.h"
 
 #ifndef PIP_LEAN_PF
-#define PIP_LEAN_PF 2  // rows of a pivot's work list in flight
+#define PIP_LEAN_PF 2  // int rows of a pivot's work list in flight
 #endif
 #ifndef PIP_LEAN_MID_INV
-#define PIP_LEAN_MID_INV 0  // (A/B switch) the mid path's row gcd and division by inverse multiplication (12 bytes of scratch per lane)
+#define PIP_LEAN_MID_INV 0  // (A/B switch) the int mid path's row gcd and division by inverse multiplication (12 bytes of scratch per lane)
 #endif
 #ifndef PIP_LEAN_WAVES
-#define PIP_LEAN_WAVES 8  // waves per SIMD the kernel is bounded to (64 VGPRs)
+#define PIP_LEAN_WAVES 8  // waves per SIMD pip_lean_kernel is bounded to (64 VGPRs)
+#endif
+#ifndef PIP_LEAN64_WAVES
+#define PIP_LEAN64_WAVES 3  // waves per SIMD pip_lean64_kernel is bounded to (168 VGPRs)
 #endif
 
-// a packed row: lane l holds columns 2l, 2l+1 as ints, 8 bytes per lane
-// (W: the columns of a row, even and <= 128; lanes beyond them hold zeros)
-__device__ __forceinline__ void row_load32p(RowRegs32<1> &r, const i64 *slot, int lane, int W = 128) {
-  int2 t = {0, 0};
-  if (2 * lane < W) t = *reinterpret_cast<const int2 *>(reinterpret_cast<const int *>(slot) + 2 * lane);
-  r.v[0][0] = t.x;
-  r.v[0][1] = t.y;
-}
-__device__ __forceinline__ void row_store32p(const RowRegs32<1> &r, i64 *slot, int lane, int W = 128) {
-  int2 t;
-  t.x = r.v[0][0];
-  t.y = r.v[0][1];
-  if (2 * lane < W) *reinterpret_cast<int2 *>(reinterpret_cast<int *>(slot) + 2 * lane) = t;
-}
+// a packed row in registers: lane l's NV values (which columns: the flavour's col())
+template <class E, int NV>
+struct LeanRow {
+  E v[NV];
+};
 
-// a row that no longer fits ints: the general format, the whole slot
-__device__ __forceinline__ void row_store64w(const i64 (&z)[2], i64 *slot, int lane, int W = 128) {
-  longlong2 t;
-  t.x = z[0];
-  t.y = z[1];
-  if (2 * lane < W) *reinterpret_cast<longlong2 *>(slot + 2 * lane) = t;
+// ---- the row flavours: what the two kernels disagree on.  T the Entier (general entry, product type), E the packed
+// element, NV values per lane = NM bitmap words per row, NCH pip_advance_kernel's column blocks of the same width (the
+// state_nch of a paused job), WP the padded row width; entries of class 0 are below 2^CLS0_BITS, a packed row's below
+// 2^ROW_BITS, a cut is taken under a denominator below 2^CUT_BITS.
+struct LeanIntRows {
+  typedef i64 T;
+  typedef int E;
+  typedef LeanRow<int, 2> Row;
+  static constexpr int NV = 2, NM = 2, NCH = 1, WP = 128, CLS0_BITS = 15, ROW_BITS = 31, CUT_BITS = 31;
+  static constexpr int ENTRY_PF = 4, PF = PIP_LEAN_PF, UNPACK_GROUP = 4;  // rows in flight: entry pass, work list, rows_unpack
+  static constexpr bool FRESH = true;  // the entry pass may read the caller's rows (PIPAMD_T_FRESHROWS)
+  static __device__ __forceinline__ int col(int lane, int h) { return 2 * lane + h; }
+  static __device__ __forceinline__ int lane_of(int j) { return j >> 1; }
+  static __device__ __forceinline__ int val_of(int j) { return j & 1; }
+  static __device__ __forceinline__ bool shape(const PipJob *J, int nvar, int W) {  // the jobs this flavour takes
+    return J->nvar == nvar && nvar < 128 && J->nparm == 0 && J->bigparm < 0 && J->W == W && W <= 128 && !(W & 1) && J->ebits != 128;
+  }
+  static __device__ __forceinline__ unsigned mag(int v) { return (unsigned)(v < 0 ? -v : v); }
+  static __device__ __forceinline__ bool fits(i64 x) { return x > -((i64)1 << 31) && x < ((i64)1 << 31); }
+  static __device__ __forceinline__ unsigned gcd(int a, int b) { return gcd_u32((unsigned)a, mag(b)); }
+  // lane l holds columns 2l, 2l + 1, 8 bytes per lane (W even; lanes beyond the row hold zeros)
+  static __device__ __forceinline__ void load(Row &r, const i64 *slot, int lane, int W) {
+    int2 t = {0, 0};
+    if (2 * lane < W) t = *reinterpret_cast<const int2 *>(reinterpret_cast<const int *>(slot) + 2 * lane);
+    r.v[0] = t.x;
+    r.v[1] = t.y;
+  }
+  static __device__ __forceinline__ void store(const Row &r, i64 *slot, int lane, int W) {
+    int2 t;
+    t.x = r.v[0];
+    t.y = r.v[1];
+    if (2 * lane < W) *reinterpret_cast<int2 *>(reinterpret_cast<int *>(slot) + 2 * lane) = t;
+  }
+  static __device__ __forceinline__ void store_wide(const i64 (&z)[2], i64 *slot, int lane, int W) {
+    longlong2 t;
+    t.x = z[0];
+    t.y = z[1];
+    if (2 * lane < W) *reinterpret_cast<longlong2 *>(slot + 2 * lane) = t;
+  }
+  // choisir_piv's cross product ab * n - nb * a: 24-bit multiplies while every row is in class 0, else below 2^62
+  template <bool SMALL>
+  static __device__ __forceinline__ void cross(int ab, int n, int nb, int a, bool &xneg, bool &xzero) {
+    if constexpr (SMALL) {
+      const int x = __mul24(ab, n) - __mul24(nb, a);
+      xneg = x < 0;
+      xzero = x == 0;
+    } else {
+      const i64 x = (i64)ab * (i64)n - (i64)nb * (i64)a;
+      xneg = x < 0;
+      xzero = x == 0;
+    }
+  }
+  // piplib_llmod (integrer.c:69-74): r's entries -> their remainders in [0, D); through a float reciprocal when the row is
+  // in class 0 and D < 2^15
+  static __device__ __forceinline__ void row_mod(Row &r, int D, bool cls0) {
+    const bool tinyD = D < (1 << 15) && cls0;
+    const float rD = __builtin_amdgcn_rcpf((float)D);
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+      const int v = r.v[h];
+      if (tinyD) {
+        const unsigned m = umod_tiny(mag(v), (unsigned)D, rD);
+        r.v[h] = v < 0 ? (m ? D - (int)m : 0) : (int)m;
+      } else {
+        const int m = v % D;
+        r.v[h] = m < 0 ? m + D : m;
+      }
+    }
+  }
+  static __device__ __forceinline__ bool small_den(i64) { return true; }
+  // small path: every operand below 2^15, every product below 2^30.  r <- (lp r - foo pr) / gcd, nd the new denominator
+  static __device__ __forceinline__ bool update_small(Row &r, const Row &pr, int lp, int foo, i64 dpiv, int pivj, i64 g0, int lane,
+                                                      i64 &nd) {
+    int z[1][2];
+    unsigned mx = 0;
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+      int v = __mul24(r.v[h], lp) - __mul24(pr.v[h], foo);
+      if (2 * lane + h == pivj) v = __mul24((int)dpiv, foo);
+      z[0][h] = v;
+      mx |= mag(v);
+    }
+    const bool ok = small_reduce<1>(z, mx, g0, lane, nd);
+    r.v[0] = z[0][0];
+    r.v[1] = z[0][1];
+    return ok;
+  }
+  // mid path: int operands, products below 2^62 in long longs -- pip_advance_kernel's update_row on the same values (its
+  // wrap-around arithmetic has nothing to wrap here, except dpiv * foo under a denominator beyond ints, which wraps the
+  // same way)
+  static __device__ __forceinline__ bool update_mid(i64 (&zw)[2], const Row &r, const Row &pr, int lp, int foo, i64 dpiv, int pivj,
+                                                    i64 g0, int lane, i64 &nd) {
+    u64 mx = 0;
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+      i64 v = (i64)r.v[h] * (i64)lp - (i64)pr.v[h] * (i64)foo;
+      if (2 * lane + h == pivj) v = wmul(dpiv, (i64)foo);
+      zw[h] = v;
+      mx |= uabs64(v);
+    }
+#if PIP_LEAN_MID_INV
+    return row_reduce<i64, 2, false>(zw, mx, g0, lane, nd, wmul(dpiv, (i64)foo));
+#else
+    return row_reduce_rem<i64, 2>(zw, mx, g0, lane, nd);  // (the remainder loop: reduce_by_inverse costs this kernel 12 bytes of scratch)
+#endif
+  }
+};
+
+struct LeanLongRows {
+  typedef i128 T;
+  typedef i64 E;
+  typedef LeanRow<i64, 4> Row;
+  static constexpr int NV = 4, NM = 4, NCH = 4, WP = 256, CLS0_BITS = 31, ROW_BITS = 63, CUT_BITS = 62;
+  static constexpr int ENTRY_PF = 1, PF = 2, UNPACK_GROUP = 2;
+  static constexpr bool FRESH = false;
+  static __device__ __forceinline__ int col(int lane, int c) { return 64 * c + lane; }
+  static __device__ __forceinline__ int lane_of(int j) { return j & 63; }
+  static __device__ __forceinline__ int val_of(int j) { return j >> 6; }
+  static __device__ __forceinline__ bool shape(const PipJob *J, int nvar, int W) {
+    return nvar < 256 && nvar >= 1 && J->nparm == 0 && J->bigparm < 0 && W > 128 && W <= 256 && J->ebits == 128;
+  }
+  static __device__ __forceinline__ u64 mag(i64 v) { return uabs64(v); }
+  static __device__ __forceinline__ bool fits(i128 x) { return fits64(x); }
+  static __device__ __forceinline__ u64 gcd(i64 a, i64 b) { return gcd_mag((u64)a, uabs64(b)); }
+  static __device__ __forceinline__ void load(Row &r, const i128 *slot, int lane, int W) {
+    const i64 *p = reinterpret_cast<const i64 *>(slot);
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+      const int j = 64 * c + lane;
+      r.v[c] = j < W ? p[j] : 0;
+    }
+  }
+  static __device__ __forceinline__ void store(const Row &r, i128 *slot, int lane, int W) {
+    i64 *p = reinterpret_cast<i64 *>(slot);
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+      const int j = 64 * c + lane;
+      if (j < W) p[j] = r.v[c];
+    }
+  }
+  static __device__ __forceinline__ void store_wide(const i128 (&z)[4], i128 *slot, int lane, int W) {
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+      const int j = 64 * c + lane;
+      if (j < W) {
+        longlong2 t;
+        t.x = (i64)(u64)(u128)z[c];
+        t.y = (i64)(u64)((u128)z[c] >> 64);
+        *reinterpret_cast<longlong2 *>(slot + j) = t;
+      }
+    }
+  }
+  // 64-bit while every row is in class 0 (entries below 2^31), else below 2^126
+  template <bool SMALL>
+  static __device__ __forceinline__ void cross(i64 ab, i64 n, i64 nb, i64 a, bool &xneg, bool &xzero) {
+    if constexpr (SMALL) {
+      const i64 x = ab * n - nb * a;
+      xneg = x < 0;
+      xzero = x == 0;
+    } else {
+      const i128 x = (i128)ab * (i128)n - (i128)nb * (i128)a;
+      xneg = x < 0;
+      xzero = x == 0;
+    }
+  }
+  static __device__ __forceinline__ void row_mod(Row &r, i64 D, bool) {
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+      const i64 m = crem(r.v[c], D);
+      r.v[c] = m < 0 ? m + D : m;
+    }
+  }
+  static __device__ __forceinline__ bool small_den(i128 g0) { return g0 < ((i128)1 << 62) && g0 > -((i128)1 << 62); }
+  // small path: every operand below 2^31, every product below 2^62; the denominator product a long long (small_den)
+  static __device__ __forceinline__ bool update_small(Row &r, const Row &pr, i64 lp, i64 foo, i128 dpiv, int pivj, i128 g0, int lane,
+                                                      i128 &nd) {
+    u64 mx = 0;
+    const i64 zf = (i64)dpiv * foo;
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+      i64 v = r.v[c] * lp - pr.v[c] * foo;
+      if (64 * c + lane == pivj) v = zf;
+      r.v[c] = v;
+      mx |= uabs64(v);
+    }
+    i64 nd64;
+    const bool ok = row_reduce<i64, 4>(r.v, mx, (i64)g0, lane, nd64, zf);
+    nd = (i128)nd64;
+    return ok;
+  }
+  // mid path: long long operands, products below 2^126 -- pip_advance_kernel's update_row on the same values (its
+  // wrap-around arithmetic has nothing to wrap here, except the products with denominators beyond long longs, which wrap
+  // the same way)
+  static __device__ __forceinline__ bool update_mid(i128 (&zw)[4], const Row &r, const Row &pr, i64 lp, i64 foo, i128 dpiv, int pivj,
+                                                    i128 g0, int lane, i128 &nd) {
+    u128 mx = 0;
+    const i128 zf = wmul(dpiv, (i128)foo);
+#pragma unroll
+    for (int c = 0; c < 4; c++) {
+      i128 v = (i128)r.v[c] * (i128)lp - (i128)pr.v[c] * (i128)foo;
+      if (64 * c + lane == pivj) v = zf;
+      zw[c] = v;
+      mx |= uabs64(v);
+    }
+    return row_reduce<i128, 4>(zw, mx, g0, lane, nd, zf);
+  }
+};
+
+// bytes of a lean kernel's LDS image for S row slots and L logical rows (smaller than pip_advance_kernel's: no pivot
+// row, constant terms as packed elements)
+template <class F>
+__host__ __device__ constexpr size_t lean_image_bytes(int S, int L) {
+  return ((sizeof(typename F::T) + sizeof(typename F::E) + 8 * F::NM + 9) * (size_t)S + 2 * (size_t)L + 2 * F::WP + 15) & ~(size_t)15;
+}
+__host__ __device__ constexpr size_t lean_lds_bytes(int SC) { return lean_image_bytes<LeanIntRows>(SC, SC + 128); }
+__host__ __device__ constexpr size_t lean64_lds_bytes(int S, int L) { return lean_image_bytes<LeanLongRows>(S, L); }
+
+// value k (uniform) of a row, read from lane src
+template <class F, class X>
+__device__ __forceinline__ X lean_entry(const X (&v)[F::NV], int k, int src) {
+  X mine = 0;
+#pragma unroll
+  for (int h = 0; h < F::NV; h++)
+    if (h == k) mine = v[h];
+  if constexpr (sizeof(X) == 4)
+    return __builtin_amdgcn_readlane(mine, src);
+  else
+    return readlane64(mine, src);
 }
 
 // rows [0, n) of a block, packed -> the general format, each within its own slot (the loads of a group of rows are back
 // before their slots are overwritten); rows of class 2 or 3 (rcls, LDS) are in the general format already
-__device__ __forceinline__ void rows_unpack(i64 *vals, int n, int lane, int W, const u8 *rcls) {
-  for (int s0 = 0; s0 < n; s0 += 4) {
-    RowRegs32<1> rr[4];
-    bool packed[4];
+template <class F>
+__device__ __forceinline__ void rows_unpack(typename F::T *vals, int n, int lane, int W, const u8 *rcls) {
+  constexpr int G = F::UNPACK_GROUP;
+  for (int s0 = 0; s0 < n; s0 += G) {
+    typename F::Row rr[G];
+    bool packed[G];
 #pragma unroll
-    for (int qq = 0; qq < 4; qq++) {
+    for (int qq = 0; qq < G; qq++) {
       packed[qq] = s0 + qq < n && rcls[s0 + qq] < 2;
-      if (packed[qq]) row_load32p(rr[qq], vals + (size_t)(s0 + qq) * W, lane, W);
+      if (packed[qq]) F::load(rr[qq], vals + (size_t)(s0 + qq) * W, lane, W);
     }
 #pragma unroll
-    for (int qq = 0; qq < 4; qq++)
-      if (packed[qq] && 2 * lane < W) {
-        longlong2 t;
-        t.x = (i64)rr[qq].v[0][0];
-        t.y = (i64)rr[qq].v[0][1];
-        *reinterpret_cast<longlong2 *>(vals + (size_t)(s0 + qq) * W + 2 * lane) = t;
+    for (int qq = 0; qq < G; qq++)
+      if (packed[qq]) {
+        typename F::T z[F::NV];
+#pragma unroll
+        for (int h = 0; h < F::NV; h++) z[h] = (typename F::T)rr[qq].v[h];
+        F::store_wide(z, vals + (size_t)(s0 + qq) * W, lane, W);
       }
   }
 }
 
-// row_publish32<1> for this kernel's LDS image (constant terms kept as ints): sign summary, non-zero bitmap and
-// magnitude class of a row of nvar unknowns + constant; returns the class (0: every entry below 2^15)
-__device__ __forceinline__ int lean_publish(const RowRegs32<1> &z, const Shared<i64> &S, int *cst, int s, int pivj, int extra_sig,
-                                            int lane, int nvar = 127) {
-  const int cz = row_entry32<1>(z, 0, nvar & 1, nvar >> 1);  // the constant term, column nvar
+// sign summary, non-zero bitmap and magnitude class (0: every entry below 2^CLS0_BITS, 1: a packed row) of a packed
+// row of nvar unknowns + constant; lane 0 publishes them for slot s (row_publish32 for this image: constant terms kept
+// as packed elements).  Returns the class.
+template <class F>
+__device__ __forceinline__ int lean_publish(const typename F::Row &z, const Shared<typename F::T> &S, typename F::E *cst, int s, int pivj,
+                                            int extra_sig, int lane, int nvar) {
+  typedef typename F::E E;
+  const E cz = lean_entry<F>(z.v, F::val_of(nvar), F::lane_of(nvar));  // the constant term, column nvar
   int sig = extra_sig | (cz > 0 ? 1 : (cz < 0 ? 2 : 0));
   if (pivj >= 0) {
-    const int pz = row_entry32<1>(z, 0, pivj & 1, pivj >> 1);
+    const E pz = lean_entry<F>(z.v, F::val_of(pivj), F::lane_of(pivj));
     sig |= (pz > 0 ? 1 : (pz < 0 ? 2 : 0)) << 6;
   }
-  const int v0 = z.v[0][0], v1 = z.v[0][1];
-  const unsigned mx = (unsigned)(v0 < 0 ? -v0 : v0) | (unsigned)(v1 < 0 ? -v1 : v1);
-  const u64 nz0 = ballot64(v0 != 0), nz1 = ballot64(v1 != 0);
-  const int cls = ballot64((mx >> 15) != 0) ? 1 : 0;
+  decltype(F::mag(cz)) mx = 0;
+  u64 nz[F::NV];
+#pragma unroll
+  for (int h = 0; h < F::NV; h++) {
+    mx |= F::mag(z.v[h]);
+    nz[h] = ballot64(z.v[h] != 0);
+  }
+  const int cls = ballot64((mx >> F::CLS0_BITS) != 0) ? 1 : 0;
   if (lane == 0) {
     S.sig[s] = (u16)sig;
     S.rcls[s] = (u8)cls;
     cst[s] = cz;
-    S.nzm[(size_t)s * 2] = nz0;
-    S.nzm[(size_t)s * 2 + 1] = nz1;
+#pragma unroll
+    for (int h = 0; h < F::NV; h++) S.nzm[(size_t)s * F::NM + h] = nz[h];
   }
   return cls;
 }
 
-// the same for a row that left the ints (z: lane l's columns 2l, 2l+1 as long longs): pip_advance_kernel's classes
-// (2: below 2^47, 3: beyond; 1 only for an entry of exactly -2^31...); the constant term kept here is truncated -- the
-// lean run ends before anything reads it
-__device__ __forceinline__ int lean_publish_wide(const i64 (&z)[2], const Shared<i64> &S, int *cst, int s, int pivj, int extra_sig,
-                                                 int lane, int nvar = 127) {
-  const i64 cz = readlane64((nvar & 1) ? z[1] : z[0], nvar >> 1);
+// the same for a row that left the packed elements (z: lane l's values as T): pip_advance_kernel's classes (2, 3); the
+// constant term kept here is truncated -- the lean run ends before anything reads it
+template <class F>
+__device__ __forceinline__ int lean_publish_wide(const typename F::T (&z)[F::NV], const Shared<typename F::T> &S, typename F::E *cst,
+                                                 int s, int pivj, int extra_sig, int lane, int nvar) {
+  typedef typename F::T T;
+  const T cz = lean_entry<F>(z, F::val_of(nvar), F::lane_of(nvar));
   int sig = extra_sig | sign_code(cz);
-  if (pivj >= 0) sig |= sign_code(readlane64((pivj & 1) ? z[1] : z[0], pivj >> 1)) << 6;
-  const u64 nz0 = ballot64(z[0] != 0), nz1 = ballot64(z[1] != 0);
-  int cls = cls_of<i64>(uabs64(z[0]) | uabs64(z[1]));
-  if (cls < 2) cls = 2;  // (it does not fit an int: at least 2^31)
+  if (pivj >= 0) sig |= sign_code(lean_entry<F>(z, F::val_of(pivj), F::lane_of(pivj))) << 6;
+  typename ET<T>::U mx = 0;
+  u64 nz[F::NV];
+#pragma unroll
+  for (int h = 0; h < F::NV; h++) {
+    mx |= uabs64(z[h]);
+    nz[h] = ballot64(z[h] != 0);
+  }
+  int cls = cls_of<T>(mx);
+  if (cls < 2) cls = 2;  // (it does not fit E: at least 2^ROW_BITS)
   if (lane == 0) {
     S.sig[s] = (u16)sig;
     S.rcls[s] = (u8)cls;
-    cst[s] = (int)cz;
-    S.nzm[(size_t)s * 2] = nz0;
-    S.nzm[(size_t)s * 2 + 1] = nz1;
+    cst[s] = (typename F::E)cz;
+#pragma unroll
+    for (int h = 0; h < F::NV; h++) S.nzm[(size_t)s * F::NM + h] = nz[h];
   }
   return cls;
 }
 
-// bytes of this kernel's LDS image for SC row slots (smaller than pip_advance_kernel's: no pivot row, int constants)
-__host__ __device__ constexpr size_t lean_lds_bytes(int SC) { return ((size_t)39 * SC + 2 * 128 + 2 * 128 + 15) & ~(size_t)15; }
-
-// choisir_piv (traiter.c:297-341) as choose_column<i64, 1, SMALL> does it, on packed rows.  SMALL: every row of the
-// tableau is in class 0, the cross products are 24-bit multiplies; else entries are below 2^31, the products below 2^62
-// and their difference a long long.
-template <bool SMALL>
-__device__ __forceinline__ int choose_column32(const Shared<i64> &S, const RowRegs32<1> &prow, const i64 *vals, int W, int nvar,
-                                               int nligne, int pivi, Scalars *sc) {
-  constexpr int NM = 2;
+// choisir_piv (traiter.c:297-341) as choose_column<T, NCH, SMALL> does it, on packed rows.  SMALL: every row of the
+// tableau is in class 0 (F::cross).
+template <class F, bool SMALL>
+__device__ __forceinline__ int lean_choose_column(const Shared<typename F::T> &S, const typename F::Row &prow, const typename F::T *vals,
+                                                  int W, int nvar, int nligne, int pivi, Scalars *sc) {
+  typedef typename F::E E;
+  constexpr int NV = F::NV, NM = F::NM;
   const int lane = threadIdx.x & 63;
-  int a[2], u[2];
-  bool cand[2];
+  E a[NV];
+  int u[NV];
+  bool cand[NV];
   u64 cm[NM];
   int count = 0;
 #pragma unroll
-  for (int h = 0; h < 2; h++) {
-    const int j = 2 * lane + h;
-    a[h] = j < nvar ? prow.v[0][h] : 0;
+  for (int h = 0; h < NV; h++) {
+    const int j = F::col(lane, h);
+    a[h] = j < nvar ? prow.v[h] : 0;
     cand[h] = a[h] > 0;
     u[h] = cand[h] ? (int)S.urow[j] : -1;
     cm[h] = ballot64(cand[h]);
     count += __popcll(cm[h]);
   }
   if (count == 0) return -1;
+  // does the row of slot rf have a non-zero entry in a candidate column?
+  auto touches = [&](int rf) {
+    const u64 *m = S.nzm + (size_t)rf * NM;
+    u64 t = 0;
+#pragma unroll
+    for (int h = 0; h < NM; h++) t |= m[h] & cm[h];
+    return t != 0;
+  };
   for (int k0 = 0; k0 < nligne && count > 1; k0 += 64) {
     const int k = k0 + lane;
     bool rel = false;
     if (k < nligne && k != pivi) {
       const int rf = S.ref[k];
-      if (!(rf & UNITBIT)) {
-        const u64 *m = S.nzm + (size_t)rf * NM;
-        rel = ((m[0] & cm[0]) | (m[1] & cm[1])) != 0;
-      }
+      if (!(rf & UNITBIT)) rel = touches(rf);
     }
     u64 relmask = ballot64(rel);
     while (relmask && count > 1) {
@@ -174,47 +425,35 @@ __device__ __forceinline__ int choose_column32(const Shared<i64> &S, const RowRe
       // unit rows above kk knock out their own column
       int nel = 0;
 #pragma unroll
-      for (int h = 0; h < 2; h++) nel += __popcll(ballot64(cand[h] && u[h] < kk));
+      for (int h = 0; h < NV; h++) nel += __popcll(ballot64(cand[h] && u[h] < kk));
       if (nel == count) goto last_unit_wins;
       if (nel) {
 #pragma unroll
-        for (int h = 0; h < 2; h++) {
+        for (int h = 0; h < NV; h++) {
           if (u[h] < kk) cand[h] = false;
           cm[h] = ballot64(cand[h]);
         }
         count -= nel;
         if (count == 1) break;
       }
-      if (!((S.nzm[(size_t)sl * NM] & cm[0]) | (S.nzm[(size_t)sl * NM + 1] & cm[1]))) continue;  // cannot separate them
+      if (!touches(sl)) continue;  // cannot separate them
       // real row kk: keep the minimal ratios
-      RowRegs32<1> n;
-      row_load32p(n, vals + (size_t)sl * W, lane, W);
+      typename F::Row n;
+      F::load(n, vals + (size_t)sl * W, lane, W);
       for (;;) {
         // reference column b = first remaining candidate
-        int ab, nb;
-        if (cm[0]) {
-          const int src = __ffsll((long long)cm[0]) - 1;
-          ab = __builtin_amdgcn_readlane(a[0], src);
-          nb = __builtin_amdgcn_readlane(n.v[0][0], src);
-        } else {
-          const int src = __ffsll((long long)cm[1]) - 1;
-          ab = __builtin_amdgcn_readlane(a[1], src);
-          nb = __builtin_amdgcn_readlane(n.v[0][1], src);
-        }
-        bool neg[2];
+        int cb = NV - 1;
+#pragma unroll
+        for (int h = NV - 2; h >= 0; h--)
+          if (cm[h]) cb = h;
+        const int src = __ffsll((long long)cm[cb]) - 1;
+        const E ab = lean_entry<F>(a, cb, src), nb = lean_entry<F>(n.v, cb, src);
+        bool neg[NV];
         int nneg = 0, nzero = 0;
 #pragma unroll
-        for (int h = 0; h < 2; h++) {
+        for (int h = 0; h < NV; h++) {
           bool xneg, xzero;
-          if constexpr (SMALL) {
-            const int x = __mul24(ab, n.v[0][h]) - __mul24(nb, a[h]);
-            xneg = x < 0;
-            xzero = x == 0;
-          } else {
-            const i64 x = (i64)ab * (i64)n.v[0][h] - (i64)nb * (i64)a[h];
-            xneg = x < 0;
-            xzero = x == 0;
-          }
+          F::template cross<SMALL>(ab, n.v[h], nb, a[h], xneg, xzero);
           neg[h] = cand[h] && xneg;
           const bool zero = cand[h] && xzero;
           nneg += __popcll(ballot64(neg[h]));
@@ -224,43 +463,84 @@ __device__ __forceinline__ int choose_column32(const Shared<i64> &S, const RowRe
         if (nneg == 0) {
           count = nzero;
         } else {
-          cand[0] = neg[0];
-          cand[1] = neg[1];
+#pragma unroll
+          for (int h = 0; h < NV; h++) cand[h] = neg[h];
           count = nneg;
         }
-        cm[0] = ballot64(cand[0]);
-        cm[1] = ballot64(cand[1]);
+#pragma unroll
+        for (int h = 0; h < NV; h++) cm[h] = ballot64(cand[h]);
         if (nneg == 0 || count == 1) break;
       }
     }
   }
-  if (count == 1) return cm[0] ? 2 * (__ffsll((long long)cm[0]) - 1) : 2 * (__ffsll((long long)cm[1]) - 1) + 1;
+  if (count == 1) {
+#pragma unroll
+    for (int h = 0; h < NV; h++)
+      if (cm[h]) return F::col(__ffsll((long long)cm[h]) - 1, h);
+  }
 last_unit_wins:
   // only unit rows left to look at: the column whose unit row comes last survives
   if (lane == 0) sc->tmp2 = -1;
   __builtin_amdgcn_wave_barrier();
 #pragma unroll
-  for (int h = 0; h < 2; h++)
-    if (cand[h]) atomicMax(&sc->tmp2, (u[h] << 10) | (2 * lane + h));
+  for (int h = 0; h < NV; h++)
+    if (cand[h]) atomicMax(&sc->tmp2, (u[h] << 10) | F::col(lane, h));
   __builtin_amdgcn_wave_barrier();
   return sc->tmp2 & 1023;
 }
 
+#ifdef PIP_PROFILE
+#define PIP_LEAN_PROF_PARAM , u64 *prof
+#else
+#define PIP_LEAN_PROF_PARAM
+#endif
+
+// ---- the entry points.  The loop below is the body of both kernels, as text: a kernel names its flavour F, its row
+// capacity Smax / Lmax and FULL, then includes this header once more with PIP_LEAN_LOOP defined.  (A __forceinline__
+// function template would read better and costs pip_lean_kernel its register budget: the same text inlined through a
+// call spills three VGPRs to scratch with this compiler)  pip_lean_kernel<SC, FULL> is here, one
+// instantiation per row-capacity class (pip_adv_e.hip); pip_lean64_kernel, not a template, is in the translation unit
+// that launches it (pip_kernels.hip).
 // FULL: 127 unknowns + constant, a row fills the wave's 128 columns (the launcher's promise, as for pip_advance_kernel);
 // else any number of unknowns up to 127 without parameters, rows of W <= 128 columns (W even).
 template <int SC, bool FULL>
 __global__ __launch_bounds__(64, PIP_LEAN_WAVES) void pip_lean_kernel(PipJob *jobs, i64 *arena, int njobs, int iter_limit,
-                                                                      PipQueue q
+                                                                      PipQueue q PIP_LEAN_PROF_PARAM) {
+  typedef LeanIntRows F;
+  constexpr int Smax = SC, Lmax = SC + 128;
+#define PIP_LEAN_LOOP
+#include "pip_lean.h"
+#undef PIP_LEAN_LOOP
+}
+template <int SC, bool FULL>
+hipError_t launch_lean(const AdvanceLaunch &a) {
+  const int grid = a.grid > 0 && a.grid < a.njobs ? a.grid : a.njobs;
+  const size_t shm = lean_lds_bytes(SC);
 #ifdef PIP_PROFILE
-                                                                      , u64 *prof
+  hipLaunchKernelGGL((pip_lean_kernel<SC, FULL>), dim3(grid), dim3(64), shm, a.stream, a.jobs, a.arena, a.njobs, a.iter_limit, a.q,
+                     (u64 *)a.prof);
+#else
+  hipLaunchKernelGGL((pip_lean_kernel<SC, FULL>), dim3(grid), dim3(64), shm, a.stream, a.jobs, a.arena, a.njobs, a.iter_limit, a.q);
 #endif
-) {
-  typedef i64 T;
-  // (diagnostic build only, tools/dbg_prof_lean.py: cycle stamps per piece of the loop -- 0 exam/integrer, 1 pivot row
-  // load, 2 choisir_piv, 3 work list, 4 queue + recycled slot, 5 wait for a work row, 6 multipliers, 7 products + row gcd +
-  // division, 8 store + summary, 9 phase C, 10 entry, 11 epilogue)
+  return hipGetLastError();
+}
+// the row-capacity classes of launch_static (pip_kernels.hip)
+#define PIP_LEAN_CLASSES(X) \
+  X(64, true) X(96, true) X(112, true) X(128, true) X(160, true) X(64, false) X(96, false) X(112, false) X(128, false) X(160, false)
+#define PIP_LEAN_DEFINE(SC, FULL) template hipError_t launch_lean<SC, FULL>(const AdvanceLaunch &);
+
+#elif defined(PIP_LEAN_LOOP)
+// ---- The lean pivot loop: the body of a kernel (jobs, arena, njobs, iter_limit, q[, prof]) that has named F (the row
+// flavour), Smax / Lmax (the row capacity of its LDS image, compile-time or not) and FULL.
+// (diagnostic build only, tools/dbg_prof_lean.py and dbg_prof_lean64.py: cycle stamps per piece of the loop -- 0
+// exam/integrer, 1 pivot row load, 2 choisir_piv, 3 work list, 4 queue + recycled slot, and the barrier after the
+// last row, 5 wait for a work row, 6 multipliers, 7 products + row gcd + division, 8 store + summary, 9 phase C,
+// 10 entry, 11 epilogue)
+  typedef typename F::T T;
+  typedef typename F::E E;
+  typedef typename F::Row Row;
   PROF_DECL;
-  constexpr int Smax = SC, Lmax = SC + 128, WP = 128, NM = 2;
+  constexpr int WP = F::WP, NM = F::NM, NV = F::NV;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ Scalars sc;
   const int nq = q.in_count ? *q.in_count : njobs;
@@ -272,7 +552,7 @@ __global__ __launch_bounds__(64, PIP_LEAN_WAVES) void pip_lean_kernel(PipJob *jo
     if (J->status == PIPAMD_ST_CAPACITY && q.out_count && lane == 0) {
       q.out_list[atomicAdd(q.out_count, 1)] = jb;
       atomicMax(q.out_maxni, PIPAMD_Q_CAPFLAG | J->ni);
-      atomicAdd(q.out_maxni + 1, 1);  // (the list\'s third control word: tableaux out of rows)
+      atomicAdd(q.out_maxni + 1, 1);  // (the list's third control word: tableaux out of rows)
     }
     return;
   }
@@ -281,9 +561,8 @@ __global__ __launch_bounds__(64, PIP_LEAN_WAVES) void pip_lean_kernel(PipJob *jo
   const int nvar = FULL ? 127 : J->nvar, W = FULL ? 128 : J->W;
   int nligne = nvar + ni;
   // what this kernel does not do stays with pip_advance_kernel: the job goes on the launch list untouched
-  const bool mine = J->nvar == nvar && nvar < 128 && J->nparm == 0 && J->bigparm < 0 && J->W == W && W <= 128 && !(W & 1) &&
-                    J->ebits != 128 && !(tflags & (PIPAMD_T_NOSKIP | PIPAMD_T_DEEPEST)) && ni <= Smax && nligne <= Lmax &&
-                    (!(tflags & PIPAMD_T_STATE) || J->state_nch == 1);
+  const bool mine = F::shape(J, nvar, W) && !(tflags & (PIPAMD_T_NOSKIP | PIPAMD_T_DEEPEST)) && ni <= Smax && nligne <= Lmax &&
+                    (!(tflags & PIPAMD_T_STATE) || J->state_nch == F::NCH);
   if (!mine) {
     if (lane == 0 && q.out_count) {
       q.out_list[atomicAdd(q.out_count, 1)] = jb;
@@ -302,13 +581,13 @@ __global__ __launch_bounds__(64, PIP_LEAN_WAVES) void pip_lean_kernel(PipJob *jo
   int nlog = J->nlog;
 
   Shared<T> S;  // the tables of pip_advance_kernel's image this kernel uses
-  int *cst;     // [S] constant terms (ints here); the entry-time sort keys share their storage
+  E *cst;       // [S] constant terms (packed elements here); the entry-time sort keys share their storage
   {
     unsigned char *p = smem;
     S.den = (T *)p;      p += sizeof(T) * Smax;
     S.nzm = (u64 *)p;    p += sizeof(u64) * (size_t)Smax * NM;
-    cst = (int *)p;
-    S.size = (float *)p; p += sizeof(int) * Smax;
+    cst = (E *)p;
+    S.size = (float *)p; p += sizeof(E) * Smax;
     S.prow = nullptr;
     S.cst = nullptr;
     S.sig = (u16 *)p;    p += sizeof(u16) * Smax;
@@ -334,80 +613,75 @@ __global__ __launch_bounds__(64, PIP_LEAN_WAVES) void pip_lean_kernel(PipJob *jo
   }
   __builtin_amdgcn_wave_barrier();
   {
-  const int L = J->L;
-  const T *g_den = (const T *)(arena + J->rows_off);
-  const int *g_flag = (const int *)(g_den + L);
-  const int *g_ref = g_flag + L;
-  for (int i = lane; i < nligne; i += 64) {
-    const int f = g_flag[i], rf = g_ref[i];
-    if (f & PIPAMD_F_UNIT) {
-      S.ref[i] = (u16)(UNITBIT | ((f & PIPAMD_F_ZERO) ? UNITZERO : 0) | rf);
-      S.urow[rf] = (u16)i;
-    } else {
-      S.ref[i] = (u16)rf;
-      S.srow[rf] = (u16)i;
-      S.fl[rf] = (u8)f;
-      S.den[rf] = g_den[i];
-      S.nf[rf] = 0;
+    const int L = J->L;
+    const T *g_den = (const T *)(arena + J->rows_off);
+    const int *g_flag = (const int *)(g_den + L);
+    const int *g_ref = g_flag + L;
+    for (int i = lane; i < nligne; i += 64) {
+      const int f = g_flag[i], rf = g_ref[i];
+      if (f & PIPAMD_F_UNIT) {
+        S.ref[i] = (u16)(UNITBIT | ((f & PIPAMD_F_ZERO) ? UNITZERO : 0) | rf);
+        S.urow[rf] = (u16)i;
+      } else {
+        S.ref[i] = (u16)rf;
+        S.srow[rf] = (u16)i;
+        S.fl[rf] = (u8)f;
+        S.den[rf] = g_den[i];
+        S.nf[rf] = 0;
+      }
     }
-  }
   }
   __builtin_amdgcn_wave_barrier();
 
-  // ---- one pass over the tableau: the rows become ints (rows of a job loaded with PIPAMD_T_ROWS_STAY come from the
-  // caller's array), summaries, sort keys.  A row with an entry of 2^31 or more: not a job for this kernel.
-  int mcw = 0;  // largest magnitude class published so far: 0 small path everywhere, 1 int rows, beyond: the lean run ends
+  // ---- one pass over the tableau: the rows become packed (int rows of a job loaded with PIPAMD_T_ROWS_STAY come from
+  // the caller's array), summaries, sort keys.  A row with an entry of 2^ROW_BITS or more: not a job for this kernel.
+  int mcw = 0;  // largest magnitude class published so far: 0 small path everywhere, 1 packed rows, beyond: the lean run ends
   {
-    constexpr int PF0 = 4;
+    constexpr int PF0 = F::ENTRY_PF, CPL = ET<T>::CPL;
     // a job that paused in an earlier launch (this kernel's or pip_advance_kernel's, rows in the general format): what the
     // entry pass cannot see in the rows -- "gcd(row, denominator) is known to be 1" -- comes from the saved summaries
     const u16 *g_sig = (tflags & PIPAMD_T_STATE) ? (const u16 *)((const u64 *)(arena + J->state_off) + (size_t)J->S * NM) : nullptr;
-    const bool fresh = (tflags & PIPAMD_T_FRESHROWS) != 0;
+    const bool fresh = F::FRESH && (tflags & PIPAMD_T_FRESHROWS) != 0;
     const T *src = fresh ? (const T *)(uintptr_t)J->src_rows : vals;
     const int pitch = fresh ? nvar + 1 : W;  // the caller's rows are nvar + 1 wide (an even number: pipamd_batch_load), the block's W
     int npacked = 0;
     bool wide = false;
     for (int s0 = 0; s0 < ni && !wide; s0 += PF0) {
-      RowRegs<T, 1> rr[PF0];
+      RowRegs<T, F::NCH> rr[PF0];
 #pragma unroll
       for (int qq = 0; qq < PF0; qq++)
-        if (s0 + qq < ni) row_load<T, 1>(rr[qq], src + (size_t)(s0 + qq) * pitch, (nvar + 2) & ~1, lane);
+        if (s0 + qq < ni) row_load<T, F::NCH>(rr[qq], src + (size_t)(s0 + qq) * pitch, (nvar + CPL) & ~(CPL - 1), lane);
 #pragma unroll
       for (int qq = 0; qq < PF0; qq++) {
         const int s = s0 + qq;
         if (s >= ni || wide) break;
-        const RowRegs<T, 1> &r = rr[qq];
-        const bool fits = ((uabs64(r.v[0][0]) | uabs64(r.v[0][1])) >> 31) == 0;  // below 2^31 in magnitude
-        if (ballot64(!fits)) {
+        typename ET<T>::U mx = 0;
+        Row z;
+#pragma unroll
+        for (int h = 0; h < NV; h++) {
+          const T v = rr[qq].v[h / CPL][h % CPL];
+          mx |= uabs64(v);
+          z.v[h] = (E)v;
+        }
+        if (ballot64((mx >> F::ROW_BITS) != 0)) {  // not below 2^ROW_BITS in magnitude
           wide = true;
           break;
         }
-        RowRegs32<1> z;
-        z.v[0][0] = (int)r.v[0][0];
-        z.v[0][1] = (int)r.v[0][1];
-        row_store32p(z, vals + (size_t)s * W, lane, W);
+        F::store(z, vals + (size_t)s * W, lane, W);
         npacked = s + 1;
         const bool den1 = S.den[s] == 1;
         const int red = g_sig ? (g_sig[s] & SIG_RED) : (den1 ? SIG_RED : 0);
-        mcw = max(mcw, lean_publish(z, S, cst, s, -1, red, lane, nvar));
+        mcw = max(mcw, lean_publish<F>(z, S, cst, s, -1, red, lane, nvar));
         if (tflags & PIPAMD_T_SORT) {
           // traiter.c:576-589: size = max_j |(int)(v_j / den)| over the unknowns (as pip_advance_kernel computes it)
           int sz = 0;
-          if (den1) {
+          const double d = to_double(S.den[s]);
 #pragma unroll
-            for (int h = 0; h < 2; h++) {
-              const int q2 = z.v[0][h];
-              const int aq = q2 < 0 ? (int)(0u - (unsigned)q2) : q2;
-              if (2 * lane + h < nvar) sz = sz > aq ? sz : aq;
-            }
-          } else {
-            const double d = to_double(S.den[s]);
-#pragma unroll
-            for (int h = 0; h < 2; h++) {
-              const int q2 = trunc_int_x86((double)z.v[0][h] / d);
-              const int aq = q2 < 0 ? (int)(0u - (unsigned)q2) : q2;
-              if (2 * lane + h < nvar) sz = sz > aq ? sz : aq;
-            }
+          for (int h = 0; h < NV; h++) {
+            const E v = z.v[h];
+            const int q2 = !den1 ? trunc_int_x86((double)v / d) : (v == (E)(int)v ? (int)v : (int)0x80000000);
+            const int aq = q2 < 0 ? (int)(0u - (unsigned)q2) : q2;
+            if (F::col(lane, h) < nvar) sz = sz > aq ? sz : aq;
           }
           const unsigned szw = wave_minmax_u32<true>((unsigned)sz);
           if (lane == 0) {
@@ -418,9 +692,9 @@ __global__ __launch_bounds__(64, PIP_LEAN_WAVES) void pip_lean_kernel(PipJob *jo
       }
     }
     if (wide) {
-      // an entry beyond 32 bits: not a job for this kernel.  Its header is untouched (FRESHROWS and SORT still stand);
-      // rows that came from the block itself and were already rewritten as ints are widened again.
-      if (!fresh) rows_unpack(vals, npacked, lane, W, S.rcls);
+      // an entry beyond E: not a job for this kernel.  Its header is untouched (FRESHROWS and SORT still stand); rows
+      // that came from the block itself and were already packed are widened again.
+      if (!fresh) rows_unpack<F>(vals, npacked, lane, W, S.rcls);
       if (lane == 0 && q.out_count) {
         q.out_list[atomicAdd(q.out_count, 1)] = jb;
         atomicMax(q.out_maxni, ni);
@@ -428,17 +702,17 @@ __global__ __launch_bounds__(64, PIP_LEAN_WAVES) void pip_lean_kernel(PipJob *jo
       return;
     }
   }
-  tflags &= ~PIPAMD_T_FRESHROWS;
+  if constexpr (F::FRESH) tflags &= ~PIPAMD_T_FRESHROWS;
   __builtin_amdgcn_wave_barrier();
   if (tflags & PIPAMD_T_SORT) {
-    sort_rows(S, nvar, nligne, (double)sc.smaxbits);
+    [[clang::always_inline]] sort_rows(S, nvar, nligne, (double)sc.smaxbits);  // (left to the inliner, sort_rows<__int128> stays a call: scratch)
     __builtin_amdgcn_wave_barrier();
     for (int i = lane; i < nligne; i += 64)
       if (!(S.ref[i] & UNITBIT)) S.srow[S.ref[i]] = (u16)i;
     tflags &= ~PIPAMD_T_SORT;
-    // the sort keys overwrote the constant terms: back from the rows (column 127)
+    // the sort keys overwrote the constant terms: back from the rows (column nvar)
     __threadfence_block();
-    for (int s = lane; s < ni; s += 64) cst[s] = reinterpret_cast<const int *>(vals + (size_t)s * W)[nvar];
+    for (int s = lane; s < ni; s += 64) cst[s] = reinterpret_cast<const E *>(vals + (size_t)s * W)[nvar];
     __builtin_amdgcn_wave_barrier();
   }
   for (int s = lane; s < ni; s += 64) {
@@ -456,13 +730,13 @@ __global__ __launch_bounds__(64, PIP_LEAN_WAVES) void pip_lean_kernel(PipJob *jo
   PROF(10);
   int status = PIPAMD_ST_RUN;
   int why = 0;  // why a job left this kernel unfinished (PipJob.pad_, read by tools/lean_split.py): 1 pivot budget,
-                // 2 a row beyond ints, 3 a cut's denominator, 5 no room in the LDS image
+                // 2 a row beyond E, 3 a cut's denominator, 5 no room in the LDS image
   for (int iter = 0;; iter++) {
     why = 1;
     if (iter >= iter_limit) break;  // status stays RUN: the next launch resumes the job
     if (nlog >= LOGCAP) break;
     why = 2;
-    if (mcw > 1) break;  // a row left the ints (it is stored in the general format): the general kernel goes on
+    if (mcw > 1) break;  // a row left E (it is stored in the general format): the general kernel goes on
     why = 0;
     int pivi = sc.pivi;
     if (pivi == BIG_I) {
@@ -493,36 +767,21 @@ __global__ __launch_bounds__(64, PIP_LEAN_WAVES) void pip_lean_kernel(PipJob *jo
           break;
         }
         const int cslot = S.ref[ci];
-        const T D64 = uni64(S.den[cslot]);
+        const T DT = uni64(S.den[cslot]);
         why = 3;
-        if (D64 <= 0 || D64 >= ((T)1 << 31)) break;  // the cut's entries (below D) might not be ints: the general kernel goes on
-        const int D = (int)D64;
-        RowRegs32<1> r;
-        row_load32p(r, vals + (size_t)cslot * W, lane, W);
+        if (DT <= 0 || DT >= ((T)1 << F::CUT_BITS)) break;  // the cut's entries (below D) might not fit E: the general kernel goes on
+        const E D = (E)DT;
+        Row r;
+        F::load(r, vals + (size_t)cslot * W, lane, W);
+        F::row_mod(r, D, S.rcls[cslot] == 0);
         bool okv = false;
-        const bool tinyD = D < (1 << 15) && S.rcls[cslot] == 0;  // |v| < 2^15 and D < 2^15: remainders through a float reciprocal
-        const float rD = __builtin_amdgcn_rcpf((float)D);
 #pragma unroll
-        for (int h = 0; h < 2; h++) {
-          const int j = 2 * lane + h;
-          const int v = r.v[0][h];
-          // piplib_llmod (integrer.c:69-74): the remainder in [0, D)
-          int pos;
-          if (tinyD) {
-            const unsigned m = umod_tiny((unsigned)(v < 0 ? -v : v), (unsigned)D, rD);
-            pos = v < 0 ? (m ? D - (int)m : 0) : (int)m;  // v mod D
-          } else {
-            const int m = v % D;
-            pos = m < 0 ? m + D : m;
-          }
-          int x;
-          if (j < nvar) {
-            x = pos;
-            okv |= x > 0;
-          } else {
-            x = pos ? pos - D : 0;  // -((-v) mod D) == (v mod D) - D unless D divides v
-          }
-          r.v[0][h] = x;
+        for (int h = 0; h < NV; h++) {
+          const E pos = r.v[h];
+          if (F::col(lane, h) < nvar)
+            okv |= pos > 0;
+          else
+            r.v[h] = pos ? pos - D : 0;  // -((-v) mod D) == (v mod D) - D unless D divides v
         }
         const bool any_v = ballot64(okv) != 0;
         int verdict;
@@ -534,12 +793,12 @@ __global__ __launch_bounds__(64, PIP_LEAN_WAVES) void pip_lean_kernel(PipJob *jo
           verdict = -1;  // no room in this launch's LDS image: pause
         else {
           verdict = PIPAMD_ST_RUN;
-          row_store32p(r, vals + (size_t)ni * W, lane, W);
-          mcw = max(mcw, lean_publish(r, S, cst, ni, -1, 0, lane, nvar));
+          F::store(r, vals + (size_t)ni * W, lane, W);
+          mcw = max(mcw, lean_publish<F>(r, S, cst, ni, -1, 0, lane, nvar));
           if (lane == 0) {
             S.fl[ni] = PIPAMD_F_MINUS;
             S.nf[ni] = 0;
-            S.den[ni] = D64;
+            S.den[ni] = DT;
             S.ref[nligne] = (u16)ni;
             S.srow[ni] = (u16)nligne;
           }
@@ -560,25 +819,25 @@ __global__ __launch_bounds__(64, PIP_LEAN_WAVES) void pip_lean_kernel(PipJob *jo
     // ---------------- A: pivot row, choisir_piv, work list
     const int pslot = S.ref[pivi];
     const T dpiv = uni64(S.den[pslot]);
-    // small path for a row: the row and the pivot row in class 0 and the pivot row's denominator below 2^15 (then the
-    // multipliers are below 2^15 as well and every product below 2^30)
-    const bool psmall = S.rcls[pslot] == 0 && dpiv > -((T)1 << 15) && dpiv < ((T)1 << 15);
+    // small path for a row: the row and the pivot row in class 0 and the pivot row's denominator below 2^CLS0_BITS (then
+    // the multipliers are below it as well and every product fits E)
+    const bool psmall = S.rcls[pslot] == 0 && dpiv > -((T)1 << F::CLS0_BITS) && dpiv < ((T)1 << F::CLS0_BITS);
     npiv++;
-    RowRegs32<1> pr;
-    row_load32p(pr, vals + (size_t)pslot * W, lane, W);
+    Row pr;
+    F::load(pr, vals + (size_t)pslot * W, lane, W);
     const int psig_v = S.sig[pslot];
 #ifdef PIP_PROFILE
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
     PROF(1);
-    const int pj = mcw == 0 ? choose_column32<true>(S, pr, vals, W, nvar, nligne, pivi, &sc)
-                            : choose_column32<false>(S, pr, vals, W, nvar, nligne, pivi, &sc);
+    const int pj = mcw == 0 ? lean_choose_column<F, true>(S, pr, vals, W, nvar, nligne, pivi, &sc)
+                            : lean_choose_column<F, false>(S, pr, vals, W, nvar, nligne, pivi, &sc);
     if (pj == -1) {  // traiter.c:782-785
       status = PIPAMD_ST_NIL;
       break;
     }
     PROF(2);
-    const int pe = pj & 1, pl = pj >> 1;
+    const int pe = F::val_of(pj), pl = F::lane_of(pj);
     int nwork = 0;
     for (int s0 = 0; s0 < ni; s0 += 64) {
       const int s = s0 + lane;
@@ -604,7 +863,7 @@ __global__ __launch_bounds__(64, PIP_LEAN_WAVES) void pip_lean_kernel(PipJob *jo
       sc.pivi2 = BIG_I;
     }
     const int pivj = pj;
-    const int pivot = __builtin_amdgcn_readlane(pr.v[0][0], pl) * (1 - pe) + __builtin_amdgcn_readlane(pr.v[0][1], pl) * pe;
+    const E pivot = lean_entry<F>(pr.v, pe, pl);
     if (lane == 0) {
       g_log[2 * nlog] = (T)pivot;
       g_log[2 * nlog + 1] = dpiv;
@@ -616,35 +875,35 @@ __global__ __launch_bounds__(64, PIP_LEAN_WAVES) void pip_lean_kernel(PipJob *jo
     // ---------------- B: eliminate the pivot column
     nupd += nwork - 1;
     {
-      // a queue of PF rows on their way from HBM / L2 (a row is two registers here): the row at its head is updated
-      // while the loads behind it are in flight
-      constexpr int PF = PIP_LEAN_PF;
-      RowRegs32<1> rq[PF];
+      // a queue of PF rows on their way from HBM / L2: the row at its head is updated while the loads behind it are in
+      // flight
+      constexpr int PF = F::PF;
+      Row rq[PF];
       int sq[PF];
 #pragma unroll
       for (int q2 = 0; q2 < PF; q2++) {
         sq[q2] = S.work[q2 < nwork ? q2 : 0];
-        if (q2 < nwork && sq[q2] != pslot) row_load32p(rq[q2], vals + (size_t)sq[q2] * W, lane, W);
+        if (q2 < nwork && sq[q2] != pslot) F::load(rq[q2], vals + (size_t)sq[q2] * W, lane, W);
       }
       // while the first rows are on their way: the pivot slot is recycled for the row replacing ku's unit row
       // (traiter.c:461-465,503-513) -- it needs no load, the pivot row is in registers
-      if (dpiv > -((T)1 << 31) && dpiv < ((T)1 << 31)) {
-        RowRegs32<1> r;
+      if (F::fits(dpiv)) {
+        Row r;
 #pragma unroll
-        for (int h = 0; h < 2; h++) r.v[0][h] = (2 * lane + h == pivj) ? (int)dpiv : -pr.v[0][h];
-        row_store32p(r, vals + (size_t)pslot * W, lane, W);
-        mcw = max(mcw, lean_publish(r, S, cst, pslot, pivj, pred, lane, nvar));
-      } else {  // the denominator is no int: that row is not one either
-        i64 zw[2];
+        for (int h = 0; h < NV; h++) r.v[h] = (F::col(lane, h) == pivj) ? (E)dpiv : (E)wneg((i64)pr.v[h]);
+        F::store(r, vals + (size_t)pslot * W, lane, W);
+        mcw = max(mcw, lean_publish<F>(r, S, cst, pslot, pivj, pred, lane, nvar));
+      } else {  // the denominator does not fit E: that row does not either
+        T zw[NV];
 #pragma unroll
-        for (int h = 0; h < 2; h++) zw[h] = (2 * lane + h == pivj) ? dpiv : -(i64)pr.v[0][h];
-        row_store64w(zw, vals + (size_t)pslot * W, lane, W);
-        mcw = max(mcw, lean_publish_wide(zw, S, cst, pslot, pivj, pred, lane, nvar));
+        for (int h = 0; h < NV; h++) zw[h] = (F::col(lane, h) == pivj) ? dpiv : -(T)pr.v[h];
+        F::store_wide(zw, vals + (size_t)pslot * W, lane, W);
+        mcw = max(mcw, lean_publish_wide<F>(zw, S, cst, pslot, pivj, pred, lane, nvar));
       }
       PROF(4);
       for (int w = 0; w < nwork; w++) {
         const int s = sq[0];
-        RowRegs32<1> r = rq[0];
+        Row r = rq[0];
 #pragma unroll
         for (int q2 = 0; q2 + 1 < PF; q2++) {
           rq[q2] = rq[q2 + 1];
@@ -652,82 +911,57 @@ __global__ __launch_bounds__(64, PIP_LEAN_WAVES) void pip_lean_kernel(PipJob *jo
         }
         if (w + PF < nwork) {
           sq[PF - 1] = S.work[w + PF];
-          if (sq[PF - 1] != pslot) row_load32p(rq[PF - 1], vals + (size_t)sq[PF - 1] * W, lane, W);
+          if (sq[PF - 1] != pslot) F::load(rq[PF - 1], vals + (size_t)sq[PF - 1] * W, lane, W);
         }
         T *row = vals + (size_t)s * W;
-        {
-          if (s == pslot) continue;
+        if (s == pslot) continue;
 #ifdef PIP_PROFILE
-          asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PF - 1) : "memory");
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PF - 1) : "memory");
 #endif
-          PROF(5);
-          // multipliers from the row's own pivot-column entry (traiter.c:470-476); ints
-          int foo = __builtin_amdgcn_readlane(r.v[0][0], pl) * (1 - pe) + __builtin_amdgcn_readlane(r.v[0][1], pl) * pe;
-          const T den_s = uni64(S.den[s]);
-          int lp = pivot;
-          T g0 = den_s;
-          if (pivot != 1) {
-            const unsigned d = gcd_u32((unsigned)pivot, (unsigned)(foo < 0 ? -foo : foo));
-            if (d != 1) {  // (d == 0 cannot be: pivot > 0)
-              lp = (int)exact_quo<i64>((i64)pivot, (i64)d);
-              foo = (int)exact_quo<i64>((i64)foo, (i64)d);
-            }
-            g0 = wmul((T)lp, den_s);
+        PROF(5);
+        // multipliers from the row's own pivot-column entry (traiter.c:470-476); packed elements
+        E foo = lean_entry<F>(r.v, pe, pl);
+        const T den_s = uni64(S.den[s]);
+        E lp = pivot;
+        T g0 = den_s;
+        if (pivot != 1) {
+          const auto d = F::gcd(pivot, foo);
+          if (d != 1) {  // (d == 0 cannot be: pivot > 0)
+            lp = (E)exact_quo<i64>((i64)pivot, (i64)d);
+            foo = (E)exact_quo<i64>((i64)foo, (i64)d);
           }
-          T nd;
-          PROF(6);
-          if (psmall && S.rcls[s] == 0) {
-            // small path: every operand below 2^15, every product below 2^30
-            int z[1][2];
-            unsigned mx = 0;
-#pragma unroll
-            for (int h = 0; h < 2; h++) {
-              int v = __mul24(r.v[0][h], lp) - __mul24(pr.v[0][h], foo);
-              if (2 * lane + h == pivj) v = __mul24((int)dpiv, foo);
-              z[0][h] = v;
-              mx |= (unsigned)(v < 0 ? -v : v);
-            }
-            if (!small_reduce<1>(z, mx, g0, lane, nd)) {
-              if (lane == 0) sc.bad = 1;
-            }
-            r.v[0][0] = z[0][0];
-            r.v[0][1] = z[0][1];
-            PROF(7);
-            row_store32p(r, row, lane, W);
-            mcw = max(mcw, lean_publish(r, S, cst, s, pivj, SIG_RED, lane, nvar));
-          } else {
-            // mid path: int operands, products below 2^62 in long longs -- pip_advance_kernel's update_row on the same
-            // values (its wrap-around arithmetic has nothing to wrap here, except dpiv * foo under a denominator
-            // beyond ints, which wraps the same way)
-            i64 zw[2];
-            u64 mx = 0;
-#pragma unroll
-            for (int h = 0; h < 2; h++) {
-              i64 v = (i64)r.v[0][h] * (i64)lp - (i64)pr.v[0][h] * (i64)foo;
-              if (2 * lane + h == pivj) v = wmul(dpiv, (i64)foo);
-              zw[h] = v;
-              mx |= uabs64(v);
-            }
-#if PIP_LEAN_MID_INV
-            if (!row_reduce<i64, 2, false>(zw, mx, g0, lane, nd, wmul(dpiv, (i64)foo))) {
-#else
-            if (!row_reduce_rem<i64, 2>(zw, mx, g0, lane, nd)) {  // (the remainder loop: reduce_by_inverse costs this kernel 12 bytes of scratch)
-#endif
-              if (lane == 0) sc.bad = 1;
-            }
-            if (ballot64(((uabs64(zw[0]) | uabs64(zw[1])) >> 31) != 0) == 0) {
-              r.v[0][0] = (int)zw[0];
-              r.v[0][1] = (int)zw[1];
-              row_store32p(r, row, lane, W);
-              mcw = max(mcw, lean_publish(r, S, cst, s, pivj, SIG_RED, lane, nvar));
-            } else {  // not an int row any more: general format, the lean run ends after this pivot
-              row_store64w(zw, row, lane, W);
-              mcw = max(mcw, lean_publish_wide(zw, S, cst, s, pivj, SIG_RED, lane, nvar));
-            }
-          }
-          if (lane == 0) S.den[s] = nd;
-          PROF(8);
+          g0 = wmul((T)lp, den_s);
         }
+        T nd;
+        PROF(6);
+        if (psmall && S.rcls[s] == 0 && F::small_den(g0)) {
+          if (!F::update_small(r, pr, lp, foo, dpiv, pivj, g0, lane, nd)) {
+            if (lane == 0) sc.bad = 1;
+          }
+          PROF(7);
+          F::store(r, row, lane, W);
+          mcw = max(mcw, lean_publish<F>(r, S, cst, s, pivj, SIG_RED, lane, nvar));
+        } else {
+          T zw[NV];
+          if (!F::update_mid(zw, r, pr, lp, foo, dpiv, pivj, g0, lane, nd)) {
+            if (lane == 0) sc.bad = 1;
+          }
+          typename ET<T>::U mx = 0;
+#pragma unroll
+          for (int h = 0; h < NV; h++) mx |= uabs64(zw[h]);
+          PROF(7);
+          if (ballot64((mx >> F::ROW_BITS) != 0) == 0) {
+#pragma unroll
+            for (int h = 0; h < NV; h++) r.v[h] = (E)zw[h];
+            F::store(r, row, lane, W);
+            mcw = max(mcw, lean_publish<F>(r, S, cst, s, pivj, SIG_RED, lane, nvar));
+          } else {  // not a packed row any more: general format, the lean run ends after this pivot
+            F::store_wide(zw, row, lane, W);
+            mcw = max(mcw, lean_publish_wide<F>(zw, S, cst, s, pivj, SIG_RED, lane, nvar));
+          }
+        }
+        if (lane == 0) S.den[s] = nd;
+        PROF(8);
       }
     }
     __builtin_amdgcn_wave_barrier();
@@ -825,7 +1059,7 @@ __global__ __launch_bounds__(64, PIP_LEAN_WAVES) void pip_lean_kernel(PipJob *jo
   }
   if (status == PIPAMD_ST_RUN || status == PIPAMD_ST_CAPACITY) {
     // the job goes on elsewhere (pip_advance_kernel, pip_rehouse_kernel): its rows in the general format again
-    rows_unpack(vals, ni, lane, W, S.rcls);
+    rows_unpack<F>(vals, ni, lane, W, S.rcls);
   }
   int mc = 0;
   for (int s = lane; s < ni; s += 64)
@@ -839,7 +1073,7 @@ __global__ __launch_bounds__(64, PIP_LEAN_WAVES) void pip_lean_kernel(PipJob *jo
     J->nlog = nlog;
     J->pad_ = why;
     J->tflags = tflags;
-    J->state_nch = 1;
+    J->state_nch = F::NCH;
     J->maxabs = (u64)mc;
     J->aux = sc.aux;
     J->status = status;
@@ -850,29 +1084,11 @@ __global__ __launch_bounds__(64, PIP_LEAN_WAVES) void pip_lean_kernel(PipJob *jo
     if (status == PIPAMD_ST_CAPACITY && q.out_count) {
       q.out_list[atomicAdd(q.out_count, 1)] = jb;
       atomicMax(q.out_maxni, PIPAMD_Q_CAPFLAG | ni);
-      atomicAdd(q.out_maxni + 1, 1);  // (the list\'s third control word: tableaux out of rows)
+      atomicAdd(q.out_maxni + 1, 1);  // (the list's third control word: tableaux out of rows)
     }
   }
   PROF(11);
 #ifdef PIP_PROFILE
   PROF_FLUSH(prof);
 #endif
-}
-
-template <int SC, bool FULL>
-hipError_t launch_lean(const AdvanceLaunch &a) {
-  const int grid = a.grid > 0 && a.grid < a.njobs ? a.grid : a.njobs;
-  const size_t shm = lean_lds_bytes(SC);
-#ifdef PIP_PROFILE
-  hipLaunchKernelGGL((pip_lean_kernel<SC, FULL>), dim3(grid), dim3(64), shm, a.stream, a.jobs, a.arena, a.njobs, a.iter_limit, a.q,
-                     (u64 *)a.prof);
-#else
-  hipLaunchKernelGGL((pip_lean_kernel<SC, FULL>), dim3(grid), dim3(64), shm, a.stream, a.jobs, a.arena, a.njobs, a.iter_limit, a.q);
-#endif
-  return hipGetLastError();
-}
-// the row-capacity classes of launch_static (pip_kernels.hip)
-#define PIP_LEAN_CLASSES(X) \
-  X(64, true) X(96, true) X(112, true) X(128, true) X(160, true) X(64, false) X(96, false) X(112, false) X(128, false) X(160, false)
-#define PIP_LEAN_DEFINE(SC, FULL) template hipError_t launch_lean<SC, FULL>(const AdvanceLaunch &);
-#endif  // PIP_LEAN_H
+#endif  // PIP_LEAN_H / PIP_LEAN_LOOP

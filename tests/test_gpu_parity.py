@@ -390,7 +390,7 @@ def test_full_size_int128_config():
 
 
 def test_lean64_kernel_paths():
-    """The lean kernel of the 128-bit flavour (csrc/pip_lean64.h, opt-in: pipamd_engine_set_lean64): one wave per tableau,
+    """The lean kernel of the 128-bit flavour (pip_lean64_kernel, csrc/pip_lean.h, opt-in: pipamd_engine_set_lean64): one wave per tableau,
     rows held as long longs while every entry fits 63 bits.  configs[4]'s pinned batch through it -- two in three
     tableaux finish there, a third leave on a row beyond 2^63 (stored in the general format mid-pivot, the tableau handed
     to pip_advance_kernel<__int128>), a few on the launch's pivot budget -- must come out as without it (statuses, pivot

@@ -1,4 +1,4 @@
-"""What the lean kernel of the 128-bit flavour (csrc/pip_lean64.h) does on configs[4]'s pinned batch (GPU box): the lean
+"""What the lean kernel of the 128-bit flavour (pip_lean64_kernel, csrc/pip_lean.h) does on configs[4]'s pinned batch (GPU box): the lean
 launch alone (pipamd_debug_single_launch) -- its duration, tableaux finished, pivots done, and why tableaux left it
 (PipJob.pad_: 1 pivot budget, 2 a row beyond long longs, 3 a cut's denominator, 5 no room in the LDS image)."""
 import json, os, sys
@@ -10,6 +10,7 @@ from piplib_amd import engine as eng
 rows = mk.rows_full("wide128")
 e = eng.Engine(0)
 e.set_max_rows(128 + 1280)
+e.set_lean64(True)  # (opt-in)
 e.set_timing(True)
 b = eng.Batch(e, rows, 255, 0, tflags=eng.T_INT, entier_bits=128)
 e.debug_single_launch(1)
