@@ -288,6 +288,8 @@ __device__ __forceinline__ u128 inv_odd64(u128 m) {
   return x;
 }
 // every division on the pivot path is exact (piplib_int_div_exact of a gcd): shift + odd inverse
+// (the divisor is a gcd or a remainder, never negative, at every call site; one pair with a negative one is answered in 64
+// bits: cquo(-2^63, -1) takes the long long shortcut and comes back as -2^63, tests/test_gpu_arith_probe.py)
 __device__ __forceinline__ i128 cquo(i128 a, i128 b) {
   if (b == 1) return a;
   if (b == 0) return 0;
@@ -1185,6 +1187,48 @@ __device__ T bezout_dev(T x, T y, T delta) {
   }
   if (v != 1) return 0;
   return fmod64(wmul(c, x), delta);
+}
+
+// The determinant replay's step (pip_kernels.hip; traiter.c:412-446), here so that the arithmetic probe (pip_probe.hip) runs it too:
+// one step of the walk over the limbs for the reduced pair (ppivot, dppiv); false = overflow
+template <class T>
+__device__ __forceinline__ bool det_step(T &det0, T &det1, T &det2, T &det3, int &ldet, T ppivot, T dppiv) {
+  // once dppiv is 1 the remaining limbs would be divided by gcd(limb, 1) = 1
+#define PIP_DET_DIVIDE(limb, i)                    \
+  if ((i) < ldet && dppiv != 1) {                  \
+    const T d_ = gcd_i64(limb, dppiv);             \
+    if (d_ != 1) {                                 \
+      limb = exact_quo(limb, d_);                  \
+      dppiv = exact_quo(dppiv, d_);                \
+    }                                              \
+  }
+  PIP_DET_DIVIDE(det0, 0)
+  PIP_DET_DIVIDE(det1, 1)
+  PIP_DET_DIVIDE(det2, 2)
+  PIP_DET_DIVIDE(det3, 3)
+#undef PIP_DET_DIVIDE
+  if (dppiv != 1) return false;
+  constexpr int B = ET<T>::BITS;
+  const int lp = log2_64(ppivot);
+  if (0 < ldet && log2_64(det0) + lp < B)
+    det0 = wmul(det0, ppivot);
+  else if (1 < ldet && log2_64(det1) + lp < B)
+    det1 = wmul(det1, ppivot);
+  else if (2 < ldet && log2_64(det2) + lp < B)
+    det2 = wmul(det2, ppivot);
+  else if (3 < ldet && log2_64(det3) + lp < B)
+    det3 = wmul(det3, ppivot);
+  else {
+    ldet++;
+    if (ldet >= PIPAMD_MAXDET) return false;
+    if (ldet == 1)
+      det0 = ppivot;
+    else if (ldet == 2)
+      det1 = ppivot;
+    else
+      det2 = ppivot;
+  }
+  return true;
 }
 
 // flag exam_coef (traiter.c:121-154) gives an Unknown row, from its sign summary

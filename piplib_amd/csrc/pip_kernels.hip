@@ -41,47 +41,6 @@ __device__ __forceinline__ void det_limb_store(PipJob *J, int i, T x) {
   } else
     J->det[i] = (i64)x;
 }
-// one step of the walk over the limbs for the reduced pair (ppivot, dppiv); false = overflow
-template <class T>
-__device__ __forceinline__ bool det_step(T &det0, T &det1, T &det2, T &det3, int &ldet, T ppivot, T dppiv) {
-  // once dppiv is 1 the remaining limbs would be divided by gcd(limb, 1) = 1
-#define PIP_DET_DIVIDE(limb, i)                    \
-  if ((i) < ldet && dppiv != 1) {                  \
-    const T d_ = gcd_i64(limb, dppiv);             \
-    if (d_ != 1) {                                 \
-      limb = exact_quo(limb, d_);                  \
-      dppiv = exact_quo(dppiv, d_);                \
-    }                                              \
-  }
-  PIP_DET_DIVIDE(det0, 0)
-  PIP_DET_DIVIDE(det1, 1)
-  PIP_DET_DIVIDE(det2, 2)
-  PIP_DET_DIVIDE(det3, 3)
-#undef PIP_DET_DIVIDE
-  if (dppiv != 1) return false;
-  constexpr int B = ET<T>::BITS;
-  const int lp = log2_64(ppivot);
-  if (0 < ldet && log2_64(det0) + lp < B)
-    det0 = wmul(det0, ppivot);
-  else if (1 < ldet && log2_64(det1) + lp < B)
-    det1 = wmul(det1, ppivot);
-  else if (2 < ldet && log2_64(det2) + lp < B)
-    det2 = wmul(det2, ppivot);
-  else if (3 < ldet && log2_64(det3) + lp < B)
-    det3 = wmul(det3, ppivot);
-  else {
-    ldet++;
-    if (ldet >= PIPAMD_MAXDET) return false;
-    if (ldet == 1)
-      det0 = ppivot;
-    else if (ldet == 2)
-      det1 = ppivot;
-    else
-      det2 = ppivot;
-  }
-  return true;
-}
-
 // One WAVE per job: gcd(pivot, dpiv) and the two quotients do not depend on the limbs, so the
 // lanes compute them for 64 pivots at once; only the walk over the limbs is sequential, on the
 // scalar unit.  Shortest latency: used where few jobs ran and someone waits for them.

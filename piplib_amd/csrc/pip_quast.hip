@@ -1522,6 +1522,49 @@ __global__ void pip_quast_pack_kernel(const w64 *cells, const w64 *off, w64 *pac
   for (w64 k = threadIdx.x; k < cw * n; k += blockDim.x) packed[cw * lo + k] = src[k];
 }
 
+// Testing aid (pip_probe.hip, pipamd_debug_arith): the helpers above on operands the caller gives, one case per lane.
+// fn: 0 gcd64, 1 quo, 2 rem, 3 pmod, 4 floordiv, 5 qudiv, 6 qumod, 7 qinv, 8 blen, 9 cmul, 10 cadd, 11 csub, 12 bezout.
+// A case: three entries in (x, y, delta; unused ones ignored), the result and the `bad` flag out; a 128-bit entry is
+// two words, low then high.
+template <class QI>
+__global__ __launch_bounds__(64) void pip_quast_probe_kernel(int fn, const w64 *in, w64 *out, int n) {
+  typedef QK<QI, 1> K;
+  typedef typename QT<QI>::U U;
+  constexpr int EW = sizeof(QI) / 8;
+  const int t = blockIdx.x * 64 + threadIdx.x;
+  if (t >= n) return;
+  QI a[3];
+  for (int k = 0; k < 3; k++) {
+    const w64 *p = in + (size_t)t * 3 * EW + k * EW;
+    if constexpr (EW == 2)
+      a[k] = (QI)(((u128)(u64)p[1] << 64) | (u64)p[0]);
+    else
+      a[k] = p[0];
+  }
+  int bad = 0;
+  QI r = 0;
+  switch (fn) {
+    case 0: r = K::gcd64(a[0], a[1]); break;
+    case 1: r = K::quo(a[0], a[1]); break;
+    case 2: r = K::rem(a[0], a[1]); break;
+    case 3: r = K::pmod(a[0], a[1]); break;
+    case 4: r = K::floordiv(a[0], a[1], bad); break;
+    case 5: r = (QI)qudiv((U)a[0], (U)a[1]); break;
+    case 6: r = (QI)qumod((U)a[0], (U)a[1]); break;
+    case 7: r = (QI)qinv((U)a[0]); break;
+    case 8: r = K::blen(a[0]); break;
+    case 9: r = K::cmul(a[0], a[1], bad); break;
+    case 10: r = K::cadd(a[0], a[1], bad); break;
+    case 11: r = K::csub(a[0], a[1], bad); break;
+    case 12: r = K::bezout(a[0], a[1], a[2], bad); break;
+    default: break;
+  }
+  w64 *o = out + (size_t)t * (EW + 1);
+  o[0] = (w64)(u64)(U)r;
+  if constexpr (EW == 2) o[1] = (w64)(u64)((U)r >> 64);
+  o[EW] = bad ? 1 : 0;
+}
+
 }  // namespace
 
 // LDS image and stack frame of a launch, by entry width (ebits 64 or 128): EB bytes an entry
@@ -1576,5 +1619,14 @@ extern "C" hipError_t pipk_launch_quast_pack(const long long *cells, const long 
                                              int cells_cap, int ebits, hipStream_t stream) {
   if (nprob <= 0) return hipSuccess;
   hipLaunchKernelGGL(pip_quast_pack_kernel, dim3(nprob), dim3(128), 0, stream, cells, off, packed, cells_cap, ebits == 128 ? 6 : 3);
+  return hipGetLastError();
+}
+// op: 2 * fn + (128-bit entries ? 1 : 0), see pip_quast_probe_kernel
+extern "C" hipError_t pipk_launch_quast_probe(int op, const long long *in, long long *out, int n, hipStream_t stream) {
+  if (n <= 0) return hipSuccess;
+  if (op & 1)
+    hipLaunchKernelGGL(pip_quast_probe_kernel<w128>, dim3((n + 63) / 64), dim3(64), 0, stream, op >> 1, in, out, n);
+  else
+    hipLaunchKernelGGL(pip_quast_probe_kernel<w64>, dim3((n + 63) / 64), dim3(64), 0, stream, op >> 1, in, out, n);
   return hipGetLastError();
 }

@@ -166,6 +166,62 @@ class Overflow(Exception):
     pass
 
 
+def det_update(det, pivot, dpiv, bits):
+    """The multi-limb determinant walk of traiter.c:412-446 on the list `det`, in place: the limbs lose the factors
+    of dpiv / gcd(pivot, dpiv) (a factor left over: Overflow), then the first limb with room below `bits` takes
+    pivot / gcd(pivot, dpiv) (no room and no limb left: Overflow)."""
+    d = math.gcd(pivot, dpiv)
+    ppivot, dppiv = pivot // d, dpiv // d
+    for i in range(len(det)):
+        d = math.gcd(det[i], dppiv)
+        det[i] //= d
+        dppiv //= d
+    if dppiv != 1:
+        raise Overflow()
+    for i in range(len(det)):
+        if _log2(det[i]) + _log2(ppivot) < bits:
+            det[i] *= ppivot  # below 2^(bits-1) by the test above: never a wrap
+            break
+    else:
+        if len(det) + 1 >= MAXDET:
+            raise Overflow()
+        det.append(ppivot)
+
+
+def row_update(v, den, prow, pivot, dpiv, pivj, st=None):
+    """The row update of traiter.c:470-501 for the row `v` (object array) under denominator `den`, against the pivot row
+    `prow` with pivot entry `pivot` = prow[pivj] and denominator `dpiv`.  Returns (z, newden, lpiv, foo): the new row,
+    its denominator and the two multipliers.  z is `v` itself where the reference would multiply by 1 and subtract 0.
+    `st`: Stats that note every intermediate the fixed-width code forms."""
+    foo = int(v[pivj])
+    d = math.gcd(pivot, foo)
+    lpiv, foo = pivot // d, foo // d
+    g = lpiv * den
+    if st is not None:
+        _note(st, g)
+    if foo == 0 and lpiv == 1:
+        z = v  # z = v * 1 - q * 0: same entries; the gcd with g = den may still reduce them
+    else:
+        a, b = v * lpiv, prow * foo
+        z = a - b
+        z[pivj] = dpiv * foo
+        if st is not None:
+            _note_arr(st, a)
+            _note_arr(st, b)
+            _note_arr(st, z)
+    gg = g
+    if gg != 1:
+        for x in z:
+            gg = math.gcd(gg, int(x))
+            if gg == 1:
+                break
+    newden = g
+    if gg != 1:
+        z = z // gg  # exact: gg divides every entry
+        newden = g // gg
+    return z, newden, lpiv, foo
+
+
 def pivot_step(rows, det, pivi, nvar, ni, st):
     ncol = nvar + 1
     nligne = nvar + ni
@@ -175,23 +231,7 @@ def pivot_step(rows, det, pivi, nvar, ni, st):
         return -1
     prow = rows[pivi].v
     pivot, dpiv = int(prow[pivj]), rows[pivi].den
-    d = math.gcd(pivot, dpiv)
-    ppivot, dppiv = pivot // d, dpiv // d
-    # multi-limb determinant, traiter.c:412-446
-    for i in range(len(det)):
-        d = math.gcd(det[i], dppiv)
-        det[i] //= d
-        dppiv //= d
-    if dppiv != 1:
-        raise Overflow()
-    for i in range(len(det)):
-        if _log2(det[i]) + _log2(ppivot) < st.bits:
-            det[i] *= ppivot  # below 2^(bits-1) by the test above: never a wrap
-            break
-    else:
-        if len(det) + 1 >= MAXDET:
-            raise Overflow()
-        det.append(ppivot)
+    det_update(det, pivot, dpiv, st.bits)
     fresh = -prow
     fresh[pivj] = dpiv
     changed = 0
@@ -199,30 +239,7 @@ def pivot_step(rows, det, pivi, nvar, ni, st):
         r = rows[k]
         if (r.flag & UNIT) or k == pivi:
             continue
-        foo = int(r.v[pivj])
-        d = math.gcd(pivot, foo)
-        lpiv, foo = pivot // d, foo // d
-        g = lpiv * r.den
-        _note(st, g)
-        if foo == 0 and lpiv == 1:
-            z = r.v  # z = v * 1 - q * 0: same entries; the gcd with g = den may still reduce them
-        else:
-            a, b = r.v * lpiv, prow * foo
-            z = a - b
-            z[pivj] = dpiv * foo
-            _note_arr(st, a)
-            _note_arr(st, b)
-            _note_arr(st, z)
-        gg = g
-        if gg != 1:
-            for x in z:
-                gg = math.gcd(gg, int(x))
-                if gg == 1:
-                    break
-        newden = g
-        if gg != 1:
-            z = z // gg  # exact: gg divides every entry
-            newden = g // gg
+        z, newden, _, _ = row_update(r.v, r.den, prow, pivot, dpiv, pivj, st)
         if newden != r.den or (z is not r.v and bool((z != r.v).any())):
             changed += 1
         r.v, r.den = z, newden
