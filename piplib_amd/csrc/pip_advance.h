@@ -1592,6 +1592,179 @@ struct PipQueue {
   int *out_maxni;
 };
 
+// ---------------------------------------------------------------- pieces of a pivot that work on the tables alone
+// pip_advance_kernel and the lean loop (pip_lean.h) hand jobs to each other in mid-solve: what one publishes or saves
+// when it pauses, the other stages, and everything else here works on the image's tables, not on rows -- so it exists
+// once, for any entry type T and NT threads per job.  Barriers stay with the caller.
+
+// one lane, before the tables are staged
+__device__ __forceinline__ void reset_scalars(Scalars &sc) {
+  sc.ovf = 0;
+  sc.aux = 0;
+  sc.smaxbits = 0;
+  sc.pivi = BIG_I;
+  sc.pivi2 = BIG_I;
+  sc.flagor = 0;
+  sc.bad = 0;
+}
+
+// HBM den | flag | ref -> ref / urow / srow / fl / den / nf (urow is NOROW everywhere before).  ZSIZE: the sort keys
+// start at 0 (not where they share storage with live data)
+template <class T, int NT, bool ZSIZE>
+__device__ __forceinline__ void stage_row_tables(const Shared<T> &S, const PipRowTables<const T> &g, int nligne, int tid) {
+  for (int i = tid; i < nligne; i += NT) {
+    const int f = g.flag[i], rf = g.ref[i];
+    if (f & PIPAMD_F_UNIT) {
+      S.ref[i] = (u16)(UNITBIT | ((f & PIPAMD_F_ZERO) ? UNITZERO : 0) | rf);
+      S.urow[rf] = (u16)i;
+    } else {
+      S.ref[i] = (u16)rf;
+      S.srow[rf] = (u16)i;
+      S.fl[rf] = (u8)f;
+      S.den[rf] = g.den[i];
+      if constexpr (ZSIZE) S.size[rf] = 0.f;
+      S.nf[rf] = 0;
+    }
+  }
+}
+// ... and back when the launch lets go of the job
+template <class T, int NT>
+__device__ __forceinline__ void publish_row_tables(const Shared<T> &S, const PipRowTables<T> &g, int nligne, int tid) {
+  for (int i = tid; i < nligne; i += NT) {
+    const int rf = S.ref[i];
+    if (rf & UNITBIT) {
+      g.den[i] = 1;
+      g.flag[i] = PIPAMD_F_UNIT | ((rf & UNITZERO) ? PIPAMD_F_ZERO : 0);
+      g.ref[i] = UNITCOL(rf);
+    } else {
+      g.den[i] = S.den[rf];
+      g.flag[i] = S.fl[rf];
+      g.ref[i] = rf;
+    }
+  }
+}
+
+// the saved summaries of a paused job (the `state` part of its block): bitmaps, sign summaries, magnitude classes
+struct SavedSummaries {
+  u64 *nzm;  // [Sl][NM]
+  u16 *sig;  // [Sl]
+  u8 *rcls;  // [Sl]
+};
+__device__ __forceinline__ SavedSummaries saved_summaries(i64 *state, int Sl, int NM) {
+  u64 *nzm = (u64 *)state;
+  u16 *sig = (u16 *)(nzm + (size_t)Sl * NM);
+  return {nzm, sig, (u8 *)(sig + Sl)};
+}
+template <class T, int NT>
+__device__ __forceinline__ void save_summaries(const Shared<T> &S, const SavedSummaries &g, int ni, int NM, int tid) {
+  for (int s = tid; s < ni; s += NT) {
+    g.sig[s] = S.sig[s];
+    g.rcls[s] = S.rcls[s];
+  }
+  for (int e = tid; e < ni * NM; e += NT) g.nzm[e] = S.nzm[e];
+}
+
+// chercher(Minus) and the tentative exam_coef flags for a launch's first iteration; later iterations get both from
+// pivot_swap_roles.  (bigparm >= 0: exam_rows does the second part.)
+template <class T, int NT>
+__device__ __forceinline__ void first_chercher(const Shared<T> &S, Scalars *sc, int ni, int bigparm, int tid) {
+  for (int s = tid; s < ni; s += NT) {
+    const int ff = S.fl[s];
+    if (ff & PIPAMD_F_MINUS)
+      atomicMin(&sc->pivi, (int)S.srow[s]);
+    else if (ff == PIPAMD_F_UNKNOWN && bigparm < 0) {
+      const int ec = exam_class(S.sig[s]);
+      S.nf[s] = (u8)ec;
+      if (ec == PIPAMD_F_MINUS) atomicMin(&sc->pivi2, (int)S.srow[s]);
+    }
+  }
+}
+// the flags exam_coef would assign were computed with the post-pivot hints; they are applied up to the first row
+// `pivi` it proves negative (traiter.c:154-156)
+template <class T, int NT>
+__device__ __forceinline__ void apply_exam_flags(const Shared<T> &S, int ni, int pivi, int tid) {
+  for (int s = tid; s < ni; s += NT)
+    if (S.fl[s] == PIPAMD_F_UNKNOWN && (int)S.srow[s] <= pivi) S.fl[s] = S.nf[s];
+}
+
+// One wave: the slots a pivot has to rewrite -- the recycled pivot slot plus every real row that is non-zero in the
+// pivot column (word `pe`, bit `pl` of its bitmap) or not yet reduced, or every row (noskip) -- into S.work; their number
+template <class T, int NM>
+__device__ __forceinline__ int pivot_work_list(const Shared<T> &S, int ni, int pslot, int pe, int pl, bool noskip, int lane) {
+  int base = 0;
+  for (int s0 = 0; s0 < ni; s0 += 64) {
+    const int s = s0 + lane;
+    bool need = false;
+    if (s < ni) {
+      if (s == pslot)
+        need = true;
+      else {
+        const bool nzb = (S.nzm[(size_t)s * NM + pe] >> pl) & 1;
+        if (nzb || !(S.sig[s] & SIG_RED) || noskip)
+          need = true;
+        else
+          S.sig[s] &= ~0xC0;  // entry in the pivot column is 0: sign hint "zero"
+      }
+    }
+    const u64 m = ballot64(need);
+    if (need) S.work[base + __popcll(m & ((1ull << lane) - 1))] = (u16)s;
+    base += __popcll(m);
+  }
+  return base;
+}
+
+// Phase C of a pivot, traiter.c:503-529: the pivot row (logical row pivi, slot pslot) becomes the unit row of column
+// pivj, its slot now holds the row that replaces ku's unit row (denominator: the pivot); every row's flag follows the
+// sign of its new pivot-column entry; the next chercher(Minus) and the tentative exam_coef flags (not with a big parameter)
+template <class T, int NT>
+__device__ __forceinline__ void pivot_swap_roles(const Shared<T> &S, Scalars *sc, int ni, int pivi, int pivj, int pslot, int ku,
+                                                 T pivot, int bigparm, int tid) {
+  if (tid == 0) {  // traiter.c:514-516
+    S.ref[pivi] = (u16)(UNITBIT | UNITZERO | pivj);
+    S.urow[pivj] = (u16)pivi;
+  }
+  for (int s = tid; s < ni; s += NT) {
+    int ff, k;
+    if (s == pslot) {  // traiter.c:503-513
+      k = ku;
+      ff = PIPAMD_F_PLUS;
+      S.den[s] = pivot;
+      S.srow[s] = (u16)ku;
+      S.ref[ku] = (u16)s;
+    } else {
+      k = S.srow[s];
+      ff = S.fl[s];
+    }
+    // traiter.c:518-529
+    const int sg = S.sig[s];
+    const int ps = SIG_PIV(sg);
+    const int fff = ps == 1 ? PIPAMD_F_PLUS : (ps == 2 ? PIPAMD_F_MINUS : PIPAMD_F_ZERO);
+    if (fff != PIPAMD_F_ZERO && fff != ff) {
+      if (ff == PIPAMD_F_ZERO)
+        ff = (fff == PIPAMD_F_MINUS) ? PIPAMD_F_UNKNOWN : fff;
+      else
+        ff = PIPAMD_F_UNKNOWN;
+    }
+    S.fl[s] = (u8)ff;
+    if (ff & PIPAMD_F_MINUS)
+      atomicMin(&sc->pivi, k);
+    else if (ff == PIPAMD_F_UNKNOWN && bigparm < 0) {
+      const int ec = exam_class(sg);
+      S.nf[s] = (u8)ec;
+      if (ec == PIPAMD_F_MINUS) atomicMin(&sc->pivi2, k);
+    }
+  }
+}
+
+// one wave: the largest magnitude class among the rows
+template <class T>
+__device__ __forceinline__ int max_row_class(const Shared<T> &S, int ni, int lane) {
+  int mc = 0;
+  for (int s = lane; s < ni; s += 64)
+    if (S.rcls[s] > mc) mc = S.rcls[s];
+  return ballot64(mc == 3) ? 3 : (ballot64(mc == 2) ? 2 : (ballot64(mc == 1) ? 1 : 0));
+}
+
 // GM: the job's row tables (the "LDS image": Shared<T>) live in HBM instead of LDS -- one block of
 // `gimg_bytes` per workgroup at `gimg` -- for jobs whose tables outgrow the 159 KiB a workgroup can
 // get.  Same code, every table access becomes a global access (cached in this CU's L1/L2); only
@@ -1624,7 +1797,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 1 && NCH == 1 && sizeof(T) == 8) ? 
     if (J->status == PIPAMD_ST_CAPACITY && q.out_count && threadIdx.x == 0) {
       q.out_list[atomicAdd(q.out_count, 1)] = jb;
       atomicMax(q.out_maxni, PIPAMD_Q_CAPFLAG | J->ni);
-      atomicAdd(q.out_maxni + 1, 1);  // (the list\'s third control word: tableaux out of rows)
+      atomicAdd(q.out_maxni + 1, 1);  // (the list's third control word: tableaux out of rows)
     }
     return;
   }
@@ -1651,9 +1824,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 1 && NCH == 1 && sizeof(T) == 8) ? 
   const int ncol = nvar + nparm + 1;
   const int ncolp = ET<T>::CPL == 2 ? ((ncol + 1) & ~1) : ncol;  // rows are whole 16-byte units
   T *vals = (T *)(arena + J->vals_off);
-  T *g_den = (T *)(arena + J->rows_off);
-  int *g_flag = (int *)(g_den + L);
-  int *g_ref = g_flag + L;
+  const PipRowTables<T> g_rows = pip_row_tables<T>(arena + J->rows_off, L);
   int nligne = nvar + ni;
   int npiv = J->npiv, ncut = J->ncut, nupd = J->nupd;
   // The determinant limbs (traiter.c:412-446) are not updated here: every pivot appends (pivot,
@@ -1702,9 +1873,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 1 && NCH == 1 && sizeof(T) == 8) ? 
   }
 
   // saved LDS state of a paused job (bitmaps, sign summaries, magnitude classes)
-  u64 *g_nzm = (u64 *)(arena + J->state_off);
-  u16 *g_sig = (u16 *)(g_nzm + (size_t)Sl * NM);
-  u8 *g_rcls = (u8 *)(g_sig + Sl);
+  const SavedSummaries g_state = saved_summaries(arena + J->state_off, Sl, NM);
 
   // A job loaded with PIPAMD_T_ROWS_STAY: its rows are still in the caller's array (slot s = input row s, pitch
   // ncol).  The one-wave bulk kernels fetch them in the pass that builds the summaries (FUSE, below); the other
@@ -1726,39 +1895,18 @@ __global__ __launch_bounds__(64 * NW, (NW == 1 && NCH == 1 && sizeof(T) == 8) ? 
   }
   // ---- stage the row tables in LDS -------------------------------------
   for (int j = tid; j < WP; j += NT) S.urow[j] = NOROW;  // prow is written whole by every phase A
-  if (tid == 0) {
-    sc.ovf = 0;
-    sc.aux = 0;
-    sc.smaxbits = 0;
-    sc.pivi = BIG_I;
-    sc.pivi2 = BIG_I;
-    sc.flagor = 0;
-    sc.bad = 0;
-  }
+  if (tid == 0) reset_scalars(sc);
   bsync<NW>();
-  for (int i = tid; i < nligne; i += NT) {
-    const int f = g_flag[i], rf = g_ref[i];
-    if (f & PIPAMD_F_UNIT) {
-      S.ref[i] = (u16)(UNITBIT | ((f & PIPAMD_F_ZERO) ? UNITZERO : 0) | rf);
-      S.urow[rf] = (u16)i;
-    } else {
-      S.ref[i] = (u16)rf;
-      S.srow[rf] = (u16)i;
-      S.fl[rf] = (u8)f;
-      S.den[rf] = g_den[i];
-      S.size[rf] = 0.f;
-      S.nf[rf] = 0;
-    }
-  }
+  stage_row_tables<T, NT, true>(S, {g_rows.den, g_rows.flag, g_rows.ref}, nligne, tid);
   bsync<NW>();
   PROF(13);
   if ((tflags & PIPAMD_T_STATE) && J->state_nch == NCH) {
     // resumed job: the summaries were saved when it paused
     for (int s = tid; s < ni; s += NT) {
-      S.sig[s] = g_sig[s];
-      S.rcls[s] = g_rcls[s];
+      S.sig[s] = g_state.sig[s];
+      S.rcls[s] = g_state.rcls[s];
     }
-    for (int e = tid; e < ni * NM; e += NT) S.nzm[e] = g_nzm[e];
+    for (int e = tid; e < ni * NM; e += NT) S.nzm[e] = g_state.nzm[e];
     for (int s = tid; s < ni; s += NT) S.cst[s] = vals[(size_t)s * W + nvar];
   } else {
     // one pass over the tableau: sign summaries, bitmaps, magnitudes, sort keys (PF rows of a
@@ -1843,18 +1991,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 1 && NCH == 1 && sizeof(T) == 8) ? 
     bsync<NW>();
   }
   PROF(15);
-  // chercher(Minus) and the tentative exam_coef flags for the first iteration; later
-  // iterations get both from phase C
-  for (int s = tid; s < ni; s += NT) {
-    const int ff = S.fl[s];
-    if (ff & PIPAMD_F_MINUS)
-      atomicMin(&sc.pivi, (int)S.srow[s]);
-    else if (ff == PIPAMD_F_UNKNOWN && bigparm < 0) {
-      const int ec = exam_class(S.sig[s]);
-      S.nf[s] = (u8)ec;
-      if (ec == PIPAMD_F_MINUS) atomicMin(&sc.pivi2, (int)S.srow[s]);
-    }
-  }
+  first_chercher<T, NT>(S, &sc, ni, bigparm, tid);
   bsync<NW>();
 
   int status = PIPAMD_ST_RUN;
@@ -1868,13 +2005,10 @@ __global__ __launch_bounds__(64 * NW, (NW == 1 && NCH == 1 && sizeof(T) == 8) ? 
       if (bigparm >= 0) {
         pivi = exam_rows<T, NW>(S, &sc, ni);
       } else {
-        // the flags exam_coef would assign were computed with the post-pivot hints; they are
-        // applied up to the first row it proves negative (traiter.c:154-156)
         for (int rep11 = 0; rep11 < PIP_DUP_REPS(11); rep11++) {
           if (PIP_DUP == 11) PIP_OPAQUE_MEM();
           pivi = sc.pivi2;
-          for (int s = tid; s < ni; s += NT)
-            if (S.fl[s] == PIPAMD_F_UNKNOWN && (int)S.srow[s] <= pivi) S.fl[s] = S.nf[s];
+          apply_exam_flags<T, NT>(S, ni, pivi, tid);
           bsync<NW>();
         }
       }
@@ -2027,10 +2161,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 1 && NCH == 1 && sizeof(T) == 8) ? 
       if (PIP_DUP == 14) PIP_OPAQUE_MEM();
       row_load<T, NCH>(pr, vals + (size_t)pslot * W, ncolp, lane);
       // (while the pivot row is on its way) largest magnitude class of any row, for the guard below
-      mc = 0;
-      for (int s = lane; s < ni; s += 64)
-        if (S.rcls[s] > mc) mc = S.rcls[s];
-      mc = ballot64(mc == 3) ? 3 : (ballot64(mc == 2) ? 2 : (ballot64(mc == 1) ? 1 : 0));
+      mc = max_row_class(S, ni, lane);
       amax = 0;
 #pragma unroll
       for (int c = 0; c < NCH; c++)
@@ -2060,32 +2191,12 @@ __global__ __launch_bounds__(64 * NW, (NW == 1 && NCH == 1 && sizeof(T) == 8) ? 
       }
       PROF(4);
       if (pj >= 0) {
-        // slots the elimination has to rewrite: the recycled pivot slot plus every real row
-        // that is non-zero in column pj or not yet reduced
         constexpr int CW = 64 * ET<T>::CPL;
         const int pe = (pj / CW) * ET<T>::CPL + (pj % ET<T>::CPL), pl = (pj % CW) / ET<T>::CPL;
         int base = 0;
         for (int rep13 = 0; rep13 < PIP_DUP_REPS(13); rep13++) {
         if (PIP_DUP == 13) PIP_OPAQUE_MEM();
-        base = 0;
-        for (int s0 = 0; s0 < ni; s0 += 64) {
-          const int s = s0 + lane;
-          bool need = false;
-          if (s < ni) {
-            if (s == pslot)
-              need = true;
-            else {
-              const bool nzb = (S.nzm[(size_t)s * NM + pe] >> pl) & 1;
-              if (nzb || !(S.sig[s] & SIG_RED) || (tflags & PIPAMD_T_NOSKIP))
-                need = true;
-              else
-                S.sig[s] &= ~0xC0;  // entry in the pivot column is 0: sign hint "zero"
-            }
-          }
-          const u64 m = ballot64(need);
-          if (need) S.work[base + __popcll(m & ((1ull << lane) - 1))] = (u16)s;
-          base += __popcll(m);
-        }
+        base = pivot_work_list<T, NM>(S, ni, pslot, pe, pl, (tflags & PIPAMD_T_NOSKIP) != 0, lane);
         }
         if (lane == 0) sc.nwork = base;
       }
@@ -2413,42 +2524,9 @@ __global__ __launch_bounds__(64 * NW, (NW == 1 && NCH == 1 && sizeof(T) == 8) ? 
       break;
     }
     // ---------------- C: swap roles, refresh the sign hints, next chercher ------
-    if (tid == 0) {  // traiter.c:514-516: the pivot row becomes the unit row of column pivj
-      S.ref[pivi] = (u16)(UNITBIT | UNITZERO | pivj);
-      S.urow[pivj] = (u16)pivi;
-    }
-    for (int rep10 = 0; rep10 < PIP_DUP_REPS(10); rep10++)
-    for (int s = tid; s < ni; s += NT) {
+    for (int rep10 = 0; rep10 < PIP_DUP_REPS(10); rep10++) {
       if (PIP_DUP == 10) PIP_OPAQUE_MEM();
-      int ff, k;
-      if (s == pslot) {  // traiter.c:503-513: its slot now holds the row that replaces ku's unit row
-        k = ku;
-        ff = PIPAMD_F_PLUS;
-        S.den[s] = pivot;
-        S.srow[s] = (u16)ku;
-        S.ref[ku] = (u16)s;
-      } else {
-        k = S.srow[s];
-        ff = S.fl[s];
-      }
-      // traiter.c:518-529
-      const int sg = S.sig[s];
-      const int ps = SIG_PIV(sg);
-      const int fff = ps == 1 ? PIPAMD_F_PLUS : (ps == 2 ? PIPAMD_F_MINUS : PIPAMD_F_ZERO);
-      if (fff != PIPAMD_F_ZERO && fff != ff) {
-        if (ff == PIPAMD_F_ZERO)
-          ff = (fff == PIPAMD_F_MINUS) ? PIPAMD_F_UNKNOWN : fff;
-        else
-          ff = PIPAMD_F_UNKNOWN;
-      }
-      S.fl[s] = (u8)ff;
-      if (ff & PIPAMD_F_MINUS)
-        atomicMin(&sc.pivi, k);
-      else if (ff == PIPAMD_F_UNKNOWN && bigparm < 0) {
-        const int ec = exam_class(sg);
-        S.nf[s] = (u8)ec;
-        if (ec == PIPAMD_F_MINUS) atomicMin(&sc.pivi2, k);
-      }
+      pivot_swap_roles<T, NT>(S, &sc, ni, pivi, pivj, pslot, ku, pivot, bigparm, tid);
     }
     bsync<NW>();
     PROF(7);
@@ -2456,27 +2534,12 @@ __global__ __launch_bounds__(64 * NW, (NW == 1 && NCH == 1 && sizeof(T) == 8) ? 
 
   // ---- epilogue: publish the row tables, the header and (if any) the solution
   bsync<NW>();
-  for (int i = tid; i < nligne; i += NT) {
-    const int rf = S.ref[i];
-    if (rf & UNITBIT) {
-      g_den[i] = 1;
-      g_flag[i] = PIPAMD_F_UNIT | ((rf & UNITZERO) ? PIPAMD_F_ZERO : 0);
-      g_ref[i] = UNITCOL(rf);
-    } else {
-      g_den[i] = S.den[rf];
-      g_flag[i] = S.fl[rf];
-      g_ref[i] = rf;
-    }
-  }
+  publish_row_tables<T, NT>(S, g_rows, nligne, tid);
   tflags &= ~PIPAMD_T_STATE;
   if (status == PIPAMD_ST_RUN || status == PIPAMD_ST_NEED_COMPA) {
     // paused (pivot budget spent, LDS image full, or waiting for the host's sign tests, which
     // only touch flags): save the summaries for the launch that resumes the job
-    for (int s = tid; s < ni; s += NT) {
-      g_sig[s] = S.sig[s];
-      g_rcls[s] = S.rcls[s];
-    }
-    for (int e = tid; e < ni * NM; e += NT) g_nzm[e] = S.nzm[e];
+    save_summaries<T, NT>(S, g_state, ni, NM, tid);
     tflags |= PIPAMD_T_STATE;
   }
   if (status == PIPAMD_ST_SOLUTION) {
@@ -2497,11 +2560,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 1 && NCH == 1 && sizeof(T) == 8) ? 
     }
   }
   int mc = 0;
-  if (wave == 0) {
-    for (int s = lane; s < ni; s += 64)
-      if (S.rcls[s] > mc) mc = S.rcls[s];
-    mc = ballot64(mc == 3) ? 3 : (ballot64(mc == 2) ? 2 : (ballot64(mc == 1) ? 1 : 0));
-  }
+  if (wave == 0) mc = max_row_class(S, ni, lane);
   if (tid == 0) {
     J->ni = ni;
     J->npiv = npiv;
@@ -2520,7 +2579,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 1 && NCH == 1 && sizeof(T) == 8) ? 
     if (status == PIPAMD_ST_CAPACITY && q.out_count) {  // no spare row left: the host re-houses it (expanser)
       q.out_list[atomicAdd(q.out_count, 1)] = jb;
       atomicMax(q.out_maxni, PIPAMD_Q_CAPFLAG | ni);
-      atomicAdd(q.out_maxni + 1, 1);  // (the list\'s third control word: tableaux out of rows)
+      atomicAdd(q.out_maxni + 1, 1);  // (the list's third control word: tableaux out of rows)
     }
   }
   if constexpr (GM) {  // give the HBM image back

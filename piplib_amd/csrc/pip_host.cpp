@@ -96,30 +96,22 @@ int pipamd_batch_layout(const pipamd_batch_desc *d, PipBatchLayout *lay, size_t 
   lay->tflags = d->tflags & ~(PIPAMD_T_ROWS_STAY | PIPAMD_T_FRESHROWS);  // the load sets FRESHROWS itself
   lay->pad = 0;
   lay->S = d->ni + d->cap_cuts;
-  lay->L = round_even(d->nvar + lay->S);
   lay->W = ebits == 128 ? ncol + d->cap_newparm : round_even(ncol + d->cap_newparm);
+  const int wp = ebits == 128 ? (lay->W <= 64 ? 64 : (lay->W <= 128 ? 128 : (lay->W <= 256 ? 256 : 512)))
+                              : (lay->W <= 128 ? 128 : (lay->W <= 256 ? 256 : 512));
+  lay->blk = pip_block_layout(d->nvar, lay->S, lay->W, ew, (int64_t)d->nvar * (d->nparm + d->cap_newparm + 1) + d->nvar, wp / 64);
   // 64-bit tableaux whose row tables outgrow LDS run with the tables in HBM; 128-bit ones must fit
-  if (lay->L > PIPAMD_LMAX || lay->S > PIPAMD_SMAX || lay->W > PIPAMD_MAXCOL || lay->S < 1 ||
-      (ebits == 128 && pipk_advance_lds_bytes((lay->L + 3) & ~3, (lay->S + 3) & ~3, lay->W, ebits) > PIPAMD_LDS_BUDGET)) {
-    pipamd_set_error("batch shape exceeds engine limits (L=%d<=%d, S=%d<=%d, W=%d<=%d, LDS image %zu<=%d bytes)", lay->L,
+  if (lay->blk.L > PIPAMD_LMAX || lay->S > PIPAMD_SMAX || lay->W > PIPAMD_MAXCOL || lay->S < 1 ||
+      (ebits == 128 && pipk_advance_lds_bytes((lay->blk.L + 3) & ~3, (lay->S + 3) & ~3, lay->W, ebits) > PIPAMD_LDS_BUDGET)) {
+    pipamd_set_error("batch shape exceeds engine limits (L=%d<=%d, S=%d<=%d, W=%d<=%d, LDS image %zu<=%d bytes)", lay->blk.L,
                      PIPAMD_LMAX, lay->S, PIPAMD_SMAX, lay->W, PIPAMD_MAXCOL,
-                     pipk_advance_lds_bytes((lay->L + 3) & ~3, (lay->S + 3) & ~3, lay->W, ebits), PIPAMD_LDS_BUDGET);
+                     pipk_advance_lds_bytes((lay->blk.L + 3) & ~3, (lay->S + 3) & ~3, lay->W, ebits), PIPAMD_LDS_BUDGET);
     return PIPAMD_E_TOOLARGE;
   }
   if (d->bigparm >= ncol || (d->bigparm >= 0 && d->bigparm <= d->nvar)) {
     pipamd_set_error("bigparm must be -1 or a parameter column (nvar < bigparm < ncol)");
     return PIPAMD_E_INVALID;
   }
-  const int64_t sol = round_even((d->nvar * (d->nparm + d->cap_newparm + 1) + d->nvar) * ew);
-  const int wp = ebits == 128 ? (lay->W <= 64 ? 64 : (lay->W <= 128 ? 128 : (lay->W <= 256 ? 256 : 512)))
-                              : (lay->W <= 128 ? 128 : (lay->W <= 256 ? 256 : 512));
-  const int nm = wp / 64;
-  // saved summaries, then the determinant log of the last launch (64-bit jobs)
-  const int64_t state = round_even(lay->S * nm + (3 * lay->L + 7) / 8) + 2 * PIPAMD_DETLOG * ew;
-  lay->sol_words = (int32_t)sol;
-  lay->state_words = (int32_t)state;
-  // rows: den[L] (entry type) | flag[L] | ref[L];  then S x W entries;  solution;  saved summaries
-  lay->per_job = ((int64_t)lay->L * ew + lay->L) + (int64_t)lay->S * lay->W * ew + sol + state;
   lay->arena_off = 0;
   *jobs_bytes = ((size_t)d->batch * sizeof(PipJob) + 255) & ~(size_t)255;
   return PIPAMD_OK;
@@ -129,7 +121,7 @@ extern "C" size_t pipamd_batch_workspace_bytes(const pipamd_batch_desc *d) {
   PipBatchLayout lay;
   size_t jb;
   if (pipamd_batch_layout(d, &lay, &jb) != PIPAMD_OK) return 0;
-  return jb + (size_t)lay.per_job * (size_t)d->batch * sizeof(int64_t);
+  return jb + (size_t)lay.blk.words * (size_t)d->batch * sizeof(int64_t);
 }
 
 extern "C" size_t pipamd_dense_pivot_bytes(const pipamd_batch_desc *d) {
@@ -244,7 +236,7 @@ struct BatchRun {
     int rc2 = next_stage();
     if (rc2) return rc2;
     const bool room = grow_round < PIPAMD_MAX_GROW;
-    const size_t per_job_bytes = (size_t)nl.per_job * sizeof(int64_t);
+    const size_t per_job_bytes = (size_t)nl.blk.words * sizeof(int64_t);
     const size_t need = per_job_bytes * (size_t)ncap + 16;
     int side_cap = 0;
     if (room) {
@@ -490,7 +482,7 @@ struct BatchRun {
       return rc ? rc : 0;
     }
     if (grow_round > 0) {  // the side arenas serve the engine's next solve: the solve ends when the copy-back has
-      HIPCHK(pipk_launch_rehouse_finish(jobs, arena, lay.batch, lay.sol_words, st));
+      HIPCHK(pipk_launch_rehouse_finish(jobs, arena, lay.batch, (int)(lay.blk.state - lay.blk.sol), st));
       finishing = true;
       return 0;
     }

@@ -22,12 +22,15 @@
  * only the walk over the limbs sequentially. */
 #define PIPAMD_DETLOG 512
 
-/* One problem ("job") in the device arena.  All offsets are in int64 units from the
- * arena base and are even (rows are 16-byte aligned).
- *   rows_off: den[L] (int64) | flag[L] (int32) | ref[L] (int32)      = 2*L int64
- *   vals_off: S slots of W int64 (zero beyond the live columns)
- *   sol_off : nvar*(nparm+1) numerators | nvar denominators
- *   state_off: LDS summaries of a paused job: nzm[S][NM] (u64) | sig[L] (u16) | rbits[L] (u8)
+/* One problem ("job") in the device arena: a PipJob header and a block of int64 words.  Every offset is in int64
+ * units and even (rows are 16-byte aligned); an entry is `ew` words (1: 64-bit entries, 2: 128-bit entries).  A block
+ * of L logical rows, S real rows (slots) and W columns, in this order (pip_block_layout below is the one place that
+ * computes it):
+ *   rows  : den[L] (entries) | flag[L] (int32) | ref[L] (int32)         -- pip_row_tables
+ *   vals  : S slots of W entries (zero beyond the live columns)
+ *   sol   : nvar*(nparm+1) numerators | nvar denominators (entries; room for the columns a job may grow)
+ *   state : summaries of a paused job: nzm[S][NM] (u64) | sig[S] (u16) | rcls[S] (u8), NM bitmap words per slot
+ *   log   : 2 * PIPAMD_DETLOG entries, the determinant log of the last launch
  * Mirrors the reference's struct T / struct L (tab.h:36-85) without pointers. */
 /* internal tflags bit: the job's rows still sit in the caller's array (src_rows); the first pivot launch
  * reads them from there while it builds its summaries and writes them into the block (PIPAMD_T_ROWS_STAY) */
@@ -56,12 +59,62 @@ typedef struct PipJob {
  * counts these jobs (the host sizes the larger blocks' arena by it) */
 #define PIPAMD_Q_CAPFLAG (1 << 30)
 
+#ifdef __HIPCC__
+#define PIP_HD __host__ __device__
+#else
+#define PIP_HD
+#endif
+
+/* Where the parts of a block start (int64 words from the block's first word) and how long it is. */
+typedef struct PipBlockLayout {
+  int32_t L, pad; /* logical rows: nvar + S, rounded up to even */
+  int64_t vals, sol, state, log, words;
+} PipBlockLayout;
+
+/* sol_entries: entries of the solution part; nm: bitmap words per slot the saved summaries have room for */
+PIP_HD constexpr PipBlockLayout pip_block_layout(int nvar, int S, int W, int ew, int64_t sol_entries, int nm) {
+  PipBlockLayout b{};
+  b.L = (nvar + S + 1) & ~1;
+  b.vals = (int64_t)b.L * ew + b.L;
+  b.sol = b.vals + (int64_t)S * W * ew;
+  b.state = b.sol + ((sol_entries * ew + 1) & ~(int64_t)1);
+  b.log = b.state + (((int64_t)S * nm + (3 * b.L + 7) / 8 + 1) & ~(int64_t)1);
+  b.words = b.log + 2 * PIPAMD_DETLOG * ew;
+  return b;
+}
+/* a job's header takes a block of layout `b` at arena word `base` */
+PIP_HD inline void pip_job_place(PipJob *J, int64_t base, const PipBlockLayout &b) {
+  J->rows_off = base;
+  J->vals_off = base + b.vals;
+  J->sol_off = base + b.sol;
+  J->state_off = base + b.state;
+  J->log_off = base + b.log;
+  J->L = b.L;
+}
+/* the row tables at the head of a block of L logical rows with entries of type T (pointer arithmetic only: the
+ * pointers are as const, and as dereferenceable, as `rows` is); the flag table in 32-bit words from the block's start */
+PIP_HD constexpr int64_t pip_flag_off32(int L, int ew) { return (int64_t)2 * L * ew; }
+template <class T>
+struct PipRowTables {
+  T *den;
+  int *flag, *ref;
+};
+/* (den as int64 words, ew per entry: for code that learns the entry width at run time) */
+PIP_HD inline PipRowTables<int64_t> pip_row_words(const void *rows, int L, int ew) {
+  int *flag = (int *)rows + pip_flag_off32(L, ew);
+  return {(int64_t *)rows, flag, flag + L};
+}
+template <class T>
+PIP_HD inline PipRowTables<T> pip_row_tables(const void *rows, int L) {
+  const PipRowTables<int64_t> w = pip_row_words(rows, L, sizeof(T) / 8);
+  return {(T *)w.den, w.flag, w.ref};
+}
+
 typedef struct PipBatchLayout {
-  int64_t arena_off; /* first job's block, int64 units */
-  int64_t per_job;   /* block size per job, int64 units */
+  int64_t arena_off;  /* first job's block, int64 units */
+  PipBlockLayout blk; /* every job's block (blk.words apart) */
   int32_t batch, nvar, nparm, ni, bigparm, tflags;
-  int32_t L, S, W;
-  int32_t sol_words, state_words;
+  int32_t S, W;
   int32_t ebits, pad;
 } PipBatchLayout;
 

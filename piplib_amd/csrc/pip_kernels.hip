@@ -155,13 +155,10 @@ __global__ void pip_batch_load_kernel(PipJob *jobs, i64 *arena, const i64 *rows,
   const int tid = threadIdx.x;
   const int ncol = lay.nvar + lay.nparm + 1;
   PipJob *J = &jobs[b];
-  const int64_t base = lay.arena_off + (int64_t)b * lay.per_job;
-  T *g_den = (T *)(arena + base);
-  int *g_flag = (int *)(g_den + lay.L);
-  int *g_ref = g_flag + lay.L;
-  const int64_t rows_words = (int64_t)lay.L * EW + lay.L;
-  T *vals = (T *)(arena + base + rows_words);
-  for (int i = tid; i < lay.L; i += blockDim.x) {
+  const int64_t base = lay.arena_off + (int64_t)b * lay.blk.words;
+  const auto [g_den, g_flag, g_ref] = pip_row_tables<T>(arena + base, lay.blk.L);
+  T *vals = (T *)(arena + base + lay.blk.vals);
+  for (int i = tid; i < lay.blk.L; i += blockDim.x) {
     if (i < lay.nvar) {
       g_flag[i] = PIPAMD_F_UNIT;
       g_ref[i] = i;
@@ -201,11 +198,7 @@ __global__ void pip_batch_load_kernel(PipJob *jobs, i64 *arena, const i64 *rows,
     vals[(size_t)s * lay.W + j] = 0;
   }
   if (tid == 0) {
-    J->rows_off = base;
-    J->vals_off = base + rows_words;
-    J->sol_off = J->vals_off + (int64_t)lay.S * lay.W * EW;
-    J->state_off = J->sol_off + lay.sol_words;
-    J->log_off = J->state_off + lay.state_words - 2 * PIPAMD_DETLOG * EW;
+    pip_job_place(J, base, lay.blk);
     J->nlog = 0;
     J->nvar = lay.nvar;
     J->nparm = lay.nparm;
@@ -214,7 +207,6 @@ __global__ void pip_batch_load_kernel(PipJob *jobs, i64 *arena, const i64 *rows,
     J->tflags = lay.tflags | PIPAMD_T_SORT | (defer ? PIPAMD_T_FRESHROWS : 0);
     J->src_rows = defer ? (int64_t)(uintptr_t)src : 0;
     J->home_sol_off = 0;
-    J->L = lay.L;
     J->S = lay.S;
     J->W = lay.W;
     J->status = PIPAMD_ST_RUN;
@@ -290,30 +282,23 @@ __global__ __launch_bounds__(256) void pip_rehouse_kernel(PipJob *jobs, i64 *are
   if (s_idx >= side_cap) return;
   const int EW = J->ebits == 128 ? 2 : 1;
   const int oL = J->L, oS = J->S, W = J->W, nligne = J->nvar + J->ni;
-  const i64 base = nl.arena_off + (i64)s_idx * nl.per_job;
-  const i64 rows_words = (i64)nl.L * EW + nl.L;
-  const i64 *oden = arena + J->rows_off;
-  const int *oflag = (const int *)(oden + (i64)oL * EW), *oref = oflag + oL;
-  i64 *nden = arena + base;
-  int *nflag = (int *)(nden + (i64)nl.L * EW), *nref = nflag + nl.L;
-  for (int e = tid; e < nl.L * EW; e += blockDim.x) nden[e] = e < nligne * EW ? oden[e] : 0;
-  for (int k = tid; k < nl.L; k += blockDim.x) {
+  const i64 base = nl.arena_off + (i64)s_idx * nl.blk.words;
+  // (entries move as int64 words, whatever their width)
+  const auto [oden, oflag, oref] = pip_row_words(arena + J->rows_off, oL, EW);
+  const auto [nden, nflag, nref] = pip_row_words(arena + base, nl.blk.L, EW);
+  for (int e = tid; e < nl.blk.L * EW; e += blockDim.x) nden[e] = e < nligne * EW ? oden[e] : 0;
+  for (int k = tid; k < nl.blk.L; k += blockDim.x) {
     nflag[k] = k < nligne ? oflag[k] : 0;
     nref[k] = k < nligne ? oref[k] : 0;
   }
   const i64 *ovals = arena + J->vals_off;
-  i64 *nvals = arena + base + rows_words;
+  i64 *nvals = arena + base + nl.blk.vals;
   const i64 ow = (i64)oS * W * EW, nw = (i64)nl.S * W * EW;
   for (i64 e = tid; e < nw; e += blockDim.x) nvals[e] = e < ow ? ovals[e] : 0;
   __syncthreads();
   if (tid == 0) {
     if (J->home_sol_off == 0) J->home_sol_off = J->sol_off;
-    J->rows_off = base;
-    J->vals_off = base + rows_words;
-    J->sol_off = J->vals_off + nw;
-    J->state_off = J->sol_off + nl.sol_words;
-    J->log_off = J->state_off + nl.state_words - 2 * PIPAMD_DETLOG * EW;
-    J->L = nl.L;
+    pip_job_place(J, base, nl.blk);
     J->S = nl.S;
     J->tflags &= ~PIPAMD_T_STATE;
     J->status = PIPAMD_ST_RUN;
@@ -374,21 +359,18 @@ __global__ void pip_patch_kernel(int *arena32, const int *buf, const i64 *index,
   for (int i = threadIdx.x; i < nw; i += blockDim.x) arena32[dst + i] = p[3 + i];
 }
 // fresh: build new tableaux (tab_alloc + tab_get, tab.c:158-248) from their rows alone.
-// Record r at buf[index[r]] (int64 words): rows_off, nvar, ni, ncol, L, S, W, 0, then ni*ncol values of the entry type T
+// Record r at buf[index[r]] (int64 words): rows_off, nvar, ni, ncol, L, S, W, vals_off, then ni*ncol values of the entry type T
 // (the offsets are the job's, in int64 words; a 128-bit value is two words, low first).
 template <class T>
 __global__ void pip_fresh_kernel(i64 *arena, const i64 *buf, const i64 *index, int n) {
-  constexpr int EW = sizeof(T) / 8;
   const int b = blockIdx.x;
   if (b >= n) return;
   const i64 *p = buf + index[b];
   const i64 rows_off = p[0];
   const int nvar = (int)p[1], ni = (int)p[2], ncol = (int)p[3], L = (int)p[4], S = (int)p[5], W = (int)p[6];
   const T *src = (const T *)(p + 8);
-  T *g_den = (T *)(arena + rows_off);
-  int *g_flag = (int *)(g_den + L);
-  int *g_ref = g_flag + L;
-  T *vals = (T *)(arena + rows_off + (i64)L * EW + L);
+  const auto [g_den, g_flag, g_ref] = pip_row_tables<T>(arena + rows_off, L);
+  T *vals = (T *)(arena + p[7]);
   for (int i = threadIdx.x; i < nvar + ni; i += blockDim.x) {
     g_den[i] = 1;
     g_flag[i] = i < nvar ? PIPAMD_F_UNIT : PIPAMD_F_UNKNOWN;
@@ -418,9 +400,7 @@ __global__ void pip_gather_kernel(const PipJob *jobs, const i64 *arena, int njob
   if (off[b + 1] == off[b]) return;  // the host does not want anything from this job
   T *o = (T *)(out + off[b]);
   const int nvar = J->nvar, nparm = J->nparm, L = J->L, W = J->W, ncol = nvar + nparm + 1;
-  const T *g_den = (const T *)(arena + J->rows_off);
-  const int *g_flag = (const int *)(g_den + L);
-  const int *g_ref = g_flag + L;
+  const auto [g_den, g_flag, g_ref] = pip_row_tables<const T>(arena + J->rows_off, L);
   const T *vals = (const T *)(arena + J->vals_off);
   const int lane = threadIdx.x;  // one wave
   if (J->status == PIPAMD_ST_NEED_COMPA) {

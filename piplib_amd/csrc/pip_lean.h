@@ -600,37 +600,11 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
     S.rcls = (u8 *)p;    p += Smax;
   }
 
-  // ---- the row tables (as pip_advance_kernel stages them)
+  // ---- the row tables (the sort keys share storage with the constant terms here: not zeroed)
   for (int j = lane; j < WP; j += 64) S.urow[j] = NOROW;
-  if (lane == 0) {
-    sc.ovf = 0;
-    sc.aux = 0;
-    sc.smaxbits = 0;
-    sc.pivi = BIG_I;
-    sc.pivi2 = BIG_I;
-    sc.flagor = 0;
-    sc.bad = 0;
-  }
+  if (lane == 0) reset_scalars(sc);
   __builtin_amdgcn_wave_barrier();
-  {
-    const int L = J->L;
-    const T *g_den = (const T *)(arena + J->rows_off);
-    const int *g_flag = (const int *)(g_den + L);
-    const int *g_ref = g_flag + L;
-    for (int i = lane; i < nligne; i += 64) {
-      const int f = g_flag[i], rf = g_ref[i];
-      if (f & PIPAMD_F_UNIT) {
-        S.ref[i] = (u16)(UNITBIT | ((f & PIPAMD_F_ZERO) ? UNITZERO : 0) | rf);
-        S.urow[rf] = (u16)i;
-      } else {
-        S.ref[i] = (u16)rf;
-        S.srow[rf] = (u16)i;
-        S.fl[rf] = (u8)f;
-        S.den[rf] = g_den[i];
-        S.nf[rf] = 0;
-      }
-    }
-  }
+  stage_row_tables<T, 64, false>(S, pip_row_tables<const T>(arena + J->rows_off, J->L), nligne, lane);
   __builtin_amdgcn_wave_barrier();
 
   // ---- one pass over the tableau: the rows become packed (int rows of a job loaded with PIPAMD_T_ROWS_STAY come from
@@ -640,7 +614,7 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
     constexpr int PF0 = F::ENTRY_PF, CPL = ET<T>::CPL;
     // a job that paused in an earlier launch (this kernel's or pip_advance_kernel's, rows in the general format): what the
     // entry pass cannot see in the rows -- "gcd(row, denominator) is known to be 1" -- comes from the saved summaries
-    const u16 *g_sig = (tflags & PIPAMD_T_STATE) ? (const u16 *)((const u64 *)(arena + J->state_off) + (size_t)J->S * NM) : nullptr;
+    const u16 *g_sig = (tflags & PIPAMD_T_STATE) ? saved_summaries(arena + J->state_off, J->S, NM).sig : nullptr;
     const bool fresh = F::FRESH && (tflags & PIPAMD_T_FRESHROWS) != 0;
     const T *src = fresh ? (const T *)(uintptr_t)J->src_rows : vals;
     const int pitch = fresh ? nvar + 1 : W;  // the caller's rows are nvar + 1 wide (an even number: pipamd_batch_load), the block's W
@@ -715,16 +689,7 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
     for (int s = lane; s < ni; s += 64) cst[s] = reinterpret_cast<const E *>(vals + (size_t)s * W)[nvar];
     __builtin_amdgcn_wave_barrier();
   }
-  for (int s = lane; s < ni; s += 64) {
-    const int ff = S.fl[s];
-    if (ff & PIPAMD_F_MINUS)
-      atomicMin(&sc.pivi, (int)S.srow[s]);
-    else if (ff == PIPAMD_F_UNKNOWN) {
-      const int ec = exam_class(S.sig[s]);
-      S.nf[s] = (u8)ec;
-      if (ec == PIPAMD_F_MINUS) atomicMin(&sc.pivi2, (int)S.srow[s]);
-    }
-  }
+  first_chercher<T, 64>(S, &sc, ni, -1, lane);
   __builtin_amdgcn_wave_barrier();
 
   PROF(10);
@@ -742,8 +707,7 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
     if (pivi == BIG_I) {
       // -------------- exam_coef (its flags were prepared by phase C), then integrer if nothing is negative
       pivi = sc.pivi2;
-      for (int s = lane; s < ni; s += 64)
-        if (S.fl[s] == PIPAMD_F_UNKNOWN && (int)S.srow[s] <= pivi) S.fl[s] = S.nf[s];
+      apply_exam_flags<T, 64>(S, ni, pivi, lane);
       __builtin_amdgcn_wave_barrier();
       if (pivi == BIG_I) {
         if (!(tflags & PIPAMD_T_INT)) {
@@ -838,25 +802,7 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
     }
     PROF(2);
     const int pe = F::val_of(pj), pl = F::lane_of(pj);
-    int nwork = 0;
-    for (int s0 = 0; s0 < ni; s0 += 64) {
-      const int s = s0 + lane;
-      bool need = false;
-      if (s < ni) {
-        if (s == pslot)
-          need = true;
-        else {
-          const bool nzb = (S.nzm[(size_t)s * NM + pe] >> pl) & 1;
-          if (nzb || !(S.sig[s] & SIG_RED))
-            need = true;
-          else
-            S.sig[s] &= ~0xC0;  // entry in the pivot column is 0: sign hint "zero"
-        }
-      }
-      const u64 m = ballot64(need);
-      if (need) S.work[nwork + __popcll(m & ((1ull << lane) - 1))] = (u16)s;
-      nwork += __popcll(m);
-    }
+    const int nwork = pivot_work_list<T, NM>(S, ni, pslot, pe, pl, false, lane);
     __builtin_amdgcn_wave_barrier();
     if (lane == 0) {  // phase C refills them
       sc.pivi = BIG_I;
@@ -971,75 +917,17 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
       break;
     }
     // ---------------- C: swap roles, refresh the sign hints, next chercher (traiter.c:503-529)
-    if (lane == 0) {
-      S.ref[pivi] = (u16)(UNITBIT | UNITZERO | pivj);
-      S.urow[pivj] = (u16)pivi;
-    }
-    for (int s = lane; s < ni; s += 64) {
-      int ff, k;
-      if (s == pslot) {
-        k = ku;
-        ff = PIPAMD_F_PLUS;
-        S.den[s] = (T)pivot;
-        S.srow[s] = (u16)ku;
-        S.ref[ku] = (u16)s;
-      } else {
-        k = S.srow[s];
-        ff = S.fl[s];
-      }
-      const int sg = S.sig[s];
-      const int ps = SIG_PIV(sg);
-      const int fff = ps == 1 ? PIPAMD_F_PLUS : (ps == 2 ? PIPAMD_F_MINUS : PIPAMD_F_ZERO);
-      if (fff != PIPAMD_F_ZERO && fff != ff) {
-        if (ff == PIPAMD_F_ZERO)
-          ff = (fff == PIPAMD_F_MINUS) ? PIPAMD_F_UNKNOWN : fff;
-        else
-          ff = PIPAMD_F_UNKNOWN;
-      }
-      S.fl[s] = (u8)ff;
-      if (ff & PIPAMD_F_MINUS)
-        atomicMin(&sc.pivi, k);
-      else if (ff == PIPAMD_F_UNKNOWN) {
-        const int ec = exam_class(sg);
-        S.nf[s] = (u8)ec;
-        if (ec == PIPAMD_F_MINUS) atomicMin(&sc.pivi2, k);
-      }
-    }
+    pivot_swap_roles<T, 64>(S, &sc, ni, pivi, pivj, pslot, ku, (T)pivot, -1, lane);
     __builtin_amdgcn_wave_barrier();
     PROF(9);
   }
 
-  // ---- epilogue: the row tables, the header and (if any) the solution, as pip_advance_kernel writes them
+  // ---- epilogue: the row tables, the header and (if any) the solution
   __builtin_amdgcn_wave_barrier();
-  {
-    const int L = J->L;
-    T *g_den = (T *)(arena + J->rows_off);
-    int *g_flag = (int *)(g_den + L);
-    int *g_ref = g_flag + L;
-    for (int i = lane; i < nligne; i += 64) {
-      const int rf = S.ref[i];
-      if (rf & UNITBIT) {
-        g_den[i] = 1;
-        g_flag[i] = PIPAMD_F_UNIT | ((rf & UNITZERO) ? PIPAMD_F_ZERO : 0);
-        g_ref[i] = UNITCOL(rf);
-      } else {
-        g_den[i] = S.den[rf];
-        g_flag[i] = S.fl[rf];
-        g_ref[i] = rf;
-      }
-    }
-  }
+  publish_row_tables<T, 64>(S, pip_row_tables<T>(arena + J->rows_off, J->L), nligne, lane);
   tflags &= ~PIPAMD_T_STATE;
   if (status == PIPAMD_ST_RUN) {
-    const int Sl = J->S;
-    u64 *g_nzm = (u64 *)(arena + J->state_off);
-    u16 *g_sig = (u16 *)(g_nzm + (size_t)Sl * NM);
-    u8 *g_rcls = (u8 *)(g_sig + Sl);
-    for (int s = lane; s < ni; s += 64) {
-      g_sig[s] = S.sig[s];
-      g_rcls[s] = S.rcls[s];
-    }
-    for (int e = lane; e < ni * NM; e += 64) g_nzm[e] = S.nzm[e];
+    save_summaries<T, 64>(S, saved_summaries(arena + J->state_off, J->S, NM), ni, NM, lane);
     tflags |= PIPAMD_T_STATE;
   }
   if (status == PIPAMD_ST_SOLUTION) {
@@ -1061,10 +949,7 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
     // the job goes on elsewhere (pip_advance_kernel, pip_rehouse_kernel): its rows in the general format again
     rows_unpack<F>(vals, ni, lane, W, S.rcls);
   }
-  int mc = 0;
-  for (int s = lane; s < ni; s += 64)
-    if (S.rcls[s] > mc) mc = S.rcls[s];
-  mc = ballot64(mc == 3) ? 3 : (ballot64(mc == 2) ? 2 : (ballot64(mc == 1) ? 1 : 0));
+  const int mc = max_row_class(S, ni, lane);
   if (lane == 0) {
     J->ni = ni;
     J->npiv = npiv;

@@ -158,6 +158,22 @@ template <class E> struct CtxT {
 };
 typedef CtxT<i64> Ctx;
 
+// The block of a tree's job: a solution over every column the block has, and room for the bitmaps of any launch
+// geometry (8 words per slot: jobs of mixed widths share launches).
+constexpr PipBlockLayout tree_block_layout(int nvar, int S, int W, int ew) {
+  return pip_block_layout(nvar, S, W, ew, (int64_t)nvar * (W - nvar) + nvar, 8);
+}
+// (the sizes and offsets blocks have always had, computed by hand: a change of pip_block_layout shows here)
+constexpr bool block_is(const PipBlockLayout &b, int L, i64 vals, i64 sol, i64 state, i64 log, i64 words) {
+  return b.L == L && b.vals == vals && b.sol == sol && b.state == state && b.log == log && b.words == words;
+}
+static_assert(block_is(tree_block_layout(5, 9, 6, 1), 14, 28, 82, 92, 170, 1194), "block layout");
+static_assert(block_is(tree_block_layout(20, 52, 28, 1), 72, 144, 1600, 1780, 2224, 3248), "block layout");
+static_assert(block_is(tree_block_layout(127, 88, 128, 1), 216, 432, 11696, 11950, 12736, 13760), "block layout");
+static_assert(block_is(tree_block_layout(5, 9, 6, 2), 14, 42, 150, 170, 248, 2296), "block layout");
+static_assert(block_is(tree_block_layout(20, 52, 28, 2), 72, 216, 3128, 3488, 3932, 5980), "block layout");
+static_assert(block_is(tree_block_layout(127, 88, 128, 2), 216, 648, 23176, 23684, 24470, 26518), "block layout");
+
 struct HostJob {
   PipJob pj;
   i64 block_off = 0;
@@ -318,26 +334,17 @@ class TreeT {
         fprintf(stderr, "[tree] job beyond the engine's limits: nvar %d nparm %d ni %d S %d W %d\n", nvar, nparm, ni, S, W);
       fail(PIPAMD_ST_CAPACITY);
     }
-    const int L = even(nvar + S);
-    const int nm = 8;  // room for the bitmaps of any launch geometry (jobs of mixed widths share launches)
-    const size_t sol = (size_t)even(nvar * (W - nvar) + nvar) * EW;
-    const size_t state = (size_t)even(S * nm + (3 * L + 7) / 8) + 2 * PIPAMD_DETLOG * EW;  // summaries | determinant log
-    // den[L] (entries) | flag[L] | ref[L], then S x W entries, the solution, the saved summaries
-    j.block_words = (size_t)(EW + 1) * L + (size_t)S * W * EW + sol + state;
+    const PipBlockLayout b = tree_block_layout(nvar, S, W, EW);
+    j.block_words = (size_t)b.words;
     ensure_arena(top_ + j.block_words);
     j.block_off = (i64)top_;
     top_ += j.block_words;
-    j.pj.rows_off = j.block_off;
-    j.pj.vals_off = j.block_off + (i64)(EW + 1) * L;
-    j.pj.sol_off = j.pj.vals_off + (i64)S * W * EW;
-    j.pj.state_off = j.pj.sol_off + (i64)sol;
-    j.pj.log_off = j.pj.state_off + (i64)state - 2 * PIPAMD_DETLOG * EW;
+    pip_job_place(&j.pj, j.block_off, b);
     j.pj.nvar = nvar;
     j.pj.nparm = nparm;
     j.pj.ni = ni;
     j.pj.bigparm = bigparm;
     j.pj.tflags = tflags | PIPAMD_T_SORT | (deepest_ ? PIPAMD_T_DEEPEST : 0);
-    j.pj.L = L;
     j.pj.S = S;
     j.pj.W = W;
     j.pj.status = PIPAMD_ST_RUN;
@@ -348,17 +355,15 @@ class TreeT {
   }
 
   // bytes of a job's row tables + rows, and typed views into a host copy of them
-  static size_t tab_words(int L, int S, int W) { return (size_t)(EW + 1) * L + (size_t)S * W * EW; }
-  static E *blk_den(std::vector<i64> &blk) { return (E *)blk.data(); }
-  static int *blk_flag(std::vector<i64> &blk, int L) { return (int *)(blk_den(blk) + L); }
-  static E *blk_vals(std::vector<i64> &blk, int L) { return (E *)(blk.data() + (size_t)(EW + 1) * L); }
+  static size_t tab_words(const PipJob &pj) { return (size_t)(pj.sol_off - pj.rows_off); }
+  static E *blk_vals(std::vector<i64> &blk, const PipJob &pj) { return (E *)(blk.data() + (pj.vals_off - pj.rows_off)); }
 
   // tab_alloc + tab_get (tab.c:158-248): nvar unit rows, ni Unknown rows with denominator 1
   void upload_fresh(HostJob &j, const std::vector<E> &rows /* ni x ncol */) {
-    const int nvar = j.pj.nvar, ni = j.pj.ni, ncol = nvar + j.pj.nparm + 1, L = j.pj.L, S = j.pj.S, W = j.pj.W;
-    std::vector<i64> blk(tab_words(L, S, W), 0);
-    E *den = blk_den(blk), *vals = blk_vals(blk, L);
-    int *flag = blk_flag(blk, L), *ref = flag + L;
+    const int nvar = j.pj.nvar, ni = j.pj.ni, ncol = nvar + j.pj.nparm + 1, L = j.pj.L, W = j.pj.W;
+    std::vector<i64> blk(tab_words(j.pj), 0);
+    E *vals = blk_vals(blk, j.pj);
+    const auto [den, flag, ref] = pip_row_tables<E>(blk.data(), L);
     for (int i = 0; i < nvar; i++) {
       den[i] = 1;
       flag[i] = PIPAMD_F_UNIT;
@@ -400,19 +405,18 @@ class TreeT {
     s.L = j.pj.L;
     s.S = j.pj.S;
     s.W = j.pj.W;
-    std::vector<i64> blk(tab_words(s.L, s.S, s.W));
+    std::vector<i64> blk(tab_words(j.pj));
     copy(blk.data(), d_arena_ + j.block_off, blk.size() * sizeof(i64), hipMemcpyDeviceToHost);
-    const E *den = blk_den(blk), *vals = blk_vals(blk, s.L);
+    const E *vals = blk_vals(blk, j.pj);
+    const auto [den, flag, ref] = pip_row_tables<E>(blk.data(), s.L);
     s.den.assign(den, den + s.L);
-    const int *flag = blk_flag(blk, s.L);
     s.flag.assign(flag, flag + s.L);
-    s.ref.assign(flag + s.L, flag + 2 * s.L);
+    s.ref.assign(ref, ref + s.L);
     s.vals.assign(vals, vals + (size_t)s.S * s.W);
     return s;
   }
   void set_flag(const HostJob &j, int row, int f) {
-    int *g_flag = (int *)((E *)(d_arena_ + j.pj.rows_off) + j.pj.L);
-    copy(g_flag + row, &f, sizeof(int), hipMemcpyHostToDevice);
+    copy(pip_row_tables<E>(d_arena_ + j.pj.rows_off, j.pj.L).flag + row, &f, sizeof(int), hipMemcpyHostToDevice);
   }
 
   // run the engine on a set of jobs until none is PIPAMD_ST_RUN
@@ -501,9 +505,9 @@ class TreeT {
     Snap s = download(j);
     HostJob n = alloc_job(j.pj.nvar, j.pj.nparm, j.pj.ni, j.pj.bigparm, 0, newS, newW);
     const int L = n.pj.L, W = n.pj.W, nl = j.pj.nvar + j.pj.ni;
-    std::vector<i64> blk(tab_words(L, n.pj.S, W), 0);
-    E *den = blk_den(blk), *vals = blk_vals(blk, L);
-    int *flag = blk_flag(blk, L), *ref = flag + L;
+    std::vector<i64> blk(tab_words(n.pj), 0);
+    E *vals = blk_vals(blk, n.pj);
+    const auto [den, flag, ref] = pip_row_tables<E>(blk.data(), L);
     for (int k = 0; k < nl; k++) {
       den[k] = s.den[k];
       flag[k] = s.flag[k];
@@ -672,8 +676,7 @@ class TreeT {
     for (int j = 0; j < ncol; j++) row[j] = cut[j];
     if (newcol >= 0) row[newcol] = wadd(row[newcol], cut[ncol]);
     copy((E *)(d_arena_ + job.pj.vals_off) + (size_t)ni * W, row.data(), W * sizeof(E), hipMemcpyHostToDevice);
-    E *g_den = (E *)(d_arena_ + job.pj.rows_off);
-    int *g_flag = (int *)(g_den + L), *g_ref = g_flag + L;
+    const auto [g_den, g_flag, g_ref] = pip_row_tables<E>(d_arena_ + job.pj.rows_off, L);
     const int fl = PIPAMD_F_MINUS;
     copy(g_den + nligne, &D, sizeof(E), hipMemcpyHostToDevice);
     copy(g_flag + nligne, &fl, sizeof(int), hipMemcpyHostToDevice);
@@ -825,7 +828,7 @@ class TreeT {
       const size_t mark = top_;
       HostJob child = alloc_job(nvar, nparm, ni, bigparm, flags, job.pj.S, job.pj.W);
       if (child.pj.L != job.pj.L || child.pj.S != job.pj.S || child.pj.W != job.pj.W) fail(PIPAMD_ST_INTERNAL);
-      copy(d_arena_ + child.block_off, d_arena_ + job.block_off, tab_words(job.pj.L, job.pj.S, job.pj.W) * sizeof(i64),
+      copy(d_arena_ + child.block_off, d_arena_ + job.block_off, tab_words(job.pj) * sizeof(i64),
            hipMemcpyDeviceToDevice);
       child.pj.ldet = job.pj.ldet;
       memcpy(child.pj.det, job.pj.det, sizeof job.pj.det);
@@ -1345,12 +1348,7 @@ class ForestT {
   }
 
  private:
-  static size_t block_words(int nvar, int S, int W) {
-    W = even(W);
-    const int L = even(nvar + S);
-    return (size_t)L * EW + (size_t)L + (size_t)S * W * EW + (size_t)even(nvar * (W - nvar) + nvar) * EW +
-           (size_t)even(S * 8 + (3 * L + 7) / 8) + 2 * PIPAMD_DETLOG * EW;
-  }
+  static size_t block_words(int nvar, int S, int W) { return (size_t)tree_block_layout(nvar, S, even(W), EW).words; }
   template <class T>
   void ensure(T *&buf, size_t &cap, size_t bytes) {
     if (bytes <= cap) return;
@@ -1382,7 +1380,9 @@ class ForestT {
   }
   // n values of the entry type at int64 word dst64
   void patch_vals(size_t dst64, const E *data, size_t n) { patch32(dst64 * 2, (const int *)data, (int)(n * 2 * EW)); }
-  void patch_flag(const PipJob &pj, int row, int f) { patch32(((size_t)pj.rows_off + (size_t)pj.L * EW) * 2 + row, &f, 1); }
+  // 32-bit word index into the arena of a job's flag table (the patch kernel's addressing)
+  static size_t flag32(const PipJob &pj) { return (size_t)pj.rows_off * 2 + (size_t)pip_flag_off32(pj.L, EW); }
+  void patch_flag(const PipJob &pj, int row, int f) { patch32(flag32(pj) + row, &f, 1); }
 
   // ---- jobs ---------------------------------------------------------------
   // allocate a job block in problem i's region; throws TOOLARGE (-> Tree path) when it is full
@@ -1395,22 +1395,15 @@ class ForestT {
     if (W > PIPAMD_MAXCOL || S > PIPAMD_SMAX || nvar + S > PIPAMD_LMAX ||
         pipk_advance_lds_bytes((even(nvar + S) + 3) & ~3, (S + 3) & ~3, W, EBITS) > PIPAMD_LDS_BUDGET)
       throw (int)PIPAMD_E_TOOLARGE;
-    const int L = even(nvar + S);
-    const size_t words = block_words(nvar, S, W);
-    if (q.top + words > q.region_words) throw (int)PIPAMD_E_TOOLARGE;
-    const i64 off = (i64)(q.region_off + q.top);
-    q.top += words;
-    pj.rows_off = off;
-    pj.vals_off = off + (i64)L * EW + (i64)L;
-    pj.sol_off = pj.vals_off + (i64)S * W * EW;
-    pj.state_off = pj.sol_off + (i64)even(nvar * (W - nvar) + nvar) * EW;
-    pj.log_off = off + (i64)words - 2 * PIPAMD_DETLOG * EW;
+    const PipBlockLayout b = tree_block_layout(nvar, S, W, EW);
+    if (q.top + (size_t)b.words > q.region_words) throw (int)PIPAMD_E_TOOLARGE;
+    pip_job_place(&pj, (i64)(q.region_off + q.top), b);
+    q.top += (size_t)b.words;
     pj.nvar = nvar;
     pj.nparm = nparm;
     pj.ni = ni;
     pj.bigparm = bigparm;
     pj.tflags = tflags | PIPAMD_T_SORT;
-    pj.L = L;
     pj.S = S;
     pj.W = W;
     pj.status = PIPAMD_ST_RUN;
@@ -1425,7 +1418,7 @@ class ForestT {
   void fresh_begin(int job) {
     const PipJob &pj = jobs_[job];
     fidx_.push_back((i64)fresh_.size());
-    const i64 hdr[8] = {pj.rows_off, pj.nvar, pj.ni, pj.nvar + pj.nparm + 1, pj.L, pj.S, pj.W, 0};
+    const i64 hdr[8] = {pj.rows_off, pj.nvar, pj.ni, pj.nvar + pj.nparm + 1, pj.L, pj.S, pj.W, pj.vals_off};
     fresh_.insert(fresh_.end(), hdr, hdr + 8);
   }
   // values of the entry type behind a record's header (EW words each, low word first)
@@ -1753,7 +1746,7 @@ class ForestT {
     memcpy(cj.det, pj.det, sizeof pj.det);
     clones_.push_back(pj.rows_off);
     clones_.push_back(cj.rows_off);
-    clones_.push_back((i64)pj.L * EW + (i64)pj.L + (i64)pj.S * pj.W * EW);
+    clones_.push_back(pj.sol_off - pj.rows_off);  // row tables and rows
     tape_push(i, S_IF, (E)0, (E)0);
     tape_push(i, S_FORM, (E)(np + 1), (E)0);
     E g = 0;
@@ -1825,7 +1818,7 @@ class ForestT {
     patch_vals((size_t)pj.rows_off + (size_t)nligne * EW, &D, 1);
     patch_flag(pj, nligne, PIPAMD_F_MINUS);
     const int slot = ni;
-    patch32(((size_t)pj.rows_off + (size_t)pj.L * EW) * 2 + pj.L + nligne, &slot, 1);
+    patch32(flag32(pj) + pj.L + nligne, &slot, 1);  // ref[nligne]
     f.ni = ni + 1;
     f.nparm = nparm;
     pj.ni = f.ni;

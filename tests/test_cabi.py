@@ -62,3 +62,22 @@ def test_no_cpu_fallback_without_gpu(lib):
     from piplib_amd import engine
     with pytest.raises(RuntimeError):
         engine.Engine(0)
+
+
+@pytest.mark.parametrize("nvar,nparm,ni,cap_cuts,cap_newparm,bits,want", [
+    # workspace of a batch of 3 = 768 bytes of job headers + 3 blocks; the figures are those of the formulas the batch
+    # layer had before csrc/pip_job.h's pip_block_layout replaced them (int64 words per block in the comment)
+    (127, 0, 64, 64, 0, 64, 445392),        # 18,526
+    (63, 0, 32, 8, 0, 64, 97680),           # 4,038
+    (5, 0, 8, 1, 0, 64, 28128),             # 1,140
+    (255, 0, 128, 700, 0, 128, 10416192),   # 433,976: 128-bit entries, rows of 256 columns
+    (20, 3, 12, 40, 4, 64, 71232),          # 2,936: parameters and room for new ones
+    (40, 2, 30, 16, 3, 128, 173040),        # 7,178: 128-bit entries, an odd number of columns
+])
+def test_block_layout_is_the_one_blocks_always_had(lib, nvar, nparm, ni, cap_cuts, cap_newparm, bits, want):
+    """The layout of a job's block in the arena (row tables, rows, solution, saved summaries, determinant log) is computed
+    in one place; the batch layer's sizes, seen through pipamd_batch_workspace_bytes, stay what they were.  (The host
+    trees' blocks are held to their figures by static_asserts in csrc/pip_tree.cpp.)"""
+    from piplib_amd.engine import BatchDesc
+    d = BatchDesc(3, nvar, nparm, ni, -1, 1, cap_cuts, cap_newparm, bits)
+    assert lib.pipamd_batch_workspace_bytes(C.byref(d)) == want

@@ -835,3 +835,43 @@ def test_lone_batches_option():
     for x, y in zip(*outs):
         assert (x == y).all()
     assert (outs[0][0] != eng.ST_RUN).all()
+
+
+@pytest.mark.parametrize("seed,nvar,ni,kw,limit,waves,ebits,integer", [
+    (5005, 5, 8, dict(nnz=3, cmax=3, x0max=5), 1, 0, 64, True),
+    (5041, 41, 30, dict(), 1, 1, 64, True),     # one wave per tableau in the general kernel
+    (5041, 41, 30, dict(), 1, 0, 128, True),    # 128-bit entries: the general kernel alone
+    (4072, 127, 64, dict(), 3, 0, 64, True),    # the headline shape: lean -> lean -> four-wave general kernel
+    (4072, 127, 64, dict(), 3, 8, 64, False),   # rational, eight waves per tableau
+])
+def test_pause_after_every_pivot(seed, nvar, ni, kw, limit, waves, ebits, integer):
+    """pipamd_engine_set_iter_limit with a limit of 1 (3 on the headline shape): every launch pauses every tableau after
+    that many pivots, so each pivot goes through the publishing of the row tables and the saved summaries by one kernel
+    and their staging by the next (lean -> lean -> general kernel on the 64-bit shapes).  Statuses, pivot and cut counts
+    and solutions are those of the same batch solved without a limit, and pivot counts and solutions the oracle's."""
+    import torch
+    import pipbatch as pb
+    from piplib_amd import engine as eng, synth
+    batch = 64
+    rows = synth.lexmin_batch(seed, batch, nvar, ni, **kw)
+    outs = []
+    for lim in (limit, 0):
+        e = eng.Engine(0)
+        if waves:
+            e.set_waves_per_job(waves)
+        e.set_bulk_min(64)
+        if lim:
+            e.set_iter_limit(lim)
+        b = eng.Batch(e, rows, nvar, 0, tflags=(eng.T_INT if integer else 0) | eng.T_ROWS_STAY, entier_bits=ebits)
+        b.load()
+        b.solve()
+        if lim:
+            assert e.last_solve_launches() > 4, e.last_solve_launches()   # the limit took effect
+        b.fetch()
+        torch.cuda.synchronize()
+        outs.append((b.status.cpu().numpy(), b.pivots.cpu().numpy(), b.cuts.cpu().numpy(), b.sol_num.cpu().numpy(),
+                     b.sol_den.cpu().numpy()))
+    for x, y in zip(*outs):
+        assert (x == y).all()
+    _compare_ids(b, rows, np.arange(batch), nvar, 1 if integer else 0, wide=ebits == 128,
+                 exe=pb.ORACLEPIP128 if ebits == 128 else None)
