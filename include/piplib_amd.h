@@ -42,7 +42,10 @@ extern "C" {
  * pipamd_engine_set_max_rows.  400: round 4 -- pipamd_solve_tableaux_lockstep128, pipamd_engine_set_lean64; the 128-bit
  * entries try the device-resident traiter() first (pipamd_last_device_tree answers for them too); nothing removed.
  * 500: the device-resident traiter() takes problems of 65 ... 128 columns too (two column blocks per wave);
- * pipamd_device_tree_fits tells whether a shape is in its box; nothing removed. */
+ * pipamd_device_tree_fits tells whether a shape is in its box; nothing removed.  Added since, the version unchanged (a
+ * binding looks them up in the library): pipamd_traiter_many / pipamd_traiter_many128 -- traiter() for many problems,
+ * flags per problem --, and the device-resident traiter() computes the dual (PIPAMD_T_DUAL) for every shape of its box,
+ * not only up to 64 inequalities. */
 #define PIPAMD_VERSION 500
 
 /* ---- error codes (return values) ---- */
@@ -310,6 +313,23 @@ int pipamd_solve_tableaux128(pipamd_engine *e, int n, const pipamd_problem *prob
                              int deepest_cut, int nthreads, pipamd_sol_cell128 **cells, size_t *n_cells, int *rcs,
                              int *statuses, int64_t *pivots);
 
+/* traiter() for `n` independent calls at once: for every i what pipamd_traiter(e, problems[i]'s shape and rows, flags[i],
+ * deepest_cut, ...) returns -- the same cells in the same order, the same rc, status and pivot count.  No empty-context
+ * test and no tab_simplify (this is traiter(), not maind.c): problems[i].nq is ignored, flags[i] says integer or rational.
+ * flags[i] is 0, PIPAMD_T_INT or PIPAMD_T_DUAL; flags == NULL stands for all 0; any other value gives that problem
+ * PIPAMD_E_INVALID in rcs[i] and does not fail the call.  statuses and pivots may be NULL.  The problems in the device
+ * tree's box (below) run in one launch of the device-resident traiter(), each with its own flags; the others, and those
+ * it hands back, go to `nthreads` host threads with a decision tree each, as in pipamd_solve_tableaux.  The lock-step
+ * scheduler is not used (it starts at the context test and has no dual).  pipamd_last_device_tree answers for the call.
+ * A front end with many pip_solve calls gathers their traiter() calls into one of these. */
+int pipamd_traiter_many(pipamd_engine *e, int n, const pipamd_problem *problems, const int *flags, int deepest_cut,
+                        int nthreads, pipamd_sol_cell **cells, size_t *n_cells, int *rcs, int *statuses,
+                        int64_t *pivots);
+/* The same on 128-bit entries: cells as pipamd_traiter128 hands them out. */
+int pipamd_traiter_many128(pipamd_engine *e, int n, const pipamd_problem *problems, const int *flags, int deepest_cut,
+                           int nthreads, pipamd_sol_cell128 **cells, size_t *n_cells, int *rcs, int *statuses,
+                           int64_t *pivots);
+
 /* The same results from a lock-step scheduler: one explicit traiter() state machine per problem
  * and, per step, ONE clone / patch / pivot-kernel / gather sequence for the whole batch, so the
  * host <-> device latency is paid once per step instead of once per problem.  Problems that need
@@ -336,8 +356,9 @@ int pipamd_solve_tableaux_lockstep128(pipamd_engine *e, int n, const pipamd_prob
  * no host round trip.  A problem in which a 64-bit operation would overflow, or that outgrows its
  * reserved rows, is handed back and served by the lock-step scheduler / the per-problem tree, which
  * reproduce the reference's wrap-around and "Integer overflow" behaviour.  pipamd_traiter,
- * pipamd_solve_tableau and pipamd_solve_tableaux try it first too (since interface version 300 also with
- * PIPAMD_T_DUAL), and so do their 128-bit counterparts with the kernel's 128-bit instantiation (there every product and
+ * pipamd_solve_tableau, pipamd_solve_tableaux and pipamd_traiter_many try it first too (since interface version 300 also
+ * with PIPAMD_T_DUAL: the list of dual values behind every rational solution, for every shape of the box -- tab_sort_rows'
+ * `pos` table has an entry for each of up to 128 inequalities of a call), and so do their 128-bit counterparts with the kernel's 128-bit instantiation (there every product and
  * sum is checked against 128 bits).  On by default (the environment
  * variable PIPAMD_NO_DEVICE_TREE switches it off for a process);
  * pipamd_last_device_tree reports how many problems of the last lock-step call each side served. */

@@ -149,8 +149,9 @@ struct QStateT {
   int nvar, nparm, ni, nc, pivi, ldet, ni0, pad1;
   QI det[MAXDET];
   // Compute_dual: tab_sort_rows' `pos` of the traiter() call in progress (traiter.c:567-620): logical row of each of
-  // the call's ni0 inequalities after its sort.  Part of the image, so a fork's frame keeps the caller's.
-  unsigned short pos[64];
+  // the call's ni0 inequalities after its sort (at most 127 + 104: a byte each, 128 of them in the 128 bytes that 64
+  // shorts took).  Part of the image, so a fork's frame keeps the caller's.
+  unsigned char pos[128];
 };
 
 // The kernel's functions as static members of a class template over the entry type and the number of column blocks: inside
@@ -413,8 +414,10 @@ static __device__ __forceinline__ int trunc_x86(double t) {
 static __device__ __forceinline__ int rdlane(int x, int l) { return __builtin_amdgcn_readlane(x, l); }
 // tab_sort_rows for 65 ... 128 rows to sort (round 4): the same selection sort -- the first row at or after i with the
 // smallest key strictly below the maximum is swapped into place i, traiter.c:591-614 -- with two rows per lane and the rows'
-// data left in LDS: keys in `skey` (128 ints), the swaps done there by lane 0.  No Compute_dual at this size.
-static __device__ __noinline__ int sort_rows_tall(Tab t, int nvar, int nligne, int lane, LDS int *skey) {
+// data left in LDS: keys in `skey` (128 ints), the swaps done there by lane 0.  pos != null (Compute_dual): while the
+// sort runs pos[r] is the inequality the row now at r was (0 for a unit row) and trades places with the row's other
+// data; afterwards it is inverted through registers into the table sort_rows describes.
+static __device__ __noinline__ int sort_rows_tall(Tab t, int nvar, int nligne, int lane, LDS unsigned char *pos, LDS int *skey) {
   const int n = nligne - nvar;
   if (n > 128) return Q_WHY_ROWS | 256;
   u64 realm[2], below[2];
@@ -455,12 +458,13 @@ static __device__ __noinline__ int sort_rows_tall(Tab t, int nvar, int nligne, i
     const int m = wave_max_i(real ? s : 0);
     smx = m > smx ? m : smx;
     if (r0 < n) skey[r0] = __float_as_int((float)(double)s);  // non-negative floats order like their bit patterns
+    if (pos && r0 < n) pos[r0] = (unsigned char)(real ? r0 : 0);
   }
   const double smax = (double)smx;
 #pragma unroll
   for (int h = 0; h < 2; h++) below[h] = __ballot(rl[h] && (double)(float)(double)sv[h] < smax);
   wsync();
-  if (!(below[0] | below[1])) return 0;  // no key is below the maximum: no row moves
+  if (below[0] | below[1])  // (else no key is below the maximum: no row moves)
   for (int i = 0; i < n; i++) {
     const int hi = i >> 6, bi = i & 63;
     if (!((realm[hi] >> bi) & 1)) continue;
@@ -484,6 +488,11 @@ static __device__ __noinline__ int sort_rows_tall(Tab t, int nvar, int nligne, i
       t.ref[kp] = r;
       t.den[kp] = d;
       skey[p] = q;
+      if (pos) {
+        const unsigned char o = pos[i];
+        pos[i] = pos[p];
+        pos[p] = o;
+      }
     }
     {
       const u64 bit_i = (below[hi] >> bi) & 1;
@@ -493,15 +502,32 @@ static __device__ __noinline__ int sort_rows_tall(Tab t, int nvar, int nligne, i
     }
     wsync();
   }
+  if (pos) {  // row -> inequality becomes inequality -> row: the row that was inequality 0 and every unit row are "0",
+              // and the last of them wins pos[0] (see sort_rows)
+    const int o0 = lane < n ? pos[lane] : -1, o1 = lane + 64 < n ? pos[lane + 64] : -1;
+    wsync();
+    pos[lane] = 0;
+    pos[lane + 64] = 0;
+    wsync();
+    const u64 z0 = __ballot(o0 == 0), z1 = __ballot(o1 == 0);
+    if (o0 > 0) pos[o0] = (unsigned char)(nvar + lane);
+    if (o1 > 0) pos[o1] = (unsigned char)(nvar + lane + 64);
+    if (z1) {
+      if (lane == 63 - __builtin_clzll(z1)) pos[0] = (unsigned char)(nvar + lane + 64);
+    } else if (z0 && lane == 63 - __builtin_clzll(z0)) {
+      pos[0] = (unsigned char)(nvar + lane);
+    }
+    wsync();
+  }
   return 0;
 }
 
 // pos != null (Compute_dual): pos[i] = the logical row inequality i (row nvar + i before the sort) ends up in; unit
 // rows among nvar.. count as inequality 0, later rows overwriting earlier ones -- the reference never sets their
 // `ineq` (traiter.c:577-578 vs 617-618), zero-filled as the oracle and the reference's own fixtures have it.
-static __device__ __noinline__ int sort_rows(Tab t, int nvar, int nligne, int lane, LDS unsigned short *pos, LDS int *skey) {
+static __device__ __noinline__ int sort_rows(Tab t, int nvar, int nligne, int lane, LDS unsigned char *pos, LDS int *skey) {
   const int n = nligne - nvar;  // rows to sort: at most 64 (a lane each) -- or up to 128, two per lane (sort_rows_tall)
-  if (n > 64) return (pos || !skey) ? (Q_WHY_ROWS | 256) : sort_rows_tall(t, nvar, nligne, lane, skey);
+  if (n > 64) return !skey ? (Q_WHY_ROWS | 256) : sort_rows_tall(t, nvar, nligne, lane, pos, skey);
   // lane l holds logical row nvar + l (flag, slot, denominator, key); the selection sort swaps lanes
   const int k = nvar + lane;
   int fl = 0, rf = 0, s = 0;
@@ -590,8 +616,8 @@ static __device__ __noinline__ int sort_rows(Tab t, int nvar, int nligne, int la
     if (lane < 64) pos[lane] = 0;
     wsync();
     const u64 zero = __ballot(lane < n && oi == 0);  // the row that was inequality 0, and every unit row
-    if (lane < n && oi > 0) pos[oi] = (unsigned short)k;
-    if (zero && lane == 63 - __builtin_clzll(zero)) pos[0] = (unsigned short)k;  // the last of them wins
+    if (lane < n && oi > 0) pos[oi] = (unsigned char)k;
+    if (zero && lane == 63 - __builtin_clzll(zero)) pos[0] = (unsigned char)k;  // the last of them wins
     wsync();
   }
   return 0;
@@ -1441,16 +1467,16 @@ static __device__ __forceinline__ void run(const QProb *probs, const w64 *input,
                 break;
               }
               if (lane == 0) tape_put(tape, tape.n, C_LIST, ni0, 0);
-              if (lane < ni0) {
-                const int k = st->pos[lane];
+              for (int q = lane; q < ni0; q += 64) {  // (ni0 <= 128: two inequalities a lane)
+                const int k = st->pos[q];
                 i64 v = 0, d = 1;
                 if (M.flag[k] & F_UNIT) {  // valeur(tp, 0, unit column of row k) over Denom(tp, 0)
                   const int u = M.ref[k];
                   d = M.den[0];
                   v = (M.flag[0] & F_UNIT) ? (M.ref[0] == u ? d : 0) : M.val[M.ref[0] * W + u];
                 }
-                tape_put(tape, tape.n + 1 + 2 * lane, C_FORM, 1, 0);
-                tape_put(tape, tape.n + 2 + 2 * lane, C_VAL, v, d);
+                tape_put(tape, tape.n + 1 + 2 * q, C_FORM, 1, 0);
+                tape_put(tape, tape.n + 2 + 2 * q, C_VAL, v, d);
               }
               tape.n += 1 + 2 * ni0;
             }

@@ -1156,6 +1156,87 @@ extern "C" int pipamd_solve_tableaux128(pipamd_engine *e, int n, const pipamd_pr
                                                      pivots, served);
 }
 
+// traiter() for many problems: the device tree first, each problem with its own flags (no context test, no tab_simplify:
+// the semantics of pipamd_traiter, not maind.c's), then `nthreads` host trees for what it did not serve.
+template <class E, class CELL>
+static void device_traiter_many(pipamd_engine *e, int n, const pipamd_problem *probs, const int *qflags, int deepest_cut,
+                                std::vector<char> &served, CELL **cells, size_t *n_cells, int *rcs, int *statuses,
+                                int64_t *pivots);
+
+template <class E, class CELL>
+static int traiter_many_any(pipamd_engine *e, int n, const pipamd_problem *probs, const int *flags, int deepest_cut, int nthreads,
+                            CELL **cells, size_t *n_cells, int *rcs, int *statuses, int64_t *pivots) {
+  if (!many_args(e, n, probs, nthreads, cells, n_cells, rcs, statuses, pivots)) return PIPAMD_E_INVALID;
+  if (n <= 0) return PIPAMD_OK;
+  // the problems as traiter_any hands them on: nq says integer or rational; QProb::flags carries the rest
+  std::vector<pipamd_problem> tp(probs, probs + n);
+  std::vector<int> tfl(n, 0), qfl(n, 0);
+  std::vector<char> served(n, 0);
+  for (int i = 0; i < n; i++) {
+    const int f = flags ? flags[i] : 0;
+    const pipamd_problem &p = probs[i];
+    if ((f != 0 && f != PIPAMD_T_INT && f != PIPAMD_T_DUAL) || !valid_shape(p.nvar, p.nparm, p.ni, p.nc, p.bigparm, p.ineq, p.ctx)) {
+      if (f != 0 && f != PIPAMD_T_INT && f != PIPAMD_T_DUAL)
+        pipamd_set_error("pipamd_traiter_many: flags must be 0, PIPAMD_T_INT or PIPAMD_T_DUAL (the dual needs a rational solve)");
+      rcs[i] = PIPAMD_E_INVALID;
+      served[i] = 1;
+      qfl[i] = -1;
+      continue;
+    }
+    tfl[i] = f;
+    tp[i].nq = (f & PIPAMD_T_INT) ? 1 : 0;
+    qfl[i] = Q_NO_CONTEXT_TEST | ((f & PIPAMD_T_DUAL) ? Q_DUAL : 0);
+  }
+  if (hipSetDevice(e->device) == hipSuccess)
+    device_traiter_many<E>(e, n, tp.data(), qfl.data(), deepest_cut, served, cells, n_cells, rcs, statuses, pivots);
+  std::atomic<int> next(0);
+  const int device = e->device;
+  auto worker = [&]() {
+    if (hipSetDevice(device) != hipSuccess) return;
+    try {
+      TreeT<E> t(e, deepest_cut);
+      for (;;) {
+        const int i = next.fetch_add(1);
+        if (i >= n) break;
+        if (served[i]) continue;
+        const pipamd_problem &p = tp[i];
+        int rc = PIPAMD_OK;
+        t.reset(deepest_cut);
+        try {
+          t.traiter_call(p.nvar, p.nparm, p.ni, p.nc, p.bigparm, tfl[i], (const i64 *)p.ineq, (const i64 *)p.ctx);
+        } catch (int code) {
+          rc = code;
+          if (statuses) statuses[i] = t.fail_status;
+          if (rc == PIPAMD_E_SOLVER)
+            pipamd_set_error("solver stopped with status %d (5 = the reference's \"Integer overflow\" exit)", t.fail_status);
+        }
+        if (pivots) pivots[i] = t.pivots;
+        rcs[i] = rc ? rc : export_tape(t.tape, &cells[i], &n_cells[i]);
+      }
+    } catch (int) {  // the tree could not be set up (stream creation failed): its problems stay E_HIP
+    }
+  };
+  bool rest = false;
+  for (int i = 0; i < n && !rest; i++) rest = !served[i];
+  if (rest) {
+    std::vector<std::thread> th;
+    for (int k = 0; k < nthreads; k++) th.emplace_back(worker);
+    for (auto &x : th) x.join();
+  }
+  return PIPAMD_OK;
+}
+extern "C" int pipamd_traiter_many(pipamd_engine *e, int n, const pipamd_problem *probs, const int *flags, int deepest_cut,
+                                   int nthreads, pipamd_sol_cell **cells, size_t *n_cells, int *rcs, int *statuses,
+                                   int64_t *pivots) {
+  return traiter_many_any<i64, pipamd_sol_cell>(e, n, probs, flags, deepest_cut, nthreads, cells, n_cells, rcs, statuses, pivots);
+}
+extern "C" int pipamd_traiter_many128(pipamd_engine *e, int n, const pipamd_problem *probs, const int *flags, int deepest_cut,
+                                      int nthreads, pipamd_sol_cell128 **cells, size_t *n_cells, int *rcs, int *statuses,
+                                      int64_t *pivots) {
+  return traiter_many_any<i128, pipamd_sol_cell128>(e, n, probs, flags, deepest_cut, nthreads, cells, n_cells, rcs, statuses,
+                                                    pivots);
+}
+
 // =========================================================================== Forest
 // Lock-step scheduler for MANY parametric problems.  The per-problem Tree above pays a few host
 // <-> device round trips per decision; on tiny problems that latency dominates.  The Forest
@@ -1872,7 +1953,7 @@ bool quast_caps(const pipamd_problem &p, QCaps &c) {
   if (p.bigparm >= ncol || (p.bigparm >= 0 && p.bigparm <= p.nvar)) return false;
   // at most 128 columns (a lane per column in one block of 64, or two blocks beyond: pip_quast_kernel<E, 2>) and 104
   // inequalities: up to 128 real rows with the cuts (tab_sort_rows has a lane per row up to 64 rows and two rows per lane
-  // beyond -- not with Compute_dual, whose `pos` table has 64 entries)
+  // beyond, with or without Compute_dual: its `pos` table has an entry for each of 128 inequalities)
   if (ncol > 128 || p.ni > 104 || p.ni + p.nvar == 0) return false;
   // Room for 10 quotients of parametric cuts, 24 cut rows and 24 nested forks.  (Smaller reserves -- 4 / 8 / 8:
   // 11 KB of LDS instead of 26 KB, twice the problems per CU -- made the launch of 10k problems 27 % shorter,
@@ -1922,7 +2003,7 @@ void quast_caps_max(QCaps &a, const QCaps &b) {
 }
 
 template <class E>
-void device_tree_chunk(pipamd_engine *e, const std::vector<int> &idx, const pipamd_problem *probs, const QCaps &cap, int qflags,
+void device_tree_chunk(pipamd_engine *e, const std::vector<int> &idx, const pipamd_problem *probs, const QCaps &cap, const int *qflags,
                        std::vector<FResultT<E>> &res, int *served, int *handed_back) {
   constexpr int EW = (int)(sizeof(E) / 8), EBITS = 64 * EW;
   const int n = (int)idx.size();
@@ -1933,7 +2014,7 @@ void device_tree_chunk(pipamd_engine *e, const std::vector<int> &idx, const pipa
   size_t words = 0;
   for (int k = 0; k < n; k++) {
     const pipamd_problem &p = probs[idx[k]];
-    qp[k] = QProb{(long long)words, p.nvar, p.nparm, p.ni, p.nc, p.bigparm, p.nq, qflags, 0};
+    qp[k] = QProb{(long long)words, p.nvar, p.nparm, p.ni, p.nc, p.bigparm, p.nq, qflags ? qflags[idx[k]] : 0, 0};
     words += (size_t)p.ni * (p.nvar + p.nparm + 1) + (size_t)p.nc * (p.nparm + 1);
   }
   if (words * sizeof(i64) > e->dt_host_cap) {  // pinned staging buffer, kept between calls
@@ -2014,9 +2095,10 @@ void device_tree_chunk(pipamd_engine *e, const std::vector<int> &idx, const pipa
   }
 }
 
+// qflags: QProb::flags of every problem (null: 0 for all); a negative entry keeps its problem out of the device tree
 template <class E>
 void device_tree(pipamd_engine *e, int n, const pipamd_problem *probs, int simplify, int deepest_cut, std::vector<FResultT<E>> &res,
-                 int *served, int *handed_back, int qflags = 0) {
+                 int *served, int *handed_back, const int *qflags = nullptr) {
   constexpr int EBITS = 64 * (int)(sizeof(E) / 8);
   struct Hold {  // the engine's device-tree buffers serve one call at a time
     pthread_mutex_t *m;
@@ -2048,7 +2130,7 @@ void device_tree(pipamd_engine *e, int n, const pipamd_problem *probs, int simpl
   order.reserve(n);
   for (int i = 0; i < n; i++) {
     QCaps c;
-    if (!device_tree_caps(probs[i], EBITS, c)) continue;
+    if ((qflags && qflags[i] < 0) || !device_tree_caps(probs[i], EBITS, c)) continue;
     order.emplace_back((c.W > 64 ? 1 << 20 : 0) + (int)(pipk_quast_lds_bytes(&c, EBITS) / 8192), i);
   }
   std::stable_sort(order.begin(), order.end(), [](const std::pair<int, int> &a, const std::pair<int, int> &b) { return a.first < b.first; });
@@ -2094,7 +2176,7 @@ static bool device_tree_one(pipamd_engine *e, const pipamd_problem &p, int simpl
   std::vector<FResultT<E>> res(1);
   res[0].rc = PIPAMD_E_TOOLARGE;
   int served = 0, back = 0;
-  device_tree<E>(e, 1, &p, simplify, deepest_cut, res, &served, &back, qflags);
+  device_tree<E>(e, 1, &p, simplify, deepest_cut, res, &served, &back, &qflags);
   pthread_mutex_lock(&e->dt_lock);
   e->dt_served = served;  // (pipamd_last_device_tree also answers for the one-problem entries)
   e->dt_fallback = back;
@@ -2123,6 +2205,24 @@ static void device_tree_many(pipamd_engine *e, int n, const pipamd_problem *prob
     if (statuses) statuses[i] = 0;
     if (pivots) pivots[i] = res[i].pivots;
     rcs[i] = res[i].is_void ? PIPAMD_OK : export_tape(res[i].tape, &cells[i], &n_cells[i]);
+  }
+}
+
+template <class E, class CELL>
+static void device_traiter_many(pipamd_engine *e, int n, const pipamd_problem *probs, const int *qflags, int deepest_cut,
+                                std::vector<char> &served, CELL **cells, size_t *n_cells, int *rcs, int *statuses,
+                                int64_t *pivots) {
+  e->dt_served = e->dt_fallback = 0;
+  if (e->no_device_tree || getenv("PIPAMD_NO_DEVICE_TREE") || n <= 0) return;
+  std::vector<FResultT<E>> res(n);
+  for (auto &r : res) r.rc = PIPAMD_E_TOOLARGE;
+  device_tree<E>(e, n, probs, 0, deepest_cut, res, &e->dt_served, &e->dt_fallback, qflags);
+  for (int i = 0; i < n; i++) {
+    if (res[i].rc != PIPAMD_OK || served[i]) continue;
+    served[i] = 1;
+    if (statuses) statuses[i] = 0;
+    if (pivots) pivots[i] = res[i].pivots;
+    rcs[i] = export_tape(res[i].tape, &cells[i], &n_cells[i]);
   }
 }
 

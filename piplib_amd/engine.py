@@ -434,6 +434,33 @@ def traiter(engine, nvar, nparm, ni, nc, bigparm, flags, tableau, context, deepe
     return (_take_cells128 if bits == 128 else _take_cells)(cells, n.value), piv.value
 
 
+def traiter_many(engine, problems, flags=None, deepest_cut=False, nthreads=8, bits=64):
+    """pipamd_traiter_many / pipamd_traiter_many128: one traiter() call per problem (objects with nvar, nparm, ni, nc,
+    bigparm, ineq, ctx; nq is ignored), flags[i] = 0, T_INT or T_DUAL (None: all 0).  Returns a list of
+    (cells | None, rc, status, pivots), the cells as traiter() returns them, None where rc != 0."""
+    L = lib()
+    name = "pipamd_traiter_many128" if bits == 128 else "pipamd_traiter_many"
+    if not hasattr(L, name):
+        raise RuntimeError(f"libpipamd has no {name}: rebuild the library")
+    fn = getattr(L, name)
+    fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    prep = PreparedProblems(problems)
+    fl = None
+    if flags is not None:
+        if len(flags) != prep.n:
+            raise ValueError("traiter_many: one flag per problem")
+        fl = (C.c_int * max(1, prep.n))(*[int(f) for f in flags])
+    _check(fn(engine._h, prep.n, prep.arr, fl, int(bool(deepest_cut)), int(nthreads),
+              prep.cells, prep.ncell, prep.rcs, prep.sts, prep.piv))
+    take = _take_cells128 if bits == 128 else _take_cells
+    out = []
+    for i in range(prep.n):
+        cells = take(prep.cells[i], prep.ncell[i])
+        out.append((cells if prep.rcs[i] == 0 else None, prep.rcs[i], prep.sts[i], prep.piv[i]))
+    return out
+
+
 class SolverError(RuntimeError):
     def __init__(self, status, pivots=0):
         super().__init__(f"solver stopped with PIPAMD_ST status {status}")
