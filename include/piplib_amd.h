@@ -45,7 +45,8 @@ extern "C" {
  * pipamd_device_tree_fits tells whether a shape is in its box; nothing removed.  Added since, the version unchanged (a
  * binding looks them up in the library): pipamd_traiter_many / pipamd_traiter_many128 -- traiter() for many problems,
  * flags per problem --, and the device-resident traiter() computes the dual (PIPAMD_T_DUAL) for every shape of its box,
- * not only up to 64 inequalities. */
+ * not only up to 64 inequalities; pipamd_batch_dual / pipamd_batch_dual_part -- the dual values of a rational batch of
+ * layer 1. */
 #define PIPAMD_VERSION 500
 
 /* ---- error codes (return values) ---- */
@@ -199,6 +200,33 @@ int pipamd_batch_poll(pipamd_engine *e);
 int pipamd_batch_results(pipamd_engine *e, const void *d_workspace, const pipamd_batch_desc *d,
                          int32_t *d_status, int32_t *d_pivots, int32_t *d_cuts, int64_t *d_sol_num,
                          int64_t *d_sol_den, void *stream);
+
+/* Compute_dual (the reference's TRAITER_DUAL, traiter.c:273-294, 567-620) for a batch solved with PIPAMD_T_DUAL in
+ * tflags: the list of dual values solution_dual emits behind a rational solution, one per input inequality.  Callable
+ * once pipamd_batch_solve / _wait has returned or _poll has returned 1; launches one kernel on `stream` and does not
+ * synchronise, like pipamd_batch_results.  `d_rows` is the array the tableaux were loaded from (pipamd_batch_load),
+ * unchanged: the reference's `pos` table -- where each inequality sits after tab_sort_rows -- does not survive the
+ * solve and is recomputed from the input rows; the caller keeps the array until the call's work on `stream` is done.
+ * d_dual_num[b][i], d_dual_den[b][i], i < ni: what solution_dual hands to sol_val, not reduced -- if inequality i's row
+ * has become a unit row, (valeur(tp, 0, its unit column), Denom(tp, 0)), otherwise (0, 1); int64 each, or little-endian
+ * (low, high) int64 pairs when entier_bits == 128.  A tableau whose status is not PIPAMD_ST_SOLUTION gets (0, 0) in
+ * every entry (a real dual never has denominator 0).
+ * PIPAMD_E_INVALID, before any HIP call: a null pointer, a descriptor without PIPAMD_T_DUAL or with PIPAMD_T_INT (the
+ * dual needs a rational solve, as in pipamd_traiter), nparm != 0 or bigparm >= 0 (layer 1 finishes only batches without
+ * parameters on its own), first / count outside the batch.  PIPAMD_E_TOOLARGE: more than 8,192 inequalities per tableau
+ * (the kernel sorts them in 48 KB of LDS).
+ * The price of PIPAMD_T_DUAL is paid in the solve: such a batch does not start with the lean launches (pip_lean_kernel
+ * / pip_lean64_kernel) but with the general one-wave bulk launch, so that every finished tableau has its rows in the
+ * general format -- a tableau the lean kernels finish keeps them packed, and teaching them to unpack would cost
+ * registers pip_lean_kernel does not have (64 VGPRs, no slack).  Dual batches of 2,048 tableaux and more are therefore
+ * slower than plain ones; statuses, pivot counts and solutions are the same, and batches without the flag take exactly
+ * the launches they took before. */
+int pipamd_batch_dual(pipamd_engine *e, const void *d_workspace, const pipamd_batch_desc *d, const int64_t *d_rows,
+                      int64_t *d_dual_num, int64_t *d_dual_den, void *stream);
+/* The same for the tableaux first .. first + count - 1 only: `d_rows` holds those `count` tableaux (what
+ * pipamd_batch_load_part was given), d_dual_num / d_dual_den are the arrays of the whole batch. */
+int pipamd_batch_dual_part(pipamd_engine *e, const void *d_workspace, const pipamd_batch_desc *d, const int64_t *d_rows,
+                           int first, int count, int64_t *d_dual_num, int64_t *d_dual_den, void *stream);
 
 /* Batch totals, device memory, 4 x uint64: [0] pivots (calls of pivoter), [1] Gomory cuts,
  * [2] rows rewritten by pivots (rows whose pivot-column entry is zero and that are already

@@ -380,8 +380,11 @@ struct BatchRun {
     // one wave per tableau over the whole batch: it finishes the tableaux whose stored entries stay below 2^63 (two in
     // three of BASELINE's configs[4]) and leaves the others to the launches below.  Opt-in (pipamd_engine_set_lean64):
     // measured on that batch it is no faster than pip_advance_kernel's four waves per tableau.
+    // A batch with PIPAMD_T_DUAL takes no lean launch: a tableau the lean kernels finish keeps its rows packed, and
+    // pip_batch_dual_kernel reads logical row 0 in the general format (pipamd_batch_dual, include/piplib_amd.h)
+    const bool dual = (lay.tflags & PIPAMD_T_DUAL) != 0;
     bool took64 = false;
-    if (e->lean64 && !e->no_lean && lay.ebits == 128 && lay.nparm == 0 && lay.bigparm < 0 && lay.W > 128 && lay.W <= 256 &&
+    if (!dual && e->lean64 && !e->no_lean && lay.ebits == 128 && lay.nparm == 0 && lay.bigparm < 0 && lay.W > 128 && lay.W <= 256 &&
         !(lay.tflags & (PIPAMD_T_NOSKIP | PIPAMD_T_DEEPEST)) && lay.batch >= (e->bulk_min > 0 ? e->bulk_min : 128) &&
         e->waves_per_job != 4 && e->waves_per_job != 8) {
       int smax = curS < 448 ? curS : 448;  // (448 rows: an image of 30 KB, five tableaux per CU)
@@ -402,7 +405,7 @@ struct BatchRun {
       if (smax > curS) smax = curS;
       // no parameters, at most 128 columns of 64-bit entries, rows skipped, plain cuts: the lean kernel (pip_lean.h) goes
       // first -- it finishes the tableaux whose entries stay below 2^15 and leaves the others to the general kernel's launch
-      const bool lean = !e->no_lean && lay.ebits != 128 && lay.nparm == 0 && lay.bigparm < 0 && lay.W <= 128 && !(lay.W & 1) &&
+      const bool lean = !dual && !e->no_lean && lay.ebits != 128 && lay.nparm == 0 && lay.bigparm < 0 && lay.W <= 128 && !(lay.W & 1) &&
                         !(lay.tflags & (PIPAMD_T_NOSKIP | PIPAMD_T_DEEPEST)) && pipk_lean_class(smax) != 0;
       // (the bulk launches leave their determinant logs to the replay behind the first tail launch; two of them log at
       // most 2 * budget pivots per tableau)
@@ -692,6 +695,51 @@ extern "C" int pipamd_batch_results(pipamd_engine *e, const void *d_ws, const pi
   HIPCHK(pipk_launch_batch_results(jobs, arena, lay.batch, lay.nvar, lay.nparm, lay.ebits, d_status, d_pivots, d_cuts,
                                    (void *)d_sol_num, (void *)d_sol_den, (hipStream_t)stream));
   return PIPAMD_OK;
+}
+
+// Compute_dual for the batch layer (header comment: include/piplib_amd.h).  Everything is checked before the first HIP
+// call; the one launch goes on `stream` and nothing here waits for it.
+extern "C" int pipamd_batch_dual_part(pipamd_engine *e, const void *d_ws, const pipamd_batch_desc *d, const int64_t *d_rows,
+                                      int first, int count, int64_t *d_dual_num, int64_t *d_dual_den, void *stream) {
+  if (!e || !d_ws || !d || !d_rows || !d_dual_num || !d_dual_den) {
+    pipamd_set_error("batch_dual: null engine, workspace, descriptor, rows or output array");
+    return PIPAMD_E_INVALID;
+  }
+  if (!(d->tflags & PIPAMD_T_DUAL)) {
+    pipamd_set_error("batch_dual: the batch was not solved with PIPAMD_T_DUAL in its descriptor's tflags");
+    return PIPAMD_E_INVALID;
+  }
+  if (d->tflags & PIPAMD_T_INT) {
+    pipamd_set_error("batch_dual: PIPAMD_T_INT and PIPAMD_T_DUAL together (the dual needs a rational solve)");
+    return PIPAMD_E_INVALID;
+  }
+  if (d->nparm != 0 || d->bigparm >= 0) {
+    pipamd_set_error("batch_dual: nparm must be 0 and bigparm -1 (the batch layer finishes only such batches on its own)");
+    return PIPAMD_E_INVALID;
+  }
+  PipBatchLayout lay;
+  size_t jb;
+  int rc = pipamd_batch_layout(d, &lay, &jb);
+  if (rc) return rc;
+  if (first < 0 || count < 0 || first > lay.batch - count) {
+    pipamd_set_error("batch_dual_part: tableaux %d..%d outside the batch of %d", first, first + count, lay.batch);
+    return PIPAMD_E_INVALID;
+  }
+  if (lay.ni > pipk_batch_dual_max_ni()) {
+    pipamd_set_error("batch_dual: %d inequalities per tableau, the dual kernel sorts at most %d", lay.ni, pipk_batch_dual_max_ni());
+    return PIPAMD_E_TOOLARGE;
+  }
+  if (hipSetDevice(e->device) != hipSuccess) return PIPAMD_E_HIP;  // HIP's current device is per host thread
+  const PipJob *jobs = (const PipJob *)d_ws;
+  const long long *arena = (const long long *)((const char *)d_ws + jb);
+  HIPCHK(pipk_launch_batch_dual(jobs, arena, (const long long *)d_rows, lay, first, count, (void *)d_dual_num,
+                                (void *)d_dual_den, (hipStream_t)stream));
+  return PIPAMD_OK;
+}
+
+extern "C" int pipamd_batch_dual(pipamd_engine *e, const void *d_ws, const pipamd_batch_desc *d, const int64_t *d_rows,
+                                 int64_t *d_dual_num, int64_t *d_dual_den, void *stream) {
+  return pipamd_batch_dual_part(e, d_ws, d, d_rows, 0, d ? d->batch : 0, d_dual_num, d_dual_den, stream);
 }
 
 extern "C" int pipamd_batch_counters(pipamd_engine *e, const void *d_ws, const pipamd_batch_desc *d, uint64_t *d_out4,

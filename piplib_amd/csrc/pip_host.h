@@ -78,6 +78,9 @@ hipError_t pipk_launch_batch_load(PipJob *jobs, long long *arena, const long lon
 hipError_t pipk_launch_batch_results(const PipJob *jobs, const long long *arena, int njobs, int nvar, int nparm,
                                      int ebits, int *status, int *pivots, int *cuts, void *sol_num, void *sol_den,
                                      hipStream_t stream);
+int pipk_batch_dual_max_ni(void); /* inequalities per tableau pip_batch_dual_kernel sorts in LDS */
+hipError_t pipk_launch_batch_dual(const PipJob *jobs, const long long *arena, const long long *rows, PipBatchLayout lay,
+                                  int first, int count, void *dual_num, void *dual_den, hipStream_t stream);
 hipError_t pipk_launch_rehouse(PipJob *jobs, long long *arena, void *const *q5, int grid, PipBatchLayout nl, int *side_count,
                                int side_cap, hipStream_t stream);
 hipError_t pipk_launch_rehouse_finish(PipJob *jobs, long long *arena, int njobs, int sol_words, hipStream_t stream);

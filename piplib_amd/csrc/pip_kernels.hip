@@ -2,8 +2,8 @@
 //
 // The pivot kernel itself (pip_advance_kernel: traiter() / pivoter() / choisir_piv() / exam_coef() / integrer() /
 // tab_sort_rows of the reference) lives in pip_advance.h and is instantiated by the pip_adv_*.hip files; this file
-// holds the determinant replay, the batch load / results / counters kernels, expanser for the batch layer, the
-// helpers of the lock-step scheduler and every launcher.
+// holds the determinant replay, the batch load / results / counters kernels, Compute_dual for the batch layer
+// (pip_batch_dual_kernel), expanser for the batch layer, the helpers of the lock-step scheduler and every launcher.
 #include "pip_lean.h"
 
 // the instantiations of the pivot kernel's launcher live in pip_adv_*.hip
@@ -251,6 +251,192 @@ __global__ void pip_batch_counters_kernel(const PipJob *jobs, int njobs, unsigne
   atomicAdd(&out[1], (unsigned long long)J->ncut);
   atomicAdd(&out[2], (unsigned long long)J->nupd);
   if (J->status == PIPAMD_ST_SOLUTION || J->status == PIPAMD_ST_NIL) atomicAdd(&out[3], 1ull);
+}
+
+// ---------------------------------------------------------------- Compute_dual for the batch layer
+// solution_dual (traiter.c:273-294) for the tableaux of a uniform batch without parameters, after their rational solve:
+// one wave per tableau.  Nothing of tab_sort_rows' `pos` table survives the solve, so it is recomputed from the input
+// rows -- the keys of traiter.c:576-589 as pip_advance_kernel's entry pass forms them for denominator 1, then the
+// selection sort of traiter.c:591-614 on (key, inequality) pairs -- and the values are read from the job's final row
+// tables in HBM (den | flag | ref by LOGICAL row, as publish_row_tables leaves them) and its logical row 0 in the general
+// row format.  Every loop bound comes from the launch's layout; what is read from the tables is range-checked.
+#define PIP_DUAL_MAXNI 8192 /* inequalities per tableau: 6 bytes of LDS each, 48 KB */
+extern "C" int pipk_batch_dual_max_ni(void) { return PIP_DUAL_MAXNI; }
+extern "C" size_t pipk_batch_dual_lds_bytes(int ni) { return (6 * (size_t)(ni > 0 ? ni : 1) + 15) & ~(size_t)15; }
+
+// |(int)a| of traiter.c:583 for an entry under denominator 1: an entry that does not fit an int gives INT_MIN (x86
+// cvttsd2si), and abs(INT_MIN) stays negative, so neither it nor -2^31 itself ever wins the row's maximum
+__device__ __forceinline__ int dual_key_term(i64 v) {
+  const int q = (v == (i64)(int)v) ? (int)v : (int)0x80000000;
+  return q < 0 ? (int)(0u - (unsigned)q) : q;
+}
+
+// The selection sort of traiter.c:591-614 on the pairs (key[r], ineq[r]), r < n, in LDS; one wave.  It chooses and
+// swaps exactly as sort_rows (pip_advance.h) does in both of its forms: for r = 0, 1, ... the first pair at or after r
+// with the smallest key strictly below smax goes to r (pairs whose key is not below smax are never picked, and nothing
+// is swapped when none is left); the pair that sat at r takes its place (not stable).
+__device__ void dual_sort_pairs(float *key, u16 *ineq, int n, double smax, int lane) {
+  if (n <= 64) {
+    // a pair per lane, in registers; keys are non-negative floats, so their bit patterns order like the values
+    unsigned k = 0xFFFFFFFFu, id = (unsigned)lane;
+    if (lane < n) {
+      const float sj = key[lane];
+      if ((double)sj < smax) k = __float_as_uint(sj);
+    }
+    for (int i = 0; i < n; i++) {
+      const unsigned m = wave_minmax_u32<false>(lane >= i ? k : 0xFFFFFFFFu);
+      if (m == 0xFFFFFFFFu) break;  // nothing below smax is left: this pair and all behind it stay
+      const int pv = __builtin_ctzll(ballot64(lane >= i && k == m));
+      if (pv != i) {
+        const unsigned ki = __builtin_amdgcn_readlane(k, i), di = __builtin_amdgcn_readlane(id, i);
+        const unsigned dp = __builtin_amdgcn_readlane(id, pv);
+        if (lane == pv) {
+          k = ki;
+          id = di;
+        }
+        if (lane == i) {
+          k = m;
+          id = dp;
+        }
+      }
+    }
+    if (lane < n) ineq[lane] = (u16)id;
+    __syncthreads();
+    return;
+  }
+  for (int i = 0; i < n; i++) {
+    float best = 0;
+    int bj = BIG_I;
+    for (int j = i + lane; j < n; j += 64) {
+      const float sj = key[j];
+      if (!((double)sj < smax)) continue;
+      if (bj == BIG_I || sj < best) {
+        best = sj;
+        bj = j;
+      }
+    }
+    for (int o = 32; o; o >>= 1) {  // the smallest key, the lowest index among equals
+      const float ob = __shfl(best, lane ^ o);
+      const int oj = __shfl(bj, lane ^ o);
+      if (oj != BIG_I && (bj == BIG_I || ob < best || (ob == best && oj < bj))) {
+        best = ob;
+        bj = oj;
+      }
+    }
+    if (bj == BIG_I) break;  // (keys do not change: no later i finds one either)
+    if (bj != i && lane == 0) {
+      const float tk = key[bj];
+      key[bj] = key[i];
+      key[i] = tk;
+      const u16 td = ineq[bj];
+      ineq[bj] = ineq[i];
+      ineq[i] = td;
+    }
+    __syncthreads();
+  }
+  __syncthreads();
+}
+
+// `rows`: the int64 input rows of the tableaux first, first + 1, ... (what pipamd_batch_load_part was given); dual_num /
+// dual_den: [batch][ni] values of the entry type.  A tableau that is not PIPAMD_ST_SOLUTION, or whose header or tables
+// are not what a finished solve of this layout leaves, gets (0, 0) throughout.
+template <class T>
+__global__ __launch_bounds__(64) void pip_batch_dual_kernel(const PipJob *jobs, const i64 *arena, const i64 *rows,
+                                                            PipBatchLayout lay, int first, T *dual_num, T *dual_den) {
+  extern __shared__ __align__(16) unsigned char dual_lds[];
+  const int lane = threadIdx.x;
+  const int b = first + blockIdx.x;
+  const int nvar = lay.nvar, ni = lay.ni, ncol = lay.nvar + 1;
+  if (ni <= 0 || ni > PIP_DUAL_MAXNI) return;
+  float *key = (float *)dual_lds;          // [ni]; after the sort its room holds pos
+  u16 *ineq = (u16 *)(dual_lds + 4 * (size_t)ni);  // [ni]
+  u16 *pos = (u16 *)dual_lds;              // [ni]: logical row of each inequality after the sort
+
+  // 1. keys: a lane per column pair, four rows in flight
+  const i64 *src = rows + (size_t)blockIdx.x * ni * ncol;
+  unsigned smaxw = 0;
+  for (int i0 = 0; i0 < ni; i0 += 4) {
+    int sz[4] = {0, 0, 0, 0};
+    for (int j = 2 * lane; j < nvar; j += 128) {
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        if (i0 + q >= ni) break;
+        const i64 *r = src + (size_t)(i0 + q) * ncol;
+        const int a0 = dual_key_term(r[j]);
+        const int a1 = j + 1 < nvar ? dual_key_term(r[j + 1]) : 0;
+        const int a = a0 > a1 ? a0 : a1;
+        sz[q] = sz[q] > a ? sz[q] : a;
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      if (i0 + q >= ni) break;
+      const unsigned szw = wave_minmax_u32<true>((unsigned)sz[q]);
+      if (lane == 0) {
+        key[i0 + q] = (float)szw;
+        ineq[i0 + q] = (u16)(i0 + q);
+      }
+      smaxw = smaxw > szw ? smaxw : szw;
+    }
+  }
+  __syncthreads();
+
+  // 2. the sort, then pos[ineq[r]] = nvar + r (all ni rows are real at load time)
+  dual_sort_pairs(key, ineq, ni, (double)smaxw, lane);
+  for (int r = lane; r < ni; r += 64) {
+    const int i = ineq[r];
+    if (i < ni) pos[i] = (u16)(nvar + r);
+  }
+  __syncthreads();
+
+  // 3. the values, as emit_dual (pip_tree.cpp) reads them from a snapshot of the job's block
+  const PipJob *J = &jobs[b];
+  const i64 base = lay.arena_off + (i64)b * lay.blk.words;
+  const int L = lay.blk.L, S = lay.S, W = lay.W, nligne = nvar + ni;
+  bool ok = J->status == PIPAMD_ST_SOLUTION && J->rows_off == base && J->vals_off == base + lay.blk.vals && J->L == L &&
+            J->W == W && J->nvar == nvar && J->ni == ni && J->nparm == 0 && nligne <= L;
+  const auto [g_den, g_flag, g_ref] = pip_row_tables<const T>(arena + base, L);
+  const T *vals = (const T *)(arena + base + lay.blk.vals);
+  int f0 = 0, r0 = 0;
+  T d0 = 0;
+  if (ok) {
+    f0 = g_flag[0];
+    r0 = g_ref[0];
+    d0 = g_den[0];
+    if (!(f0 & PIPAMD_F_UNIT) && (r0 < 0 || r0 >= S)) ok = false;
+  }
+  for (int i = lane; i < ni; i += 64) {
+    T num = 0, den = 0;
+    const int k = pos[i];
+    if (ok && k >= nvar && k < nligne) {
+      if (g_flag[k] & PIPAMD_F_UNIT) {
+        const int u = g_ref[k];
+        if (u >= 0 && u < nvar) {  // valeur(tp, 0, u), Denom(tp, 0)
+          num = (f0 & PIPAMD_F_UNIT) ? (r0 == u ? d0 : (T)0) : vals[(size_t)r0 * W + u];
+          den = d0;
+        }
+      } else {
+        num = 0;
+        den = 1;
+      }
+    }
+    dual_num[(size_t)b * ni + i] = num;
+    dual_den[(size_t)b * ni + i] = den;
+  }
+}
+
+extern "C" hipError_t pipk_launch_batch_dual(const PipJob *jobs, const i64 *arena, const i64 *rows, PipBatchLayout lay,
+                                             int first, int count, void *dual_num, void *dual_den, hipStream_t stream) {
+  if (count <= 0 || lay.ni <= 0) return hipSuccess;
+  if (lay.ni > PIP_DUAL_MAXNI || lay.nparm != 0) return hipErrorInvalidValue;
+  const size_t shm = pipk_batch_dual_lds_bytes(lay.ni);
+  if (lay.ebits == 128)
+    hipLaunchKernelGGL(pip_batch_dual_kernel<i128>, dim3(count), dim3(64), shm, stream, jobs, arena, rows, lay, first,
+                       (i128 *)dual_num, (i128 *)dual_den);
+  else
+    hipLaunchKernelGGL(pip_batch_dual_kernel<i64>, dim3(count), dim3(64), shm, stream, jobs, arena, rows, lay, first,
+                       (i64 *)dual_num, (i64 *)dual_den);
+  return hipGetLastError();
 }
 
 // ---------------------------------------------------------------- expanser for the batch layer

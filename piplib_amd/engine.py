@@ -255,6 +255,46 @@ class Batch:
                                           C.c_void_p(self.cuts.data_ptr()), C.c_void_p(self.sol_num.data_ptr()),
                                           C.c_void_p(self.sol_den.data_ptr()), st))
 
+    def _dual_out(self):
+        B, ni = self.desc.batch, self.desc.ni
+        shape = (B, ni) + ((2,) if self.entier_bits == 128 else ())
+        return (self.torch.empty(shape, dtype=self.torch.int64, device=self.dev),
+                self.torch.empty(shape, dtype=self.torch.int64, device=self.dev))
+
+    def dual(self, stream=None):
+        """pipamd_batch_dual after a solve with T_DUAL: device tensors (dual_num, dual_den) of shape (batch, ni) -- plus a
+        trailing 2, (low, high), for 128-bit entries: see wide_to_int() --, the pairs solution_dual emits, not reduced;
+        (0, 0) throughout for a tableau without a solution.  Does not synchronise."""
+        if self.rows is None:
+            raise RuntimeError("Batch.dual needs the rows the batch was loaded from: use dual_part() with load_parts()")
+        L = lib()
+        if not hasattr(L, "pipamd_batch_dual"):
+            raise RuntimeError("libpipamd has no pipamd_batch_dual: rebuild the library")
+        L.pipamd_batch_dual.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BatchDesc)] + [C.c_void_p] * 4
+        num, den = self._dual_out()
+        st = C.c_void_p(stream) if stream is not None else self._stream()
+        _check(L.pipamd_batch_dual(self.e._h, C.c_void_p(self.ws.data_ptr()), C.byref(self.desc),
+                                   C.c_void_p(self.rows.data_ptr()), C.c_void_p(num.data_ptr()),
+                                   C.c_void_p(den.data_ptr()), st))
+        return num, den
+
+    def dual_part(self, rows, first, stream=None, out=None):
+        """pipamd_batch_dual_part for the tableaux first .. first + len(rows) - 1, loaded from the resident array `rows`
+        (as load_part was given it); returns (dual_num, dual_den) of the whole batch's shape, only those tableaux written
+        (pass the pair back as `out` to fill it part by part)."""
+        assert rows.is_cuda and rows.is_contiguous()
+        L = lib()
+        if not hasattr(L, "pipamd_batch_dual_part"):
+            raise RuntimeError("libpipamd has no pipamd_batch_dual_part: rebuild the library")
+        L.pipamd_batch_dual_part.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BatchDesc), C.c_void_p, C.c_int, C.c_int,
+                                             C.c_void_p, C.c_void_p, C.c_void_p]
+        num, den = out if out is not None else self._dual_out()
+        st = C.c_void_p(stream) if stream is not None else self._stream()
+        _check(L.pipamd_batch_dual_part(self.e._h, C.c_void_p(self.ws.data_ptr()), C.byref(self.desc),
+                                        C.c_void_p(rows.data_ptr()), int(first), int(rows.shape[0]),
+                                        C.c_void_p(num.data_ptr()), C.c_void_p(den.data_ptr()), st))
+        return num, den
+
     def counters(self):
         """dict of batch totals (pivots, cuts, rows_rewritten, finished) -- synchronises."""
         out = self.torch.zeros(4, dtype=self.torch.int64, device=self.dev)
