@@ -805,6 +805,8 @@ __device__ __forceinline__ T reduce_den(T g0, typename WT<TW>::U g, int s, typen
 
 template <class T, int N>
 __device__ __forceinline__ bool row_reduce_rem(T (&z)[N], typename ET<T>::U mx, T g0, int lane, T &newden);
+template <class T, int N, bool FROM = true>
+__device__ __forceinline__ bool row_reduce_rem_from(T (&z)[N], typename ET<T>::U mx, T g0, typename ET<T>::U gs, int lane, T &newden);
 
 // pivoter()'s row gcd and division (traiter.c:479-501): z (N entries per lane, `mx` = OR of the lane's |z|) is divided by
 // g = gcd(g0, z_0, ..., z_n) in place; newden = g0 / g.  False where the reference would divide by zero.
@@ -877,12 +879,15 @@ __device__ __forceinline__ bool row_reduce(T (&z)[N], typename ET<T>::U mx, T g0
 // remainder, repeat until all remainders vanish (typically <= 2 rounds).
 // The second half: z (N entries per lane, `mx` = OR of the lane's |z|) is divided by g = gcd(g0, z_0, ..., z_n) in place;
 // newden = g0 / g.  False where the reference would divide by zero.
-template <class T, int N>
-__device__ __forceinline__ bool row_reduce_rem(T (&z)[N], typename ET<T>::U mx, T g0, int lane, T &newden) {
+// `gs`: where the refinement starts -- |g0|, or the gcd of |g0| with entries of the row the caller has folded in already
+// (gs = 1: the row gcd is 1, nothing is read).  gcd is associative: the same g, the same quotients.  A caller with nothing
+// folded passes |g0| (g0 = 0 -- the one input with a `false` verdict -- included); FROM = false promises gs == |g0|.
+template <class T, int N, bool FROM>
+__device__ __forceinline__ bool row_reduce_rem_from(T (&z)[N], typename ET<T>::U mx, T g0, typename ET<T>::U gs, int lane, T &newden) {
   typedef typename ET<T>::U U;
   newden = g0;
-  if (g0 == 1) return true;
-  U g = (U)uni64((T)uabs64(g0));
+  if (gs == 1) return true;  // (g0 = -1 as well: every remainder modulo 1 vanishes)
+  U g = (U)uni64((T)gs);
   // 32-bit remainders when everything fits (the common case): one v_rcp-based
   // division instead of the 64-bit software routine
   const bool small = (ballot64((mx >> 32) != 0) == 0) && (g >> 32) == 0;
@@ -922,6 +927,10 @@ __device__ __forceinline__ bool row_reduce_rem(T (&z)[N], typename ET<T>::U mx, 
       const unsigned q = ((unsigned)uabs64(zz) >> s) * inv;
       z[e] = zz < 0 ? wneg((T)q) : (T)q;
     }
+    if (FROM && (uabs64(g0) >> 32) != 0) {  // (g began below |g0|: the denominator's quotient need not fit 32 bits)
+      newden = (T)((U)(g0 >> s) * inv_odd64((U)m));
+      return true;
+    }
     const unsigned qd = ((unsigned)uabs64(g0) >> s) * inv;
     newden = g0 < 0 ? wneg((T)qd) : (T)qd;
     return true;
@@ -932,6 +941,10 @@ __device__ __forceinline__ bool row_reduce_rem(T (&z)[N], typename ET<T>::U mx, 
   for (int e = 0; e < N; e++) z[e] = (T)((U)(z[e] >> s) * inv);
   newden = (T)((U)(g0 >> s) * inv);
   return true;
+}
+template <class T, int N>
+__device__ __forceinline__ bool row_reduce_rem(T (&z)[N], typename ET<T>::U mx, T g0, int lane, T &newden) {
+  return row_reduce_rem_from<T, N, false>(z, mx, g0, (typename ET<T>::U)uabs64(g0), lane, newden);
 }
 
 // `narrow64` (128-bit entries only): every entry of the row and of the pivot row and both multipliers fit a long long --
@@ -1031,12 +1044,14 @@ __device__ __forceinline__ unsigned umod_tiny_low(unsigned a, unsigned g, float 
 // the same bits as the 64-bit code above.  64-bit entries only.
 // Second half of the small row update: z (ints, |z| < 2^31, `mx` = OR of the lane's |z|) is divided by
 // g = gcd(g0, z_0, ..., z_n) in place; newden = g0 / g.  False where the reference would divide by zero.
-template <int NCH>
-__device__ __forceinline__ bool small_reduce(int (&z)[NCH][2], unsigned mx, i64 g0, int lane, i64 &newden) {
+// `gs`: where the refinement starts, as for row_reduce_rem_from (|g0|, or its gcd with entries already folded in); FROM =
+// false promises gs == |g0|.
+template <int NCH, bool FROM = true>
+__device__ __forceinline__ bool small_reduce_from(int (&z)[NCH][2], unsigned mx, i64 g0, u64 gs, int lane, i64 &newden) {
   newden = g0;
   bool ok = true;
-  if (g0 != 1) {
-    u64 g64 = (u64)uni64((i64)uabs64(g0));
+  if (gs != 1) {  // (g0 = -1 as well: every remainder modulo 1 vanishes)
+    u64 g64 = (u64)uni64((i64)gs);
     if ((g64 >> 32) == 0) {
       unsigned g = (unsigned)g64;
       // every |z| and g below 2^20 (the rule on this path): remainders through a float reciprocal of the wave-uniform
@@ -1087,11 +1102,15 @@ __device__ __forceinline__ bool small_reduce(int (&z)[NCH][2], unsigned mx, i64 
             const unsigned qq = ((unsigned)(v < 0 ? -v : v) >> sh) * inv;
             z[c][h] = v < 0 ? -(int)qq : (int)qq;
           }
-        const unsigned qd = ((unsigned)uabs64(g0) >> sh) * inv;
-        newden = g0 < 0 ? wneg((i64)qd) : (i64)qd;
+        if (FROM && (uabs64(g0) >> 32) != 0) {  // (g began below |g0|: the denominator's quotient need not fit 32 bits)
+          newden = cquo(g0, (i64)g);
+        } else {
+          const unsigned qd = ((unsigned)uabs64(g0) >> sh) * inv;
+          newden = g0 < 0 ? wneg((i64)qd) : (i64)qd;
+        }
       }
     } else if (ballot64(mx != 0) == 0) {
-      // a zero row under a denominator beyond 32 bits: gcd(g0, 0, ..., 0) = |g0|
+      // a zero row under a denominator beyond 32 bits: gcd(g0, 0, ..., 0) = |g0| (no entry to fold: gs is |g0|)
       newden = g0 < 0 ? -1 : 1;
     } else {
       // a denominator beyond 32 bits with 31-bit entries: the gcd is that of the entries (found by
@@ -1142,6 +1161,10 @@ __device__ __forceinline__ bool small_reduce(int (&z)[NCH][2], unsigned mx, i64 
     }
   }
   return ok;
+}
+template <int NCH>
+__device__ __forceinline__ bool small_reduce(int (&z)[NCH][2], unsigned mx, i64 g0, int lane, i64 &newden) {
+  return small_reduce_from<NCH, false>(z, mx, g0, (u64)uabs64(g0), lane, newden);
 }
 
 template <int NCH>

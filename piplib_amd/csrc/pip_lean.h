@@ -29,6 +29,14 @@
 //   compile-time row capacity SC.  A row is two 32-bit registers per lane (columns 2l, 2l + 1).  Small path (96 % of the
 //   headline's pivots): 24-bit multiplies, the row gcd by float-reciprocal remainders, 32-bit summaries and cuts; mid
 //   path (round 4): v_mad_i64_i32 products below 2^62.  64 VGPRs, no scratch, eight waves per SIMD.
+//   Round 5 (PIP_LEAN_PREP): what a row's update needs of the row before it arrives -- gcd(pivot, foo), the multipliers,
+//   the denominator product g0 and its gcd with the one entry of the new row known beforehand, dpiv * foo -- is
+//   computed for all rows of a pivot at once, one row per lane (lean_prepare_rows; the rows' entries in the pivot column
+//   are gathered from HBM ahead of the row queue), and the row loop takes each row's scalars out of the lanes: the
+//   scalar unit no longer runs a binary gcd, two exact quotients and a 64-bit product per row, and the row gcd starts
+//   from the folded value (small_reduce_from / row_reduce_rem_from) -- no remainder pass at all when that is 1.
+//   (PIP_LEAN_KEEPCUT) a cut integrer() has just built stays in registers as the next pivot row.
+//   (tests/test_gpu_lean_prep.py, tests/test_gpu_lean_prep_probe.py.)
 //   (tests/test_gpu_parity.py: test_lean_kernel_paths, test_lean_kernel_other_widths, and every batch test of the suite.)
 // LeanLongRows, pip_lean64_kernel: the same one width up.  128-bit Entier, long long rows, 129 ... 256 columns, run-time
 //   row capacity; lane l holds columns l, 64 + l, 128 + l, 192 + l (the geometry of pip_advance_kernel<__int128, 4>, so
@@ -38,7 +46,9 @@
 //   (the batch pinned by tests/golden/gmp/wide128.json) the reference's GMP build forms a value beyond 2^63 on 587, yet on
 //   two in three every STORED entry stays below 2^63 from the first pivot to the last (657 of the 1,000 finish in this
 //   kernel, 325 leave on a row beyond 2^63).  Small path: 64-bit arithmetic; mid path: 64 x 64 -> 128-bit products (four
-//   32-bit multiply-adds each, not ten), reduce_by_inverse picks the narrowest width that holds them.  OPT-IN
+//   32-bit multiply-adds each, not ten), reduce_by_inverse picks the narrowest width that holds them.  The per-lane
+//   preparation of a pivot's rows (below) is NOT taken: with it the kernel needs 168 VGPRs and 12 bytes of scratch, so
+//   PREP is false here and the row loop computes each row's multipliers itself, as before.  OPT-IN
 //   (pipamd_engine_set_lean64): measured on that batch it is no faster than the four-wave pip_advance_kernel<__int128>
 //   (16 registers a row, 128 VGPRs, 400 bytes of scratch per lane, three waves in four waiting during choisir_piv),
 //   DESIGN.md section 3.  (tests/test_gpu_parity.py: test_lean64_kernel_paths, test_full_size_int128_config, against the
@@ -52,6 +62,12 @@
 #endif
 #ifndef PIP_LEAN_MID_INV
 #define PIP_LEAN_MID_INV 0  // (A/B switch) the int mid path's row gcd and division by inverse multiplication (12 bytes of scratch per lane)
+#endif
+#ifndef PIP_LEAN_PREP
+#define PIP_LEAN_PREP 1  // (A/B switch) int rows: multipliers and first gcd fold of a pivot's rows prepared one row per lane (lean_prepare_rows)
+#endif
+#ifndef PIP_LEAN_KEEPCUT
+#define PIP_LEAN_KEEPCUT 1  // (A/B switch) a cut that integrer() has just built stays in registers as the pivot row
 #endif
 #ifndef PIP_LEAN_WAVES
 #define PIP_LEAN_WAVES 8  // waves per SIMD pip_lean_kernel is bounded to (64 VGPRs)
@@ -74,9 +90,11 @@ struct LeanIntRows {
   typedef i64 T;
   typedef int E;
   typedef LeanRow<int, 2> Row;
+  typedef unsigned G;  // a prepared row's starting gcd as its lane keeps it (0: nothing folded, or beyond G)
   static constexpr int NV = 2, NM = 2, NCH = 1, WP = 128, CLS0_BITS = 15, ROW_BITS = 31, CUT_BITS = 31;
   static constexpr int ENTRY_PF = 4, PF = PIP_LEAN_PF, UNPACK_GROUP = 4;  // rows in flight: entry pass, work list, rows_unpack
   static constexpr bool FRESH = true;  // the entry pass may read the caller's rows (PIPAMD_T_FRESHROWS)
+  static constexpr bool PREP = PIP_LEAN_PREP != 0;  // a pivot's rows are prepared one row per lane (lean_prepare_rows)
   static __device__ __forceinline__ int col(int lane, int h) { return 2 * lane + h; }
   static __device__ __forceinline__ int lane_of(int j) { return j >> 1; }
   static __device__ __forceinline__ int val_of(int j) { return j & 1; }
@@ -93,6 +111,8 @@ struct LeanIntRows {
     r.v[0] = t.x;
     r.v[1] = t.y;
   }
+  // column j of a packed row, from any lane
+  static __device__ __forceinline__ int gather(const i64 *slot, int j) { return reinterpret_cast<const int *>(slot)[j]; }
   static __device__ __forceinline__ void store(const Row &r, i64 *slot, int lane, int W) {
     int2 t;
     t.x = r.v[0];
@@ -136,9 +156,10 @@ struct LeanIntRows {
     }
   }
   static __device__ __forceinline__ bool small_den(i64) { return true; }
-  // small path: every operand below 2^15, every product below 2^30.  r <- (lp r - foo pr) / gcd, nd the new denominator
-  static __device__ __forceinline__ bool update_small(Row &r, const Row &pr, int lp, int foo, i64 dpiv, int pivj, i64 g0, int lane,
-                                                      i64 &nd) {
+  // small path: every operand below 2^15, every product below 2^30.  r <- (lp r - foo pr) / gcd, nd the new denominator;
+  // gs: where the row gcd starts (gcd(|g0|, |dpiv foo|) from lean_prepare_rows; 0: nothing prepared, from |g0|)
+  static __device__ __forceinline__ bool update_small(Row &r, const Row &pr, int lp, int foo, i64 dpiv, int pivj, i64 g0, u64 gs,
+                                                      int lane, i64 &nd) {
     int z[1][2];
     unsigned mx = 0;
 #pragma unroll
@@ -148,7 +169,7 @@ struct LeanIntRows {
       z[0][h] = v;
       mx |= mag(v);
     }
-    const bool ok = small_reduce<1>(z, mx, g0, lane, nd);
+    const bool ok = small_reduce_from<1>(z, mx, g0, gs ? gs : uabs64(g0), lane, nd);
     r.v[0] = z[0][0];
     r.v[1] = z[0][1];
     return ok;
@@ -157,7 +178,7 @@ struct LeanIntRows {
   // wrap-around arithmetic has nothing to wrap here, except dpiv * foo under a denominator beyond ints, which wraps the
   // same way)
   static __device__ __forceinline__ bool update_mid(i64 (&zw)[2], const Row &r, const Row &pr, int lp, int foo, i64 dpiv, int pivj,
-                                                    i64 g0, int lane, i64 &nd) {
+                                                    i64 g0, u64 gs, int lane, i64 &nd) {
     u64 mx = 0;
 #pragma unroll
     for (int h = 0; h < 2; h++) {
@@ -167,9 +188,9 @@ struct LeanIntRows {
       mx |= uabs64(v);
     }
 #if PIP_LEAN_MID_INV
-    return row_reduce<i64, 2, false>(zw, mx, g0, lane, nd, wmul(dpiv, (i64)foo));
+    return row_reduce<i64, 2, false>(zw, mx, g0, lane, nd, wmul(dpiv, (i64)foo), gs);
 #else
-    return row_reduce_rem<i64, 2>(zw, mx, g0, lane, nd);  // (the remainder loop: reduce_by_inverse costs this kernel 12 bytes of scratch)
+    return row_reduce_rem_from<i64, 2>(zw, mx, g0, gs ? gs : uabs64(g0), lane, nd);  // (the remainder loop: reduce_by_inverse costs this kernel 12 bytes of scratch)
 #endif
   }
 };
@@ -178,9 +199,11 @@ struct LeanLongRows {
   typedef i128 T;
   typedef i64 E;
   typedef LeanRow<i64, 4> Row;
+  typedef u64 G;
   static constexpr int NV = 4, NM = 4, NCH = 4, WP = 256, CLS0_BITS = 31, ROW_BITS = 63, CUT_BITS = 62;
   static constexpr int ENTRY_PF = 1, PF = 2, UNPACK_GROUP = 2;
   static constexpr bool FRESH = false;
+  static constexpr bool PREP = false;  // (128-bit gcds one per lane: 12 bytes of scratch under the 168-register bound, see the header comment)
   static __device__ __forceinline__ int col(int lane, int c) { return 64 * c + lane; }
   static __device__ __forceinline__ int lane_of(int j) { return j & 63; }
   static __device__ __forceinline__ int val_of(int j) { return j >> 6; }
@@ -198,6 +221,7 @@ struct LeanLongRows {
       r.v[c] = j < W ? p[j] : 0;
     }
   }
+  static __device__ __forceinline__ i64 gather(const i128 *slot, int j) { return reinterpret_cast<const i64 *>(slot)[j]; }
   static __device__ __forceinline__ void store(const Row &r, i128 *slot, int lane, int W) {
     i64 *p = reinterpret_cast<i64 *>(slot);
 #pragma unroll
@@ -240,8 +264,8 @@ struct LeanLongRows {
   }
   static __device__ __forceinline__ bool small_den(i128 g0) { return g0 < ((i128)1 << 62) && g0 > -((i128)1 << 62); }
   // small path: every operand below 2^31, every product below 2^62; the denominator product a long long (small_den)
-  static __device__ __forceinline__ bool update_small(Row &r, const Row &pr, i64 lp, i64 foo, i128 dpiv, int pivj, i128 g0, int lane,
-                                                      i128 &nd) {
+  static __device__ __forceinline__ bool update_small(Row &r, const Row &pr, i64 lp, i64 foo, i128 dpiv, int pivj, i128 g0, u128 gs,
+                                                      int lane, i128 &nd) {
     u64 mx = 0;
     const i64 zf = (i64)dpiv * foo;
 #pragma unroll
@@ -252,7 +276,7 @@ struct LeanLongRows {
       mx |= uabs64(v);
     }
     i64 nd64;
-    const bool ok = row_reduce<i64, 4>(r.v, mx, (i64)g0, lane, nd64, zf);
+    const bool ok = row_reduce<i64, 4>(r.v, mx, (i64)g0, lane, nd64, zf, (u64)gs);  // (small_den: gs <= |g0| < 2^62)
     nd = (i128)nd64;
     return ok;
   }
@@ -260,7 +284,7 @@ struct LeanLongRows {
   // wrap-around arithmetic has nothing to wrap here, except the products with denominators beyond long longs, which wrap
   // the same way)
   static __device__ __forceinline__ bool update_mid(i128 (&zw)[4], const Row &r, const Row &pr, i64 lp, i64 foo, i128 dpiv, int pivj,
-                                                    i128 g0, int lane, i128 &nd) {
+                                                    i128 g0, u128 gs, int lane, i128 &nd) {
     u128 mx = 0;
     const i128 zf = wmul(dpiv, (i128)foo);
 #pragma unroll
@@ -270,7 +294,7 @@ struct LeanLongRows {
       zw[c] = v;
       mx |= uabs64(v);
     }
-    return row_reduce<i128, 4>(zw, mx, g0, lane, nd, zf);
+    return row_reduce<i128, 4>(zw, mx, g0, lane, nd, zf, gs);
   }
 };
 
@@ -294,6 +318,68 @@ __device__ __forceinline__ X lean_entry(const X (&v)[F::NV], int k, int src) {
     return __builtin_amdgcn_readlane(mine, src);
   else
     return readlane64(mine, src);
+}
+
+// lane k's copy of a value (k uniform)
+template <class X>
+__device__ __forceinline__ X lean_lane(X v, int k) {
+  if constexpr (sizeof(X) == 4)
+    return (X)__builtin_amdgcn_readlane((int)v, k);
+  else if constexpr (sizeof(X) == 8)
+    return (X)readlane64((i64)v, k);
+  else
+    return (X)readlane64((i128)v, k);
+}
+
+// The part of a row's update that needs no more of the row than its entry `foo` in the pivot column (traiter.c:470-476):
+// the multipliers lp = pivot / d and foo / d, d = gcd(pivot, foo); the denominator product g0 = lp * den; and the first
+// fold of the row gcd, gs = gcd(|g0|, |dpiv * foo|) -- dpiv * foo is the new row's entry in the pivot column, the one
+// entry known before the row arrives.  gs = 0: nothing folded (that entry is 0, or g0 is 0 or +-1), the row gcd starts
+// from |g0|.  Plain per-lane code: pip_lean's row loop used to run it once per row on the scalar unit, lean_prepare_rows
+// runs it for 64 rows at once, one per lane.
+template <class F>
+__device__ __forceinline__ void lean_prep_lane(typename F::E pivot, typename F::T dpiv, typename F::T den, typename F::E &foo,
+                                               typename F::E &lp, typename F::T &g0, typename ET<typename F::T>::U &gs) {
+  typedef typename F::T T;
+  typedef typename F::E E;
+  lp = pivot;
+  g0 = den;
+  if (pivot != 1) {
+    const auto d = F::gcd(pivot, foo);
+    if (d != 1) {  // (d == 0 cannot be: pivot > 0)
+      lp = (E)exact_quo<i64>((i64)pivot, (i64)d);
+      foo = (E)exact_quo<i64>((i64)foo, (i64)d);
+    }
+    g0 = wmul((T)lp, den);
+  }
+  gs = 0;
+  const auto ag = uabs64(g0);
+  const T zf = wmul(dpiv, (T)foo);
+  if (ag > 1 && zf != 0) gs = gcd_mag(ag, uabs64(zf));
+}
+
+// Lane k prepares the row of S.work[w0 + k] (k < nwork - w0; the recycled pivot slot is skipped): `fk` is the row's entry
+// in the pivot column, gathered by the caller (F::gather, issued ahead of the row queue's loads); the denominator and the
+// magnitude class come from LDS.  Out, per lane: the multipliers, g0, the starting gcd (as F::G); returns the mask of
+// the lanes whose row takes the small path.
+template <class F>
+__device__ __forceinline__ u64 lean_prepare_rows(const Shared<typename F::T> &S, int sk, bool active, typename F::E fk, typename F::E pivot,
+                                                 typename F::T dpiv, bool psmall, typename F::E &m_lp, typename F::E &m_foo,
+                                                 typename F::T &m_g0, typename F::G &m_gs) {
+  typedef typename F::T T;
+  bool small = false;
+  m_lp = pivot;
+  m_foo = 0;
+  m_g0 = 1;
+  m_gs = 0;
+  if (active) {
+    typename ET<T>::U gs;
+    m_foo = fk;
+    lean_prep_lane<F>(pivot, dpiv, S.den[sk], m_foo, m_lp, m_g0, gs);
+    m_gs = (typename F::G)gs == gs ? (typename F::G)gs : 0;
+    small = psmall && S.rcls[sk] == 0 && F::small_den(m_g0);
+  }
+  return ballot64(small);
 }
 
 // rows [0, n) of a block, packed -> the general format, each within its own slot (the loads of a group of rows are back
@@ -570,13 +656,14 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
     }
     return;
   }
-  T *vals = (T *)(arena + J->vals_off);
+  T *vals = (T *)(arena + uni64((i64)J->vals_off));
   // (what only the prologue and the epilogue need -- the row tables in HBM, the saved summaries, the counters -- is
   // derived from the job header where it is used, so that it holds no scalar registers across the pivot loop)
   const int ncut0 = J->ncut - ni;  // cuts so far = ncut0 + ni (every row this kernel appends is a cut)
-  const int cap_ni = min(J->S, J->L - nvar);  // rows the job's block holds
+  // (wave-uniform, but loaded through vector memory: pinned to scalar registers, the pivot loop needs the vector ones)
+  const int cap_ni = __builtin_amdgcn_readfirstlane(min(J->S, J->L - nvar));  // rows the job's block holds
   int npiv = J->npiv, nupd = J->nupd;
-  T *g_log = (T *)(arena + J->log_off);
+  T *g_log = (T *)(arena + uni64((i64)J->log_off));
   constexpr int LOGCAP = PIPAMD_DETLOG;
   int nlog = J->nlog;
 
@@ -704,6 +791,8 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
     if (mcw > 1) break;  // a row left E (it is stored in the general format): the general kernel goes on
     why = 0;
     int pivi = sc.pivi;
+    Row pr;                // the pivot row
+    bool have_pr = false;  // ... is in registers already: the cut integrer() has just built and stored
     if (pivi == BIG_I) {
       // -------------- exam_coef (its flags were prepared by phase C), then integrer if nothing is negative
       pivi = sc.pivi2;
@@ -735,7 +824,7 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
         why = 3;
         if (DT <= 0 || DT >= ((T)1 << F::CUT_BITS)) break;  // the cut's entries (below D) might not fit E: the general kernel goes on
         const E D = (E)DT;
-        Row r;
+        Row &r = pr;  // (PIP_LEAN_KEEPCUT: the cut is the next pivot row)
         F::load(r, vals + (size_t)cslot * W, lane, W);
         F::row_mod(r, D, S.rcls[cslot] == 0);
         bool okv = false;
@@ -777,6 +866,7 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
         pivi = nligne;
         ni++;
         nligne++;
+        have_pr = PIP_LEAN_KEEPCUT != 0;
       }
     }
     PROF(0);
@@ -787,8 +877,7 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
     // the multipliers are below it as well and every product fits E)
     const bool psmall = S.rcls[pslot] == 0 && dpiv > -((T)1 << F::CLS0_BITS) && dpiv < ((T)1 << F::CLS0_BITS);
     npiv++;
-    Row pr;
-    F::load(pr, vals + (size_t)pslot * W, lane, W);
+    if (!have_pr) F::load(pr, vals + (size_t)pslot * W, lane, W);
     const int psig_v = S.sig[pslot];
 #ifdef PIP_PROFILE
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -826,6 +915,20 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
       constexpr int PF = F::PF;
       Row rq[PF];
       int sq[PF];
+      // (F::PREP) the wave-uniform part of every row's update, for the first 64 rows of the work list, one row per lane
+      // (lean_prepare_rows): the gather of the pivot column goes out ahead of the queue's loads
+      E m_lp = 0, m_foo = 0;
+      T m_g0 = 0;
+      typename F::G m_gs = 0;
+      u64 m_small = 0;
+      int pk = 0;
+      bool pact = false;
+      E pf = 0;
+      if constexpr (F::PREP) {
+        pk = S.work[lane < nwork ? lane : 0];
+        pact = lane < nwork && pk != pslot;
+        if (pact) pf = F::gather(vals + (size_t)pk * W, pivj);
+      }
 #pragma unroll
       for (int q2 = 0; q2 < PF; q2++) {
         sq[q2] = S.work[q2 < nwork ? q2 : 0];
@@ -848,6 +951,16 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
       }
       PROF(4);
       for (int w = 0; w < nwork; w++) {
+        if constexpr (F::PREP) {
+          if ((w & 63) == 0) {
+            if (w) {  // (more than 64 work rows: the next 64)
+              pk = S.work[w + lane < nwork ? w + lane : 0];
+              pact = w + lane < nwork && pk != pslot;
+              if (pact) pf = F::gather(vals + (size_t)pk * W, pivj);
+            }
+            m_small = lean_prepare_rows<F>(S, pk, pact, pf, pivot, dpiv, psmall, m_lp, m_foo, m_g0, m_gs);
+          }
+        }
         const int s = sq[0];
         Row r = rq[0];
 #pragma unroll
@@ -866,22 +979,36 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
 #endif
         PROF(5);
         // multipliers from the row's own pivot-column entry (traiter.c:470-476); packed elements
-        E foo = lean_entry<F>(r.v, pe, pl);
-        const T den_s = uni64(S.den[s]);
-        E lp = pivot;
-        T g0 = den_s;
-        if (pivot != 1) {
-          const auto d = F::gcd(pivot, foo);
-          if (d != 1) {  // (d == 0 cannot be: pivot > 0)
-            lp = (E)exact_quo<i64>((i64)pivot, (i64)d);
-            foo = (E)exact_quo<i64>((i64)foo, (i64)d);
+        E foo, lp;
+        T g0;
+        typename ET<T>::U gs = 0;  // where the row gcd starts (0: from |g0|)
+        bool small;
+        if constexpr (F::PREP) {  // prepared by the row's lane
+          const int k = w & 63;
+          foo = lean_lane(m_foo, k);
+          lp = lean_lane(m_lp, k);
+          g0 = lean_lane(m_g0, k);
+          gs = lean_lane(m_gs, k);
+          small = (m_small >> k) & 1;
+        } else {
+          foo = lean_entry<F>(r.v, pe, pl);
+          const T den_s = uni64(S.den[s]);
+          lp = pivot;
+          g0 = den_s;
+          if (pivot != 1) {
+            const auto d = F::gcd(pivot, foo);
+            if (d != 1) {  // (d == 0 cannot be: pivot > 0)
+              lp = (E)exact_quo<i64>((i64)pivot, (i64)d);
+              foo = (E)exact_quo<i64>((i64)foo, (i64)d);
+            }
+            g0 = wmul((T)lp, den_s);
           }
-          g0 = wmul((T)lp, den_s);
+          small = psmall && S.rcls[s] == 0 && F::small_den(g0);
         }
         T nd;
         PROF(6);
-        if (psmall && S.rcls[s] == 0 && F::small_den(g0)) {
-          if (!F::update_small(r, pr, lp, foo, dpiv, pivj, g0, lane, nd)) {
+        if (small) {
+          if (!F::update_small(r, pr, lp, foo, dpiv, pivj, g0, gs, lane, nd)) {
             if (lane == 0) sc.bad = 1;
           }
           PROF(7);
@@ -889,7 +1016,7 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
           mcw = max(mcw, lean_publish<F>(r, S, cst, s, pivj, SIG_RED, lane, nvar));
         } else {
           T zw[NV];
-          if (!F::update_mid(zw, r, pr, lp, foo, dpiv, pivj, g0, lane, nd)) {
+          if (!F::update_mid(zw, r, pr, lp, foo, dpiv, pivj, g0, gs, lane, nd)) {
             if (lane == 0) sc.bad = 1;
           }
           typename ET<T>::U mx = 0;

@@ -5,6 +5,8 @@
 //
 //   pipamd_debug_arith(engine, op, in, out, n)            one case per lane, n cases
 //   pipamd_debug_row_update(engine, path, in, out, ncases) one wave per case (the row functions ballot and readlane)
+// and the lean kernel's per-lane preparation and its reductions from a given gcd (tests/test_gpu_lean_prep_probe.py):
+// pipamd_debug_arith op 128, pipamd_debug_row_update paths 32 ... 35.
 //
 // `in` / `out`: device pointers to int64 words, 16-byte aligned; a 128-bit value is two words, low then high (as
 // det_limb).  Exported, not declared in include/piplib_amd.h (like pipamd_debug_lean): no part of the interface.
@@ -24,7 +26,9 @@ enum {
   P_UMOD128, P_UMOD128_32, P_UMODS64, P_UMODS128, P_UMOD_TINY, P_UMOD_TINY_LOW, P_ROWMOD_INT, P_ROWMOD_LONG,
   P_LOG2_64, P_LOG2_128, P_BITLEN64, P_BITLEN128, P_CTZ128, P_FITS64, P_BEZOUT64, P_BEZOUT128, P_DET64, P_DET128,
   P_NOPS,
-  P_QUAST0 = 64, P_QUAST_NOPS = 26  // device tree: 64 + 2 * function + (128-bit ? 1 : 0); 3 values in, value + bad out
+  P_QUAST0 = 64, P_QUAST_NOPS = 26,  // device tree: 64 + 2 * function + (128-bit ? 1 : 0); 3 values in, value + bad out
+  P_LEAN_PREP = 128  // lean_prepare_rows<LeanIntRows>, 64 rows a wave: pivot, dpiv, psmall (those of the wave's first case hold
+                     // for the wave), foo, den, rcls in; lp, foo', g0, starting gcd, small-path predicate out
 };
 struct ProbeIO {
   int nin, nout;
@@ -116,11 +120,39 @@ __global__ __launch_bounds__(64) void pip_probe_arith_kernel(int op, const i64 *
   }
 }
 
+__global__ __launch_bounds__(64) void pip_probe_lean_prep_kernel(const i64 *in, i64 *out, long long n) {
+  typedef LeanIntRows F;
+  __shared__ i64 den[64];
+  __shared__ u8 rcls[64];
+  const int lane = threadIdx.x;
+  const long long t0 = (long long)blockIdx.x * 64, t = t0 + lane;
+  const bool active = t < n;
+  const i64 *a = in + (active ? t : t0) * 6;
+  Shared<i64> S = {};
+  S.den = den;
+  S.rcls = rcls;
+  den[lane] = a[4];
+  rcls[lane] = (u8)a[5];
+  __syncthreads();
+  const int pivot = __builtin_amdgcn_readfirstlane((int)a[0]);
+  const i64 dpiv = uni64(a[1]);
+  const bool psmall = __builtin_amdgcn_readfirstlane((int)(a[2] != 0)) != 0;
+  int m_lp, m_foo;
+  i64 m_g0;
+  F::G m_gs;
+  const u64 small = lean_prepare_rows<F>(S, lane, active, (int)a[3], pivot, dpiv, psmall, m_lp, m_foo, m_g0, m_gs);
+  if (active) {
+    i64 *o = out + t * 5;
+    o[0] = m_lp, o[1] = m_foo, o[2] = m_g0, o[3] = (i64)m_gs, o[4] = (i64)((small >> lane) & 1);
+  }
+}
+
 // ---- pipamd_debug_row_update: one wave per case.  Values of a case are of the path's Entier T (one word, or two for the
 // 128-bit paths): in  lpiv, foo, dpiv, g0, pivj, gpre, p[WP], q[WP];  out  ok, newden, z[WP].
 enum {
   R_G64_1, R_G64_2, R_G64_4, R_G64R, R_S64, R_G128_1, R_G128_4, R_N128_1, R_N128_4, R_NN128_1, R_NN128_4,
-  R_LI_S, R_LI_M, R_LL_S, R_LL_M, R_NPATHS
+  R_LI_S, R_LI_M, R_LL_S, R_LL_M, R_NPATHS,
+  R_GS0 = 32, R_LI_S_GS = R_GS0, R_LI_M_GS, R_LL_S_GS, R_LL_M_GS, R_GS_END  // the lean flavours with `gpre` as the starting gcd gs
 };
 template <class T>
 __device__ __forceinline__ T ldv(const i64 *p, size_t k) {
@@ -172,7 +204,7 @@ __global__ __launch_bounds__(64) void pip_probe_row_kernel(const i64 *in, i64 *o
 }
 
 // the lean flavours: the probe packs the rows (int / long long) as the lean kernels hold them
-template <class F, bool SMALL>
+template <class F, bool SMALL, bool GS = false>
 __global__ __launch_bounds__(64) void pip_probe_lean_kernel(const i64 *in, i64 *out, int ncases) {
   typedef typename F::T T;
   typedef typename F::E E;
@@ -183,6 +215,7 @@ __global__ __launch_bounds__(64) void pip_probe_lean_kernel(const i64 *in, i64 *
   i64 *co = out + (size_t)cs * EW * (2 + WP);
   const T lpiv = ldv<T>(ci, 0), foo = ldv<T>(ci, 1), dpiv = ldv<T>(ci, 2), g0 = ldv<T>(ci, 3);
   const int pivj = (int)ci[EW * 4];
+  const typename ET<T>::U gs = GS ? (typename ET<T>::U)ldv<T>(ci, 5) : 0;
   typename F::Row r, pr;
 #pragma unroll
   for (int h = 0; h < F::NV; h++) {
@@ -192,12 +225,12 @@ __global__ __launch_bounds__(64) void pip_probe_lean_kernel(const i64 *in, i64 *
   T nd = 0;
   bool ok;
   if constexpr (SMALL) {
-    ok = F::update_small(r, pr, (E)lpiv, (E)foo, dpiv, pivj, g0, lane, nd);
+    ok = F::update_small(r, pr, (E)lpiv, (E)foo, dpiv, pivj, g0, gs, lane, nd);
 #pragma unroll
     for (int h = 0; h < F::NV; h++) stv<T>(co, 2 + F::col(lane, h), (T)r.v[h]);
   } else {
     T zw[F::NV];
-    ok = F::update_mid(zw, r, pr, (E)lpiv, (E)foo, dpiv, pivj, g0, lane, nd);
+    ok = F::update_mid(zw, r, pr, (E)lpiv, (E)foo, dpiv, pivj, g0, gs, lane, nd);
 #pragma unroll
     for (int h = 0; h < F::NV; h++) stv<T>(co, 2 + F::col(lane, h), zw[h]);
   }
@@ -223,16 +256,22 @@ int probe_finish(hipError_t e) {
 
 extern "C" int pipamd_debug_arith(pipamd_engine *e, int op, const long long *in, long long *out, long long n) {
   const bool quast = op >= P_QUAST0 && op < P_QUAST0 + P_QUAST_NOPS;
-  if (!e || n < 0 || n > (1ll << 30) || !probe_ptrs_ok(in, out) || !(quast || (op >= 0 && op < P_NOPS))) return PIPAMD_E_INVALID;
+  if (!e || n < 0 || n > (1ll << 30) || !probe_ptrs_ok(in, out) || !(quast || op == P_LEAN_PREP || (op >= 0 && op < P_NOPS)))
+    return PIPAMD_E_INVALID;
   if (hipSetDevice(e->device) != hipSuccess) return PIPAMD_E_HIP;
   if (n == 0) return PIPAMD_OK;
   if (quast) return probe_finish(pipk_launch_quast_probe(op - P_QUAST0, in, out, (int)n, 0));
+  if (op == P_LEAN_PREP) {
+    hipLaunchKernelGGL(pip_probe_lean_prep_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, in, out, n);
+    return probe_finish(hipGetLastError());
+  }
   hipLaunchKernelGGL(pip_probe_arith_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, 0, op, in, out, n);
   return probe_finish(hipGetLastError());
 }
 
 extern "C" int pipamd_debug_row_update(pipamd_engine *e, int path, const long long *in, long long *out, int ncases) {
-  if (!e || ncases < 0 || !probe_ptrs_ok(in, out) || path < 0 || path >= R_NPATHS) return PIPAMD_E_INVALID;
+  if (!e || ncases < 0 || !probe_ptrs_ok(in, out) || path < 0 || (path >= R_NPATHS && !(path >= R_GS0 && path < R_GS_END)))
+    return PIPAMD_E_INVALID;
   if (hipSetDevice(e->device) != hipSuccess) return PIPAMD_E_HIP;
   if (ncases == 0) return PIPAMD_OK;
 #define PIP_PROBE_ROW(...) hipLaunchKernelGGL((__VA_ARGS__), dim3(ncases), dim3(64), 0, 0, in, out, ncases)
@@ -252,6 +291,10 @@ extern "C" int pipamd_debug_row_update(pipamd_engine *e, int path, const long lo
     case R_LI_M: PIP_PROBE_ROW(pip_probe_lean_kernel<LeanIntRows, false>); break;
     case R_LL_S: PIP_PROBE_ROW(pip_probe_lean_kernel<LeanLongRows, true>); break;
     case R_LL_M: PIP_PROBE_ROW(pip_probe_lean_kernel<LeanLongRows, false>); break;
+    case R_LI_S_GS: PIP_PROBE_ROW(pip_probe_lean_kernel<LeanIntRows, true, true>); break;
+    case R_LI_M_GS: PIP_PROBE_ROW(pip_probe_lean_kernel<LeanIntRows, false, true>); break;
+    case R_LL_S_GS: PIP_PROBE_ROW(pip_probe_lean_kernel<LeanLongRows, true, true>); break;
+    case R_LL_M_GS: PIP_PROBE_ROW(pip_probe_lean_kernel<LeanLongRows, false, true>); break;
   }
 #undef PIP_PROBE_ROW
   return probe_finish(hipGetLastError());
