@@ -126,6 +126,13 @@ int pipamd_engine_set_lone_batches(pipamd_engine *e, int on);
  * entry fits 63 bits (half the traffic and registers), tableaux with a wider entry handed over to the 128-bit kernel.
  * Default 0: on BASELINE's configs[4] it is no faster than the four-waves-per-tableau 128-bit kernel. */
 int pipamd_engine_set_lean64(pipamd_engine *e, int on);
+/* Bulk batches whose one parameter is the big one (nparm == 1, bigparm == nvar + 1, at most 126 unknowns, 64-bit entries:
+ * what pipamd_batch_load_shifted builds for lexicographic maxima and unknowns of either sign): 1 = their one-wave launches
+ * are the lean kernel's big-parameter flavour (csrc/pip_lean.h), as for batches without parameters.  Same statuses, pivot
+ * counts and solutions.  Default 0, the launches such a batch always took: measured on 10,000 tableaux of 126 unknowns x 64
+ * inequalities the flavour is 13-35 % ahead with eight batches in flight and for a lone Maximize batch, but 3 % behind for a
+ * lone Urs_unknowns batch.  A caller that keeps batches in flight switches it on. */
+int pipamd_engine_set_lean_big(pipamd_engine *e, int on);
 /* A tail launch of a 128-bit batch over at most 256 tableaux gives each a whole CU (sixteen waves): the hundreds of rows a
  * late pivot of a long tableau rewrites spread over four times the waves (built in; pipamd_engine_set_tail_waves or
  * _set_waves_per_job switch it off). */
@@ -200,6 +207,41 @@ int pipamd_batch_poll(pipamd_engine *e);
 int pipamd_batch_results(pipamd_engine *e, const void *d_workspace, const pipamd_batch_desc *d,
                          int32_t *d_status, int32_t *d_pivots, int32_t *d_cuts, int64_t *d_sol_num,
                          int64_t *d_sol_den, void *stream);
+
+/* Lexicographic maxima and unknowns of either sign: pip_solve with Maximize or Urs_unknowns (piplib.c:777-797, 846-858)
+ * for a whole batch.  The reference rewrites every inequality under a new "big parameter" Bg (tab_Matrix2Tableau,
+ * tab.c:292-393), solves with traiter(..., bigparm = Bg, ...) and undoes the shift in the answer (sol_vector_edit,
+ * sol.c:435-512).  Such a tableau needs no host decision -- exam_coef decides every sign from the big coefficient, then
+ * the constant (traiter.c:107-157), and integrer cuts on the constant alone (integrer.c:373-377) -- so layer 1 finishes
+ * the batch on its own, through the launch sequence of a batch without parameters (with pipamd_engine_set_lean_big, bulk
+ * batches of at most 126 unknowns start with the lean kernel's big-parameter flavour, csrc/pip_lean.h).
+ * The descriptor `d` describes the tableau AS IT IS SOLVED, for these entries and for pipamd_batch_workspace_bytes /
+ * pipamd_batch_solve alike: nparm == 1, bigparm == nvar + 1 (column order unknowns | constant | big).
+ * pipamd_batch_load_shifted: `d_rows` holds the caller's PLAIN system, batch x ni x (nvar + 1) int64 (unknowns then
+ * constant); the load kernel writes per row what tab.c:342-377 writes for a new big parameter:
+ *     PIPAMD_SHIFT_MAX:  -a_j | c | +sum a_j          PIPAMD_SHIFT_URS:  a_j | c | -sum a_j
+ * The sum wraps in 64 bits as the reference's long long build does; with entier_bits == 128 it is exact.
+ * PIPAMD_T_ROWS_STAY in tflags is ignored by these two entries (the caller's array is not the tableau; it may be
+ * released once the load's work on `stream` is done).  _part: tableaux first .. first + count - 1, as
+ * pipamd_batch_load_part.
+ * pipamd_batch_results_shifted: sol_vector_edit with SOL_REMOVE and SOL_MAX / SOL_SHIFT.  For unknown i with big
+ * numerator B, constant numerator N and denominator D (what pipamd_batch_results hands out as sol_num[b][i][0..1],
+ * sol_den[b][i]): g = gcd(N, D) >= 0 (gcd(0, D) = D), d_x_num[b][i] = N / g, negated for PIPAMD_SHIFT_MAX;
+ * d_x_den[b][i] = D / g, or 0 if B != D -- the reference's mark for an unbounded unknown (it prints "/0"), the numerator
+ * kept.  A tableau whose status is not PIPAMD_ST_SOLUTION gets (0, 0) in every entry.  int64 each, or (low, high) pairs
+ * for entier_bits == 128; status, pivots and cuts as in pipamd_batch_results; each of the five arrays may be NULL.
+ * PIPAMD_E_INVALID, before any HIP call: a null engine, workspace, descriptor or rows pointer; shift other than +-1;
+ * nparm != 1 or bigparm != nvar + 1; first / count outside the batch.
+ * pipamd_batch_dual still refuses batches with a big parameter. */
+#define PIPAMD_SHIFT_MAX 1    /* Maximize:     lexicographic maximum, unknowns >= 0      */
+#define PIPAMD_SHIFT_URS (-1) /* Urs_unknowns: lexicographic minimum, unknowns of any sign */
+int pipamd_batch_load_shifted(pipamd_engine *e, void *d_workspace, const pipamd_batch_desc *d, const int64_t *d_rows,
+                              int shift, void *stream);
+int pipamd_batch_load_shifted_part(pipamd_engine *e, void *d_workspace, const pipamd_batch_desc *d, const int64_t *d_rows,
+                                   int shift, int first, int count, void *stream);
+int pipamd_batch_results_shifted(pipamd_engine *e, const void *d_workspace, const pipamd_batch_desc *d, int shift,
+                                 int32_t *d_status, int32_t *d_pivots, int32_t *d_cuts, int64_t *d_x_num, int64_t *d_x_den,
+                                 void *stream);
 
 /* Compute_dual (the reference's TRAITER_DUAL, traiter.c:273-294, 567-620) for a batch solved with PIPAMD_T_DUAL in
  * tflags: the list of dual values solution_dual emits behind a rational solution, one per input inequality.  Callable

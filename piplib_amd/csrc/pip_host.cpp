@@ -305,7 +305,7 @@ struct BatchRun {
     void *big[2] = {&e->d_scratch, &e->scratch_bytes};
     // a uniform batch without parameters whose rows fill a wave's 128 columns exactly: FULL kernels
     const int hints = ((lay.nparm == 0 && lay.bigparm < 0 && lay.nvar + 1 == 128 && lay.W == 128) ? 1 : 0) |
-                      (lean ? (lay.ebits == 128 ? 8 : 2) : 0) | (replay ? 0 : 4);
+                      (lean ? (lay.ebits == 128 ? 8 : (lay.bigparm >= 0 ? 2 | 16 : 2)) : 0) | (replay ? 0 : 4);
     HIPCHK(pipk_launch_advance_q(jobs, arena, lay.batch, lay.nvar + smax, smax, lay.W, budget, waves, lay.ebits, q5, grid,
                                  big, hints, e->d_prof, st));
     if (!e->no_timing) HIPCHK(hipEventRecord(e->ev[2 * e->nlaunch + 1], st));
@@ -405,7 +405,12 @@ struct BatchRun {
       if (smax > curS) smax = curS;
       // no parameters, at most 128 columns of 64-bit entries, rows skipped, plain cuts: the lean kernel (pip_lean.h) goes
       // first -- it finishes the tableaux whose entries stay below 2^15 and leaves the others to the general kernel's launch
-      const bool lean = !dual && !e->no_lean && lay.ebits != 128 && lay.nparm == 0 && lay.bigparm < 0 && lay.W <= 128 && !(lay.W & 1) &&
+      // ... and its BIG flavour for the batches whose one parameter is the big one (lexicographic maxima, unknowns of either
+      // sign: pipamd_batch_load_shifted), which need no host decision either.  Opt-in (pipamd_engine_set_lean_big):
+      // measured, it is ahead by 13-35 % except for a lone Urs_unknowns batch, where it is 3 % behind
+      const bool plain = lay.nparm == 0 && lay.bigparm < 0;
+      const bool bigone = e->lean_big && lay.nparm == 1 && lay.bigparm == lay.nvar + 1 && lay.nvar + 2 <= lay.W;
+      const bool lean = !dual && !e->no_lean && lay.ebits != 128 && (plain || bigone) && lay.W <= 128 && !(lay.W & 1) &&
                         !(lay.tflags & (PIPAMD_T_NOSKIP | PIPAMD_T_DEEPEST)) && pipk_lean_class(smax) != 0;
       // (the bulk launches leave their determinant logs to the replay behind the first tail launch; two of them log at
       // most 2 * budget pivots per tableau)
@@ -603,6 +608,15 @@ extern "C" int pipamd_engine_set_lean64(pipamd_engine *e, int on) {
   return PIPAMD_OK;
 }
 
+// The lean kernel's BIG flavour (pip_lean_kernel<SC, false, true>, csrc/pip_lean.h) for the bulk launches of batches whose one
+// parameter is the big one (nparm == 1, bigparm == nvar + 1, at most 128 columns of 64-bit entries); default off: such a
+// batch then takes the launches it always took.  pipamd_debug_lean(e, 0) / PIPAMD_NO_LEAN switch it off like the plain flavour.
+extern "C" int pipamd_engine_set_lean_big(pipamd_engine *e, int on) {
+  if (!e) return PIPAMD_E_INVALID;
+  e->lean_big = on ? 1 : 0;
+  return PIPAMD_OK;
+}
+
 extern "C" int pipamd_engine_set_timing(pipamd_engine *e, int on) {
   if (!e) return PIPAMD_E_INVALID;
   e->no_timing = !on;
@@ -694,6 +708,69 @@ extern "C" int pipamd_batch_results(pipamd_engine *e, const void *d_ws, const pi
   const long long *arena = (const long long *)((const char *)d_ws + jb);
   HIPCHK(pipk_launch_batch_results(jobs, arena, lay.batch, lay.nvar, lay.nparm, lay.ebits, d_status, d_pivots, d_cuts,
                                    (void *)d_sol_num, (void *)d_sol_den, (hipStream_t)stream));
+  return PIPAMD_OK;
+}
+
+// Maximize / Urs_unknowns for the batch layer (header comment: include/piplib_amd.h).  Everything is checked before the
+// first HIP call; the one launch goes on `stream` and nothing here waits for it.
+static int shifted_check(const char *who, const void *e, const void *d_ws, const pipamd_batch_desc *d, int shift) {
+  if (!e || !d_ws || !d) {
+    pipamd_set_error("%s: null engine, workspace or descriptor", who);
+    return PIPAMD_E_INVALID;
+  }
+  if (shift != PIPAMD_SHIFT_MAX && shift != PIPAMD_SHIFT_URS) {
+    pipamd_set_error("%s: shift must be PIPAMD_SHIFT_MAX (1) or PIPAMD_SHIFT_URS (-1), not %d", who, shift);
+    return PIPAMD_E_INVALID;
+  }
+  if (d->nparm != 1 || d->bigparm != d->nvar + 1) {
+    pipamd_set_error("%s: the descriptor must describe the shifted tableau (nparm == 1, bigparm == nvar + 1)", who);
+    return PIPAMD_E_INVALID;
+  }
+  return PIPAMD_OK;
+}
+
+extern "C" int pipamd_batch_load_shifted_part(pipamd_engine *e, void *d_ws, const pipamd_batch_desc *d, const int64_t *d_rows,
+                                              int shift, int first, int count, void *stream) {
+  int rc = shifted_check("batch_load_shifted", e, d_ws, d, shift);
+  if (rc) return rc;
+  if (!d_rows) {
+    pipamd_set_error("batch_load_shifted: null rows pointer");
+    return PIPAMD_E_INVALID;
+  }
+  PipBatchLayout lay;
+  size_t jb;
+  rc = pipamd_batch_layout(d, &lay, &jb);
+  if (rc) return rc;
+  if (first < 0 || count < 0 || first > lay.batch - count) {
+    pipamd_set_error("batch_load_shifted_part: tableaux %d..%d outside the batch of %d", first, first + count, lay.batch);
+    return PIPAMD_E_INVALID;
+  }
+  if (hipSetDevice(e->device) != hipSuccess) return PIPAMD_E_HIP;  // HIP's current device is per host thread
+  PipJob *jobs = (PipJob *)d_ws;
+  long long *arena = (long long *)((char *)d_ws + jb);
+  HIPCHK(pipk_launch_batch_load_shifted(jobs, arena, (const long long *)d_rows, lay, shift, first, count, (hipStream_t)stream));
+  return PIPAMD_OK;
+}
+
+extern "C" int pipamd_batch_load_shifted(pipamd_engine *e, void *d_ws, const pipamd_batch_desc *d, const int64_t *d_rows, int shift,
+                                         void *stream) {
+  return pipamd_batch_load_shifted_part(e, d_ws, d, d_rows, shift, 0, d ? d->batch : 0, stream);
+}
+
+extern "C" int pipamd_batch_results_shifted(pipamd_engine *e, const void *d_ws, const pipamd_batch_desc *d, int shift,
+                                            int32_t *d_status, int32_t *d_pivots, int32_t *d_cuts, int64_t *d_x_num,
+                                            int64_t *d_x_den, void *stream) {
+  int rc = shifted_check("batch_results_shifted", e, d_ws, d, shift);
+  if (rc) return rc;
+  PipBatchLayout lay;
+  size_t jb;
+  rc = pipamd_batch_layout(d, &lay, &jb);
+  if (rc) return rc;
+  if (hipSetDevice(e->device) != hipSuccess) return PIPAMD_E_HIP;  // HIP's current device is per host thread
+  const PipJob *jobs = (const PipJob *)d_ws;
+  const long long *arena = (const long long *)((const char *)d_ws + jb);
+  HIPCHK(pipk_launch_batch_results_shifted(jobs, arena, lay.batch, lay.nvar, lay.ebits, shift, d_status, d_pivots, d_cuts,
+                                           (void *)d_x_num, (void *)d_x_den, (hipStream_t)stream));
   return PIPAMD_OK;
 }
 

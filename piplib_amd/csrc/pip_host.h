@@ -21,6 +21,7 @@ struct pipamd_engine {
   int lone_batches;  /* 1: no general one-wave launch between the lean launch and the tail (pipamd_engine_set_lone_batches) */
   int no_lean;       /* 1: bulk launches without the lean kernel (pip_lean.h) */
   int lean64;        /* 1: 128-bit batches of 129 ... 256 columns start with pip_lean64_kernel (pip_lean.h; pipamd_engine_set_lean64) */
+  int lean_big;      /* 1: bulk batches whose one parameter is the big one start with the lean kernel's BIG flavour (pipamd_engine_set_lean_big) */
   int no_lean2;      /* 1: the second one-wave bulk launch is the general kernel even where the lean kernel could resume */
   int *h_run;        /* pinned: {jobs still running, their largest row count | PIPAMD_Q_CAPFLAG, how many of them are out of rows} */
   int *d_q;          /* launch-list control words (a pool, see pipamd_batch_solve) and the two job lists */
@@ -75,6 +76,11 @@ hipError_t pipk_launch_advance_q(PipJob *jobs, long long *arena, int njobs, int 
 hipError_t pipk_launch_replay_all(PipJob *jobs, long long *arena, int njobs, int ebits, int wave_per_job, hipStream_t stream);
 hipError_t pipk_launch_batch_load(PipJob *jobs, long long *arena, const long long *rows, PipBatchLayout lay, int first,
                                   int count, hipStream_t stream);
+hipError_t pipk_launch_batch_load_shifted(PipJob *jobs, long long *arena, const long long *rows, PipBatchLayout lay, int shift,
+                                          int first, int count, hipStream_t stream);
+hipError_t pipk_launch_batch_results_shifted(const PipJob *jobs, const long long *arena, int njobs, int nvar, int ebits,
+                                             int shift, int *status, int *pivots, int *cuts, void *x_num, void *x_den,
+                                             hipStream_t stream);
 hipError_t pipk_launch_batch_results(const PipJob *jobs, const long long *arena, int njobs, int nvar, int nparm,
                                      int ebits, int *status, int *pivots, int *cuts, void *sol_num, void *sol_den,
                                      hipStream_t stream);

@@ -17,6 +17,9 @@ PIP_ADV_GROUP_F(PIP_ADV_EXTERN)
 #define PIP_LEAN_EXTERN(SC, FULL) extern template hipError_t launch_lean<SC, FULL>(const AdvanceLaunch &);
 PIP_LEAN_CLASSES(PIP_LEAN_EXTERN)
 #undef PIP_LEAN_EXTERN
+#define PIP_LEAN_BIG_EXTERN(SC) extern template hipError_t launch_lean<SC, false, true>(const AdvanceLaunch &);
+PIP_LEAN_BIG_CLASSES(PIP_LEAN_BIG_EXTERN)
+#undef PIP_LEAN_BIG_EXTERN
 
 // ------------------------------------------------------------- determinant replay
 // traiter.c:394-446 for the pivots a launch logged: d = gcd(pivot, dpiv); the limbs lose the
@@ -148,12 +151,17 @@ __global__ __launch_bounds__(64) void pip_det_replay_lanes_kernel(PipJob *jobs, 
 // tab_alloc + tab_get (tab.c:158-248) for a uniform batch: nvar unit rows, then
 // ni Unknown rows with denominator 1; spare slots and columns zeroed.  Input rows are int64
 // whatever the entry type of the tableau.
-template <class T>
-__global__ void pip_batch_load_kernel(PipJob *jobs, i64 *arena, const i64 *rows, PipBatchLayout lay, int first) {
+// SHIFTED (pipamd_batch_load_shifted; the layout has nparm == 1, bigparm == nvar + 1): `rows` holds the caller's plain
+// system, nvar + 1 columns a row, and the tableau gets what tab_Matrix2Tableau writes for a new big parameter
+// (tab.c:342-377): shift > 0 (Maximize) -a_j | c | +sum a_j, shift < 0 (Urs_unknowns) a_j | c | -sum a_j; the sum in
+// the entry type (64-bit entries: it wraps as the reference's long long build does).
+template <class T, bool SHIFTED = false>
+__global__ void pip_batch_load_kernel(PipJob *jobs, i64 *arena, const i64 *rows, PipBatchLayout lay, int first, int shift) {
   constexpr int EW = ET<T>::EW;
   const int b = first + blockIdx.x;  // `rows` holds the tableaux first, first + 1, ... of the batch
   const int tid = threadIdx.x;
   const int ncol = lay.nvar + lay.nparm + 1;
+  const int srccol = SHIFTED ? lay.nvar + 1 : ncol;  // columns of a row of `rows`
   PipJob *J = &jobs[b];
   const int64_t base = lay.arena_off + (int64_t)b * lay.blk.words;
   const auto [g_den, g_flag, g_ref] = pip_row_tables<T>(arena + base, lay.blk.L);
@@ -175,10 +183,34 @@ __global__ void pip_batch_load_kernel(PipJob *jobs, i64 *arena, const i64 *rows,
   }
   // input rows; spare slots only need their columns beyond ncol cleared (a cut row writes its
   // first ncol columns itself, a parametric cut relies on the new column being 0 elsewhere)
-  const i64 *src = rows + (size_t)blockIdx.x * lay.ni * ncol;
+  const i64 *src = rows + (size_t)blockIdx.x * lay.ni * srccol;
   const int pad = lay.W - ncol;
-  const bool defer = lay.pad != 0 && EW == 1;  // PIPAMD_T_ROWS_STAY: the first pivot launch fetches the rows itself
-  if (!defer) {
+  const bool defer = !SHIFTED && lay.pad != 0 && EW == 1;  // PIPAMD_T_ROWS_STAY: the first pivot launch fetches the rows itself
+  if constexpr (SHIFTED) {
+    const int nvar = lay.nvar;
+    int s = tid / lay.W, j = tid % lay.W;
+    const int ds = (int)blockDim.x / lay.W, dj = (int)blockDim.x % lay.W;
+    for (int e = tid; e < lay.ni * lay.W; e += blockDim.x) {
+      const i64 *r = src + (size_t)s * srccol;
+      T v = 0;
+      if (j < nvar)
+        v = shift > 0 ? wneg((T)r[j]) : (T)r[j];
+      else if (j == nvar)
+        v = (T)r[nvar];
+      else if (j == nvar + 1) {  // the new column: one thread per row sums the row
+        T sum = 0;
+        for (int k = 0; k < nvar; k++) sum = wadd(sum, (T)r[k]);
+        v = shift > 0 ? sum : wneg(sum);
+      }
+      vals[e] = v;
+      s += ds;
+      j += dj;
+      if (j >= lay.W) {
+        j -= lay.W;
+        s++;
+      }
+    }
+  } else if (!defer) {
     // (row, column) advance with the thread stride: no division per element
     const int ds = (int)blockDim.x / lay.W, dj = (int)blockDim.x % lay.W;
     int s = tid / lay.W, j = tid % lay.W;
@@ -220,6 +252,39 @@ __global__ void pip_batch_load_kernel(PipJob *jobs, i64 *arena, const i64 *rows,
     J->maxabs = 0;
     J->state_nch = 0;
     J->ebits = ET<T>::BITS;
+  }
+}
+
+// sol_vector_edit (sol.c:435-512) with SOL_REMOVE and SOL_MAX / SOL_SHIFT for a batch solved under a big parameter
+// (nparm == 1; the job's solution block holds big coefficient then constant per unknown, then the denominators): the
+// value of unknown i is constant / denominator in lowest terms, negated for Maximize (shift > 0); its denominator is 0
+// -- the reference's mark for "unbounded" -- unless the big coefficient equals the denominator (the shift cancels).
+// A tableau that is not PIPAMD_ST_SOLUTION gets (0, 0) throughout.
+template <class T>
+__global__ void pip_batch_results_shifted_kernel(const PipJob *jobs, const i64 *arena, int njobs, int nvar, int shift, int *status,
+                                                 int *pivots, int *cuts, T *x_num, T *x_den) {
+  const int b = blockIdx.x;
+  if (b >= njobs) return;
+  const PipJob *J = &jobs[b];
+  if (threadIdx.x == 0) {
+    if (status) status[b] = J->status;
+    if (pivots) pivots[b] = J->npiv;
+    if (cuts) cuts[b] = J->ncut;
+  }
+  const T *sn = (const T *)(arena + J->sol_off);
+  const bool ok = J->status == PIPAMD_ST_SOLUTION;
+  for (int i = threadIdx.x; i < nvar; i += blockDim.x) {
+    T xn = 0, xd = 0;
+    if (ok) {
+      const T B = sn[2 * i], N = sn[2 * i + 1], D = sn[2 * nvar + i];
+      T g = gcd_i64(N, D);  // (gcd(0, D) = |D|)
+      if (g == 0) g = 1;
+      xn = cquo(N, g);
+      if (shift > 0) xn = wneg(xn);
+      xd = B != D ? (T)0 : cquo(D, g);
+    }
+    if (x_num) x_num[(size_t)b * nvar + i] = xn;
+    if (x_den) x_den[(size_t)b * nvar + i] = xd;
   }
 }
 
@@ -710,7 +775,7 @@ extern "C" int pipk_lean_class(int smax) {
 __global__ __launch_bounds__(64, PIP_LEAN64_WAVES) void pip_lean64_kernel(PipJob *jobs, i64 *arena, int njobs, int Smax, int Lmax,
                                                                           int iter_limit, PipQueue q PIP_LEAN_PROF_PARAM) {
   typedef LeanLongRows F;
-  constexpr bool FULL = false;
+  constexpr bool FULL = false, BIG = false;
 #define PIP_LEAN_LOOP
 #include "pip_lean.h"
 #undef PIP_LEAN_LOOP
@@ -744,11 +809,22 @@ static hipError_t launch_lean64(const AdvanceLaunch &a) {
 }
 extern "C" size_t pipk_lean64_lds_bytes(int Smax, int Lmax) { return lean64_lds_bytes((Smax + 3) & ~3, (Lmax + 3) & ~3); }
 // the lean bulk kernel over a launch list; the caller has checked pipk_lean_class(a.Smax) != 0
-static hipError_t launch_lean_class(AdvanceLaunch a) {
+// (big: every job has one parameter, the big one, in column nvar + 1 -- the BIG flavour, run-time column counts)
+static hipError_t launch_lean_class(AdvanceLaunch a, bool big) {
   const int sc = pipk_lean_class(a.Smax);
   a.Smax = sc;
   a.Lmax = sc + 128;
   a.shm = pipk_advance_lds_bytes(a.Lmax, a.Smax, 128, 64);
+  if (big) {
+    switch (sc) {
+      case 64: return launch_lean<64, false, true>(a);
+      case 96: return launch_lean<96, false, true>(a);
+      case 112: return launch_lean<112, false, true>(a);
+      case 128: return launch_lean<128, false, true>(a);
+      case 160: return launch_lean<160, false, true>(a);
+    }
+    return hipErrorInvalidValue;
+  }
   switch (sc) {
     case 64: return a.full ? launch_lean<64, true>(a) : launch_lean<64, false>(a);
     case 96: return a.full ? launch_lean<96, true>(a) : launch_lean<96, false>(a);
@@ -809,6 +885,7 @@ static hipError_t launch_by_shape(const AdvanceLaunch &a, bool one, int wp, int 
 // this bit.  Bit 2: no determinant replay behind the launch (see pipk_launch_replay_all).  Bit 3 (one wave per job, 128-bit
 // entries, 129 ... 256 columns, pipk_lean64_lds_bytes(Smax, Lmax) within the LDS budget, else refused) = the lean kernel of
 // pip_lean.h on long long rows: it runs the jobs it can (no parameters, entries below 2^63) and leaves the others on the output list.
+// Bit 4 (with bit 1): every job has nparm == 1 and bigparm == nvar + 1 -- the lean kernel's BIG flavour.
 extern "C" hipError_t pipk_launch_advance_q(PipJob *jobs, i64 *arena, int njobs, int Lmax, int Smax, int Wmax,
                                             int iter_limit, int waves_per_job, int ebits, void *const *q5, int grid,
                                             void **big, int hints, unsigned long long *prof, hipStream_t stream) {
@@ -872,7 +949,7 @@ extern "C" hipError_t pipk_launch_advance_q(PipJob *jobs, i64 *arena, int njobs,
   hipError_t le;
   if (hints & 2) {
     if (!one || ebits != 64 || wp != 128 || a.gimg || !pipk_lean_class(a.Smax)) return hipErrorInvalidValue;
-    le = launch_lean_class(a);
+    le = launch_lean_class(a, (hints & 16) != 0);
   } else if (hints & 8) {  // the lean kernel of the 128-bit flavour (pip_lean.h on long long rows): 129 ... 256 columns, one wave per job
     if (!one || ebits != 128 || wp != 256 || pipk_lean64_lds_bytes(a.Smax, a.Lmax) > PIPAMD_LDS_BUDGET) return hipErrorInvalidValue;
     le = launch_lean64(a);
@@ -948,9 +1025,36 @@ extern "C" hipError_t pipk_launch_batch_load(PipJob *jobs, i64 *arena, const i64
                                              int count, hipStream_t stream) {
   if (count <= 0) return hipSuccess;
   if (lay.ebits == 128)
-    hipLaunchKernelGGL(pip_batch_load_kernel<i128>, dim3(count), dim3(256), 0, stream, jobs, arena, rows, lay, first);
+    hipLaunchKernelGGL(pip_batch_load_kernel<i128>, dim3(count), dim3(256), 0, stream, jobs, arena, rows, lay, first, 0);
   else
-    hipLaunchKernelGGL(pip_batch_load_kernel<i64>, dim3(count), dim3(256), 0, stream, jobs, arena, rows, lay, first);
+    hipLaunchKernelGGL(pip_batch_load_kernel<i64>, dim3(count), dim3(256), 0, stream, jobs, arena, rows, lay, first, 0);
+  return hipGetLastError();
+}
+
+// the same from a plain system under a new big parameter (shift = +1 Maximize, -1 Urs_unknowns); lay.nparm == 1,
+// lay.bigparm == lay.nvar + 1 (the caller has checked), `rows` nvar + 1 columns a row
+extern "C" hipError_t pipk_launch_batch_load_shifted(PipJob *jobs, i64 *arena, const i64 *rows, PipBatchLayout lay, int shift,
+                                                     int first, int count, hipStream_t stream) {
+  if (count <= 0) return hipSuccess;
+  if (lay.nparm != 1 || lay.bigparm != lay.nvar + 1 || lay.W < lay.nvar + 2 || (shift != 1 && shift != -1)) return hipErrorInvalidValue;
+  lay.pad = 0;
+  if (lay.ebits == 128)
+    hipLaunchKernelGGL((pip_batch_load_kernel<i128, true>), dim3(count), dim3(256), 0, stream, jobs, arena, rows, lay, first, shift);
+  else
+    hipLaunchKernelGGL((pip_batch_load_kernel<i64, true>), dim3(count), dim3(256), 0, stream, jobs, arena, rows, lay, first, shift);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t pipk_launch_batch_results_shifted(const PipJob *jobs, const i64 *arena, int njobs, int nvar, int ebits,
+                                                        int shift, int *status, int *pivots, int *cuts, void *x_num, void *x_den,
+                                                        hipStream_t stream) {
+  if (njobs <= 0) return hipSuccess;
+  if (ebits == 128)
+    hipLaunchKernelGGL(pip_batch_results_shifted_kernel<i128>, dim3(njobs), dim3(128), 0, stream, jobs, arena, njobs, nvar, shift,
+                       status, pivots, cuts, (i128 *)x_num, (i128 *)x_den);
+  else
+    hipLaunchKernelGGL(pip_batch_results_shifted_kernel<i64>, dim3(njobs), dim3(128), 0, stream, jobs, arena, njobs, nvar, shift,
+                       status, pivots, cuts, (i64 *)x_num, (i64 *)x_den);
   return hipGetLastError();
 }
 

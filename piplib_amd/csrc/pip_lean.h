@@ -2,7 +2,7 @@
 // batches live in, written once (the text under PIP_LEAN_LOOP at the end of this file) against a "row flavour", compiled
 // for the two flavours below.
 //
-// A lean kernel is one wave per tableau, no parameters, no big parameter, rows skipped, plain cuts -- and EVERY entry of
+// A lean kernel is one wave per tableau, no parameters (BIG flavour of the int rows: the big parameter alone), rows skipped, plain cuts -- and EVERY entry of
 // EVERY row stored at HALF the width of the flavour's Entier T (the packed element E).  Under that invariant
 //   * rows live in HBM packed (the first half of the row's slot of W entries of T): half the traffic of the reference's
 //     rows, half the working set, half the registers;
@@ -38,6 +38,18 @@
 //   (PIP_LEAN_KEEPCUT) a cut integrer() has just built stays in registers as the next pivot row.
 //   (tests/test_gpu_lean_prep.py, tests/test_gpu_lean_prep_probe.py.)
 //   (tests/test_gpu_parity.py: test_lean_kernel_paths, test_lean_kernel_other_widths, and every batch test of the suite.)
+//   BIG, pip_lean_kernel<SC, false, true>: the same kernel for the tableaux whose ONE parameter is the big one (nparm == 1,
+//   bigparm == nvar + 1, nvar + 2 <= W <= 128: what pip_solve builds for Maximize / Urs_unknowns, tab.c:292-393).  Such
+//   a tableau needs no host decision -- exam_coef decides every sign from the big coefficient, then the constant
+//   (traiter.c:107-157), integrer treats the big parameter as divisible by any number (integrer.c:373-377), so every
+//   cut is a constant cut -- and the big column is one more column of the packed row that every pivot updates.  What
+//   differs, all under `if constexpr (BIG)`: the caller's rows are nvar + 2 wide; lean_publish puts the big entry's
+//   sign into the summary as row_publish does (bits 2-3 and 4-5), so that a job paused here resumes in
+//   pip_advance_kernel and the other way round; exam_rows instead of the prepared exam flags; the cut's big column is
+//   0; solution() emits two numerators per unknown, the big one gathered from the packed row.  PREP and KEEPCUT stay
+//   on: 64 VGPRs, no scratch, eight waves per SIMD like the plain flavour, whose instantiations compile to what they
+//   compiled to before.  OPT-IN (pipamd_engine_set_lean_big): 13-35 % ahead of pip_advance_kernel's launches except on a
+//   lone Urs_unknowns batch, 3 % behind.  (tests/test_gpu_lean_bigparm.py, tests/test_gpu_batch_shift.py.)
 // LeanLongRows, pip_lean64_kernel: the same one width up.  128-bit Entier, long long rows, 129 ... 256 columns, run-time
 //   row capacity; lane l holds columns l, 64 + l, 128 + l, 192 + l (the geometry of pip_advance_kernel<__int128, 4>, so
 //   that the saved summaries of a paused job mean the same to both kernels).  The overflow-safe flavour (piplib.h:42-88)
@@ -100,6 +112,11 @@ struct LeanIntRows {
   static __device__ __forceinline__ int val_of(int j) { return j & 1; }
   static __device__ __forceinline__ bool shape(const PipJob *J, int nvar, int W) {  // the jobs this flavour takes
     return J->nvar == nvar && nvar < 128 && J->nparm == 0 && J->bigparm < 0 && J->W == W && W <= 128 && !(W & 1) && J->ebits != 128;
+  }
+  // ... and the BIG flavour: one parameter, the big one, behind the constant (unknowns | constant | big)
+  static __device__ __forceinline__ bool shape_big(const PipJob *J, int nvar, int W) {
+    return J->nvar == nvar && J->nparm == 1 && J->bigparm == nvar + 1 && J->W == W && nvar + 2 <= W && W <= 128 && !(W & 1) &&
+           J->ebits != 128;
   }
   static __device__ __forceinline__ unsigned mag(int v) { return (unsigned)(v < 0 ? -v : v); }
   static __device__ __forceinline__ bool fits(i64 x) { return x > -((i64)1 << 31) && x < ((i64)1 << 31); }
@@ -210,6 +227,7 @@ struct LeanLongRows {
   static __device__ __forceinline__ bool shape(const PipJob *J, int nvar, int W) {
     return nvar < 256 && nvar >= 1 && J->nparm == 0 && J->bigparm < 0 && W > 128 && W <= 256 && J->ebits == 128;
   }
+  static __device__ __forceinline__ bool shape_big(const PipJob *, int, int) { return false; }  // (no BIG flavour of long long rows)
   static __device__ __forceinline__ u64 mag(i64 v) { return uabs64(v); }
   static __device__ __forceinline__ bool fits(i128 x) { return fits64(x); }
   static __device__ __forceinline__ u64 gcd(i64 a, i64 b) { return gcd_mag((u64)a, uabs64(b)); }
@@ -408,8 +426,9 @@ __device__ __forceinline__ void rows_unpack(typename F::T *vals, int n, int lane
 
 // sign summary, non-zero bitmap and magnitude class (0: every entry below 2^CLS0_BITS, 1: a packed row) of a packed
 // row of nvar unknowns + constant; lane 0 publishes them for slot s (row_publish32 for this image: constant terms kept
-// as packed elements).  Returns the class.
-template <class F>
+// as packed elements).  Returns the class.  BIG: column nvar + 1 is the big parameter's; its sign goes into the summary as
+// row_publish writes it for a tableau whose one parameter is the big one (bits 2-3 and 4-5).
+template <class F, bool BIG = false>
 __device__ __forceinline__ int lean_publish(const typename F::Row &z, const Shared<typename F::T> &S, typename F::E *cst, int s, int pivj,
                                             int extra_sig, int lane, int nvar) {
   typedef typename F::E E;
@@ -418,6 +437,10 @@ __device__ __forceinline__ int lean_publish(const typename F::Row &z, const Shar
   if (pivj >= 0) {
     const E pz = lean_entry<F>(z.v, F::val_of(pivj), F::lane_of(pivj));
     sig |= (pz > 0 ? 1 : (pz < 0 ? 2 : 0)) << 6;
+  }
+  if constexpr (BIG) {
+    const E bz = lean_entry<F>(z.v, F::val_of(nvar + 1), F::lane_of(nvar + 1));
+    sig |= bz > 0 ? (4 | 16) : (bz < 0 ? (8 | 32) : 0);
   }
   decltype(F::mag(cz)) mx = 0;
   u64 nz[F::NV];
@@ -439,13 +462,17 @@ __device__ __forceinline__ int lean_publish(const typename F::Row &z, const Shar
 
 // the same for a row that left the packed elements (z: lane l's values as T): pip_advance_kernel's classes (2, 3); the
 // constant term kept here is truncated -- the lean run ends before anything reads it
-template <class F>
+template <class F, bool BIG = false>
 __device__ __forceinline__ int lean_publish_wide(const typename F::T (&z)[F::NV], const Shared<typename F::T> &S, typename F::E *cst,
                                                  int s, int pivj, int extra_sig, int lane, int nvar) {
   typedef typename F::T T;
   const T cz = lean_entry<F>(z, F::val_of(nvar), F::lane_of(nvar));
   int sig = extra_sig | sign_code(cz);
   if (pivj >= 0) sig |= sign_code(lean_entry<F>(z, F::val_of(pivj), F::lane_of(pivj))) << 6;
+  if constexpr (BIG) {
+    const int bs = sign_code(lean_entry<F>(z, F::val_of(nvar + 1), F::lane_of(nvar + 1)));
+    sig |= bs == 1 ? (4 | 16) : (bs == 2 ? (8 | 32) : 0);
+  }
   typename ET<T>::U mx = 0;
   u64 nz[F::NV];
 #pragma unroll
@@ -589,7 +616,8 @@ last_unit_wins:
 // that launches it (pip_kernels.hip).
 // FULL: 127 unknowns + constant, a row fills the wave's 128 columns (the launcher's promise, as for pip_advance_kernel);
 // else any number of unknowns up to 127 without parameters, rows of W <= 128 columns (W even).
-template <int SC, bool FULL>
+// BIG (FULL == false only): one parameter, the big one, in column nvar + 1; up to 126 unknowns.
+template <int SC, bool FULL, bool BIG = false>
 __global__ __launch_bounds__(64, PIP_LEAN_WAVES) void pip_lean_kernel(PipJob *jobs, i64 *arena, int njobs, int iter_limit,
                                                                       PipQueue q PIP_LEAN_PROF_PARAM) {
   typedef LeanIntRows F;
@@ -598,15 +626,15 @@ __global__ __launch_bounds__(64, PIP_LEAN_WAVES) void pip_lean_kernel(PipJob *jo
 #include "pip_lean.h"
 #undef PIP_LEAN_LOOP
 }
-template <int SC, bool FULL>
+template <int SC, bool FULL, bool BIG = false>
 hipError_t launch_lean(const AdvanceLaunch &a) {
   const int grid = a.grid > 0 && a.grid < a.njobs ? a.grid : a.njobs;
   const size_t shm = lean_lds_bytes(SC);
 #ifdef PIP_PROFILE
-  hipLaunchKernelGGL((pip_lean_kernel<SC, FULL>), dim3(grid), dim3(64), shm, a.stream, a.jobs, a.arena, a.njobs, a.iter_limit, a.q,
+  hipLaunchKernelGGL((pip_lean_kernel<SC, FULL, BIG>), dim3(grid), dim3(64), shm, a.stream, a.jobs, a.arena, a.njobs, a.iter_limit, a.q,
                      (u64 *)a.prof);
 #else
-  hipLaunchKernelGGL((pip_lean_kernel<SC, FULL>), dim3(grid), dim3(64), shm, a.stream, a.jobs, a.arena, a.njobs, a.iter_limit, a.q);
+  hipLaunchKernelGGL((pip_lean_kernel<SC, FULL, BIG>), dim3(grid), dim3(64), shm, a.stream, a.jobs, a.arena, a.njobs, a.iter_limit, a.q);
 #endif
   return hipGetLastError();
 }
@@ -614,6 +642,9 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
 #define PIP_LEAN_CLASSES(X) \
   X(64, true) X(96, true) X(112, true) X(128, true) X(160, true) X(64, false) X(96, false) X(112, false) X(128, false) X(160, false)
 #define PIP_LEAN_DEFINE(SC, FULL) template hipError_t launch_lean<SC, FULL>(const AdvanceLaunch &);
+// ... and of the BIG flavour (run-time column counts only)
+#define PIP_LEAN_BIG_CLASSES(X) X(64) X(96) X(112) X(128) X(160)
+#define PIP_LEAN_BIG_DEFINE(SC) template hipError_t launch_lean<SC, false, true>(const AdvanceLaunch &);
 
 #elif defined(PIP_LEAN_LOOP)
 // ---- The lean pivot loop: the body of a kernel (jobs, arena, njobs, iter_limit, q[, prof]) that has named F (the row
@@ -647,7 +678,7 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
   const int nvar = FULL ? 127 : J->nvar, W = FULL ? 128 : J->W;
   int nligne = nvar + ni;
   // what this kernel does not do stays with pip_advance_kernel: the job goes on the launch list untouched
-  const bool mine = F::shape(J, nvar, W) && !(tflags & (PIPAMD_T_NOSKIP | PIPAMD_T_DEEPEST)) && ni <= Smax && nligne <= Lmax &&
+  const bool mine = (BIG ? F::shape_big(J, nvar, W) : F::shape(J, nvar, W)) && !(tflags & (PIPAMD_T_NOSKIP | PIPAMD_T_DEEPEST)) && ni <= Smax && nligne <= Lmax &&
                     (!(tflags & PIPAMD_T_STATE) || J->state_nch == F::NCH);
   if (!mine) {
     if (lane == 0 && q.out_count) {
@@ -704,14 +735,15 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
     const u16 *g_sig = (tflags & PIPAMD_T_STATE) ? saved_summaries(arena + J->state_off, J->S, NM).sig : nullptr;
     const bool fresh = F::FRESH && (tflags & PIPAMD_T_FRESHROWS) != 0;
     const T *src = fresh ? (const T *)(uintptr_t)J->src_rows : vals;
-    const int pitch = fresh ? nvar + 1 : W;  // the caller's rows are nvar + 1 wide (an even number: pipamd_batch_load), the block's W
+    constexpr int NCOL1 = BIG ? 2 : 1;  // columns behind the unknowns: the constant (BIG: and the big parameter's)
+    const int pitch = fresh ? nvar + NCOL1 : W;  // the caller's rows are that wide (an even number: pipamd_batch_load), the block's W
     int npacked = 0;
     bool wide = false;
     for (int s0 = 0; s0 < ni && !wide; s0 += PF0) {
       RowRegs<T, F::NCH> rr[PF0];
 #pragma unroll
       for (int qq = 0; qq < PF0; qq++)
-        if (s0 + qq < ni) row_load<T, F::NCH>(rr[qq], src + (size_t)(s0 + qq) * pitch, (nvar + CPL) & ~(CPL - 1), lane);
+        if (s0 + qq < ni) row_load<T, F::NCH>(rr[qq], src + (size_t)(s0 + qq) * pitch, (nvar + NCOL1 - 1 + CPL) & ~(CPL - 1), lane);
 #pragma unroll
       for (int qq = 0; qq < PF0; qq++) {
         const int s = s0 + qq;
@@ -732,7 +764,7 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
         npacked = s + 1;
         const bool den1 = S.den[s] == 1;
         const int red = g_sig ? (g_sig[s] & SIG_RED) : (den1 ? SIG_RED : 0);
-        mcw = max(mcw, lean_publish<F>(z, S, cst, s, -1, red, lane, nvar));
+        mcw = max(mcw, lean_publish<F, BIG>(z, S, cst, s, -1, red, lane, nvar));
         if (tflags & PIPAMD_T_SORT) {
           // traiter.c:576-589: size = max_j |(int)(v_j / den)| over the unknowns (as pip_advance_kernel computes it)
           int sz = 0;
@@ -776,7 +808,7 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
     for (int s = lane; s < ni; s += 64) cst[s] = reinterpret_cast<const E *>(vals + (size_t)s * W)[nvar];
     __builtin_amdgcn_wave_barrier();
   }
-  first_chercher<T, 64>(S, &sc, ni, -1, lane);
+  first_chercher<T, 64>(S, &sc, ni, BIG ? nvar + 1 : -1, lane);
   __builtin_amdgcn_wave_barrier();
 
   PROF(10);
@@ -795,10 +827,19 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
     bool have_pr = false;  // ... is in registers already: the cut integrer() has just built and stored
     if (pivi == BIG_I) {
       // -------------- exam_coef (its flags were prepared by phase C), then integrer if nothing is negative
-      pivi = sc.pivi2;
-      apply_exam_flags<T, 64>(S, ni, pivi, lane);
-      __builtin_amdgcn_wave_barrier();
+      if constexpr (BIG) {
+        // exam_coef with a big parameter (traiter.c:107-157), as pip_advance_kernel runs it: the first Unknown row whose big
+        // coefficient is negative, else the constants
+        [[clang::always_inline]] pivi = exam_rows<T, 1>(S, &sc, ni);
+      } else {
+        pivi = sc.pivi2;
+        apply_exam_flags<T, 64>(S, ni, pivi, lane);
+        __builtin_amdgcn_wave_barrier();
+      }
       if (pivi == BIG_I) {
+        // (BIG: the one parameter is the big one, so exam_rows has decided every row -- a negative big coefficient, else a
+        // positive one, else the constant -- and pip_advance_kernel's test for rows left Unknown, PIPAMD_ST_NEED_COMPA, has
+        // nothing to find: it is not repeated here)
         if (!(tflags & PIPAMD_T_INT)) {
           status = PIPAMD_ST_SOLUTION;
           break;
@@ -835,6 +876,8 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
             okv |= pos > 0;
           else
             r.v[h] = pos ? pos - D : 0;  // -((-v) mod D) == (v mod D) - D unless D divides v
+          if constexpr (BIG)
+            if (F::col(lane, h) == nvar + 1) r.v[h] = 0;  // the big parameter is divisible by any number (integrer.c:373-377)
         }
         const bool any_v = ballot64(okv) != 0;
         int verdict;
@@ -847,7 +890,7 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
         else {
           verdict = PIPAMD_ST_RUN;
           F::store(r, vals + (size_t)ni * W, lane, W);
-          mcw = max(mcw, lean_publish<F>(r, S, cst, ni, -1, 0, lane, nvar));
+          mcw = max(mcw, lean_publish<F, BIG>(r, S, cst, ni, -1, 0, lane, nvar));
           if (lane == 0) {
             S.fl[ni] = PIPAMD_F_MINUS;
             S.nf[ni] = 0;
@@ -941,13 +984,13 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
 #pragma unroll
         for (int h = 0; h < NV; h++) r.v[h] = (F::col(lane, h) == pivj) ? (E)dpiv : (E)wneg((i64)pr.v[h]);
         F::store(r, vals + (size_t)pslot * W, lane, W);
-        mcw = max(mcw, lean_publish<F>(r, S, cst, pslot, pivj, pred, lane, nvar));
+        mcw = max(mcw, lean_publish<F, BIG>(r, S, cst, pslot, pivj, pred, lane, nvar));
       } else {  // the denominator does not fit E: that row does not either
         T zw[NV];
 #pragma unroll
         for (int h = 0; h < NV; h++) zw[h] = (F::col(lane, h) == pivj) ? dpiv : -(T)pr.v[h];
         F::store_wide(zw, vals + (size_t)pslot * W, lane, W);
-        mcw = max(mcw, lean_publish_wide<F>(zw, S, cst, pslot, pivj, pred, lane, nvar));
+        mcw = max(mcw, lean_publish_wide<F, BIG>(zw, S, cst, pslot, pivj, pred, lane, nvar));
       }
       PROF(4);
       for (int w = 0; w < nwork; w++) {
@@ -1013,7 +1056,7 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
           }
           PROF(7);
           F::store(r, row, lane, W);
-          mcw = max(mcw, lean_publish<F>(r, S, cst, s, pivj, SIG_RED, lane, nvar));
+          mcw = max(mcw, lean_publish<F, BIG>(r, S, cst, s, pivj, SIG_RED, lane, nvar));
         } else {
           T zw[NV];
           if (!F::update_mid(zw, r, pr, lp, foo, dpiv, pivj, g0, gs, lane, nd)) {
@@ -1027,10 +1070,10 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
 #pragma unroll
             for (int h = 0; h < NV; h++) r.v[h] = (E)zw[h];
             F::store(r, row, lane, W);
-            mcw = max(mcw, lean_publish<F>(r, S, cst, s, pivj, SIG_RED, lane, nvar));
+            mcw = max(mcw, lean_publish<F, BIG>(r, S, cst, s, pivj, SIG_RED, lane, nvar));
           } else {  // not a packed row any more: general format, the lean run ends after this pivot
             F::store_wide(zw, row, lane, W);
-            mcw = max(mcw, lean_publish_wide<F>(zw, S, cst, s, pivj, SIG_RED, lane, nvar));
+            mcw = max(mcw, lean_publish_wide<F, BIG>(zw, S, cst, s, pivj, SIG_RED, lane, nvar));
           }
         }
         if (lane == 0) S.den[s] = nd;
@@ -1044,7 +1087,7 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
       break;
     }
     // ---------------- C: swap roles, refresh the sign hints, next chercher (traiter.c:503-529)
-    pivot_swap_roles<T, 64>(S, &sc, ni, pivi, pivj, pslot, ku, (T)pivot, -1, lane);
+    pivot_swap_roles<T, 64>(S, &sc, ni, pivi, pivj, pslot, ku, (T)pivot, BIG ? nvar + 1 : -1, lane);
     __builtin_amdgcn_wave_barrier();
     PROF(9);
   }
@@ -1059,16 +1102,22 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
   }
   if (status == PIPAMD_ST_SOLUTION) {
     // solution(), traiter.c:255-271: the constant column of rows 0..nvar-1
+    // (BIG: two numerators per unknown, the big parameter's coefficient -- from the packed row in HBM -- then the constant)
+    constexpr int NN = BIG ? 2 : 1;
     T *sol_num = (T *)(arena + J->sol_off);
-    T *sol_den = sol_num + nvar;
+    T *sol_den = sol_num + NN * nvar;
+    if constexpr (BIG) __threadfence_block();
     for (int i = lane; i < nvar; i += 64) {
       const int rf = S.ref[i];
       T v = 0, d = 1;
+      [[maybe_unused]] T bv = 0;
       if (!(rf & UNITBIT)) {
         v = (T)cst[rf];  // (the constant terms are kept current in LDS by lean_publish)
         d = S.den[rf];
+        if constexpr (BIG) bv = (T)F::gather(vals + (size_t)rf * W, nvar + 1);  // (every row is a packed row here: mcw <= 1)
       }
-      sol_num[i] = v;
+      if constexpr (BIG) sol_num[NN * i] = bv;
+      sol_num[NN * i + NN - 1] = v;
       sol_den[i] = d;
     }
   }

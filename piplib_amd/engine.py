@@ -14,6 +14,7 @@ ST_RUN, ST_SOLUTION, ST_NIL, ST_NEED_COMPA, ST_NEED_PARMCUT, ST_OVERFLOW, ST_CAP
 T_INT, T_DUAL = 1, 2
 T_NOSKIP = 2048
 T_ROWS_STAY = 8192  # the rows of Batch.load stay valid until the next solve: no copy pass (include/piplib_amd.h)
+SHIFT_MAX, SHIFT_URS = 1, -1  # Batch(shift=...): Maximize / Urs_unknowns (PIPAMD_SHIFT_MAX, PIPAMD_SHIFT_URS)
 
 
 class BatchDesc(C.Structure):
@@ -59,6 +60,10 @@ def lib():
         L.pipamd_batch_load_part.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BatchDesc), C.c_void_p, C.c_int, C.c_int,
                                              C.c_void_p]
         L.pipamd_batch_results.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BatchDesc)] + [C.c_void_p] * 6
+        L.pipamd_batch_load_shifted_part.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BatchDesc), C.c_void_p, C.c_int,
+                                                     C.c_int, C.c_int, C.c_void_p]
+        L.pipamd_batch_results_shifted.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BatchDesc), C.c_int] + [C.c_void_p] * 6
+        L.pipamd_engine_set_lean_big.argtypes = [C.c_void_p, C.c_int]
         L.pipamd_batch_counters.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BatchDesc), C.c_void_p, C.c_void_p]
         L.pipamd_last_solve_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         L.pipamd_free.argtypes = [C.c_void_p]
@@ -122,6 +127,11 @@ class Engine:
         lib().pipamd_engine_set_lean64.argtypes = [C.c_void_p, C.c_int]
         _check(lib().pipamd_engine_set_lean64(self._h, int(bool(on))))
 
+    def set_lean_big(self, on):
+        """bulk batches under a big parameter (Batch(shift=...), or nparm=1, bigparm=nvar + 1) start with the lean kernel's
+        big-parameter flavour (csrc/pip_lean.h; default off: include/piplib_amd.h)"""
+        _check(lib().pipamd_engine_set_lean_big(self._h, int(bool(on))))
+
     def set_tail_waves(self, n):
         lib().pipamd_engine_set_tail_waves.argtypes = [C.c_void_p, C.c_int]
         _check(lib().pipamd_engine_set_tail_waves(self._h, int(n)))
@@ -176,14 +186,22 @@ class Batch:
     """A uniform batch of tableaux resident in HBM (layer 1 of the C ABI)."""
 
     def __init__(self, engine, rows, nvar, nparm, bigparm=-1, tflags=T_INT, cap_cuts=None, cap_newparm=0,
-                 entier_bits=64, shape=None):
+                 entier_bits=64, shape=None, shift=0):
         """rows: (batch, ni, ncol) int64, host or device; or None with shape=(batch, ni, ncol) for a workspace whose
-        tableaux come from load_parts()"""
+        tableaux come from load_parts().
+        shift=SHIFT_MAX / SHIFT_URS: the lexicographic maximum / unknowns of either sign (pip_solve's Maximize,
+        Urs_unknowns).  rows are then the PLAIN system, nvar + 1 columns (nparm=0): the batch is solved under a big
+        parameter (nparm=1, bigparm=nvar + 1, set here), load() / load_part() go through pipamd_batch_load_shifted and
+        fetch_shifted() decodes the answer into x_num, x_den."""
         import torch
         self.torch = torch
         self.e = engine
         B, ni, ncol = rows.shape if rows is not None else shape
         assert ncol == nvar + nparm + 1
+        self.shift = int(shift)
+        if self.shift:
+            assert self.shift in (SHIFT_MAX, SHIFT_URS) and nparm == 0 and bigparm == -1
+            nparm, bigparm = 1, nvar + 1
         if cap_cuts is None:
             cap_cuts = max(0, min(ni + 64, 2048 - ni)) if (tflags & T_INT) else 0
         self.desc = BatchDesc(B, nvar, nparm, ni, bigparm, tflags, cap_cuts, cap_newparm, entier_bits)
@@ -205,11 +223,16 @@ class Batch:
         # 128-bit values come back as (low, high) int64 pairs: see wide_to_int()
         self.sol_num = torch.empty((B, nvar, nparm + 1) + ((2,) if ew == 2 else ()), dtype=torch.int64, device=self.dev)
         self.sol_den = torch.empty((B, nvar) + ((2,) if ew == 2 else ()), dtype=torch.int64, device=self.dev)
+        if self.shift:  # fetch_shifted(): unknown i of tableau b is x_num / x_den, x_den == 0: unbounded
+            self.x_num = torch.empty_like(self.sol_den)
+            self.x_den = torch.empty_like(self.sol_den)
 
     def _stream(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.dev).cuda_stream)
 
     def load(self):
+        if self.shift:
+            return self.load_part(self.rows, 0)
         _check(lib().pipamd_batch_load(self.e._h, C.c_void_p(self.ws.data_ptr()), C.byref(self.desc),
                                        C.c_void_p(self.rows.data_ptr()), self._stream()))
 
@@ -217,6 +240,10 @@ class Batch:
         """tableaux first .. first + len(rows) - 1 of the batch from a resident row array (pipamd_batch_load_part)"""
         assert rows.is_cuda and rows.is_contiguous()
         st = C.c_void_p(stream) if stream is not None else self._stream()
+        if self.shift:
+            _check(lib().pipamd_batch_load_shifted_part(self.e._h, C.c_void_p(self.ws.data_ptr()), C.byref(self.desc),
+                                                    C.c_void_p(rows.data_ptr()), self.shift, int(first), int(rows.shape[0]), st))
+            return
         _check(lib().pipamd_batch_load_part(self.e._h, C.c_void_p(self.ws.data_ptr()), C.byref(self.desc),
                                             C.c_void_p(rows.data_ptr()), int(first), int(rows.shape[0]), st))
 
@@ -254,6 +281,16 @@ class Batch:
                                           C.c_void_p(self.status.data_ptr()), C.c_void_p(self.pivots.data_ptr()),
                                           C.c_void_p(self.cuts.data_ptr()), C.c_void_p(self.sol_num.data_ptr()),
                                           C.c_void_p(self.sol_den.data_ptr()), st))
+
+    def fetch_shifted(self, stream=None):
+        """pipamd_batch_results_shifted of a Batch(shift=...): status, pivots, cuts and the decoded answer x_num, x_den
+        (sol_vector_edit: reduced, negated for SHIFT_MAX, x_den == 0 where the unknown is unbounded).  Does not synchronise."""
+        assert self.shift
+        st = C.c_void_p(stream) if stream is not None else self._stream()
+        _check(lib().pipamd_batch_results_shifted(self.e._h, C.c_void_p(self.ws.data_ptr()), C.byref(self.desc), self.shift,
+                                              C.c_void_p(self.status.data_ptr()), C.c_void_p(self.pivots.data_ptr()),
+                                              C.c_void_p(self.cuts.data_ptr()), C.c_void_p(self.x_num.data_ptr()),
+                                              C.c_void_p(self.x_den.data_ptr()), st))
 
     def _dual_out(self):
         B, ni = self.desc.batch, self.desc.ni
