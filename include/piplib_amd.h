@@ -46,7 +46,8 @@ extern "C" {
  * binding looks them up in the library): pipamd_traiter_many / pipamd_traiter_many128 -- traiter() for many problems,
  * flags per problem --, and the device-resident traiter() computes the dual (PIPAMD_T_DUAL) for every shape of its box,
  * not only up to 64 inequalities; pipamd_batch_dual / pipamd_batch_dual_part -- the dual values of a rational batch of
- * layer 1. */
+ * layer 1; pipamd_batch_load_system / pipamd_batch_dual_system and their _part forms -- layer 1 from the plain system
+ * pip_solve takes (equalities, tab_simplify, the dual under Maximize / Urs_unknowns and of equalities). */
 #define PIPAMD_VERSION 500
 
 /* ---- error codes (return values) ---- */
@@ -269,6 +270,53 @@ int pipamd_batch_dual(pipamd_engine *e, const void *d_workspace, const pipamd_ba
  * pipamd_batch_load_part was given), d_dual_num / d_dual_den are the arrays of the whole batch. */
 int pipamd_batch_dual_part(pipamd_engine *e, const void *d_workspace, const pipamd_batch_desc *d, const int64_t *d_rows,
                            int first, int count, int64_t *d_dual_num, int64_t *d_dual_den, void *stream);
+
+/* The system pip_solve(inequnk, NULL, -1, options) takes, for a whole batch: what tab_Matrix2Tableau (tab.c:292-393) and
+ * tab_simplify (tab.c:396-427) do to it on the way to traiter(), and what pip_solve does to the dual on the way back
+ * (sol_vector_edit with flags 0, sol.c:475-500; pip_quast_equalities_dual, piplib.c:651-690).  `d_rows` holds the caller's
+ * PLAIN systems, batch x nrows x (nvar + 1) int64 (unknowns then constant: a PolyLib row without its marker column).  The
+ * rows whose marker is 0 -- the equalities -- are named by ONE host list for the batch (same-shaped systems have them in
+ * the same rows).  The descriptor `d` describes the tableau AS IT IS SOLVED, as for the shifted entries:
+ * d->ni == nrows + neq; shift == 0: nparm == 0, bigparm == -1; shift == +-1: nparm == 1, bigparm == nvar + 1.
+ * pipamd_batch_load_system: input row r becomes tableau row r + (equalities before r), written as tab.c:342-377 writes it,
+ *     shift == 0:  a_j | c        PIPAMD_SHIFT_MAX:  -a_j | c | +sum a_j        PIPAMD_SHIFT_URS:  a_j | c | -sum a_j
+ * (the sum in the entry type, as pipamd_batch_load_shifted), and an equality is followed by its negation in EVERY column,
+ * the constant and the big column included (tab.c:380-388).  With `simplify`, tab_simplify then runs on each of the ni
+ * rows: g = the gcd of every column but the constant (the big one included); for g > 1 those columns are divided by g
+ * and the constant is divided with the floor; a row with g of 0 or 1 stays.  pip_solve simplifies every integer problem
+ * (piplib.c:848-849): a batch loaded without it takes another pivot sequence to the same answer.  Row tables, spare slots
+ * and the job header as pipamd_batch_load; PIPAMD_T_ROWS_STAY is ignored (the caller's array is not the tableau; it may
+ * be released once the load's work on `stream` is done).  The solve and the result entries are the existing ones
+ * (pipamd_batch_results, or pipamd_batch_results_shifted for shift == +-1).
+ * pipamd_batch_dual_system: Compute_dual for a batch loaded this way and solved with PIPAMD_T_DUAL, callable where
+ * pipamd_batch_dual is; one kernel on `stream`, no synchronisation; `d_rows` is the array the batch was loaded from.
+ * d_dual_num[b][r], d_dual_den[b][r], r < nrows: ONE pair per input row, as pip_solve's answer lists them -- the pair of
+ * pipamd_batch_dual for the row's tableau row, in lowest terms (g = gcd(N, D): N / g, D / g); for an equality with the
+ * values u (its row) and v (the negated row) u if u != 0, else -v, so an equality's value may be negative.  (0, 0)
+ * throughout for a tableau whose status is not PIPAMD_ST_SOLUTION.  int64 each, or (low, high) pairs for
+ * entier_bits == 128.  pipamd_batch_dual itself still refuses batches with a big parameter.
+ * PIPAMD_E_INVALID, before any HIP call: a null engine, workspace, descriptor, `sys` or rows pointer; shift not 0, 1 or
+ * -1; a descriptor that does not match the shift; nrows < 0; neq < 0 or > nrows; d->ni != nrows + neq; eq_rows null with
+ * neq > 0, not strictly increasing or out of range; simplify not 0 or 1, or 1 without PIPAMD_T_INT; first / count
+ * outside the batch; for the dual entries a null output array, no PIPAMD_T_DUAL, or PIPAMD_T_INT.  PIPAMD_E_TOOLARGE for
+ * the dual entries: d->ni above 8,192, as pipamd_batch_dual. */
+typedef struct pipamd_system {
+  int32_t nrows;          /* rows of the caller's system (PipMatrix NbRows), nvar + 1 int64 each: unknowns | constant */
+  int32_t neq;            /* how many of them are equalities */
+  const int32_t *eq_rows; /* HOST array of their indices, strictly increasing, the same for every system of the batch;
+                             read before the call returns (the caller may free it at once); NULL when neq == 0 */
+  int32_t shift;          /* 0, PIPAMD_SHIFT_MAX or PIPAMD_SHIFT_URS */
+  int32_t simplify;       /* 1: tab_simplify on the tableau, as pip_solve does whenever Nq; needs PIPAMD_T_INT */
+} pipamd_system;
+int pipamd_batch_load_system(pipamd_engine *e, void *d_workspace, const pipamd_batch_desc *d, const pipamd_system *sys,
+                             const int64_t *d_rows, void *stream);
+int pipamd_batch_load_system_part(pipamd_engine *e, void *d_workspace, const pipamd_batch_desc *d, const pipamd_system *sys,
+                                  const int64_t *d_rows, int first, int count, void *stream);
+int pipamd_batch_dual_system(pipamd_engine *e, const void *d_workspace, const pipamd_batch_desc *d, const pipamd_system *sys,
+                             const int64_t *d_rows, int64_t *d_dual_num, int64_t *d_dual_den, void *stream);
+int pipamd_batch_dual_system_part(pipamd_engine *e, const void *d_workspace, const pipamd_batch_desc *d,
+                                  const pipamd_system *sys, const int64_t *d_rows, int first, int count, int64_t *d_dual_num,
+                                  int64_t *d_dual_den, void *stream);
 
 /* Batch totals, device memory, 4 x uint64: [0] pivots (calls of pivoter), [1] Gomory cuts,
  * [2] rows rewritten by pivots (rows whose pivot-column entry is zero and that are already

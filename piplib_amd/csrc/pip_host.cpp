@@ -819,6 +819,124 @@ extern "C" int pipamd_batch_dual(pipamd_engine *e, const void *d_ws, const pipam
   return pipamd_batch_dual_part(e, d_ws, d, d_rows, 0, d ? d->batch : 0, d_dual_num, d_dual_den, stream);
 }
 
+// pip_solve's plain system for the batch layer (header comment: include/piplib_amd.h): equalities, tab_simplify and the
+// dual as pip_solve hands it out.  Everything is checked before the first HIP call, the caller's equality list is read
+// into a mask that travels with the launch, and nothing here waits for the stream.
+static int system_check(const char *who, const void *e, const void *d_ws, const pipamd_batch_desc *d, const pipamd_system *sys,
+                        const void *d_rows, PipEqMask *eq) {
+  if (!e || !d_ws || !d || !sys || !d_rows) {
+    pipamd_set_error("%s: null engine, workspace, descriptor, system or rows pointer", who);
+    return PIPAMD_E_INVALID;
+  }
+  if (sys->shift != 0 && sys->shift != PIPAMD_SHIFT_MAX && sys->shift != PIPAMD_SHIFT_URS) {
+    pipamd_set_error("%s: shift must be 0, PIPAMD_SHIFT_MAX (1) or PIPAMD_SHIFT_URS (-1), not %d", who, sys->shift);
+    return PIPAMD_E_INVALID;
+  }
+  if (sys->shift ? (d->nparm != 1 || d->bigparm != d->nvar + 1) : (d->nparm != 0 || d->bigparm != -1)) {
+    pipamd_set_error("%s: the descriptor must describe the tableau as it is solved (shift 0: nparm == 0, bigparm == -1; "
+                     "otherwise nparm == 1, bigparm == nvar + 1)", who);
+    return PIPAMD_E_INVALID;
+  }
+  if (sys->nrows < 0 || sys->neq < 0 || sys->neq > sys->nrows || d->ni != sys->nrows + sys->neq) {
+    pipamd_set_error("%s: %d rows with %d equalities do not make the descriptor's %d inequalities", who, sys->nrows, sys->neq,
+                     d->ni);
+    return PIPAMD_E_INVALID;
+  }
+  if (sys->nrows > PIPAMD_SMAX) {
+    pipamd_set_error("%s: %d rows, the engine holds at most %d", who, sys->nrows, PIPAMD_SMAX);
+    return PIPAMD_E_TOOLARGE;
+  }
+  if (sys->neq > 0 && !sys->eq_rows) {
+    pipamd_set_error("%s: %d equalities and no list of them", who, sys->neq);
+    return PIPAMD_E_INVALID;
+  }
+  if (sys->simplify != 0 && sys->simplify != 1) {
+    pipamd_set_error("%s: simplify must be 0 or 1, not %d", who, sys->simplify);
+    return PIPAMD_E_INVALID;
+  }
+  if (sys->simplify && !(d->tflags & PIPAMD_T_INT)) {
+    pipamd_set_error("%s: simplify without PIPAMD_T_INT (pip_solve simplifies integer problems only)", who);
+    return PIPAMD_E_INVALID;
+  }
+  memset(eq, 0, sizeof *eq);
+  for (int i = 0; i < sys->neq; i++) {
+    const int r = sys->eq_rows[i];
+    if (r < 0 || r >= sys->nrows || (i > 0 && r <= sys->eq_rows[i - 1])) {
+      pipamd_set_error("%s: eq_rows[%d] = %d is out of range or not above its predecessor", who, i, r);
+      return PIPAMD_E_INVALID;
+    }
+    eq->w[r >> 6] |= (uint64_t)1 << (r & 63);
+  }
+  return PIPAMD_OK;
+}
+
+extern "C" int pipamd_batch_load_system_part(pipamd_engine *e, void *d_ws, const pipamd_batch_desc *d, const pipamd_system *sys,
+                                             const int64_t *d_rows, int first, int count, void *stream) {
+  PipEqMask eq;
+  int rc = system_check("batch_load_system", e, d_ws, d, sys, d_rows, &eq);
+  if (rc) return rc;
+  PipBatchLayout lay;
+  size_t jb;
+  rc = pipamd_batch_layout(d, &lay, &jb);
+  if (rc) return rc;
+  if (first < 0 || count < 0 || first > lay.batch - count) {
+    pipamd_set_error("batch_load_system_part: tableaux %d..%d outside the batch of %d", first, first + count, lay.batch);
+    return PIPAMD_E_INVALID;
+  }
+  if (hipSetDevice(e->device) != hipSuccess) return PIPAMD_E_HIP;  // HIP's current device is per host thread
+  PipJob *jobs = (PipJob *)d_ws;
+  long long *arena = (long long *)((char *)d_ws + jb);
+  HIPCHK(pipk_launch_batch_load_system(jobs, arena, (const long long *)d_rows, lay, sys->shift, sys->simplify, sys->nrows, &eq,
+                                       first, count, (hipStream_t)stream));
+  return PIPAMD_OK;
+}
+
+extern "C" int pipamd_batch_load_system(pipamd_engine *e, void *d_ws, const pipamd_batch_desc *d, const pipamd_system *sys,
+                                        const int64_t *d_rows, void *stream) {
+  return pipamd_batch_load_system_part(e, d_ws, d, sys, d_rows, 0, d ? d->batch : 0, stream);
+}
+
+extern "C" int pipamd_batch_dual_system_part(pipamd_engine *e, const void *d_ws, const pipamd_batch_desc *d,
+                                             const pipamd_system *sys, const int64_t *d_rows, int first, int count,
+                                             int64_t *d_dual_num, int64_t *d_dual_den, void *stream) {
+  PipEqMask eq;
+  int rc = system_check("batch_dual_system", e, d_ws, d, sys, d_rows, &eq);
+  if (rc) return rc;
+  if (!d_dual_num || !d_dual_den) {
+    pipamd_set_error("batch_dual_system: null output array");
+    return PIPAMD_E_INVALID;
+  }
+  if (!(d->tflags & PIPAMD_T_DUAL) || (d->tflags & PIPAMD_T_INT)) {
+    pipamd_set_error("batch_dual_system: the batch must have been solved with PIPAMD_T_DUAL and without PIPAMD_T_INT (the dual "
+                     "needs a rational solve)");
+    return PIPAMD_E_INVALID;
+  }
+  PipBatchLayout lay;
+  size_t jb;
+  rc = pipamd_batch_layout(d, &lay, &jb);
+  if (rc) return rc;
+  if (first < 0 || count < 0 || first > lay.batch - count) {
+    pipamd_set_error("batch_dual_system_part: tableaux %d..%d outside the batch of %d", first, first + count, lay.batch);
+    return PIPAMD_E_INVALID;
+  }
+  if (lay.ni > pipk_batch_dual_max_ni()) {
+    pipamd_set_error("batch_dual_system: %d inequalities per tableau, the dual kernel sorts at most %d", lay.ni,
+                     pipk_batch_dual_max_ni());
+    return PIPAMD_E_TOOLARGE;
+  }
+  if (hipSetDevice(e->device) != hipSuccess) return PIPAMD_E_HIP;  // HIP's current device is per host thread
+  const PipJob *jobs = (const PipJob *)d_ws;
+  const long long *arena = (const long long *)((const char *)d_ws + jb);
+  HIPCHK(pipk_launch_batch_dual_system(jobs, arena, (const long long *)d_rows, lay, sys->nrows, &eq, first, count,
+                                       (void *)d_dual_num, (void *)d_dual_den, (hipStream_t)stream));
+  return PIPAMD_OK;
+}
+
+extern "C" int pipamd_batch_dual_system(pipamd_engine *e, const void *d_ws, const pipamd_batch_desc *d, const pipamd_system *sys,
+                                        const int64_t *d_rows, int64_t *d_dual_num, int64_t *d_dual_den, void *stream) {
+  return pipamd_batch_dual_system_part(e, d_ws, d, sys, d_rows, 0, d ? d->batch : 0, d_dual_num, d_dual_den, stream);
+}
+
 extern "C" int pipamd_batch_counters(pipamd_engine *e, const void *d_ws, const pipamd_batch_desc *d, uint64_t *d_out4,
                                      void *stream) {
   if (e && hipSetDevice(e->device) != hipSuccess) return PIPAMD_E_HIP;  // HIP's current device is per host thread

@@ -87,6 +87,11 @@ hipError_t pipk_launch_batch_results(const PipJob *jobs, const long long *arena,
 int pipk_batch_dual_max_ni(void); /* inequalities per tableau pip_batch_dual_kernel sorts in LDS */
 hipError_t pipk_launch_batch_dual(const PipJob *jobs, const long long *arena, const long long *rows, PipBatchLayout lay,
                                   int first, int count, void *dual_num, void *dual_den, hipStream_t stream);
+hipError_t pipk_launch_batch_load_system(PipJob *jobs, long long *arena, const long long *rows, PipBatchLayout lay, int shift,
+                                         int simplify, int nrows, const PipEqMask *eq, int first, int count, hipStream_t stream);
+hipError_t pipk_launch_batch_dual_system(const PipJob *jobs, const long long *arena, const long long *rows, PipBatchLayout lay,
+                                         int nrows, const PipEqMask *eq, int first, int count, void *dual_num, void *dual_den,
+                                         hipStream_t stream);
 hipError_t pipk_launch_rehouse(PipJob *jobs, long long *arena, void *const *q5, int grid, PipBatchLayout nl, int *side_count,
                                int side_cap, hipStream_t stream);
 hipError_t pipk_launch_rehouse_finish(PipJob *jobs, long long *arena, int njobs, int sol_words, hipStream_t stream);

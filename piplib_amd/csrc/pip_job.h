@@ -59,6 +59,13 @@ typedef struct PipJob {
  * counts these jobs (the host sizes the larger blocks' arena by it) */
 #define PIPAMD_Q_CAPFLAG (1 << 30)
 
+/* Which rows of a caller's plain system are equalities (pipamd_system.eq_rows): bit r % 64 of w[r / 64], zero beyond
+ * the system's rows.  The host builds it from the caller's list and hands it to the kernels by value, as 2,000 bytes of
+ * kernel arguments: nothing of the caller's list has to outlive the call. */
+typedef struct PipEqMask {
+  uint64_t w[(PIPAMD_SMAX + 63) / 64];
+} PipEqMask;
+
 #ifdef __HIPCC__
 #define PIP_HD __host__ __device__
 #else

@@ -2,8 +2,9 @@
 //
 // The pivot kernel itself (pip_advance_kernel: traiter() / pivoter() / choisir_piv() / exam_coef() / integrer() /
 // tab_sort_rows of the reference) lives in pip_advance.h and is instantiated by the pip_adv_*.hip files; this file
-// holds the determinant replay, the batch load / results / counters kernels, Compute_dual for the batch layer
-// (pip_batch_dual_kernel), expanser for the batch layer, the helpers of the lock-step scheduler and every launcher.
+// holds the determinant replay, the batch load / results / counters kernels (pip_batch_load_system_kernel: the load from
+// pip_solve's plain system), Compute_dual for the batch layer (pip_batch_dual_kernel, pip_batch_dual_system_kernel),
+// expanser for the batch layer, the helpers of the lock-step scheduler and every launcher.
 #include "pip_lean.h"
 
 // the instantiations of the pivot kernel's launcher live in pip_adv_*.hip
@@ -241,6 +242,154 @@ __global__ void pip_batch_load_kernel(PipJob *jobs, i64 *arena, const i64 *rows,
     J->home_sol_off = 0;
     J->S = lay.S;
     J->W = lay.W;
+    J->status = PIPAMD_ST_RUN;
+    J->aux = 0;
+    J->npiv = 0;
+    J->ncut = 0;
+    J->nupd = 0;
+    J->ldet = 1;
+    for (int i = 0; i < 2 * PIPAMD_MAXDET; i++) J->det[i] = 0;
+    J->det[0] = 1;
+    J->maxabs = 0;
+    J->state_nch = 0;
+    J->ebits = ET<T>::BITS;
+  }
+}
+
+// ---------------------------------------------------------------- batch load from a plain system
+// pipamd_batch_load_system: tab_Matrix2Tableau (tab.c:328-389) and, for integer problems, tab_simplify (tab.c:396-427)
+// for a uniform batch.  `rows` holds the caller's system, nrows x (nvar + 1) int64 a tableau; input row r becomes
+// tableau row r + (equalities before r), written as pip_batch_load_kernel<T, true> writes it (shift == 0: a_j | c), and
+// an equality is followed by its negation in every column.  One WAVE per input row, a lane per column (CPL columns a
+// lane): the row's sum and the gcd of its columns are reductions over the lanes that hold it.  The row tables, the spare
+// slots and the job header are pip_batch_load_kernel's.
+__device__ __forceinline__ i64 sys_shfl(i64 v, int src) { return shfl64(v, src); }
+__device__ __forceinline__ i128 sys_shfl(i128 v, int src) {
+  const u64 lo = (u64)shfl64((i64)(u64)(u128)v, src), hi = (u64)shfl64((i64)(u64)((u128)v >> 64), src);
+  return (i128)(((u128)hi << 64) | lo);
+}
+template <class T>
+__device__ __forceinline__ T sys_wave_sum(T v, int lane) {
+  for (int o = 32; o; o >>= 1) v = wadd(v, sys_shfl(v, lane ^ o));
+  return v;
+}
+// gcd of the lanes' magnitudes (gcd(0, x) = x); any bit pattern ends the binary gcd
+__device__ __forceinline__ u64 sys_wave_gcd(u64 g, int lane) {
+  for (int o = 32; o; o >>= 1) g = gcd_mag(g, (u64)shfl64((i64)g, lane ^ o));
+  return (u64)uni64((i64)g);
+}
+// x / g for a g > 1 that divides x; g is a magnitude of up to 64 bits (2^63 for a row of INT64_MINs)
+__device__ __forceinline__ i64 sys_exact(i64 x, u64 g) {
+  const u64 q = uabs64(x) / g;
+  return x < 0 ? wneg((i64)q) : (i64)q;
+}
+__device__ __forceinline__ i128 sys_exact(i128 x, u64 g) { return cquo(x, (i128)g); }
+// floor(c / g), g > 1, for a constant of at most 2^63 in magnitude (an input value or its negation)
+template <class T>
+__device__ __forceinline__ T sys_floor(T c, u64 g) {
+  const u64 uc = (u64)uabs64(c);
+  return c < 0 ? wneg((T)(i64)((uc + (g - 1)) / g)) : (T)(i64)(uc / g);
+}
+
+template <class T, int CPL>
+__global__ __launch_bounds__(256) void pip_batch_load_system_kernel(PipJob *jobs, i64 *arena, const i64 *rows, PipBatchLayout lay,
+                                                                    int first, int shift, int simplify, int nrows, PipEqMask eq) {
+  typedef typename ET<T>::U U;
+  const int b = first + blockIdx.x;  // `rows` holds the systems first, first + 1, ... of the batch
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int nvar = lay.nvar, ncol = nvar + lay.nparm + 1, srccol = nvar + 1, W = lay.W;
+  PipJob *J = &jobs[b];
+  const int64_t base = lay.arena_off + (int64_t)b * lay.blk.words;
+  const auto [g_den, g_flag, g_ref] = pip_row_tables<T>(arena + base, lay.blk.L);
+  T *vals = (T *)(arena + base + lay.blk.vals);
+  for (int i = tid; i < lay.blk.L; i += blockDim.x) {
+    if (i < nvar) {
+      g_flag[i] = PIPAMD_F_UNIT;
+      g_ref[i] = i;
+      g_den[i] = 1;
+    } else if (i < nvar + lay.ni) {
+      g_flag[i] = PIPAMD_F_UNKNOWN;
+      g_ref[i] = i - nvar;
+      g_den[i] = 1;
+    } else {
+      g_flag[i] = 0;
+      g_ref[i] = 0;
+      g_den[i] = 0;
+    }
+  }
+  const i64 *src = rows + (size_t)blockIdx.x * nrows * srccol;
+  int wcur = 0, before = 0;  // equalities among the rows below 64 * wcur
+  for (int r = wave; r < nrows; r += 4) {
+    for (; wcur < (r >> 6); wcur++) before += __popcll(eq.w[wcur]);
+    const u64 word = eq.w[r >> 6];
+    const int k = r + before + __popcll(word & ((1ull << (r & 63)) - 1));
+    const bool twin = (word >> (r & 63)) & 1;
+    if (k + (int)twin >= lay.ni) break;  // (the host has held the list against ni)
+    const i64 *in = src + (size_t)r * srccol;
+    T v[CPL], sum = 0;
+    u64 g = 0;
+#pragma unroll
+    for (int c = 0; c < CPL; c++) {
+      const int j = lane + 64 * c;
+      const i64 a = j < srccol ? in[j] : 0;
+      v[c] = (T)a;  // the constant as it is, zero beyond it
+      if (j < nvar) {
+        sum = wadd(sum, (T)a);
+        if (simplify) g = gcd_mag(g, uabs64(a));
+        if (shift > 0) v[c] = wneg((T)a);
+      }
+    }
+    T big = 0;
+    if (shift) {  // the new column, tab.c:368-377
+      sum = sys_wave_sum(sum, lane);
+      big = shift > 0 ? sum : wneg(sum);
+#pragma unroll
+      for (int c = 0; c < CPL; c++)
+        if (lane + 64 * c == nvar + 1) v[c] = big;
+    }
+    // tab_simplify: the gcd of every column but the constant, the new one included; a row with 0 or 1 stays.  It is below
+    // 2^64 in the 128-bit flavour too: it divides an input value, or every one of them is zero and so is their exact sum
+    if (simplify) {
+      g = sys_wave_gcd(g, lane);
+      if (shift) g = (u64)gcd_mag((U)g, (U)uni64((T)uabs64(big)));
+    }
+    T *out = vals + (size_t)k * W;
+#pragma unroll
+    for (int c = 0; c < CPL; c++) {
+      const int j = lane + 64 * c;
+      if (j >= W) continue;
+      T x = v[c], y = wneg(x);
+      if (g > 1) {
+        if (j == nvar) {
+          x = sys_floor(x, g);
+          y = sys_floor(y, g);
+        } else {
+          x = sys_exact(x, g);
+          y = wneg(x);
+        }
+      }
+      out[j] = x;
+      if (twin) out[W + j] = y;
+    }
+  }
+  // spare slots: their columns beyond ncol (as pip_batch_load_kernel)
+  const int pad = W - ncol;
+  for (int e = tid; e < (lay.S - lay.ni) * pad; e += blockDim.x) {
+    int s = lay.ni + e / pad, j = ncol + e % pad;
+    vals[(size_t)s * W + j] = 0;
+  }
+  if (tid == 0) {
+    pip_job_place(J, base, lay.blk);
+    J->nlog = 0;
+    J->nvar = nvar;
+    J->nparm = lay.nparm;
+    J->ni = lay.ni;
+    J->bigparm = lay.bigparm;
+    J->tflags = lay.tflags | PIPAMD_T_SORT;
+    J->src_rows = 0;
+    J->home_sol_off = 0;
+    J->S = lay.S;
+    J->W = W;
     J->status = PIPAMD_ST_RUN;
     J->aux = 0;
     J->npiv = 0;
@@ -501,6 +650,140 @@ extern "C" hipError_t pipk_launch_batch_dual(const PipJob *jobs, const i64 *aren
   else
     hipLaunchKernelGGL(pip_batch_dual_kernel<i64>, dim3(count), dim3(64), shm, stream, jobs, arena, rows, lay, first,
                        (i64 *)dual_num, (i64 *)dual_den);
+  return hipGetLastError();
+}
+
+// The same for a batch loaded from a plain system (pipamd_batch_load_system), with or without a big parameter: `rows`
+// holds the caller's nrows x (nvar + 1) rows, of which `eq` marks the equalities; the tableau has ni = nrows + equalities
+// rows.  tab_sort_rows saw the expanded rows: a row's key is taken over the unknown columns alone (traiter.c:581), where
+// the shift and the negation change signs only, so an equality's two rows have the key of the input row.  Per INPUT row
+// one pair, as pip_solve hands it out: reduced as sol_vector_edit with flags 0 reduces it (sol.c:475-500), and for an
+// equality with the values u (its row) and v (the negated row) u if u != 0, else -v (piplib.c:670-688).
+template <class T>
+__global__ __launch_bounds__(64) void pip_batch_dual_system_kernel(const PipJob *jobs, const i64 *arena, const i64 *rows,
+                                                                   PipBatchLayout lay, int first, int nrows, PipEqMask eq,
+                                                                   T *dual_num, T *dual_den) {
+  extern __shared__ __align__(16) unsigned char dual_lds[];
+  const int lane = threadIdx.x;
+  const int b = first + blockIdx.x;
+  const int nvar = lay.nvar, ni = lay.ni, srccol = lay.nvar + 1;
+  if (ni <= 0 || ni > PIP_DUAL_MAXNI || nrows <= 0 || nrows > ni) return;
+  float *key = (float *)dual_lds;          // [ni]; after the sort its room holds pos
+  u16 *ineq = (u16 *)(dual_lds + 4 * (size_t)ni);  // [ni]
+  u16 *pos = (u16 *)dual_lds;              // [ni]: logical row of each tableau row after the sort
+
+  // 1. keys: a lane per column pair, four input rows in flight; an equality's key goes to both of its rows
+  const i64 *src = rows + (size_t)blockIdx.x * nrows * srccol;
+  unsigned smaxw = 0;
+  int k = 0;  // tableau row of the input row at hand
+  for (int i0 = 0; i0 < nrows; i0 += 4) {
+    int sz[4] = {0, 0, 0, 0};
+    for (int j = 2 * lane; j < nvar; j += 128) {
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        if (i0 + q >= nrows) break;
+        const i64 *r = src + (size_t)(i0 + q) * srccol;
+        const int a0 = dual_key_term(r[j]);
+        const int a1 = j + 1 < nvar ? dual_key_term(r[j + 1]) : 0;
+        const int a = a0 > a1 ? a0 : a1;
+        sz[q] = sz[q] > a ? sz[q] : a;
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      if (i0 + q >= nrows) break;
+      const unsigned szw = wave_minmax_u32<true>((unsigned)sz[q]);
+      const int twin = (int)((eq.w[(i0 + q) >> 6] >> ((i0 + q) & 63)) & 1);
+      if (lane <= twin && k + lane < ni) {
+        key[k + lane] = (float)szw;
+        ineq[k + lane] = (u16)(k + lane);
+      }
+      k += 1 + twin;
+      smaxw = smaxw > szw ? smaxw : szw;
+    }
+  }
+  __syncthreads();
+  bool ok = k == ni;  // (the host has held the list against ni)
+
+  // 2. the sort, then pos[ineq[r]] = nvar + r (all ni rows are real at load time)
+  if (ok) dual_sort_pairs(key, ineq, ni, (double)smaxw, lane);
+  for (int r = lane; ok && r < ni; r += 64) {
+    const int i = ineq[r];
+    if (i < ni) pos[i] = (u16)(nvar + r);
+  }
+  __syncthreads();
+
+  // 3. the values, as pip_batch_dual_kernel reads them
+  const PipJob *J = &jobs[b];
+  const i64 base = lay.arena_off + (i64)b * lay.blk.words;
+  const int L = lay.blk.L, S = lay.S, W = lay.W, nligne = nvar + ni;
+  ok = ok && J->status == PIPAMD_ST_SOLUTION && J->rows_off == base && J->vals_off == base + lay.blk.vals && J->L == L &&
+       J->W == W && J->nvar == nvar && J->ni == ni && J->nparm == lay.nparm && nligne <= L;
+  const PipRowTables<const T> tb = pip_row_tables<const T>(arena + base, L);
+  const T *vals = (const T *)(arena + base + lay.blk.vals);
+  int f0 = 0, r0 = 0;
+  T d0 = 0;
+  if (ok) {
+    f0 = tb.flag[0];
+    r0 = tb.ref[0];
+    d0 = tb.den[0];
+    if (!(f0 & PIPAMD_F_UNIT) && (r0 < 0 || r0 >= S)) ok = false;
+  }
+  // tableau row t: (valeur(tp, 0, its unit column), Denom(tp, 0)) if it has become a unit row, otherwise (0, 1)
+  auto value = [&](int t, T &num, T &den) {
+    num = 0;
+    den = 0;
+    const int p = pos[t];
+    if (p < nvar || p >= nligne) return;
+    if (tb.flag[p] & PIPAMD_F_UNIT) {
+      const int u = tb.ref[p];
+      if (u >= 0 && u < nvar) {
+        num = (f0 & PIPAMD_F_UNIT) ? (r0 == u ? d0 : (T)0) : vals[(size_t)r0 * W + u];
+        den = d0;
+      }
+    } else
+      den = 1;
+  };
+  int before = 0;  // equalities among the input rows below r0w
+  for (int r0w = 0; r0w < nrows; r0w += 64) {
+    const u64 word = eq.w[r0w >> 6];
+    const int r = r0w + lane;
+    if (r < nrows) {
+      T num = 0, den = 0;
+      if (ok) {
+        const int t = r + before + __popcll(word & ((1ull << lane) - 1));
+        const bool twin = (word >> lane) & 1;
+        if (t + (int)twin < ni) {
+          value(t, num, den);
+          if (twin && num == 0) {
+            value(t + 1, num, den);
+            num = wneg(num);
+          }
+          T g = gcd_i64(num, den);
+          if (g == 0) g = 1;
+          num = cquo(num, g);
+          den = cquo(den, g);
+        }
+      }
+      dual_num[(size_t)b * nrows + r] = num;
+      dual_den[(size_t)b * nrows + r] = den;
+    }
+    before += __popcll(word);
+  }
+}
+
+extern "C" hipError_t pipk_launch_batch_dual_system(const PipJob *jobs, const i64 *arena, const i64 *rows, PipBatchLayout lay,
+                                                    int nrows, const PipEqMask *eq, int first, int count, void *dual_num,
+                                                    void *dual_den, hipStream_t stream) {
+  if (count <= 0 || lay.ni <= 0 || nrows <= 0) return hipSuccess;
+  if (lay.ni > PIP_DUAL_MAXNI || nrows > lay.ni) return hipErrorInvalidValue;
+  const size_t shm = pipk_batch_dual_lds_bytes(lay.ni);
+  if (lay.ebits == 128)
+    hipLaunchKernelGGL(pip_batch_dual_system_kernel<i128>, dim3(count), dim3(64), shm, stream, jobs, arena, rows, lay, first,
+                       nrows, *eq, (i128 *)dual_num, (i128 *)dual_den);
+  else
+    hipLaunchKernelGGL(pip_batch_dual_system_kernel<i64>, dim3(count), dim3(64), shm, stream, jobs, arena, rows, lay, first,
+                       nrows, *eq, (i64 *)dual_num, (i64 *)dual_den);
   return hipGetLastError();
 }
 
@@ -1042,6 +1325,34 @@ extern "C" hipError_t pipk_launch_batch_load_shifted(PipJob *jobs, i64 *arena, c
     hipLaunchKernelGGL((pip_batch_load_kernel<i128, true>), dim3(count), dim3(256), 0, stream, jobs, arena, rows, lay, first, shift);
   else
     hipLaunchKernelGGL((pip_batch_load_kernel<i64, true>), dim3(count), dim3(256), 0, stream, jobs, arena, rows, lay, first, shift);
+  return hipGetLastError();
+}
+
+// the same from the caller's plain system: equalities expanded, shift 0 / +1 / -1, tab_simplify (the caller has held
+// the layout against the shift and the equality list against lay.ni)
+extern "C" hipError_t pipk_launch_batch_load_system(PipJob *jobs, i64 *arena, const i64 *rows, PipBatchLayout lay, int shift,
+                                                    int simplify, int nrows, const PipEqMask *eq, int first, int count,
+                                                    hipStream_t stream) {
+  if (count <= 0) return hipSuccess;
+  if (shift < -1 || shift > 1 || lay.nparm != (shift ? 1 : 0) || (shift && lay.bigparm != lay.nvar + 1) ||
+      lay.W < lay.nvar + lay.nparm + 1 || lay.W > 512 || nrows < 0 || nrows > lay.ni)
+    return hipErrorInvalidValue;
+  lay.pad = 0;
+#define PIP_LOAD_SYSTEM(T, CPL)                                                                                            \
+  hipLaunchKernelGGL((pip_batch_load_system_kernel<T, CPL>), dim3(count), dim3(256), 0, stream, jobs, arena, rows, lay, first, \
+                     shift, simplify, nrows, *eq)
+  if (lay.ebits == 128) {
+    if (lay.W <= 128)
+      PIP_LOAD_SYSTEM(i128, 2);
+    else
+      PIP_LOAD_SYSTEM(i128, 8);
+  } else {
+    if (lay.W <= 128)
+      PIP_LOAD_SYSTEM(i64, 2);
+    else
+      PIP_LOAD_SYSTEM(i64, 8);
+  }
+#undef PIP_LOAD_SYSTEM
   return hipGetLastError();
 }
 

@@ -22,6 +22,12 @@ class BatchDesc(C.Structure):
                 ("batch", "nvar", "nparm", "ni", "bigparm", "tflags", "cap_cuts", "cap_newparm", "entier_bits")]
 
 
+class System(C.Structure):
+    """pipamd_system: the plain system of Batch(system=True) -- rows, equality rows (a host list), shift, simplify"""
+    _fields_ = [("nrows", C.c_int32), ("neq", C.c_int32), ("eq_rows", C.POINTER(C.c_int32)), ("shift", C.c_int32),
+                ("simplify", C.c_int32)]
+
+
 ABI_VERSION = 500  # include/piplib_amd.h PIPAMD_VERSION
 _lib = None
 
@@ -64,6 +70,10 @@ def lib():
                                                      C.c_int, C.c_int, C.c_void_p]
         L.pipamd_batch_results_shifted.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BatchDesc), C.c_int] + [C.c_void_p] * 6
         L.pipamd_engine_set_lean_big.argtypes = [C.c_void_p, C.c_int]
+        L.pipamd_batch_load_system_part.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BatchDesc), C.POINTER(System), C.c_void_p,
+                                                    C.c_int, C.c_int, C.c_void_p]
+        L.pipamd_batch_dual_system_part.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BatchDesc), C.POINTER(System), C.c_void_p,
+                                                    C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.pipamd_batch_counters.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BatchDesc), C.c_void_p, C.c_void_p]
         L.pipamd_last_solve_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         L.pipamd_free.argtypes = [C.c_void_p]
@@ -186,19 +196,33 @@ class Batch:
     """A uniform batch of tableaux resident in HBM (layer 1 of the C ABI)."""
 
     def __init__(self, engine, rows, nvar, nparm, bigparm=-1, tflags=T_INT, cap_cuts=None, cap_newparm=0,
-                 entier_bits=64, shape=None, shift=0):
+                 entier_bits=64, shape=None, shift=0, system=False, eq_rows=(), simplify=0):
         """rows: (batch, ni, ncol) int64, host or device; or None with shape=(batch, ni, ncol) for a workspace whose
         tableaux come from load_parts().
         shift=SHIFT_MAX / SHIFT_URS: the lexicographic maximum / unknowns of either sign (pip_solve's Maximize,
         Urs_unknowns).  rows are then the PLAIN system, nvar + 1 columns (nparm=0): the batch is solved under a big
         parameter (nparm=1, bigparm=nvar + 1, set here), load() / load_part() go through pipamd_batch_load_shifted and
-        fetch_shifted() decodes the answer into x_num, x_den."""
+        fetch_shifted() decodes the answer into x_num, x_den.
+        system=True: rows are the PLAIN system pip_solve takes, (batch, nrows, nvar + 1), of which the rows listed in
+        eq_rows (strictly increasing, the same for every system) are equalities; shift may be 0 too; simplify=1 runs
+        tab_simplify on the tableau (integer batches, as pip_solve does).  The tableau has nrows + len(eq_rows)
+        inequalities; load() / load_part() go through pipamd_batch_load_system and dual_system() gives the dual as
+        pip_solve lists it, one reduced pair per row of the system."""
         import torch
         self.torch = torch
         self.e = engine
         B, ni, ncol = rows.shape if rows is not None else shape
         assert ncol == nvar + nparm + 1
         self.shift = int(shift)
+        self.system = None
+        if system:
+            assert nparm == 0 and bigparm == -1
+            eq = [int(r) for r in eq_rows]
+            self._eq = (C.c_int32 * max(1, len(eq)))(*eq)  # (kept alive with the batch: System points into it)
+            self.system = System(ni, len(eq), C.cast(self._eq, C.POINTER(C.c_int32)) if eq else None, self.shift, int(simplify))
+            ni += len(eq)
+        else:
+            assert not eq_rows and not simplify
         if self.shift:
             assert self.shift in (SHIFT_MAX, SHIFT_URS) and nparm == 0 and bigparm == -1
             nparm, bigparm = 1, nvar + 1
@@ -231,7 +255,7 @@ class Batch:
         return C.c_void_p(self.torch.cuda.current_stream(self.dev).cuda_stream)
 
     def load(self):
-        if self.shift:
+        if self.shift or self.system is not None:
             return self.load_part(self.rows, 0)
         _check(lib().pipamd_batch_load(self.e._h, C.c_void_p(self.ws.data_ptr()), C.byref(self.desc),
                                        C.c_void_p(self.rows.data_ptr()), self._stream()))
@@ -240,6 +264,8 @@ class Batch:
         """tableaux first .. first + len(rows) - 1 of the batch from a resident row array (pipamd_batch_load_part)"""
         assert rows.is_cuda and rows.is_contiguous()
         st = C.c_void_p(stream) if stream is not None else self._stream()
+        if self.system is not None:
+            return self.load_system_part(rows, first, stream)
         if self.shift:
             _check(lib().pipamd_batch_load_shifted_part(self.e._h, C.c_void_p(self.ws.data_ptr()), C.byref(self.desc),
                                                     C.c_void_p(rows.data_ptr()), self.shift, int(first), int(rows.shape[0]), st))
@@ -330,6 +356,42 @@ class Batch:
         _check(L.pipamd_batch_dual_part(self.e._h, C.c_void_p(self.ws.data_ptr()), C.byref(self.desc),
                                         C.c_void_p(rows.data_ptr()), int(first), int(rows.shape[0]),
                                         C.c_void_p(num.data_ptr()), C.c_void_p(den.data_ptr()), st))
+        return num, den
+
+    def load_system(self, stream=None):
+        """pipamd_batch_load_system of a Batch(system=True): the whole batch from its resident plain rows"""
+        return self.load_system_part(self.rows, 0, stream)
+
+    def load_system_part(self, rows, first, stream=None):
+        """pipamd_batch_load_system_part: tableaux first .. first + len(rows) - 1 from the resident plain systems `rows`"""
+        assert self.system is not None and rows.is_cuda and rows.is_contiguous()
+        st = C.c_void_p(stream) if stream is not None else self._stream()
+        _check(lib().pipamd_batch_load_system_part(self.e._h, C.c_void_p(self.ws.data_ptr()), C.byref(self.desc),
+                                                   C.byref(self.system), C.c_void_p(rows.data_ptr()), int(first),
+                                                   int(rows.shape[0]), st))
+
+    def _dual_system_out(self):
+        shape = (self.desc.batch, self.system.nrows) + ((2,) if self.entier_bits == 128 else ())
+        return (self.torch.empty(shape, dtype=self.torch.int64, device=self.dev),
+                self.torch.empty(shape, dtype=self.torch.int64, device=self.dev))
+
+    def dual_system(self, stream=None):
+        """pipamd_batch_dual_system after a solve with T_DUAL of a Batch(system=True): device tensors (dual_num, dual_den)
+        of shape (batch, nrows) -- plus a trailing 2 for 128-bit entries --, one reduced pair per row of the system, an
+        equality's two values merged; (0, 0) throughout for a tableau without a solution.  Does not synchronise."""
+        if self.rows is None:
+            raise RuntimeError("Batch.dual_system needs the rows the batch was loaded from: use dual_system_part()")
+        return self.dual_system_part(self.rows, 0, stream)
+
+    def dual_system_part(self, rows, first, stream=None, out=None):
+        """pipamd_batch_dual_system_part for the tableaux first .. first + len(rows) - 1, loaded from the resident array
+        `rows`; returns (dual_num, dual_den) of the whole batch's shape (pass the pair back as `out` to fill it part by part)."""
+        assert self.system is not None and rows.is_cuda and rows.is_contiguous()
+        num, den = out if out is not None else self._dual_system_out()
+        st = C.c_void_p(stream) if stream is not None else self._stream()
+        _check(lib().pipamd_batch_dual_system_part(self.e._h, C.c_void_p(self.ws.data_ptr()), C.byref(self.desc),
+                                                   C.byref(self.system), C.c_void_p(rows.data_ptr()), int(first),
+                                                   int(rows.shape[0]), C.c_void_p(num.data_ptr()), C.c_void_p(den.data_ptr()), st))
         return num, den
 
     def counters(self):
