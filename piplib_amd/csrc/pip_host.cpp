@@ -129,24 +129,44 @@ extern "C" size_t pipamd_dense_pivot_bytes(const pipamd_batch_desc *d) {
   return 2ull * (size_t)d->ni * (size_t)(d->nvar + d->nparm + 1) * (d->entier_bits == 128 ? 16 : 8);
 }
 
-extern "C" int pipamd_batch_load_part(pipamd_engine *e, void *d_ws, const pipamd_batch_desc *d, const int64_t *d_rows,
-                                      int first, int count, void *stream) {
-  if (e && hipSetDevice(e->device) != hipSuccess) return PIPAMD_E_HIP;  // HIP's current device is per host thread
+// What every entry that works on a loaded batch starts with: the layout of the descriptor, the tableaux first ..
+// first + count - 1 held against the batch, the engine's device made current, the workspace split into its job headers
+// and its arena.  Argument errors are reported before the first HIP call.
+struct BatchView {
   PipBatchLayout lay;
-  size_t jb;
-  if (!e || !d_ws || !d_rows) return PIPAMD_E_INVALID;
-  int rc = pipamd_batch_layout(d, &lay, &jb);
-  if (rc) return rc;
-  if (first < 0 || count < 0 || first > lay.batch - count) {
-    pipamd_set_error("batch_load_part: tableaux %d..%d outside the batch of %d", first, first + count, lay.batch);
+  PipJob *jobs;
+  long long *arena;
+};
+
+static int batch_view(const char *who, const pipamd_engine *e, const void *d_ws, const pipamd_batch_desc *d, int first, int count,
+                      BatchView *v) {
+  if (!e || !d_ws || !d) {
+    pipamd_set_error("%s: null engine, workspace or descriptor", who);
     return PIPAMD_E_INVALID;
   }
-  PipJob *jobs = (PipJob *)d_ws;
-  long long *arena = (long long *)((char *)d_ws + jb);
+  size_t jb;
+  int rc = pipamd_batch_layout(d, &v->lay, &jb);
+  if (rc) return rc;
+  if (first < 0 || count < 0 || first > v->lay.batch - count) {
+    pipamd_set_error("%s_part: tableaux %d..%d outside the batch of %d", who, first, first + count, v->lay.batch);
+    return PIPAMD_E_INVALID;
+  }
+  if (hipSetDevice(e->device) != hipSuccess) return PIPAMD_E_HIP;  // HIP's current device is per host thread
+  v->jobs = (PipJob *)d_ws;
+  v->arena = (long long *)((char *)d_ws + jb);
+  return PIPAMD_OK;
+}
+
+extern "C" int pipamd_batch_load_part(pipamd_engine *e, void *d_ws, const pipamd_batch_desc *d, const int64_t *d_rows,
+                                      int first, int count, void *stream) {
+  if (!d_rows) return PIPAMD_E_INVALID;
+  BatchView v;
+  int rc = batch_view("batch_load", e, d_ws, d, first, count, &v);
+  if (rc) return rc;
   // PIPAMD_T_ROWS_STAY: no copy pass, the first pivot launch reads the caller's rows (whole 16-byte units)
   const int ncol = d->nvar + d->nparm + 1;
-  lay.pad = (d->tflags & PIPAMD_T_ROWS_STAY) && lay.ebits != 128 && ncol % 2 == 0 && ((uintptr_t)d_rows & 15) == 0;
-  HIPCHK(pipk_launch_batch_load(jobs, arena, (const long long *)d_rows, lay, first, count, (hipStream_t)stream));
+  v.lay.pad = (d->tflags & PIPAMD_T_ROWS_STAY) && v.lay.ebits != 128 && ncol % 2 == 0 && ((uintptr_t)d_rows & 15) == 0;
+  HIPCHK(pipk_launch_batch_load(v.jobs, v.arena, (const long long *)d_rows, v.lay, first, count, (hipStream_t)stream));
   return PIPAMD_OK;
 }
 
@@ -698,16 +718,11 @@ extern "C" int pipamd_engine_set_round_rows(pipamd_engine *e, int rows) {
 extern "C" int pipamd_batch_results(pipamd_engine *e, const void *d_ws, const pipamd_batch_desc *d, int32_t *d_status,
                                     int32_t *d_pivots, int32_t *d_cuts, int64_t *d_sol_num, int64_t *d_sol_den,
                                     void *stream) {
-  if (e && hipSetDevice(e->device) != hipSuccess) return PIPAMD_E_HIP;  // HIP's current device is per host thread
-  PipBatchLayout lay;
-  size_t jb;
-  if (!e || !d_ws) return PIPAMD_E_INVALID;
-  int rc = pipamd_batch_layout(d, &lay, &jb);
+  BatchView v;
+  int rc = batch_view("batch_results", e, d_ws, d, 0, 0, &v);
   if (rc) return rc;
-  const PipJob *jobs = (const PipJob *)d_ws;
-  const long long *arena = (const long long *)((const char *)d_ws + jb);
-  HIPCHK(pipk_launch_batch_results(jobs, arena, lay.batch, lay.nvar, lay.nparm, lay.ebits, d_status, d_pivots, d_cuts,
-                                   (void *)d_sol_num, (void *)d_sol_den, (hipStream_t)stream));
+  HIPCHK(pipk_launch_batch_results(v.jobs, v.arena, v.lay.batch, v.lay.nvar, v.lay.nparm, v.lay.ebits, d_status, d_pivots,
+                                   d_cuts, (void *)d_sol_num, (void *)d_sol_den, (hipStream_t)stream));
   return PIPAMD_OK;
 }
 
@@ -729,6 +744,18 @@ static int shifted_check(const char *who, const void *e, const void *d_ws, const
   return PIPAMD_OK;
 }
 
+// the load from a plain system whose description has been checked (`eq`: its equalities as a mask)
+static int load_system(const char *who, pipamd_engine *e, void *d_ws, const pipamd_batch_desc *d, const pipamd_system *sys,
+                       const PipEqMask *eq, const int64_t *d_rows, int first, int count, void *stream) {
+  BatchView v;
+  int rc = batch_view(who, e, d_ws, d, first, count, &v);
+  if (rc) return rc;
+  HIPCHK(pipk_launch_batch_load_system(v.jobs, v.arena, (const long long *)d_rows, v.lay, sys->shift, sys->simplify, sys->nrows,
+                                       eq, first, count, (hipStream_t)stream));
+  return PIPAMD_OK;
+}
+
+// the shifted load is the load of a system without equalities, not simplified
 extern "C" int pipamd_batch_load_shifted_part(pipamd_engine *e, void *d_ws, const pipamd_batch_desc *d, const int64_t *d_rows,
                                               int shift, int first, int count, void *stream) {
   int rc = shifted_check("batch_load_shifted", e, d_ws, d, shift);
@@ -737,19 +764,9 @@ extern "C" int pipamd_batch_load_shifted_part(pipamd_engine *e, void *d_ws, cons
     pipamd_set_error("batch_load_shifted: null rows pointer");
     return PIPAMD_E_INVALID;
   }
-  PipBatchLayout lay;
-  size_t jb;
-  rc = pipamd_batch_layout(d, &lay, &jb);
-  if (rc) return rc;
-  if (first < 0 || count < 0 || first > lay.batch - count) {
-    pipamd_set_error("batch_load_shifted_part: tableaux %d..%d outside the batch of %d", first, first + count, lay.batch);
-    return PIPAMD_E_INVALID;
-  }
-  if (hipSetDevice(e->device) != hipSuccess) return PIPAMD_E_HIP;  // HIP's current device is per host thread
-  PipJob *jobs = (PipJob *)d_ws;
-  long long *arena = (long long *)((char *)d_ws + jb);
-  HIPCHK(pipk_launch_batch_load_shifted(jobs, arena, (const long long *)d_rows, lay, shift, first, count, (hipStream_t)stream));
-  return PIPAMD_OK;
+  const pipamd_system sys = {d->ni, 0, nullptr, shift, 0};
+  const PipEqMask eq = {};
+  return load_system("batch_load_shifted", e, d_ws, d, &sys, &eq, d_rows, first, count, stream);
 }
 
 extern "C" int pipamd_batch_load_shifted(pipamd_engine *e, void *d_ws, const pipamd_batch_desc *d, const int64_t *d_rows, int shift,
@@ -762,56 +779,56 @@ extern "C" int pipamd_batch_results_shifted(pipamd_engine *e, const void *d_ws, 
                                             int64_t *d_x_den, void *stream) {
   int rc = shifted_check("batch_results_shifted", e, d_ws, d, shift);
   if (rc) return rc;
-  PipBatchLayout lay;
-  size_t jb;
-  rc = pipamd_batch_layout(d, &lay, &jb);
+  BatchView v;
+  rc = batch_view("batch_results_shifted", e, d_ws, d, 0, 0, &v);
   if (rc) return rc;
-  if (hipSetDevice(e->device) != hipSuccess) return PIPAMD_E_HIP;  // HIP's current device is per host thread
-  const PipJob *jobs = (const PipJob *)d_ws;
-  const long long *arena = (const long long *)((const char *)d_ws + jb);
-  HIPCHK(pipk_launch_batch_results_shifted(jobs, arena, lay.batch, lay.nvar, lay.ebits, shift, d_status, d_pivots, d_cuts,
-                                           (void *)d_x_num, (void *)d_x_den, (hipStream_t)stream));
+  HIPCHK(pipk_launch_batch_results_shifted(v.jobs, v.arena, v.lay.batch, v.lay.nvar, v.lay.ebits, shift, d_status, d_pivots,
+                                           d_cuts, (void *)d_x_num, (void *)d_x_den, (hipStream_t)stream));
   return PIPAMD_OK;
 }
 
 // Compute_dual for the batch layer (header comment: include/piplib_amd.h).  Everything is checked before the first HIP
 // call; the one launch goes on `stream` and nothing here waits for it.
+// What both dual entries refuse (`d_rows`: the rows the batch was loaded from).
+static int dual_check(const char *who, const pipamd_batch_desc *d, const void *d_rows, const void *d_dual_num,
+                      const void *d_dual_den) {
+  if (!d || !d_rows || !d_dual_num || !d_dual_den) {
+    pipamd_set_error("%s: null descriptor, rows or output array", who);
+    return PIPAMD_E_INVALID;
+  }
+  if (!(d->tflags & PIPAMD_T_DUAL) || (d->tflags & PIPAMD_T_INT)) {
+    pipamd_set_error("%s: the batch must have been solved with PIPAMD_T_DUAL and without PIPAMD_T_INT (the dual needs a "
+                     "rational solve)", who);
+    return PIPAMD_E_INVALID;
+  }
+  if (d->ni > pipk_batch_dual_max_ni()) {
+    pipamd_set_error("%s: %d inequalities per tableau, the dual kernel sorts at most %d", who, d->ni, pipk_batch_dual_max_ni());
+    return PIPAMD_E_TOOLARGE;
+  }
+  return PIPAMD_OK;
+}
+
+// the launch of either dual entry, its arguments checked; eq == nullptr: the plain one (nrows == d->ni, pairs not reduced)
+static int dual_launch(const char *who, pipamd_engine *e, const void *d_ws, const pipamd_batch_desc *d, int nrows,
+                       const PipEqMask *eq, const int64_t *d_rows, int first, int count, int64_t *d_dual_num,
+                       int64_t *d_dual_den, void *stream) {
+  BatchView v;
+  int rc = batch_view(who, e, d_ws, d, first, count, &v);
+  if (rc) return rc;
+  HIPCHK(pipk_launch_batch_dual(v.jobs, v.arena, (const long long *)d_rows, v.lay, nrows, eq, first, count, (void *)d_dual_num,
+                                (void *)d_dual_den, (hipStream_t)stream));
+  return PIPAMD_OK;
+}
+
 extern "C" int pipamd_batch_dual_part(pipamd_engine *e, const void *d_ws, const pipamd_batch_desc *d, const int64_t *d_rows,
                                       int first, int count, int64_t *d_dual_num, int64_t *d_dual_den, void *stream) {
-  if (!e || !d_ws || !d || !d_rows || !d_dual_num || !d_dual_den) {
-    pipamd_set_error("batch_dual: null engine, workspace, descriptor, rows or output array");
-    return PIPAMD_E_INVALID;
-  }
-  if (!(d->tflags & PIPAMD_T_DUAL)) {
-    pipamd_set_error("batch_dual: the batch was not solved with PIPAMD_T_DUAL in its descriptor's tflags");
-    return PIPAMD_E_INVALID;
-  }
-  if (d->tflags & PIPAMD_T_INT) {
-    pipamd_set_error("batch_dual: PIPAMD_T_INT and PIPAMD_T_DUAL together (the dual needs a rational solve)");
-    return PIPAMD_E_INVALID;
-  }
+  int rc = dual_check("batch_dual", d, d_rows, d_dual_num, d_dual_den);
+  if (rc) return rc;
   if (d->nparm != 0 || d->bigparm >= 0) {
     pipamd_set_error("batch_dual: nparm must be 0 and bigparm -1 (the batch layer finishes only such batches on its own)");
     return PIPAMD_E_INVALID;
   }
-  PipBatchLayout lay;
-  size_t jb;
-  int rc = pipamd_batch_layout(d, &lay, &jb);
-  if (rc) return rc;
-  if (first < 0 || count < 0 || first > lay.batch - count) {
-    pipamd_set_error("batch_dual_part: tableaux %d..%d outside the batch of %d", first, first + count, lay.batch);
-    return PIPAMD_E_INVALID;
-  }
-  if (lay.ni > pipk_batch_dual_max_ni()) {
-    pipamd_set_error("batch_dual: %d inequalities per tableau, the dual kernel sorts at most %d", lay.ni, pipk_batch_dual_max_ni());
-    return PIPAMD_E_TOOLARGE;
-  }
-  if (hipSetDevice(e->device) != hipSuccess) return PIPAMD_E_HIP;  // HIP's current device is per host thread
-  const PipJob *jobs = (const PipJob *)d_ws;
-  const long long *arena = (const long long *)((const char *)d_ws + jb);
-  HIPCHK(pipk_launch_batch_dual(jobs, arena, (const long long *)d_rows, lay, first, count, (void *)d_dual_num,
-                                (void *)d_dual_den, (hipStream_t)stream));
-  return PIPAMD_OK;
+  return dual_launch("batch_dual", e, d_ws, d, d->ni, nullptr, d_rows, first, count, d_dual_num, d_dual_den, stream);
 }
 
 extern "C" int pipamd_batch_dual(pipamd_engine *e, const void *d_ws, const pipamd_batch_desc *d, const int64_t *d_rows,
@@ -875,20 +892,7 @@ extern "C" int pipamd_batch_load_system_part(pipamd_engine *e, void *d_ws, const
   PipEqMask eq;
   int rc = system_check("batch_load_system", e, d_ws, d, sys, d_rows, &eq);
   if (rc) return rc;
-  PipBatchLayout lay;
-  size_t jb;
-  rc = pipamd_batch_layout(d, &lay, &jb);
-  if (rc) return rc;
-  if (first < 0 || count < 0 || first > lay.batch - count) {
-    pipamd_set_error("batch_load_system_part: tableaux %d..%d outside the batch of %d", first, first + count, lay.batch);
-    return PIPAMD_E_INVALID;
-  }
-  if (hipSetDevice(e->device) != hipSuccess) return PIPAMD_E_HIP;  // HIP's current device is per host thread
-  PipJob *jobs = (PipJob *)d_ws;
-  long long *arena = (long long *)((char *)d_ws + jb);
-  HIPCHK(pipk_launch_batch_load_system(jobs, arena, (const long long *)d_rows, lay, sys->shift, sys->simplify, sys->nrows, &eq,
-                                       first, count, (hipStream_t)stream));
-  return PIPAMD_OK;
+  return load_system("batch_load_system", e, d_ws, d, sys, &eq, d_rows, first, count, stream);
 }
 
 extern "C" int pipamd_batch_load_system(pipamd_engine *e, void *d_ws, const pipamd_batch_desc *d, const pipamd_system *sys,
@@ -902,34 +906,9 @@ extern "C" int pipamd_batch_dual_system_part(pipamd_engine *e, const void *d_ws,
   PipEqMask eq;
   int rc = system_check("batch_dual_system", e, d_ws, d, sys, d_rows, &eq);
   if (rc) return rc;
-  if (!d_dual_num || !d_dual_den) {
-    pipamd_set_error("batch_dual_system: null output array");
-    return PIPAMD_E_INVALID;
-  }
-  if (!(d->tflags & PIPAMD_T_DUAL) || (d->tflags & PIPAMD_T_INT)) {
-    pipamd_set_error("batch_dual_system: the batch must have been solved with PIPAMD_T_DUAL and without PIPAMD_T_INT (the dual "
-                     "needs a rational solve)");
-    return PIPAMD_E_INVALID;
-  }
-  PipBatchLayout lay;
-  size_t jb;
-  rc = pipamd_batch_layout(d, &lay, &jb);
+  rc = dual_check("batch_dual_system", d, d_rows, d_dual_num, d_dual_den);
   if (rc) return rc;
-  if (first < 0 || count < 0 || first > lay.batch - count) {
-    pipamd_set_error("batch_dual_system_part: tableaux %d..%d outside the batch of %d", first, first + count, lay.batch);
-    return PIPAMD_E_INVALID;
-  }
-  if (lay.ni > pipk_batch_dual_max_ni()) {
-    pipamd_set_error("batch_dual_system: %d inequalities per tableau, the dual kernel sorts at most %d", lay.ni,
-                     pipk_batch_dual_max_ni());
-    return PIPAMD_E_TOOLARGE;
-  }
-  if (hipSetDevice(e->device) != hipSuccess) return PIPAMD_E_HIP;  // HIP's current device is per host thread
-  const PipJob *jobs = (const PipJob *)d_ws;
-  const long long *arena = (const long long *)((const char *)d_ws + jb);
-  HIPCHK(pipk_launch_batch_dual_system(jobs, arena, (const long long *)d_rows, lay, sys->nrows, &eq, first, count,
-                                       (void *)d_dual_num, (void *)d_dual_den, (hipStream_t)stream));
-  return PIPAMD_OK;
+  return dual_launch("batch_dual_system", e, d_ws, d, sys->nrows, &eq, d_rows, first, count, d_dual_num, d_dual_den, stream);
 }
 
 extern "C" int pipamd_batch_dual_system(pipamd_engine *e, const void *d_ws, const pipamd_batch_desc *d, const pipamd_system *sys,
@@ -939,13 +918,11 @@ extern "C" int pipamd_batch_dual_system(pipamd_engine *e, const void *d_ws, cons
 
 extern "C" int pipamd_batch_counters(pipamd_engine *e, const void *d_ws, const pipamd_batch_desc *d, uint64_t *d_out4,
                                      void *stream) {
-  if (e && hipSetDevice(e->device) != hipSuccess) return PIPAMD_E_HIP;  // HIP's current device is per host thread
-  PipBatchLayout lay;
-  size_t jb;
-  if (!e || !d_ws || !d_out4) return PIPAMD_E_INVALID;
-  int rc = pipamd_batch_layout(d, &lay, &jb);
+  if (!d_out4) return PIPAMD_E_INVALID;
+  BatchView v;
+  int rc = batch_view("batch_counters", e, d_ws, d, 0, 0, &v);
   if (rc) return rc;
-  HIPCHK(pipk_launch_batch_counters((const PipJob *)d_ws, lay.batch, (unsigned long long *)d_out4, (hipStream_t)stream));
+  HIPCHK(pipk_launch_batch_counters(v.jobs, v.lay.batch, (unsigned long long *)d_out4, (hipStream_t)stream));
   return PIPAMD_OK;
 }
 

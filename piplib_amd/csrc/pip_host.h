@@ -76,8 +76,6 @@ hipError_t pipk_launch_advance_q(PipJob *jobs, long long *arena, int njobs, int 
 hipError_t pipk_launch_replay_all(PipJob *jobs, long long *arena, int njobs, int ebits, int wave_per_job, hipStream_t stream);
 hipError_t pipk_launch_batch_load(PipJob *jobs, long long *arena, const long long *rows, PipBatchLayout lay, int first,
                                   int count, hipStream_t stream);
-hipError_t pipk_launch_batch_load_shifted(PipJob *jobs, long long *arena, const long long *rows, PipBatchLayout lay, int shift,
-                                          int first, int count, hipStream_t stream);
 hipError_t pipk_launch_batch_results_shifted(const PipJob *jobs, const long long *arena, int njobs, int nvar, int ebits,
                                              int shift, int *status, int *pivots, int *cuts, void *x_num, void *x_den,
                                              hipStream_t stream);
@@ -85,13 +83,12 @@ hipError_t pipk_launch_batch_results(const PipJob *jobs, const long long *arena,
                                      int ebits, int *status, int *pivots, int *cuts, void *sol_num, void *sol_den,
                                      hipStream_t stream);
 int pipk_batch_dual_max_ni(void); /* inequalities per tableau pip_batch_dual_kernel sorts in LDS */
+/* eq == NULL: pipamd_batch_dual (nrows == lay.ni, pairs not reduced); otherwise pipamd_batch_dual_system */
 hipError_t pipk_launch_batch_dual(const PipJob *jobs, const long long *arena, const long long *rows, PipBatchLayout lay,
-                                  int first, int count, void *dual_num, void *dual_den, hipStream_t stream);
+                                  int nrows, const PipEqMask *eq, int first, int count, void *dual_num, void *dual_den,
+                                  hipStream_t stream);
 hipError_t pipk_launch_batch_load_system(PipJob *jobs, long long *arena, const long long *rows, PipBatchLayout lay, int shift,
                                          int simplify, int nrows, const PipEqMask *eq, int first, int count, hipStream_t stream);
-hipError_t pipk_launch_batch_dual_system(const PipJob *jobs, const long long *arena, const long long *rows, PipBatchLayout lay,
-                                         int nrows, const PipEqMask *eq, int first, int count, void *dual_num, void *dual_den,
-                                         hipStream_t stream);
 hipError_t pipk_launch_rehouse(PipJob *jobs, long long *arena, void *const *q5, int grid, PipBatchLayout nl, int *side_count,
                                int side_cap, hipStream_t stream);
 hipError_t pipk_launch_rehouse_finish(PipJob *jobs, long long *arena, int njobs, int sol_words, hipStream_t stream);

@@ -3,7 +3,7 @@
 // The pivot kernel itself (pip_advance_kernel: traiter() / pivoter() / choisir_piv() / exam_coef() / integrer() /
 // tab_sort_rows of the reference) lives in pip_advance.h and is instantiated by the pip_adv_*.hip files; this file
 // holds the determinant replay, the batch load / results / counters kernels (pip_batch_load_system_kernel: the load from
-// pip_solve's plain system), Compute_dual for the batch layer (pip_batch_dual_kernel, pip_batch_dual_system_kernel),
+// pip_solve's plain system), Compute_dual for the batch layer (pip_batch_dual_kernel),
 // expanser for the batch layer, the helpers of the lock-step scheduler and every launcher.
 #include "pip_lean.h"
 
@@ -151,22 +151,13 @@ __global__ __launch_bounds__(64) void pip_det_replay_lanes_kernel(PipJob *jobs, 
 // ---------------------------------------------------------------- batch load
 // tab_alloc + tab_get (tab.c:158-248) for a uniform batch: nvar unit rows, then
 // ni Unknown rows with denominator 1; spare slots and columns zeroed.  Input rows are int64
-// whatever the entry type of the tableau.
-// SHIFTED (pipamd_batch_load_shifted; the layout has nparm == 1, bigparm == nvar + 1): `rows` holds the caller's plain
-// system, nvar + 1 columns a row, and the tableau gets what tab_Matrix2Tableau writes for a new big parameter
-// (tab.c:342-377): shift > 0 (Maximize) -a_j | c | +sum a_j, shift < 0 (Urs_unknowns) a_j | c | -sum a_j; the sum in
-// the entry type (64-bit entries: it wraps as the reference's long long build does).
-template <class T, bool SHIFTED = false>
-__global__ void pip_batch_load_kernel(PipJob *jobs, i64 *arena, const i64 *rows, PipBatchLayout lay, int first, int shift) {
-  constexpr int EW = ET<T>::EW;
-  const int b = first + blockIdx.x;  // `rows` holds the tableaux first, first + 1, ... of the batch
-  const int tid = threadIdx.x;
-  const int ncol = lay.nvar + lay.nparm + 1;
-  const int srccol = SHIFTED ? lay.nvar + 1 : ncol;  // columns of a row of `rows`
-  PipJob *J = &jobs[b];
-  const int64_t base = lay.arena_off + (int64_t)b * lay.blk.words;
-  const auto [g_den, g_flag, g_ref] = pip_row_tables<T>(arena + base, lay.blk.L);
-  T *vals = (T *)(arena + base + lay.blk.vals);
+// whatever the entry type of the tableau.  The three pieces below are what every load kernel does around its own way
+// of writing the ni input rows.
+
+// the row tables of a block: unit rows, unknown rows, empty slots
+template <class T>
+__device__ __forceinline__ void load_row_tables(i64 *blk, const PipBatchLayout &lay, int tid) {
+  const auto [g_den, g_flag, g_ref] = pip_row_tables<T>(blk, lay.blk.L);
   for (int i = tid; i < lay.blk.L; i += blockDim.x) {
     if (i < lay.nvar) {
       g_flag[i] = PIPAMD_F_UNIT;
@@ -182,36 +173,59 @@ __global__ void pip_batch_load_kernel(PipJob *jobs, i64 *arena, const i64 *rows,
       g_den[i] = 0;
     }
   }
-  // input rows; spare slots only need their columns beyond ncol cleared (a cut row writes its
-  // first ncol columns itself, a parametric cut relies on the new column being 0 elsewhere)
-  const i64 *src = rows + (size_t)blockIdx.x * lay.ni * srccol;
-  const int pad = lay.W - ncol;
-  const bool defer = !SHIFTED && lay.pad != 0 && EW == 1;  // PIPAMD_T_ROWS_STAY: the first pivot launch fetches the rows itself
-  if constexpr (SHIFTED) {
-    const int nvar = lay.nvar;
-    int s = tid / lay.W, j = tid % lay.W;
-    const int ds = (int)blockDim.x / lay.W, dj = (int)blockDim.x % lay.W;
-    for (int e = tid; e < lay.ni * lay.W; e += blockDim.x) {
-      const i64 *r = src + (size_t)s * srccol;
-      T v = 0;
-      if (j < nvar)
-        v = shift > 0 ? wneg((T)r[j]) : (T)r[j];
-      else if (j == nvar)
-        v = (T)r[nvar];
-      else if (j == nvar + 1) {  // the new column: one thread per row sums the row
-        T sum = 0;
-        for (int k = 0; k < nvar; k++) sum = wadd(sum, (T)r[k]);
-        v = shift > 0 ? sum : wneg(sum);
-      }
-      vals[e] = v;
-      s += ds;
-      j += dj;
-      if (j >= lay.W) {
-        j -= lay.W;
-        s++;
-      }
-    }
-  } else if (!defer) {
+}
+
+// spare slots (the rows from first_pad_row on) only need their columns beyond ncol cleared: a cut row writes its
+// first ncol columns itself, a parametric cut relies on the new column being 0 elsewhere
+template <class T>
+__device__ __forceinline__ void load_clear_spare(T *vals, const PipBatchLayout &lay, int first_pad_row, int tid) {
+  const int ncol = lay.nvar + lay.nparm + 1, pad = lay.W - ncol;
+  for (int e = tid; e < (lay.S - first_pad_row) * pad; e += blockDim.x) {
+    int s = first_pad_row + e / pad, j = ncol + e % pad;
+    vals[(size_t)s * lay.W + j] = 0;
+  }
+}
+
+// the job header (one thread).  defer (PIPAMD_T_ROWS_STAY): the first pivot launch fetches the rows from `src` itself
+template <class T>
+__device__ __forceinline__ void load_job_header(PipJob *J, int64_t base, const PipBatchLayout &lay, bool defer, const i64 *src) {
+  pip_job_place(J, base, lay.blk);
+  J->nlog = 0;
+  J->nvar = lay.nvar;
+  J->nparm = lay.nparm;
+  J->ni = lay.ni;
+  J->bigparm = lay.bigparm;
+  J->tflags = lay.tflags | PIPAMD_T_SORT | (defer ? PIPAMD_T_FRESHROWS : 0);
+  J->src_rows = defer ? (int64_t)(uintptr_t)src : 0;
+  J->home_sol_off = 0;
+  J->S = lay.S;
+  J->W = lay.W;
+  J->status = PIPAMD_ST_RUN;
+  J->aux = 0;
+  J->npiv = 0;
+  J->ncut = 0;
+  J->nupd = 0;
+  J->ldet = 1;
+  for (int i = 0; i < 2 * PIPAMD_MAXDET; i++) J->det[i] = 0;
+  J->det[0] = 1;
+  J->maxabs = 0;
+  J->state_nch = 0;
+  J->ebits = ET<T>::BITS;
+}
+
+// pipamd_batch_load: `rows` holds the tableau rows themselves, nvar + nparm + 1 columns a row
+template <class T>
+__global__ void pip_batch_load_kernel(PipJob *jobs, i64 *arena, const i64 *rows, PipBatchLayout lay, int first) {
+  constexpr int EW = ET<T>::EW;
+  const int b = first + blockIdx.x;  // `rows` holds the tableaux first, first + 1, ... of the batch
+  const int tid = threadIdx.x;
+  const int ncol = lay.nvar + lay.nparm + 1;
+  const int64_t base = lay.arena_off + (int64_t)b * lay.blk.words;
+  T *vals = (T *)(arena + base + lay.blk.vals);
+  load_row_tables<T>(arena + base, lay, tid);
+  const i64 *src = rows + (size_t)blockIdx.x * lay.ni * ncol;
+  const bool defer = lay.pad != 0 && EW == 1;  // PIPAMD_T_ROWS_STAY: the first pivot launch fetches the rows itself
+  if (!defer) {
     // (row, column) advance with the thread stride: no division per element
     const int ds = (int)blockDim.x / lay.W, dj = (int)blockDim.x % lay.W;
     int s = tid / lay.W, j = tid % lay.W;
@@ -225,44 +239,19 @@ __global__ void pip_batch_load_kernel(PipJob *jobs, i64 *arena, const i64 *rows,
       }
     }
   }
-  const int first_pad_row = defer ? 0 : lay.ni;
-  for (int e = tid; e < (lay.S - first_pad_row) * pad; e += blockDim.x) {
-    int s = first_pad_row + e / pad, j = ncol + e % pad;
-    vals[(size_t)s * lay.W + j] = 0;
-  }
-  if (tid == 0) {
-    pip_job_place(J, base, lay.blk);
-    J->nlog = 0;
-    J->nvar = lay.nvar;
-    J->nparm = lay.nparm;
-    J->ni = lay.ni;
-    J->bigparm = lay.bigparm;
-    J->tflags = lay.tflags | PIPAMD_T_SORT | (defer ? PIPAMD_T_FRESHROWS : 0);
-    J->src_rows = defer ? (int64_t)(uintptr_t)src : 0;
-    J->home_sol_off = 0;
-    J->S = lay.S;
-    J->W = lay.W;
-    J->status = PIPAMD_ST_RUN;
-    J->aux = 0;
-    J->npiv = 0;
-    J->ncut = 0;
-    J->nupd = 0;
-    J->ldet = 1;
-    for (int i = 0; i < 2 * PIPAMD_MAXDET; i++) J->det[i] = 0;
-    J->det[0] = 1;
-    J->maxabs = 0;
-    J->state_nch = 0;
-    J->ebits = ET<T>::BITS;
-  }
+  load_clear_spare(vals, lay, defer ? 0 : lay.ni, tid);
+  if (tid == 0) load_job_header<T>(&jobs[b], base, lay, defer, src);
 }
 
 // ---------------------------------------------------------------- batch load from a plain system
 // pipamd_batch_load_system: tab_Matrix2Tableau (tab.c:328-389) and, for integer problems, tab_simplify (tab.c:396-427)
 // for a uniform batch.  `rows` holds the caller's system, nrows x (nvar + 1) int64 a tableau; input row r becomes
-// tableau row r + (equalities before r), written as pip_batch_load_kernel<T, true> writes it (shift == 0: a_j | c), and
-// an equality is followed by its negation in every column.  One WAVE per input row, a lane per column (CPL columns a
-// lane): the row's sum and the gcd of its columns are reductions over the lanes that hold it.  The row tables, the spare
-// slots and the job header are pip_batch_load_kernel's.
+// tableau row r + (equalities before r): a_j | c without a shift; under a new big parameter (tab.c:342-377; the layout
+// has nparm == 1, bigparm == nvar + 1) -a_j | c | +sum a_j for shift > 0 (Maximize) and a_j | c | -sum a_j for
+// shift < 0 (Urs_unknowns), the sum in the entry type (64-bit entries: it wraps as the reference's long long build
+// does); an equality is followed by its negation in every column.  One WAVE per input row, a lane per column (CPL
+// columns a lane): the row's sum and the gcd of its columns are reductions over the lanes that hold it.
+// pipamd_batch_load_shifted is the launch with no equality, simplify == 0 and nrows == ni.
 __device__ __forceinline__ i64 sys_shfl(i64 v, int src) { return shfl64(v, src); }
 __device__ __forceinline__ i128 sys_shfl(i128 v, int src) {
   const u64 lo = (u64)shfl64((i64)(u64)(u128)v, src), hi = (u64)shfl64((i64)(u64)((u128)v >> 64), src);
@@ -297,26 +286,10 @@ __global__ __launch_bounds__(256) void pip_batch_load_system_kernel(PipJob *jobs
   typedef typename ET<T>::U U;
   const int b = first + blockIdx.x;  // `rows` holds the systems first, first + 1, ... of the batch
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int nvar = lay.nvar, ncol = nvar + lay.nparm + 1, srccol = nvar + 1, W = lay.W;
-  PipJob *J = &jobs[b];
+  const int nvar = lay.nvar, srccol = nvar + 1, W = lay.W;
   const int64_t base = lay.arena_off + (int64_t)b * lay.blk.words;
-  const auto [g_den, g_flag, g_ref] = pip_row_tables<T>(arena + base, lay.blk.L);
   T *vals = (T *)(arena + base + lay.blk.vals);
-  for (int i = tid; i < lay.blk.L; i += blockDim.x) {
-    if (i < nvar) {
-      g_flag[i] = PIPAMD_F_UNIT;
-      g_ref[i] = i;
-      g_den[i] = 1;
-    } else if (i < nvar + lay.ni) {
-      g_flag[i] = PIPAMD_F_UNKNOWN;
-      g_ref[i] = i - nvar;
-      g_den[i] = 1;
-    } else {
-      g_flag[i] = 0;
-      g_ref[i] = 0;
-      g_den[i] = 0;
-    }
-  }
+  load_row_tables<T>(arena + base, lay, tid);
   const i64 *src = rows + (size_t)blockIdx.x * nrows * srccol;
   int wcur = 0, before = 0;  // equalities among the rows below 64 * wcur
   for (int r = wave; r < nrows; r += 4) {
@@ -372,36 +345,8 @@ __global__ __launch_bounds__(256) void pip_batch_load_system_kernel(PipJob *jobs
       if (twin) out[W + j] = y;
     }
   }
-  // spare slots: their columns beyond ncol (as pip_batch_load_kernel)
-  const int pad = W - ncol;
-  for (int e = tid; e < (lay.S - lay.ni) * pad; e += blockDim.x) {
-    int s = lay.ni + e / pad, j = ncol + e % pad;
-    vals[(size_t)s * W + j] = 0;
-  }
-  if (tid == 0) {
-    pip_job_place(J, base, lay.blk);
-    J->nlog = 0;
-    J->nvar = nvar;
-    J->nparm = lay.nparm;
-    J->ni = lay.ni;
-    J->bigparm = lay.bigparm;
-    J->tflags = lay.tflags | PIPAMD_T_SORT;
-    J->src_rows = 0;
-    J->home_sol_off = 0;
-    J->S = lay.S;
-    J->W = W;
-    J->status = PIPAMD_ST_RUN;
-    J->aux = 0;
-    J->npiv = 0;
-    J->ncut = 0;
-    J->nupd = 0;
-    J->ldet = 1;
-    for (int i = 0; i < 2 * PIPAMD_MAXDET; i++) J->det[i] = 0;
-    J->det[0] = 1;
-    J->maxabs = 0;
-    J->state_nch = 0;
-    J->ebits = ET<T>::BITS;
-  }
+  load_clear_spare(vals, lay, lay.ni, tid);
+  if (tid == 0) load_job_header<T>(&jobs[b], base, lay, false, nullptr);
 }
 
 // sol_vector_edit (sol.c:435-512) with SOL_REMOVE and SOL_MAX / SOL_SHIFT for a batch solved under a big parameter
@@ -551,118 +496,26 @@ __device__ void dual_sort_pairs(float *key, u16 *ineq, int n, double smax, int l
   __syncthreads();
 }
 
-// `rows`: the int64 input rows of the tableaux first, first + 1, ... (what pipamd_batch_load_part was given); dual_num /
-// dual_den: [batch][ni] values of the entry type.  A tableau that is not PIPAMD_ST_SOLUTION, or whose header or tables
-// are not what a finished solve of this layout leaves, gets (0, 0) throughout.
-template <class T>
+// `rows` holds the int64 rows the tableaux first, first + 1, ... were loaded from, nrows x (nvar + 1) a tableau, of
+// which `eq` marks the equalities: the tableau has ni = nrows + equalities rows.  tab_sort_rows saw the expanded rows: a
+// row's key is taken over the unknown columns alone (traiter.c:581), where a shift and the negation change signs only,
+// so an equality's two rows have the key of the input row.  dual_num / dual_den: [batch][nrows] values of the entry
+// type, one pair per INPUT row.  A tableau that is not PIPAMD_ST_SOLUTION, or whose header or tables are not what a
+// finished solve of this layout leaves, gets (0, 0) throughout.
+//   EQ == PipNoEq (pipamd_batch_dual: rows loaded by pipamd_batch_load, so no equalities and nrows == ni; no mask
+//     travels with the launch): the pair solution_dual hands to sol_val, not reduced.
+//   EQ == PipEqMask (pipamd_batch_dual_system, with or without a big parameter): the pair as pip_solve hands it out,
+//     reduced as sol_vector_edit with flags 0 reduces it (sol.c:475-500), and for an equality with the values u (its
+//     row) and v (the negated row) u if u != 0, else -v (piplib.c:670-688).
+struct PipNoEq {};
+__device__ __forceinline__ u64 dual_eq_word(const PipEqMask &eq, int w) { return eq.w[w]; }
+__device__ __forceinline__ u64 dual_eq_word(const PipNoEq &, int) { return 0; }
+
+template <class T, class EQ>
 __global__ __launch_bounds__(64) void pip_batch_dual_kernel(const PipJob *jobs, const i64 *arena, const i64 *rows,
-                                                            PipBatchLayout lay, int first, T *dual_num, T *dual_den) {
-  extern __shared__ __align__(16) unsigned char dual_lds[];
-  const int lane = threadIdx.x;
-  const int b = first + blockIdx.x;
-  const int nvar = lay.nvar, ni = lay.ni, ncol = lay.nvar + 1;
-  if (ni <= 0 || ni > PIP_DUAL_MAXNI) return;
-  float *key = (float *)dual_lds;          // [ni]; after the sort its room holds pos
-  u16 *ineq = (u16 *)(dual_lds + 4 * (size_t)ni);  // [ni]
-  u16 *pos = (u16 *)dual_lds;              // [ni]: logical row of each inequality after the sort
-
-  // 1. keys: a lane per column pair, four rows in flight
-  const i64 *src = rows + (size_t)blockIdx.x * ni * ncol;
-  unsigned smaxw = 0;
-  for (int i0 = 0; i0 < ni; i0 += 4) {
-    int sz[4] = {0, 0, 0, 0};
-    for (int j = 2 * lane; j < nvar; j += 128) {
-#pragma unroll
-      for (int q = 0; q < 4; q++) {
-        if (i0 + q >= ni) break;
-        const i64 *r = src + (size_t)(i0 + q) * ncol;
-        const int a0 = dual_key_term(r[j]);
-        const int a1 = j + 1 < nvar ? dual_key_term(r[j + 1]) : 0;
-        const int a = a0 > a1 ? a0 : a1;
-        sz[q] = sz[q] > a ? sz[q] : a;
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      if (i0 + q >= ni) break;
-      const unsigned szw = wave_minmax_u32<true>((unsigned)sz[q]);
-      if (lane == 0) {
-        key[i0 + q] = (float)szw;
-        ineq[i0 + q] = (u16)(i0 + q);
-      }
-      smaxw = smaxw > szw ? smaxw : szw;
-    }
-  }
-  __syncthreads();
-
-  // 2. the sort, then pos[ineq[r]] = nvar + r (all ni rows are real at load time)
-  dual_sort_pairs(key, ineq, ni, (double)smaxw, lane);
-  for (int r = lane; r < ni; r += 64) {
-    const int i = ineq[r];
-    if (i < ni) pos[i] = (u16)(nvar + r);
-  }
-  __syncthreads();
-
-  // 3. the values, as emit_dual (pip_tree.cpp) reads them from a snapshot of the job's block
-  const PipJob *J = &jobs[b];
-  const i64 base = lay.arena_off + (i64)b * lay.blk.words;
-  const int L = lay.blk.L, S = lay.S, W = lay.W, nligne = nvar + ni;
-  bool ok = J->status == PIPAMD_ST_SOLUTION && J->rows_off == base && J->vals_off == base + lay.blk.vals && J->L == L &&
-            J->W == W && J->nvar == nvar && J->ni == ni && J->nparm == 0 && nligne <= L;
-  const auto [g_den, g_flag, g_ref] = pip_row_tables<const T>(arena + base, L);
-  const T *vals = (const T *)(arena + base + lay.blk.vals);
-  int f0 = 0, r0 = 0;
-  T d0 = 0;
-  if (ok) {
-    f0 = g_flag[0];
-    r0 = g_ref[0];
-    d0 = g_den[0];
-    if (!(f0 & PIPAMD_F_UNIT) && (r0 < 0 || r0 >= S)) ok = false;
-  }
-  for (int i = lane; i < ni; i += 64) {
-    T num = 0, den = 0;
-    const int k = pos[i];
-    if (ok && k >= nvar && k < nligne) {
-      if (g_flag[k] & PIPAMD_F_UNIT) {
-        const int u = g_ref[k];
-        if (u >= 0 && u < nvar) {  // valeur(tp, 0, u), Denom(tp, 0)
-          num = (f0 & PIPAMD_F_UNIT) ? (r0 == u ? d0 : (T)0) : vals[(size_t)r0 * W + u];
-          den = d0;
-        }
-      } else {
-        num = 0;
-        den = 1;
-      }
-    }
-    dual_num[(size_t)b * ni + i] = num;
-    dual_den[(size_t)b * ni + i] = den;
-  }
-}
-
-extern "C" hipError_t pipk_launch_batch_dual(const PipJob *jobs, const i64 *arena, const i64 *rows, PipBatchLayout lay,
-                                             int first, int count, void *dual_num, void *dual_den, hipStream_t stream) {
-  if (count <= 0 || lay.ni <= 0) return hipSuccess;
-  if (lay.ni > PIP_DUAL_MAXNI || lay.nparm != 0) return hipErrorInvalidValue;
-  const size_t shm = pipk_batch_dual_lds_bytes(lay.ni);
-  if (lay.ebits == 128)
-    hipLaunchKernelGGL(pip_batch_dual_kernel<i128>, dim3(count), dim3(64), shm, stream, jobs, arena, rows, lay, first,
-                       (i128 *)dual_num, (i128 *)dual_den);
-  else
-    hipLaunchKernelGGL(pip_batch_dual_kernel<i64>, dim3(count), dim3(64), shm, stream, jobs, arena, rows, lay, first,
-                       (i64 *)dual_num, (i64 *)dual_den);
-  return hipGetLastError();
-}
-
-// The same for a batch loaded from a plain system (pipamd_batch_load_system), with or without a big parameter: `rows`
-// holds the caller's nrows x (nvar + 1) rows, of which `eq` marks the equalities; the tableau has ni = nrows + equalities
-// rows.  tab_sort_rows saw the expanded rows: a row's key is taken over the unknown columns alone (traiter.c:581), where
-// the shift and the negation change signs only, so an equality's two rows have the key of the input row.  Per INPUT row
-// one pair, as pip_solve hands it out: reduced as sol_vector_edit with flags 0 reduces it (sol.c:475-500), and for an
-// equality with the values u (its row) and v (the negated row) u if u != 0, else -v (piplib.c:670-688).
-template <class T>
-__global__ __launch_bounds__(64) void pip_batch_dual_system_kernel(const PipJob *jobs, const i64 *arena, const i64 *rows,
-                                                                   PipBatchLayout lay, int first, int nrows, PipEqMask eq,
-                                                                   T *dual_num, T *dual_den) {
+                                                            PipBatchLayout lay, int first, int nrows, EQ eq, T *dual_num,
+                                                            T *dual_den) {
+  constexpr bool SYSTEM = std::is_same<EQ, PipEqMask>::value;
   extern __shared__ __align__(16) unsigned char dual_lds[];
   const int lane = threadIdx.x;
   const int b = first + blockIdx.x;
@@ -693,7 +546,7 @@ __global__ __launch_bounds__(64) void pip_batch_dual_system_kernel(const PipJob 
     for (int q = 0; q < 4; q++) {
       if (i0 + q >= nrows) break;
       const unsigned szw = wave_minmax_u32<true>((unsigned)sz[q]);
-      const int twin = (int)((eq.w[(i0 + q) >> 6] >> ((i0 + q) & 63)) & 1);
+      const int twin = (int)((dual_eq_word(eq, (i0 + q) >> 6) >> ((i0 + q) & 63)) & 1);
       if (lane <= twin && k + lane < ni) {
         key[k + lane] = (float)szw;
         ineq[k + lane] = (u16)(k + lane);
@@ -713,7 +566,7 @@ __global__ __launch_bounds__(64) void pip_batch_dual_system_kernel(const PipJob 
   }
   __syncthreads();
 
-  // 3. the values, as pip_batch_dual_kernel reads them
+  // 3. the values, as emit_dual (pip_tree.cpp) reads them from a snapshot of the job's block
   const PipJob *J = &jobs[b];
   const i64 base = lay.arena_off + (i64)b * lay.blk.words;
   const int L = lay.blk.L, S = lay.S, W = lay.W, nligne = nvar + ni;
@@ -746,7 +599,7 @@ __global__ __launch_bounds__(64) void pip_batch_dual_system_kernel(const PipJob 
   };
   int before = 0;  // equalities among the input rows below r0w
   for (int r0w = 0; r0w < nrows; r0w += 64) {
-    const u64 word = eq.w[r0w >> 6];
+    const u64 word = dual_eq_word(eq, r0w >> 6);
     const int r = r0w + lane;
     if (r < nrows) {
       T num = 0, den = 0;
@@ -755,14 +608,16 @@ __global__ __launch_bounds__(64) void pip_batch_dual_system_kernel(const PipJob 
         const bool twin = (word >> lane) & 1;
         if (t + (int)twin < ni) {
           value(t, num, den);
-          if (twin && num == 0) {
-            value(t + 1, num, den);
-            num = wneg(num);
+          if constexpr (SYSTEM) {
+            if (twin && num == 0) {
+              value(t + 1, num, den);
+              num = wneg(num);
+            }
+            T g = gcd_i64(num, den);
+            if (g == 0) g = 1;
+            num = cquo(num, g);
+            den = cquo(den, g);
           }
-          T g = gcd_i64(num, den);
-          if (g == 0) g = 1;
-          num = cquo(num, g);
-          den = cquo(den, g);
         }
       }
       dual_num[(size_t)b * nrows + r] = num;
@@ -772,18 +627,28 @@ __global__ __launch_bounds__(64) void pip_batch_dual_system_kernel(const PipJob 
   }
 }
 
-extern "C" hipError_t pipk_launch_batch_dual_system(const PipJob *jobs, const i64 *arena, const i64 *rows, PipBatchLayout lay,
-                                                    int nrows, const PipEqMask *eq, int first, int count, void *dual_num,
-                                                    void *dual_den, hipStream_t stream) {
+// eq == nullptr: pipamd_batch_dual (the caller has checked lay.nparm == 0); otherwise pipamd_batch_dual_system
+extern "C" hipError_t pipk_launch_batch_dual(const PipJob *jobs, const i64 *arena, const i64 *rows, PipBatchLayout lay,
+                                             int nrows, const PipEqMask *eq, int first, int count, void *dual_num,
+                                             void *dual_den, hipStream_t stream) {
   if (count <= 0 || lay.ni <= 0 || nrows <= 0) return hipSuccess;
-  if (lay.ni > PIP_DUAL_MAXNI || nrows > lay.ni) return hipErrorInvalidValue;
+  if (lay.ni > PIP_DUAL_MAXNI || nrows > lay.ni || (!eq && (nrows != lay.ni || lay.nparm != 0))) return hipErrorInvalidValue;
   const size_t shm = pipk_batch_dual_lds_bytes(lay.ni);
-  if (lay.ebits == 128)
-    hipLaunchKernelGGL(pip_batch_dual_system_kernel<i128>, dim3(count), dim3(64), shm, stream, jobs, arena, rows, lay, first,
-                       nrows, *eq, (i128 *)dual_num, (i128 *)dual_den);
-  else
-    hipLaunchKernelGGL(pip_batch_dual_system_kernel<i64>, dim3(count), dim3(64), shm, stream, jobs, arena, rows, lay, first,
-                       nrows, *eq, (i64 *)dual_num, (i64 *)dual_den);
+#define PIP_DUAL(T, EQ, MASK)                                                                                          \
+  hipLaunchKernelGGL((pip_batch_dual_kernel<T, EQ>), dim3(count), dim3(64), shm, stream, jobs, arena, rows, lay, first, \
+                     nrows, MASK, (T *)dual_num, (T *)dual_den)
+  if (lay.ebits == 128) {
+    if (eq)
+      PIP_DUAL(i128, PipEqMask, *eq);
+    else
+      PIP_DUAL(i128, PipNoEq, PipNoEq{});
+  } else {
+    if (eq)
+      PIP_DUAL(i64, PipEqMask, *eq);
+    else
+      PIP_DUAL(i64, PipNoEq, PipNoEq{});
+  }
+#undef PIP_DUAL
   return hipGetLastError();
 }
 
@@ -1308,23 +1173,9 @@ extern "C" hipError_t pipk_launch_batch_load(PipJob *jobs, i64 *arena, const i64
                                              int count, hipStream_t stream) {
   if (count <= 0) return hipSuccess;
   if (lay.ebits == 128)
-    hipLaunchKernelGGL(pip_batch_load_kernel<i128>, dim3(count), dim3(256), 0, stream, jobs, arena, rows, lay, first, 0);
+    hipLaunchKernelGGL(pip_batch_load_kernel<i128>, dim3(count), dim3(256), 0, stream, jobs, arena, rows, lay, first);
   else
-    hipLaunchKernelGGL(pip_batch_load_kernel<i64>, dim3(count), dim3(256), 0, stream, jobs, arena, rows, lay, first, 0);
-  return hipGetLastError();
-}
-
-// the same from a plain system under a new big parameter (shift = +1 Maximize, -1 Urs_unknowns); lay.nparm == 1,
-// lay.bigparm == lay.nvar + 1 (the caller has checked), `rows` nvar + 1 columns a row
-extern "C" hipError_t pipk_launch_batch_load_shifted(PipJob *jobs, i64 *arena, const i64 *rows, PipBatchLayout lay, int shift,
-                                                     int first, int count, hipStream_t stream) {
-  if (count <= 0) return hipSuccess;
-  if (lay.nparm != 1 || lay.bigparm != lay.nvar + 1 || lay.W < lay.nvar + 2 || (shift != 1 && shift != -1)) return hipErrorInvalidValue;
-  lay.pad = 0;
-  if (lay.ebits == 128)
-    hipLaunchKernelGGL((pip_batch_load_kernel<i128, true>), dim3(count), dim3(256), 0, stream, jobs, arena, rows, lay, first, shift);
-  else
-    hipLaunchKernelGGL((pip_batch_load_kernel<i64, true>), dim3(count), dim3(256), 0, stream, jobs, arena, rows, lay, first, shift);
+    hipLaunchKernelGGL(pip_batch_load_kernel<i64>, dim3(count), dim3(256), 0, stream, jobs, arena, rows, lay, first);
   return hipGetLastError();
 }
 

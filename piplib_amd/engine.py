@@ -318,9 +318,8 @@ class Batch:
                                               C.c_void_p(self.cuts.data_ptr()), C.c_void_p(self.x_num.data_ptr()),
                                               C.c_void_p(self.x_den.data_ptr()), st))
 
-    def _dual_out(self):
-        B, ni = self.desc.batch, self.desc.ni
-        shape = (B, ni) + ((2,) if self.entier_bits == 128 else ())
+    def _dual_out(self, nrows):
+        shape = (self.desc.batch, nrows) + ((2,) if self.entier_bits == 128 else ())
         return (self.torch.empty(shape, dtype=self.torch.int64, device=self.dev),
                 self.torch.empty(shape, dtype=self.torch.int64, device=self.dev))
 
@@ -330,16 +329,7 @@ class Batch:
         (0, 0) throughout for a tableau without a solution.  Does not synchronise."""
         if self.rows is None:
             raise RuntimeError("Batch.dual needs the rows the batch was loaded from: use dual_part() with load_parts()")
-        L = lib()
-        if not hasattr(L, "pipamd_batch_dual"):
-            raise RuntimeError("libpipamd has no pipamd_batch_dual: rebuild the library")
-        L.pipamd_batch_dual.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BatchDesc)] + [C.c_void_p] * 4
-        num, den = self._dual_out()
-        st = C.c_void_p(stream) if stream is not None else self._stream()
-        _check(L.pipamd_batch_dual(self.e._h, C.c_void_p(self.ws.data_ptr()), C.byref(self.desc),
-                                   C.c_void_p(self.rows.data_ptr()), C.c_void_p(num.data_ptr()),
-                                   C.c_void_p(den.data_ptr()), st))
-        return num, den
+        return self.dual_part(self.rows, 0, stream)
 
     def dual_part(self, rows, first, stream=None, out=None):
         """pipamd_batch_dual_part for the tableaux first .. first + len(rows) - 1, loaded from the resident array `rows`
@@ -351,7 +341,7 @@ class Batch:
             raise RuntimeError("libpipamd has no pipamd_batch_dual_part: rebuild the library")
         L.pipamd_batch_dual_part.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BatchDesc), C.c_void_p, C.c_int, C.c_int,
                                              C.c_void_p, C.c_void_p, C.c_void_p]
-        num, den = out if out is not None else self._dual_out()
+        num, den = out if out is not None else self._dual_out(self.desc.ni)
         st = C.c_void_p(stream) if stream is not None else self._stream()
         _check(L.pipamd_batch_dual_part(self.e._h, C.c_void_p(self.ws.data_ptr()), C.byref(self.desc),
                                         C.c_void_p(rows.data_ptr()), int(first), int(rows.shape[0]),
@@ -370,11 +360,6 @@ class Batch:
                                                    C.byref(self.system), C.c_void_p(rows.data_ptr()), int(first),
                                                    int(rows.shape[0]), st))
 
-    def _dual_system_out(self):
-        shape = (self.desc.batch, self.system.nrows) + ((2,) if self.entier_bits == 128 else ())
-        return (self.torch.empty(shape, dtype=self.torch.int64, device=self.dev),
-                self.torch.empty(shape, dtype=self.torch.int64, device=self.dev))
-
     def dual_system(self, stream=None):
         """pipamd_batch_dual_system after a solve with T_DUAL of a Batch(system=True): device tensors (dual_num, dual_den)
         of shape (batch, nrows) -- plus a trailing 2 for 128-bit entries --, one reduced pair per row of the system, an
@@ -387,7 +372,7 @@ class Batch:
         """pipamd_batch_dual_system_part for the tableaux first .. first + len(rows) - 1, loaded from the resident array
         `rows`; returns (dual_num, dual_den) of the whole batch's shape (pass the pair back as `out` to fill it part by part)."""
         assert self.system is not None and rows.is_cuda and rows.is_contiguous()
-        num, den = out if out is not None else self._dual_system_out()
+        num, den = out if out is not None else self._dual_out(self.system.nrows)
         st = C.c_void_p(stream) if stream is not None else self._stream()
         _check(lib().pipamd_batch_dual_system_part(self.e._h, C.c_void_p(self.ws.data_ptr()), C.byref(self.desc),
                                                    C.byref(self.system), C.c_void_p(rows.data_ptr()), int(first),

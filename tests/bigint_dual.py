@@ -86,6 +86,7 @@ CRAFTED = [[1, 0, 0, -1], [A24 + 1, 1, 0, -2], [A24, 0, 1, -3], [1 << 31, 2, 1, 
 FAMILIES = {"lexmin12": ("lexmin_batch", (11, 64, 7, 12), None, 64),
             "lexmin64": ("lexmin_batch", (13, 32, 10, 64), None, 64),
             "lexmin65": ("lexmin_batch", (14, 32, 10, 65), None, 64),
+            "lexmin130": ("lexmin_batch", (16, 32, 10, 130), None, 64),
             "dense20": ("dense_batch", (15, 32, 8, 20), None, 128),
             "bulk16": ("lexmin_batch", (17, 2048, 15, 16), tuple(range(64)) + tuple(range(1984, 2048)), 64)}
 _cache = {}

@@ -6,8 +6,8 @@ import bigint_dual as bd
 import bigint_pip as bp
 
 # family: (solutions, tableaux with a non-zero dual value, max_bits over the compared tableaux)
-FIGURES = {"lexmin12": (64, 27, 25), "lexmin64": (32, 28, 43), "lexmin65": (32, 29, 40), "dense20": (32, 27, 90),
-           "bulk16": (128, 13, 21)}
+FIGURES = {"lexmin12": (64, 27, 25), "lexmin64": (32, 28, 43), "lexmin65": (32, 29, 40), "lexmin130": (32, 28, 37),
+           "dense20": (32, 27, 90), "bulk16": (128, 13, 21)}
 
 
 @pytest.mark.parametrize("name", sorted(FIGURES))

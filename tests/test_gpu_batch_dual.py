@@ -106,7 +106,8 @@ def test_smallest_shape(engines, bits):
 
 @pytest.mark.parametrize("name", ["lexmin64", "lexmin65"])
 def test_both_forms_of_the_sort(engines, name):
-    """64 inequalities: the last shape with a row per lane; 65: the first with the strided scan"""
+    """64 inequalities: the last shape with a row per lane; 65: the first with the strided scan -- and the first whose
+    values take a second 64-row word of the kernel's last step"""
     from piplib_amd import engine as eng
     on, off = engines
     rows, idx, res = bd.family(name, 64)
@@ -115,6 +116,37 @@ def test_both_forms_of_the_sort(engines, name):
     assert len(idx) == 32
     _against_bigint(b, pairs, res, idx)
     _against_host(off, b, pairs, rows, range(8), 64)
+
+
+def test_a_third_word_of_rows(engines):
+    """130 inequalities: the kernel's last step, 64 input rows a turn, takes a third turn (65, the second, is lexmin65
+    above); still the LDS form of the sort"""
+    from piplib_amd import engine as eng
+    on, off = engines
+    rows, idx, res = bd.family("lexmin130", 64)
+    assert rows.shape[1:] == (130, 11) and len(idx) == 32
+    b = _solve(on, rows, eng.T_DUAL)
+    pairs = _pairs(b, b.dual())
+    _against_bigint(b, pairs, res, idx)
+    _against_host(off, b, pairs, rows, range(4), 64)
+
+
+def test_pairs_are_not_reduced(engines):
+    """pipamd_batch_dual hands out solution_dual's pairs as they are (pipamd_batch_dual_system reduces them): the
+    tableaux of lexmin12 whose dual, by bigint_dual alone, has a pair with a non-zero numerator and gcd above 1"""
+    import math
+    from piplib_amd import engine as eng
+    on, _ = engines
+    rows, idx, res = bd.family("lexmin12", 64)
+    pick = [k for k in idx if res[k][0] == bp.ST_SOLUTION and any(n and math.gcd(n, d) > 1 for n, d in res[k][2])]
+    assert 3 in pick and (68, 328) in res[3][2]  # (chosen on the CPU: 17 / 82 unreduced)
+    sub = np.ascontiguousarray(rows[pick])
+    b = _solve(on, sub, eng.T_DUAL)
+    pairs = _pairs(b, b.dual())
+    for k, got in zip(pick, pairs):
+        assert res[k][3].exact
+        assert got == res[k][2], (k, got, res[k][2])
+        assert got != [(n // math.gcd(n, d), d // math.gcd(n, d)) for n, d in res[k][2]], k
 
 
 @pytest.mark.parametrize("bits", [64, 128])

@@ -11,7 +11,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 BATCH = 160
-FAMILIES = {(5, 8): (31, dict(nnz=3, cmax=3, x0max=5)), (62, 32): (7094, {})}
+FAMILIES = {(5, 8): (31, dict(nnz=3, cmax=3, x0max=5)), (62, 32): (7094, {}), (131, 8): (44, dict(nnz=3, cmax=4, x0max=6))}
 
 
 @functools.lru_cache(maxsize=None)
@@ -80,6 +80,8 @@ def _ints(t, bits):
     (5, 8, 0, 0, 64), (5, 8, 1, 0, 64), (62, 32, 0, 0, 64), (62, 32, 1, 0, 64),
     (5, 8, 1, 1, 64),    # tableaux without a solution among them: (0, 0)
     (5, 8, 1, 0, 128),   # (low, high) pairs
+    # 133 tableau columns: the load kernel's eight-columns-a-lane instantiation, in both entry widths
+    (131, 8, 0, 0, 64), (131, 8, 1, 0, 64), (131, 8, 0, 0, 128),
 ])
 def test_batch_shift(nvar, ni, box, nil, bits, shift, nq):
     from piplib_amd import engine as eng

@@ -1,5 +1,5 @@
 """-m gpu: Batch(system=True) -- pip_solve's plain system for the batch layer (pipamd_batch_load_system,
-pipamd_batch_dual_system; pip_batch_load_system_kernel and pip_batch_dual_system_kernel, csrc/pip_kernels.hip).
+pipamd_batch_dual_system; pip_batch_load_system_kernel and pip_batch_dual_kernel<T, PipEqMask>, csrc/pip_kernels.hip).
 
 Authorities: tests/system_model.py (Python ints; tests/test_system_model.py holds it to the reference's pip_solve), the CPU
 oracle on the model's tableau (status, pivots, solution), the same tableau loaded with pipamd_batch_load (cuts and the
@@ -201,6 +201,21 @@ def test_without_equalities_as_the_existing_loads(shift, nq):
     if shift:
         _same(b, c, ("x_num", "x_den"))
     assert (b.status == 1).sum().item() >= 6
+
+
+def test_dual_without_equalities_as_the_plain_dual():
+    """neq == 0, shift 0, rational with dual: dual_system() is dual() of the same rows loaded with pipamd_batch_load,
+    each pair reduced -- one comparison over the whole batch"""
+    import system_model as sy
+    from piplib_amd import engine as eng
+    rows, nvar, _ = _family("s12", 1)
+    b = _solve_system(rows, nvar, (), 0, 0, 0, 1)
+    c = eng.Batch(_engine(), rows, nvar, 0, tflags=eng.T_DUAL)
+    c.load()
+    c = _finish(c, lambda c: c.dual())
+    _same(b, c)
+    assert (b.status == 1).sum().item() >= 6
+    assert _duals(b, 64) == [[list(sy.reduce_pair(n, d)) for n, d in t] for t in _duals(c, 64)]
 
 
 @pytest.mark.parametrize("mode", list(MODES))

@@ -1,13 +1,14 @@
-"""The time of the batch loads: pipamd_batch_load_system against pipamd_batch_load_shifted on the same rows.
+"""The time of the batch loads from plain rows: pipamd_batch_load_shifted and pipamd_batch_load_system on the same rows.
 
     python tools/load_system_rate.py [--batch N] [--reps R]
 
 Input: N (default 10,000) plain systems of 126 unknowns and 64 rows (synth.lexmin_batch, the shape of
 tools/lexmax_rate.py), loaded under Maximize (shift = +1, 128 columns).  Four legs take turns in one process, R
 (default 5) rounds after a warm-up round: the shifted load, the system load without equalities and without tab_simplify
-(the same bytes), the system load with tab_simplify, and the system load with 8 equalities (72 tableau rows).  The tableau
-of the second leg is first held to the first one's, bit for bit in what a solve leaves.  Times are device events round
-the load alone.  One JSON line: per leg the median, the smallest and the largest time in microseconds.
+(the same bytes and, since the shifted entry forwards to the system load, the same kernel: the two legs differ in the
+host entry alone), the system load with tab_simplify, and the system load with 8 equalities (72 tableau rows).  The
+tableau of the second leg is first held to the first one's, bit for bit in what a solve leaves.  Times are device events
+round the load alone.  One JSON line: per leg the median, the smallest and the largest time in microseconds.
 A manual tool, not a test."""
 import argparse
 import json
