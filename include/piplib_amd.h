@@ -47,7 +47,9 @@ extern "C" {
  * flags per problem --, and the device-resident traiter() computes the dual (PIPAMD_T_DUAL) for every shape of its box,
  * not only up to 64 inequalities; pipamd_batch_dual / pipamd_batch_dual_part -- the dual values of a rational batch of
  * layer 1; pipamd_batch_load_system / pipamd_batch_dual_system and their _part forms -- layer 1 from the plain system
- * pip_solve takes (equalities, tab_simplify, the dual under Maximize / Urs_unknowns and of equalities). */
+ * pip_solve takes (equalities, tab_simplify, the dual under Maximize / Urs_unknowns and of equalities);
+ * pipamd_batch_load_matrices / pipamd_batch_dual_matrices and their _part forms -- the same from PolyLib matrices, each
+ * system with its own row count and its equalities where its marker column has them (PIPAMD_ST_BADINPUT). */
 #define PIPAMD_VERSION 500
 
 /* ---- error codes (return values) ---- */
@@ -85,6 +87,7 @@ extern "C" {
 #define PIPAMD_ST_RANGE 7        /* entries too large for the exact fast pivot-column choice */
 #define PIPAMD_ST_INTERNAL 8
 #define PIPAMD_ST_MAXCOL 9       /* "Too many variables" (integrer.c:324) */
+#define PIPAMD_ST_BADINPUT 10    /* a system the load could not take (see pipamd_batch_load_matrices) */
 
 /* ---- row flags (reference tab.h:55-62) ---- */
 #define PIPAMD_F_UNIT 1
@@ -276,7 +279,7 @@ int pipamd_batch_dual_part(pipamd_engine *e, const void *d_workspace, const pipa
  * (sol_vector_edit with flags 0, sol.c:475-500; pip_quast_equalities_dual, piplib.c:651-690).  `d_rows` holds the caller's
  * PLAIN systems, batch x nrows x (nvar + 1) int64 (unknowns then constant: a PolyLib row without its marker column).  The
  * rows whose marker is 0 -- the equalities -- are named by ONE host list for the batch (same-shaped systems have them in
- * the same rows).  The descriptor `d` describes the tableau AS IT IS SOLVED, as for the shifted entries:
+ * the same rows; systems that are not shaped alike: pipamd_batch_load_matrices below).  The descriptor `d` describes the tableau AS IT IS SOLVED, as for the shifted entries:
  * d->ni == nrows + neq; shift == 0: nparm == 0, bigparm == -1; shift == +-1: nparm == 1, bigparm == nvar + 1.
  * pipamd_batch_load_system: input row r becomes tableau row r + (equalities before r), written as tab.c:342-377 writes it,
  *     shift == 0:  a_j | c        PIPAMD_SHIFT_MAX:  -a_j | c | +sum a_j        PIPAMD_SHIFT_URS:  a_j | c | -sum a_j
@@ -317,6 +320,49 @@ int pipamd_batch_dual_system(pipamd_engine *e, const void *d_workspace, const pi
 int pipamd_batch_dual_system_part(pipamd_engine *e, const void *d_workspace, const pipamd_batch_desc *d,
                                   const pipamd_system *sys, const int64_t *d_rows, int first, int count, int64_t *d_dual_num,
                                   int64_t *d_dual_den, void *stream);
+
+/* The same for systems that are NOT shaped alike: what pip_solve literally takes, a PolyLib matrix per system, each with
+ * its own number of rows and its equalities wherever they fell.  `d_rows` is batch x max_rows x (nvar + 2) int64: system
+ * b has max_rows rows of room, of which the first nrows_b = d_nrows[b] are its rows, marker | a_0 .. a_(nvar-1) | c.  A row
+ * whose marker is 0 is an equality, any other marker an inequality (piplib.c:769, tab.c:380); rows at and beyond nrows_b
+ * are never read.  Row counts and markers stay on the device with the rows: no host list, no class of systems per call.
+ * The descriptor describes the tableau as it is solved, as for the system entries (shift == 0: nparm == 0,
+ * bigparm == -1; shift == +-1: nparm == 1, bigparm == nvar + 1), except that d->ni is ROOM, not a row count: system b
+ * becomes a tableau of ni_b = nrows_b + (its equalities) rows and needs ni_b <= d->ni; the spare rows behind it are
+ * cap_cuts plus d->ni - ni_b.
+ * pipamd_batch_load_matrices: each system's tableau, row tables and job header (ni = ni_b) are exactly what
+ * pipamd_batch_load_system builds for that system alone -- the row order, the shift, the negated twin of an equality,
+ * tab_simplify with `simplify` --, spare slots cleared from slot ni_b on; PIPAMD_T_ROWS_STAY is ignored.  A system with
+ * nrows_b < 1, nrows_b > max_rows or ni_b > d->ni is BAD: the load finishes it itself -- an empty tableau (ni = 0) with
+ * status PIPAMD_ST_BADINPUT, nothing outside its own max_rows x (nvar + 2) room read.  pipamd_batch_solve skips it (it
+ * is not PIPAMD_ST_RUN) and solves the other tableaux as if it were not there; the result entries give it zeros.  The
+ * solve and the result entries are the existing ones.
+ * pipamd_batch_dual_matrices: as pipamd_batch_dual_system, callable where that is; `d_rows` and `d_nrows` are the arrays
+ * the batch was loaded from, unchanged.  d_dual_num[b][r], d_dual_den[b][r], r < max_rows: for r < nrows_b the pair
+ * pipamd_batch_dual_system computes for that system alone (an equality: u if u != 0, else -v), (0, 0) for r >= nrows_b,
+ * and (0, 0) throughout for a tableau that is not PIPAMD_ST_SOLUTION.
+ * _part: the tableaux first .. first + count - 1; `d_rows` and `d_nrows` hold the `count` systems of the part, the dual
+ * arrays are the whole batch's.
+ * PIPAMD_E_INVALID, before any HIP call: a null engine, workspace, descriptor, `m` or rows pointer; shift not 0, 1 or
+ * -1; a descriptor that does not match the shift; max_rows < 1 or d->ni < 1; reserved != 0; simplify not 0 or 1, or 1
+ * without PIPAMD_T_INT; first / count outside the batch; for the dual entries a null output array, no PIPAMD_T_DUAL, or
+ * PIPAMD_T_INT.  PIPAMD_E_TOOLARGE: max_rows above the engine's 16,000 rows; for the dual entries d->ni above 8,192. */
+typedef struct pipamd_matrices {
+  int32_t max_rows;       /* rows of room per system in d_rows (>= 1, <= the engine's 16,000) */
+  int32_t shift;          /* 0, PIPAMD_SHIFT_MAX or PIPAMD_SHIFT_URS */
+  int32_t simplify;       /* as pipamd_system.simplify; needs PIPAMD_T_INT */
+  int32_t reserved;       /* 0 */
+  const int32_t *d_nrows; /* DEVICE array, one int32 per system: its row count.  NULL: every system has max_rows rows */
+} pipamd_matrices;        /* 24 bytes, offsets 0 4 8 12 16 */
+int pipamd_batch_load_matrices(pipamd_engine *e, void *d_workspace, const pipamd_batch_desc *d, const pipamd_matrices *m,
+                               const int64_t *d_rows, void *stream);
+int pipamd_batch_load_matrices_part(pipamd_engine *e, void *d_workspace, const pipamd_batch_desc *d, const pipamd_matrices *m,
+                                    const int64_t *d_rows, int first, int count, void *stream);
+int pipamd_batch_dual_matrices(pipamd_engine *e, const void *d_workspace, const pipamd_batch_desc *d, const pipamd_matrices *m,
+                               const int64_t *d_rows, int64_t *d_dual_num, int64_t *d_dual_den, void *stream);
+int pipamd_batch_dual_matrices_part(pipamd_engine *e, const void *d_workspace, const pipamd_batch_desc *d,
+                                    const pipamd_matrices *m, const int64_t *d_rows, int first, int count, int64_t *d_dual_num,
+                                    int64_t *d_dual_den, void *stream);
 
 /* Batch totals, device memory, 4 x uint64: [0] pivots (calls of pivoter), [1] Gomory cuts,
  * [2] rows rewritten by pivots (rows whose pivot-column entry is zero and that are already

@@ -745,13 +745,14 @@ static int shifted_check(const char *who, const void *e, const void *d_ws, const
 }
 
 // the load from a plain system whose description has been checked (`eq`: its equalities as a mask)
+// (`mk` instead: the systems carry their markers and row counts, pipamd_batch_load_matrices)
 static int load_system(const char *who, pipamd_engine *e, void *d_ws, const pipamd_batch_desc *d, const pipamd_system *sys,
-                       const PipEqMask *eq, const int64_t *d_rows, int first, int count, void *stream) {
+                       const PipEqMask *eq, const PipEqMarkers *mk, const int64_t *d_rows, int first, int count, void *stream) {
   BatchView v;
   int rc = batch_view(who, e, d_ws, d, first, count, &v);
   if (rc) return rc;
   HIPCHK(pipk_launch_batch_load_system(v.jobs, v.arena, (const long long *)d_rows, v.lay, sys->shift, sys->simplify, sys->nrows,
-                                       eq, first, count, (hipStream_t)stream));
+                                       eq, mk, first, count, (hipStream_t)stream));
   return PIPAMD_OK;
 }
 
@@ -766,7 +767,7 @@ extern "C" int pipamd_batch_load_shifted_part(pipamd_engine *e, void *d_ws, cons
   }
   const pipamd_system sys = {d->ni, 0, nullptr, shift, 0};
   const PipEqMask eq = {};
-  return load_system("batch_load_shifted", e, d_ws, d, &sys, &eq, d_rows, first, count, stream);
+  return load_system("batch_load_shifted", e, d_ws, d, &sys, &eq, nullptr, d_rows, first, count, stream);
 }
 
 extern "C" int pipamd_batch_load_shifted(pipamd_engine *e, void *d_ws, const pipamd_batch_desc *d, const int64_t *d_rows, int shift,
@@ -808,15 +809,16 @@ static int dual_check(const char *who, const pipamd_batch_desc *d, const void *d
   return PIPAMD_OK;
 }
 
-// the launch of either dual entry, its arguments checked; eq == nullptr: the plain one (nrows == d->ni, pairs not reduced)
+// the launch of a dual entry, its arguments checked; eq == nullptr: the plain one (nrows == d->ni, pairs not reduced);
+// `mk` instead: pipamd_batch_dual_matrices
 static int dual_launch(const char *who, pipamd_engine *e, const void *d_ws, const pipamd_batch_desc *d, int nrows,
-                       const PipEqMask *eq, const int64_t *d_rows, int first, int count, int64_t *d_dual_num,
-                       int64_t *d_dual_den, void *stream) {
+                       const PipEqMask *eq, const PipEqMarkers *mk, const int64_t *d_rows, int first, int count,
+                       int64_t *d_dual_num, int64_t *d_dual_den, void *stream) {
   BatchView v;
   int rc = batch_view(who, e, d_ws, d, first, count, &v);
   if (rc) return rc;
-  HIPCHK(pipk_launch_batch_dual(v.jobs, v.arena, (const long long *)d_rows, v.lay, nrows, eq, first, count, (void *)d_dual_num,
-                                (void *)d_dual_den, (hipStream_t)stream));
+  HIPCHK(pipk_launch_batch_dual(v.jobs, v.arena, (const long long *)d_rows, v.lay, nrows, eq, mk, first, count,
+                                (void *)d_dual_num, (void *)d_dual_den, (hipStream_t)stream));
   return PIPAMD_OK;
 }
 
@@ -828,7 +830,7 @@ extern "C" int pipamd_batch_dual_part(pipamd_engine *e, const void *d_ws, const 
     pipamd_set_error("batch_dual: nparm must be 0 and bigparm -1 (the batch layer finishes only such batches on its own)");
     return PIPAMD_E_INVALID;
   }
-  return dual_launch("batch_dual", e, d_ws, d, d->ni, nullptr, d_rows, first, count, d_dual_num, d_dual_den, stream);
+  return dual_launch("batch_dual", e, d_ws, d, d->ni, nullptr, nullptr, d_rows, first, count, d_dual_num, d_dual_den, stream);
 }
 
 extern "C" int pipamd_batch_dual(pipamd_engine *e, const void *d_ws, const pipamd_batch_desc *d, const int64_t *d_rows,
@@ -839,21 +841,43 @@ extern "C" int pipamd_batch_dual(pipamd_engine *e, const void *d_ws, const pipam
 // pip_solve's plain system for the batch layer (header comment: include/piplib_amd.h): equalities, tab_simplify and the
 // dual as pip_solve hands it out.  Everything is checked before the first HIP call, the caller's equality list is read
 // into a mask that travels with the launch, and nothing here waits for the stream.
-static int system_check(const char *who, const void *e, const void *d_ws, const pipamd_batch_desc *d, const pipamd_system *sys,
-                        const void *d_rows, PipEqMask *eq) {
-  if (!e || !d_ws || !d || !sys || !d_rows) {
+// What the system and the matrices entries refuse alike: null pointers (`desc`: the system or matrices description), the
+// shift and the descriptor against it ...
+static int plain_check(const char *who, const void *e, const void *d_ws, const pipamd_batch_desc *d, const void *desc,
+                       const void *d_rows, int shift) {
+  if (!e || !d_ws || !d || !desc || !d_rows) {
     pipamd_set_error("%s: null engine, workspace, descriptor, system or rows pointer", who);
     return PIPAMD_E_INVALID;
   }
-  if (sys->shift != 0 && sys->shift != PIPAMD_SHIFT_MAX && sys->shift != PIPAMD_SHIFT_URS) {
-    pipamd_set_error("%s: shift must be 0, PIPAMD_SHIFT_MAX (1) or PIPAMD_SHIFT_URS (-1), not %d", who, sys->shift);
+  if (shift != 0 && shift != PIPAMD_SHIFT_MAX && shift != PIPAMD_SHIFT_URS) {
+    pipamd_set_error("%s: shift must be 0, PIPAMD_SHIFT_MAX (1) or PIPAMD_SHIFT_URS (-1), not %d", who, shift);
     return PIPAMD_E_INVALID;
   }
-  if (sys->shift ? (d->nparm != 1 || d->bigparm != d->nvar + 1) : (d->nparm != 0 || d->bigparm != -1)) {
+  if (shift ? (d->nparm != 1 || d->bigparm != d->nvar + 1) : (d->nparm != 0 || d->bigparm != -1)) {
     pipamd_set_error("%s: the descriptor must describe the tableau as it is solved (shift 0: nparm == 0, bigparm == -1; "
                      "otherwise nparm == 1, bigparm == nvar + 1)", who);
     return PIPAMD_E_INVALID;
   }
+  return PIPAMD_OK;
+}
+
+// ... and simplify
+static int simplify_check(const char *who, const pipamd_batch_desc *d, int simplify) {
+  if (simplify != 0 && simplify != 1) {
+    pipamd_set_error("%s: simplify must be 0 or 1, not %d", who, simplify);
+    return PIPAMD_E_INVALID;
+  }
+  if (simplify && !(d->tflags & PIPAMD_T_INT)) {
+    pipamd_set_error("%s: simplify without PIPAMD_T_INT (pip_solve simplifies integer problems only)", who);
+    return PIPAMD_E_INVALID;
+  }
+  return PIPAMD_OK;
+}
+
+static int system_check(const char *who, const void *e, const void *d_ws, const pipamd_batch_desc *d, const pipamd_system *sys,
+                        const void *d_rows, PipEqMask *eq) {
+  int rc = plain_check(who, e, d_ws, d, sys, d_rows, sys ? sys->shift : 0);
+  if (rc) return rc;
   if (sys->nrows < 0 || sys->neq < 0 || sys->neq > sys->nrows || d->ni != sys->nrows + sys->neq) {
     pipamd_set_error("%s: %d rows with %d equalities do not make the descriptor's %d inequalities", who, sys->nrows, sys->neq,
                      d->ni);
@@ -867,14 +891,8 @@ static int system_check(const char *who, const void *e, const void *d_ws, const 
     pipamd_set_error("%s: %d equalities and no list of them", who, sys->neq);
     return PIPAMD_E_INVALID;
   }
-  if (sys->simplify != 0 && sys->simplify != 1) {
-    pipamd_set_error("%s: simplify must be 0 or 1, not %d", who, sys->simplify);
-    return PIPAMD_E_INVALID;
-  }
-  if (sys->simplify && !(d->tflags & PIPAMD_T_INT)) {
-    pipamd_set_error("%s: simplify without PIPAMD_T_INT (pip_solve simplifies integer problems only)", who);
-    return PIPAMD_E_INVALID;
-  }
+  rc = simplify_check(who, d, sys->simplify);
+  if (rc) return rc;
   memset(eq, 0, sizeof *eq);
   for (int i = 0; i < sys->neq; i++) {
     const int r = sys->eq_rows[i];
@@ -892,7 +910,7 @@ extern "C" int pipamd_batch_load_system_part(pipamd_engine *e, void *d_ws, const
   PipEqMask eq;
   int rc = system_check("batch_load_system", e, d_ws, d, sys, d_rows, &eq);
   if (rc) return rc;
-  return load_system("batch_load_system", e, d_ws, d, sys, &eq, d_rows, first, count, stream);
+  return load_system("batch_load_system", e, d_ws, d, sys, &eq, nullptr, d_rows, first, count, stream);
 }
 
 extern "C" int pipamd_batch_load_system(pipamd_engine *e, void *d_ws, const pipamd_batch_desc *d, const pipamd_system *sys,
@@ -908,12 +926,66 @@ extern "C" int pipamd_batch_dual_system_part(pipamd_engine *e, const void *d_ws,
   if (rc) return rc;
   rc = dual_check("batch_dual_system", d, d_rows, d_dual_num, d_dual_den);
   if (rc) return rc;
-  return dual_launch("batch_dual_system", e, d_ws, d, sys->nrows, &eq, d_rows, first, count, d_dual_num, d_dual_den, stream);
+  return dual_launch("batch_dual_system", e, d_ws, d, sys->nrows, &eq, nullptr, d_rows, first, count, d_dual_num, d_dual_den,
+                     stream);
 }
 
 extern "C" int pipamd_batch_dual_system(pipamd_engine *e, const void *d_ws, const pipamd_batch_desc *d, const pipamd_system *sys,
                                         const int64_t *d_rows, int64_t *d_dual_num, int64_t *d_dual_den, void *stream) {
   return pipamd_batch_dual_system_part(e, d_ws, d, sys, d_rows, 0, d ? d->batch : 0, d_dual_num, d_dual_den, stream);
+}
+
+// PolyLib matrices with a row count and markers per system (header comment: include/piplib_amd.h).  Which rows are
+// equalities and how many rows a system has is found on the device; what is left to refuse here is the description.
+static int matrices_check(const char *who, const void *e, const void *d_ws, const pipamd_batch_desc *d, const pipamd_matrices *m,
+                          const void *d_rows, PipEqMarkers *mk) {
+  int rc = plain_check(who, e, d_ws, d, m, d_rows, m ? m->shift : 0);
+  if (rc) return rc;
+  if (m->max_rows < 1 || d->ni < 1 || m->reserved != 0) {
+    pipamd_set_error("%s: max_rows (%d) and the descriptor's ni (%d) must be at least 1, reserved (%d) must be 0", who, m->max_rows,
+                     d->ni, m->reserved);
+    return PIPAMD_E_INVALID;
+  }
+  if (m->max_rows > PIPAMD_SMAX) {
+    pipamd_set_error("%s: %d rows of room per system, the engine holds at most %d", who, m->max_rows, PIPAMD_SMAX);
+    return PIPAMD_E_TOOLARGE;
+  }
+  rc = simplify_check(who, d, m->simplify);
+  if (rc) return rc;
+  mk->nrows = m->d_nrows;
+  mk->max_rows = m->max_rows;
+  return PIPAMD_OK;
+}
+
+extern "C" int pipamd_batch_load_matrices_part(pipamd_engine *e, void *d_ws, const pipamd_batch_desc *d, const pipamd_matrices *m,
+                                               const int64_t *d_rows, int first, int count, void *stream) {
+  PipEqMarkers mk;
+  int rc = matrices_check("batch_load_matrices", e, d_ws, d, m, d_rows, &mk);
+  if (rc) return rc;
+  const pipamd_system sys = {m->max_rows, 0, nullptr, m->shift, m->simplify};
+  return load_system("batch_load_matrices", e, d_ws, d, &sys, nullptr, &mk, d_rows, first, count, stream);
+}
+
+extern "C" int pipamd_batch_load_matrices(pipamd_engine *e, void *d_ws, const pipamd_batch_desc *d, const pipamd_matrices *m,
+                                          const int64_t *d_rows, void *stream) {
+  return pipamd_batch_load_matrices_part(e, d_ws, d, m, d_rows, 0, d ? d->batch : 0, stream);
+}
+
+extern "C" int pipamd_batch_dual_matrices_part(pipamd_engine *e, const void *d_ws, const pipamd_batch_desc *d,
+                                               const pipamd_matrices *m, const int64_t *d_rows, int first, int count,
+                                               int64_t *d_dual_num, int64_t *d_dual_den, void *stream) {
+  PipEqMarkers mk;
+  int rc = matrices_check("batch_dual_matrices", e, d_ws, d, m, d_rows, &mk);
+  if (rc) return rc;
+  rc = dual_check("batch_dual_matrices", d, d_rows, d_dual_num, d_dual_den);
+  if (rc) return rc;
+  return dual_launch("batch_dual_matrices", e, d_ws, d, m->max_rows, nullptr, &mk, d_rows, first, count, d_dual_num, d_dual_den,
+                     stream);
+}
+
+extern "C" int pipamd_batch_dual_matrices(pipamd_engine *e, const void *d_ws, const pipamd_batch_desc *d, const pipamd_matrices *m,
+                                          const int64_t *d_rows, int64_t *d_dual_num, int64_t *d_dual_den, void *stream) {
+  return pipamd_batch_dual_matrices_part(e, d_ws, d, m, d_rows, 0, d ? d->batch : 0, d_dual_num, d_dual_den, stream);
 }
 
 extern "C" int pipamd_batch_counters(pipamd_engine *e, const void *d_ws, const pipamd_batch_desc *d, uint64_t *d_out4,

@@ -66,6 +66,14 @@ typedef struct PipEqMask {
   uint64_t w[(PIPAMD_SMAX + 63) / 64];
 } PipEqMask;
 
+/* The same question answered on the device (pipamd_matrices): every system has max_rows rows of room, each row led by
+ * its PolyLib marker (0: an equality), and a row count of its own in `nrows` (a DEVICE array, one per system of the
+ * launch; NULL: max_rows each).  The kernels build a system's mask words in LDS from its marker column. */
+typedef struct PipEqMarkers {
+  const int32_t *nrows;
+  int32_t max_rows;
+} PipEqMarkers;
+
 #ifdef __HIPCC__
 #define PIP_HD __host__ __device__
 #else

@@ -156,14 +156,14 @@ __global__ __launch_bounds__(64) void pip_det_replay_lanes_kernel(PipJob *jobs, 
 
 // the row tables of a block: unit rows, unknown rows, empty slots
 template <class T>
-__device__ __forceinline__ void load_row_tables(i64 *blk, const PipBatchLayout &lay, int tid) {
+__device__ __forceinline__ void load_row_tables(i64 *blk, const PipBatchLayout &lay, int ni, int tid) {
   const auto [g_den, g_flag, g_ref] = pip_row_tables<T>(blk, lay.blk.L);
   for (int i = tid; i < lay.blk.L; i += blockDim.x) {
     if (i < lay.nvar) {
       g_flag[i] = PIPAMD_F_UNIT;
       g_ref[i] = i;
       g_den[i] = 1;
-    } else if (i < lay.nvar + lay.ni) {
+    } else if (i < lay.nvar + ni) {
       g_flag[i] = PIPAMD_F_UNKNOWN;
       g_ref[i] = i - lay.nvar;
       g_den[i] = 1;
@@ -186,21 +186,23 @@ __device__ __forceinline__ void load_clear_spare(T *vals, const PipBatchLayout &
   }
 }
 
-// the job header (one thread).  defer (PIPAMD_T_ROWS_STAY): the first pivot launch fetches the rows from `src` itself
+// the job header (one thread) of a tableau of `ni` rows that starts with `status`.  defer (PIPAMD_T_ROWS_STAY): the first
+// pivot launch fetches the rows from `src` itself
 template <class T>
-__device__ __forceinline__ void load_job_header(PipJob *J, int64_t base, const PipBatchLayout &lay, bool defer, const i64 *src) {
+__device__ __forceinline__ void load_job_header(PipJob *J, int64_t base, const PipBatchLayout &lay, int ni, int status, bool defer,
+                                                const i64 *src) {
   pip_job_place(J, base, lay.blk);
   J->nlog = 0;
   J->nvar = lay.nvar;
   J->nparm = lay.nparm;
-  J->ni = lay.ni;
+  J->ni = ni;
   J->bigparm = lay.bigparm;
   J->tflags = lay.tflags | PIPAMD_T_SORT | (defer ? PIPAMD_T_FRESHROWS : 0);
   J->src_rows = defer ? (int64_t)(uintptr_t)src : 0;
   J->home_sol_off = 0;
   J->S = lay.S;
   J->W = lay.W;
-  J->status = PIPAMD_ST_RUN;
+  J->status = status;
   J->aux = 0;
   J->npiv = 0;
   J->ncut = 0;
@@ -222,7 +224,7 @@ __global__ void pip_batch_load_kernel(PipJob *jobs, i64 *arena, const i64 *rows,
   const int ncol = lay.nvar + lay.nparm + 1;
   const int64_t base = lay.arena_off + (int64_t)b * lay.blk.words;
   T *vals = (T *)(arena + base + lay.blk.vals);
-  load_row_tables<T>(arena + base, lay, tid);
+  load_row_tables<T>(arena + base, lay, lay.ni, tid);
   const i64 *src = rows + (size_t)blockIdx.x * lay.ni * ncol;
   const bool defer = lay.pad != 0 && EW == 1;  // PIPAMD_T_ROWS_STAY: the first pivot launch fetches the rows itself
   if (!defer) {
@@ -240,7 +242,7 @@ __global__ void pip_batch_load_kernel(PipJob *jobs, i64 *arena, const i64 *rows,
     }
   }
   load_clear_spare(vals, lay, defer ? 0 : lay.ni, tid);
-  if (tid == 0) load_job_header<T>(&jobs[b], base, lay, defer, src);
+  if (tid == 0) load_job_header<T>(&jobs[b], base, lay, lay.ni, PIPAMD_ST_RUN, defer, src);
 }
 
 // ---------------------------------------------------------------- batch load from a plain system
@@ -280,25 +282,73 @@ __device__ __forceinline__ T sys_floor(T c, u64 g) {
   return c < 0 ? wneg((T)(i64)((uc + (g - 1)) / g)) : (T)(i64)(uc / g);
 }
 
-template <class T, int CPL>
+// Which rows are equalities, and how many rows a system has, is the kernel's EQ policy (pip_batch_dual_kernel below has
+// the same ones):
+//   PipEqMask: one mask and one row count for the batch, both from the launch (pipamd_batch_load_system, _shifted).
+//   PipEqMarkers (pipamd_batch_load_matrices): every system has max_rows rows of room, nvar + 2 words a row with the
+//     PolyLib marker first (0: an equality), and a row count of its own on the device.  The block builds the system's
+//     mask words in LDS from the marker column, a ballot per 64 rows, and its tableau has ni_b = rows + equalities rows
+//     of the lay.ni the layout has room for.  A system whose count is below 1 or above max_rows, or whose tableau does
+//     not fit, is finished here: no row of it is read, its tableau is empty and its status PIPAMD_ST_BADINPUT.
+//   PipNoEq (the dual kernel only): no equalities, nothing travels with the launch.
+struct PipNoEq {};
+__device__ __forceinline__ u64 eq_word(const PipEqMask &eq, const u64 *, int w) { return eq.w[w]; }
+__device__ __forceinline__ u64 eq_word(const PipEqMarkers &, const u64 *words, int w) { return words[w]; }
+__device__ __forceinline__ u64 eq_word(const PipNoEq &, const u64 *, int) { return 0; }
+
+// PipEqMarkers, by the NWAVE waves of a block: the mask words of system `sys` of the launch, whose rows start at `src`
+// (`srcrow` words a row), into `words` (LDS; room for the words of min(max_rows, room) rows).  Returns the system's row
+// count and, in ni_b, its tableau's; both 0 for a bad system.  Every thread of the block gets the same answer.
+template <int NWAVE>
+__device__ __forceinline__ int eq_from_markers(const PipEqMarkers &mk, int sys, const i64 *src, int srcrow, int room, u64 *words,
+                                               int &ni_b) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int n = __builtin_amdgcn_readfirstlane(mk.nrows ? mk.nrows[sys] : mk.max_rows);
+  if (n < 1 || n > mk.max_rows || n > room) n = 0;
+  const int nw = (n + 63) >> 6;
+  for (int q = wave; q < nw; q += NWAVE) {
+    const int r = 64 * q + lane;
+    const u64 word = ballot64(r < n && src[(size_t)r * srcrow] == 0);
+    if (lane == 0) words[q] = word;
+  }
+  __syncthreads();
+  int neq = 0;
+  for (int q = 0; q < nw; q++) neq += __popcll(words[q]);
+  if (n + neq > room) n = 0;
+  ni_b = n ? n + neq : 0;
+  return n;
+}
+
+template <class T, int CPL, class EQ>
 __global__ __launch_bounds__(256) void pip_batch_load_system_kernel(PipJob *jobs, i64 *arena, const i64 *rows, PipBatchLayout lay,
-                                                                    int first, int shift, int simplify, int nrows, PipEqMask eq) {
+                                                                    int first, int shift, int simplify, int nrows, EQ eq) {
   typedef typename ET<T>::U U;
+  constexpr bool MARKED = std::is_same<EQ, PipEqMarkers>::value;
+  constexpr int MK = MARKED ? 1 : 0;  // words of a source row before its unknowns
   const int b = first + blockIdx.x;  // `rows` holds the systems first, first + 1, ... of the batch
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int nvar = lay.nvar, srccol = nvar + 1, W = lay.W;
+  const int nvar = lay.nvar, srccol = nvar + 1, srcrow = srccol + MK, W = lay.W;
   const int64_t base = lay.arena_off + (int64_t)b * lay.blk.words;
   T *vals = (T *)(arena + base + lay.blk.vals);
-  load_row_tables<T>(arena + base, lay, tid);
-  const i64 *src = rows + (size_t)blockIdx.x * nrows * srccol;
+  int ni = lay.ni;  // rows of this tableau
+  const i64 *src;
+  const u64 *eqw = nullptr;
+  if constexpr (MARKED) {
+    __shared__ u64 words[(PIPAMD_SMAX + 63) / 64];
+    src = rows + (size_t)blockIdx.x * eq.max_rows * srcrow;
+    nrows = eq_from_markers<4>(eq, blockIdx.x, src, srcrow, lay.ni, words, ni);
+    eqw = words;
+  }
+  load_row_tables<T>(arena + base, lay, ni, tid);
+  if constexpr (!MARKED) src = rows + (size_t)blockIdx.x * nrows * srccol;
   int wcur = 0, before = 0;  // equalities among the rows below 64 * wcur
   for (int r = wave; r < nrows; r += 4) {
-    for (; wcur < (r >> 6); wcur++) before += __popcll(eq.w[wcur]);
-    const u64 word = eq.w[r >> 6];
+    for (; wcur < (r >> 6); wcur++) before += __popcll(eq_word(eq, eqw, wcur));
+    const u64 word = eq_word(eq, eqw, r >> 6);
     const int k = r + before + __popcll(word & ((1ull << (r & 63)) - 1));
     const bool twin = (word >> (r & 63)) & 1;
-    if (k + (int)twin >= lay.ni) break;  // (the host has held the list against ni)
-    const i64 *in = src + (size_t)r * srccol;
+    if (k + (int)twin >= ni) break;  // (the host has held the list against ni; the markers' count gave ni)
+    const i64 *in = src + (size_t)r * srcrow + MK;
     T v[CPL], sum = 0;
     u64 g = 0;
 #pragma unroll
@@ -345,8 +395,9 @@ __global__ __launch_bounds__(256) void pip_batch_load_system_kernel(PipJob *jobs
       if (twin) out[W + j] = y;
     }
   }
-  load_clear_spare(vals, lay, lay.ni, tid);
-  if (tid == 0) load_job_header<T>(&jobs[b], base, lay, false, nullptr);
+  load_clear_spare(vals, lay, ni, tid);
+  if (tid == 0)
+    load_job_header<T>(&jobs[b], base, lay, ni, MARKED && nrows == 0 ? PIPAMD_ST_BADINPUT : PIPAMD_ST_RUN, false, nullptr);
 }
 
 // sol_vector_edit (sol.c:435-512) with SOL_REMOVE and SOL_MAX / SOL_SHIFT for a batch solved under a big parameter
@@ -507,26 +558,40 @@ __device__ void dual_sort_pairs(float *key, u16 *ineq, int n, double smax, int l
 //   EQ == PipEqMask (pipamd_batch_dual_system, with or without a big parameter): the pair as pip_solve hands it out,
 //     reduced as sol_vector_edit with flags 0 reduces it (sol.c:475-500), and for an equality with the values u (its
 //     row) and v (the negated row) u if u != 0, else -v (piplib.c:670-688).
-struct PipNoEq {};
-__device__ __forceinline__ u64 dual_eq_word(const PipEqMask &eq, int w) { return eq.w[w]; }
-__device__ __forceinline__ u64 dual_eq_word(const PipNoEq &, int) { return 0; }
-
+//   EQ == PipEqMarkers (pipamd_batch_dual_matrices): the same pair, for systems of max_rows rows of room that carry
+//     their markers and a row count each (eq_from_markers above: the mask the load built, rebuilt from the same rows).
+//     The tableau at hand has ni_b = rows + equalities rows, which its header must agree with, and ni_b pairs are
+//     sorted; the LDS tables keep the room of lay.ni.  [batch][max_rows] pairs are written, (0, 0) from the system's
+//     row count on, and throughout for a bad system.
 template <class T, class EQ>
 __global__ __launch_bounds__(64) void pip_batch_dual_kernel(const PipJob *jobs, const i64 *arena, const i64 *rows,
                                                             PipBatchLayout lay, int first, int nrows, EQ eq, T *dual_num,
                                                             T *dual_den) {
-  constexpr bool SYSTEM = std::is_same<EQ, PipEqMask>::value;
+  constexpr bool SYSTEM = !std::is_same<EQ, PipNoEq>::value;
+  constexpr bool MARKED = std::is_same<EQ, PipEqMarkers>::value;
+  constexpr int MK = MARKED ? 1 : 0;  // words of a source row before its unknowns
   extern __shared__ __align__(16) unsigned char dual_lds[];
   const int lane = threadIdx.x;
   const int b = first + blockIdx.x;
-  const int nvar = lay.nvar, ni = lay.ni, srccol = lay.nvar + 1;
-  if (ni <= 0 || ni > PIP_DUAL_MAXNI || nrows <= 0 || nrows > ni) return;
+  const int nvar = lay.nvar, srccol = lay.nvar + 1, srcrow = srccol + MK;
+  const int nout = nrows;  // pairs written per system
+  int ni = lay.ni;         // rows of this tableau
+  if (ni <= 0 || ni > PIP_DUAL_MAXNI || nrows <= 0 || (!MARKED && nrows > ni)) return;
   float *key = (float *)dual_lds;          // [ni]; after the sort its room holds pos
   u16 *ineq = (u16 *)(dual_lds + 4 * (size_t)ni);  // [ni]
   u16 *pos = (u16 *)dual_lds;              // [ni]: logical row of each tableau row after the sort
 
   // 1. keys: a lane per column pair, four input rows in flight; an equality's key goes to both of its rows
-  const i64 *src = rows + (size_t)blockIdx.x * nrows * srccol;
+  const i64 *src;
+  const u64 *eqw = nullptr;
+  if constexpr (MARKED) {
+    __shared__ u64 words[PIP_DUAL_MAXNI / 64];
+    src = rows + (size_t)blockIdx.x * eq.max_rows * srcrow;
+    nrows = eq_from_markers<1>(eq, blockIdx.x, src, srcrow, lay.ni, words, ni);
+    eqw = words;
+  } else {
+    src = rows + (size_t)blockIdx.x * nrows * srccol;
+  }
   unsigned smaxw = 0;
   int k = 0;  // tableau row of the input row at hand
   for (int i0 = 0; i0 < nrows; i0 += 4) {
@@ -535,7 +600,7 @@ __global__ __launch_bounds__(64) void pip_batch_dual_kernel(const PipJob *jobs, 
 #pragma unroll
       for (int q = 0; q < 4; q++) {
         if (i0 + q >= nrows) break;
-        const i64 *r = src + (size_t)(i0 + q) * srccol;
+        const i64 *r = src + (size_t)(i0 + q) * srcrow + MK;
         const int a0 = dual_key_term(r[j]);
         const int a1 = j + 1 < nvar ? dual_key_term(r[j + 1]) : 0;
         const int a = a0 > a1 ? a0 : a1;
@@ -546,7 +611,7 @@ __global__ __launch_bounds__(64) void pip_batch_dual_kernel(const PipJob *jobs, 
     for (int q = 0; q < 4; q++) {
       if (i0 + q >= nrows) break;
       const unsigned szw = wave_minmax_u32<true>((unsigned)sz[q]);
-      const int twin = (int)((dual_eq_word(eq, (i0 + q) >> 6) >> ((i0 + q) & 63)) & 1);
+      const int twin = (int)((eq_word(eq, eqw, (i0 + q) >> 6) >> ((i0 + q) & 63)) & 1);
       if (lane <= twin && k + lane < ni) {
         key[k + lane] = (float)szw;
         ineq[k + lane] = (u16)(k + lane);
@@ -556,7 +621,8 @@ __global__ __launch_bounds__(64) void pip_batch_dual_kernel(const PipJob *jobs, 
     }
   }
   __syncthreads();
-  bool ok = k == ni;  // (the host has held the list against ni)
+  bool ok = k == ni;  // (the host has held the list against ni; the markers' count gave ni)
+  if constexpr (MARKED) ok = ok && nrows > 0;
 
   // 2. the sort, then pos[ineq[r]] = nvar + r (all ni rows are real at load time)
   if (ok) dual_sort_pairs(key, ineq, ni, (double)smaxw, lane);
@@ -598,12 +664,12 @@ __global__ __launch_bounds__(64) void pip_batch_dual_kernel(const PipJob *jobs, 
       den = 1;
   };
   int before = 0;  // equalities among the input rows below r0w
-  for (int r0w = 0; r0w < nrows; r0w += 64) {
-    const u64 word = dual_eq_word(eq, r0w >> 6);
+  for (int r0w = 0; r0w < nout; r0w += 64) {
+    const u64 word = (!MARKED || r0w < nrows) ? eq_word(eq, eqw, r0w >> 6) : 0;
     const int r = r0w + lane;
-    if (r < nrows) {
+    if (r < nout) {
       T num = 0, den = 0;
-      if (ok) {
+      if (ok && (!MARKED || r < nrows)) {
         const int t = r + before + __popcll(word & ((1ull << lane) - 1));
         const bool twin = (word >> lane) & 1;
         if (t + (int)twin < ni) {
@@ -620,30 +686,37 @@ __global__ __launch_bounds__(64) void pip_batch_dual_kernel(const PipJob *jobs, 
           }
         }
       }
-      dual_num[(size_t)b * nrows + r] = num;
-      dual_den[(size_t)b * nrows + r] = den;
+      dual_num[(size_t)b * nout + r] = num;
+      dual_den[(size_t)b * nout + r] = den;
     }
     before += __popcll(word);
   }
 }
 
-// eq == nullptr: pipamd_batch_dual (the caller has checked lay.nparm == 0); otherwise pipamd_batch_dual_system
+// mk != nullptr: pipamd_batch_dual_matrices (nrows is not looked at: mk->max_rows pairs a system); otherwise
+// eq == nullptr: pipamd_batch_dual (the caller has checked lay.nparm == 0), or pipamd_batch_dual_system
 extern "C" hipError_t pipk_launch_batch_dual(const PipJob *jobs, const i64 *arena, const i64 *rows, PipBatchLayout lay,
-                                             int nrows, const PipEqMask *eq, int first, int count, void *dual_num,
-                                             void *dual_den, hipStream_t stream) {
+                                             int nrows, const PipEqMask *eq, const PipEqMarkers *mk, int first, int count,
+                                             void *dual_num, void *dual_den, hipStream_t stream) {
+  if (mk) nrows = mk->max_rows;
   if (count <= 0 || lay.ni <= 0 || nrows <= 0) return hipSuccess;
-  if (lay.ni > PIP_DUAL_MAXNI || nrows > lay.ni || (!eq && (nrows != lay.ni || lay.nparm != 0))) return hipErrorInvalidValue;
+  if (lay.ni > PIP_DUAL_MAXNI || (!mk && nrows > lay.ni) || (!mk && !eq && (nrows != lay.ni || lay.nparm != 0)))
+    return hipErrorInvalidValue;
   const size_t shm = pipk_batch_dual_lds_bytes(lay.ni);
 #define PIP_DUAL(T, EQ, MASK)                                                                                          \
   hipLaunchKernelGGL((pip_batch_dual_kernel<T, EQ>), dim3(count), dim3(64), shm, stream, jobs, arena, rows, lay, first, \
                      nrows, MASK, (T *)dual_num, (T *)dual_den)
   if (lay.ebits == 128) {
-    if (eq)
+    if (mk)
+      PIP_DUAL(i128, PipEqMarkers, *mk);
+    else if (eq)
       PIP_DUAL(i128, PipEqMask, *eq);
     else
       PIP_DUAL(i128, PipNoEq, PipNoEq{});
   } else {
-    if (eq)
+    if (mk)
+      PIP_DUAL(i64, PipEqMarkers, *mk);
+    else if (eq)
       PIP_DUAL(i64, PipEqMask, *eq);
     else
       PIP_DUAL(i64, PipNoEq, PipNoEq{});
@@ -1180,18 +1253,26 @@ extern "C" hipError_t pipk_launch_batch_load(PipJob *jobs, i64 *arena, const i64
 }
 
 // the same from the caller's plain system: equalities expanded, shift 0 / +1 / -1, tab_simplify (the caller has held
-// the layout against the shift and the equality list against lay.ni)
+// the layout against the shift and the equality list against lay.ni).  mk != nullptr: the systems carry their markers
+// and row counts (pipamd_batch_load_matrices; nrows and eq are not looked at)
 extern "C" hipError_t pipk_launch_batch_load_system(PipJob *jobs, i64 *arena, const i64 *rows, PipBatchLayout lay, int shift,
-                                                    int simplify, int nrows, const PipEqMask *eq, int first, int count,
-                                                    hipStream_t stream) {
+                                                    int simplify, int nrows, const PipEqMask *eq, const PipEqMarkers *mk,
+                                                    int first, int count, hipStream_t stream) {
   if (count <= 0) return hipSuccess;
+  if (mk) nrows = mk->max_rows;
   if (shift < -1 || shift > 1 || lay.nparm != (shift ? 1 : 0) || (shift && lay.bigparm != lay.nvar + 1) ||
-      lay.W < lay.nvar + lay.nparm + 1 || lay.W > 512 || nrows < 0 || nrows > lay.ni)
+      lay.W < lay.nvar + lay.nparm + 1 || lay.W > 512 || nrows < 0 || (mk ? nrows > PIPAMD_SMAX : nrows > lay.ni))
     return hipErrorInvalidValue;
   lay.pad = 0;
-#define PIP_LOAD_SYSTEM(T, CPL)                                                                                            \
-  hipLaunchKernelGGL((pip_batch_load_system_kernel<T, CPL>), dim3(count), dim3(256), 0, stream, jobs, arena, rows, lay, first, \
-                     shift, simplify, nrows, *eq)
+#define PIP_LOAD_SYSTEM(T, CPL)                                                                                              \
+  do {                                                                                                                       \
+    if (mk)                                                                                                                  \
+      hipLaunchKernelGGL((pip_batch_load_system_kernel<T, CPL, PipEqMarkers>), dim3(count), dim3(256), 0, stream, jobs, arena, \
+                         rows, lay, first, shift, simplify, nrows, *mk);                                                     \
+    else                                                                                                                     \
+      hipLaunchKernelGGL((pip_batch_load_system_kernel<T, CPL, PipEqMask>), dim3(count), dim3(256), 0, stream, jobs, arena,    \
+                         rows, lay, first, shift, simplify, nrows, *eq);                                                     \
+  } while (0)
   if (lay.ebits == 128) {
     if (lay.W <= 128)
       PIP_LOAD_SYSTEM(i128, 2);

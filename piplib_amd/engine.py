@@ -11,6 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PIPAMD_LIB") or os.path.join(HERE, "libpipamd.so")
 
 ST_RUN, ST_SOLUTION, ST_NIL, ST_NEED_COMPA, ST_NEED_PARMCUT, ST_OVERFLOW, ST_CAPACITY, ST_RANGE, ST_INTERNAL, ST_MAXCOL = range(10)
+ST_BADINPUT = 10  # a system Batch(matrices=True).load_matrices() could not take (PIPAMD_ST_BADINPUT)
 T_INT, T_DUAL = 1, 2
 T_NOSKIP = 2048
 T_ROWS_STAY = 8192  # the rows of Batch.load stay valid until the next solve: no copy pass (include/piplib_amd.h)
@@ -26,6 +27,13 @@ class System(C.Structure):
     """pipamd_system: the plain system of Batch(system=True) -- rows, equality rows (a host list), shift, simplify"""
     _fields_ = [("nrows", C.c_int32), ("neq", C.c_int32), ("eq_rows", C.POINTER(C.c_int32)), ("shift", C.c_int32),
                 ("simplify", C.c_int32)]
+
+
+class Matrices(C.Structure):
+    """pipamd_matrices: the PolyLib matrices of Batch(matrices=True) -- room per system, shift, simplify, and the device
+    array of the systems' row counts (NULL: max_rows each)"""
+    _fields_ = [("max_rows", C.c_int32), ("shift", C.c_int32), ("simplify", C.c_int32), ("reserved", C.c_int32),
+                ("d_nrows", C.c_void_p)]
 
 
 ABI_VERSION = 500  # include/piplib_amd.h PIPAMD_VERSION
@@ -74,6 +82,10 @@ def lib():
                                                     C.c_int, C.c_int, C.c_void_p]
         L.pipamd_batch_dual_system_part.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BatchDesc), C.POINTER(System), C.c_void_p,
                                                     C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.pipamd_batch_load_matrices_part.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BatchDesc), C.POINTER(Matrices), C.c_void_p,
+                                                      C.c_int, C.c_int, C.c_void_p]
+        L.pipamd_batch_dual_matrices_part.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BatchDesc), C.POINTER(Matrices), C.c_void_p,
+                                                      C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.pipamd_batch_counters.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BatchDesc), C.c_void_p, C.c_void_p]
         L.pipamd_last_solve_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         L.pipamd_free.argtypes = [C.c_void_p]
@@ -196,7 +208,7 @@ class Batch:
     """A uniform batch of tableaux resident in HBM (layer 1 of the C ABI)."""
 
     def __init__(self, engine, rows, nvar, nparm, bigparm=-1, tflags=T_INT, cap_cuts=None, cap_newparm=0,
-                 entier_bits=64, shape=None, shift=0, system=False, eq_rows=(), simplify=0):
+                 entier_bits=64, shape=None, shift=0, system=False, eq_rows=(), simplify=0, matrices=False, nrows=None, ni=None):
         """rows: (batch, ni, ncol) int64, host or device; or None with shape=(batch, ni, ncol) for a workspace whose
         tableaux come from load_parts().
         shift=SHIFT_MAX / SHIFT_URS: the lexicographic maximum / unknowns of either sign (pip_solve's Maximize,
@@ -207,21 +219,39 @@ class Batch:
         eq_rows (strictly increasing, the same for every system) are equalities; shift may be 0 too; simplify=1 runs
         tab_simplify on the tableau (integer batches, as pip_solve does).  The tableau has nrows + len(eq_rows)
         inequalities; load() / load_part() go through pipamd_batch_load_system and dual_system() gives the dual as
-        pip_solve lists it, one reduced pair per row of the system."""
+        pip_solve lists it, one reduced pair per row of the system.
+        matrices=True: rows are PolyLib matrices, (batch, max_rows, nvar + 2) with the marker first (0: an equality);
+        nrows: an int32 tensor or array of the systems' row counts (None: max_rows each), kept on the device with the
+        rows; ni: the room for the tallest tableau (rows + equalities; default 2 * max_rows).  shift and simplify as for
+        system=True; load_matrices() / dual_matrices() go through pipamd_batch_load_matrices / pipamd_batch_dual_matrices,
+        and a system the load cannot take ends ST_BADINPUT."""
         import torch
         self.torch = torch
         self.e = engine
-        B, ni, ncol = rows.shape if rows is not None else shape
-        assert ncol == nvar + nparm + 1
+        B, ni_in, ncol = rows.shape if rows is not None else shape
         self.shift = int(shift)
         self.system = None
+        self.matrices = None
+        if matrices:
+            assert ncol == nvar + 2 and nparm == 0 and bigparm == -1 and not system and not eq_rows
+            self.matrices = Matrices(ni_in, self.shift, int(simplify), 0, None)
+            self.nrows = None
+            if nrows is not None:
+                dev = torch.device("cuda", engine.device)
+                self.nrows = (nrows if torch.is_tensor(nrows) else torch.as_tensor(nrows)).to(device=dev, dtype=torch.int32).contiguous()
+                assert self.nrows.shape == (B,)
+                self.matrices.d_nrows = self.nrows.data_ptr()
+            ni = int(ni) if ni is not None else 2 * ni_in
+        else:
+            assert ncol == nvar + nparm + 1 and nrows is None and ni is None
+            ni = ni_in
         if system:
             assert nparm == 0 and bigparm == -1
             eq = [int(r) for r in eq_rows]
             self._eq = (C.c_int32 * max(1, len(eq)))(*eq)  # (kept alive with the batch: System points into it)
             self.system = System(ni, len(eq), C.cast(self._eq, C.POINTER(C.c_int32)) if eq else None, self.shift, int(simplify))
             ni += len(eq)
-        else:
+        elif not matrices:
             assert not eq_rows and not simplify
         if self.shift:
             assert self.shift in (SHIFT_MAX, SHIFT_URS) and nparm == 0 and bigparm == -1
@@ -255,6 +285,8 @@ class Batch:
         return C.c_void_p(self.torch.cuda.current_stream(self.dev).cuda_stream)
 
     def load(self):
+        if self.matrices is not None:
+            return self.load_matrices()
         if self.shift or self.system is not None:
             return self.load_part(self.rows, 0)
         _check(lib().pipamd_batch_load(self.e._h, C.c_void_p(self.ws.data_ptr()), C.byref(self.desc),
@@ -263,6 +295,7 @@ class Batch:
     def load_part(self, rows, first, stream=None):
         """tableaux first .. first + len(rows) - 1 of the batch from a resident row array (pipamd_batch_load_part)"""
         assert rows.is_cuda and rows.is_contiguous()
+        assert self.matrices is None, "a Batch(matrices=True) is loaded with load_matrices_part(rows, nrows, first)"
         st = C.c_void_p(stream) if stream is not None else self._stream()
         if self.system is not None:
             return self.load_system_part(rows, first, stream)
@@ -377,6 +410,47 @@ class Batch:
         _check(lib().pipamd_batch_dual_system_part(self.e._h, C.c_void_p(self.ws.data_ptr()), C.byref(self.desc),
                                                    C.byref(self.system), C.c_void_p(rows.data_ptr()), int(first),
                                                    int(rows.shape[0]), C.c_void_p(num.data_ptr()), C.c_void_p(den.data_ptr()), st))
+        return num, den
+
+    def _matrices_part(self, rows, nrows):
+        """the pipamd_matrices of a part: the batch's, with the part's own row counts"""
+        assert self.matrices is not None and rows.is_cuda and rows.is_contiguous()
+        assert tuple(rows.shape[1:]) == (self.matrices.max_rows, self.desc.nvar + 2)
+        m = Matrices(self.matrices.max_rows, self.matrices.shift, self.matrices.simplify, 0, None)
+        if nrows is not None:
+            assert nrows.is_cuda and nrows.is_contiguous() and nrows.dtype == self.torch.int32 and nrows.shape == (rows.shape[0],)
+            m.d_nrows = nrows.data_ptr()
+        return m
+
+    def load_matrices(self, stream=None):
+        """pipamd_batch_load_matrices of a Batch(matrices=True): the whole batch from its resident matrices and row counts"""
+        return self.load_matrices_part(self.rows, self.nrows, 0, stream)
+
+    def load_matrices_part(self, rows, nrows, first, stream=None):
+        """pipamd_batch_load_matrices_part: tableaux first .. first + len(rows) - 1 from the resident matrices `rows` and
+        their row counts `nrows` (a resident int32 tensor, or None: max_rows each)"""
+        m = self._matrices_part(rows, nrows)
+        st = C.c_void_p(stream) if stream is not None else self._stream()
+        _check(lib().pipamd_batch_load_matrices_part(self.e._h, C.c_void_p(self.ws.data_ptr()), C.byref(self.desc), C.byref(m),
+                                                     C.c_void_p(rows.data_ptr()), int(first), int(rows.shape[0]), st))
+
+    def dual_matrices(self, stream=None):
+        """pipamd_batch_dual_matrices after a solve with T_DUAL of a Batch(matrices=True): device tensors (dual_num,
+        dual_den) of shape (batch, max_rows) -- plus a trailing 2 for 128-bit entries --, one reduced pair per row of a
+        system, (0, 0) beyond its rows and throughout for a tableau without a solution.  Does not synchronise."""
+        if self.rows is None:
+            raise RuntimeError("Batch.dual_matrices needs the matrices the batch was loaded from: use dual_matrices_part()")
+        return self.dual_matrices_part(self.rows, self.nrows, 0, stream)
+
+    def dual_matrices_part(self, rows, nrows, first, stream=None, out=None):
+        """pipamd_batch_dual_matrices_part for the tableaux first .. first + len(rows) - 1, loaded from `rows` and `nrows`;
+        returns (dual_num, dual_den) of the whole batch's shape (pass the pair back as `out` to fill it part by part)."""
+        m = self._matrices_part(rows, nrows)
+        num, den = out if out is not None else self._dual_out(self.matrices.max_rows)
+        st = C.c_void_p(stream) if stream is not None else self._stream()
+        _check(lib().pipamd_batch_dual_matrices_part(self.e._h, C.c_void_p(self.ws.data_ptr()), C.byref(self.desc), C.byref(m),
+                                                     C.c_void_p(rows.data_ptr()), int(first), int(rows.shape[0]),
+                                                     C.c_void_p(num.data_ptr()), C.c_void_p(den.data_ptr()), st))
         return num, den
 
     def counters(self):
