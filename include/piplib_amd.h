@@ -117,7 +117,10 @@ int pipamd_engine_set_waves_per_job(pipamd_engine *e, int waves);
 /* Waves per tableau of the tail launch of pipamd_batch_solve (4, the default, or 8).  Eight spread
  * the 15-25 rows a late pivot of a long tableau rewrites over twice the waves: a caller that runs
  * one batch at a time gains ~8 %; with many batches in flight the extra waves of a tail crowd out
- * other batches' bulk launches (-3 %).  64-bit entries of <= 128 columns; 4 otherwise. */
+ * other batches' bulk launches (-3 %).  64-bit entries of <= 128 columns; 4 otherwise.
+ * A tail launch of a 128-bit batch over at most 256 tableaux gives each a whole CU (sixteen waves): the hundreds of rows a
+ * late pivot of a long tableau rewrites spread over four times the waves (built in; this call or
+ * pipamd_engine_set_waves_per_job switch it off). */
 int pipamd_engine_set_tail_waves(pipamd_engine *e, int waves);
 /* One batch at a time (1) or many in flight on other engines (0, the default).  A bulk-sized batch of 127 unknowns in
  * 64 bits starts with the lean one-wave launch (entries below 2^15); the tableaux that launch leaves go through the
@@ -137,9 +140,6 @@ int pipamd_engine_set_lean64(pipamd_engine *e, int on);
  * inequalities the flavour is 13-35 % ahead with eight batches in flight and for a lone Maximize batch, but 3 % behind for a
  * lone Urs_unknowns batch.  A caller that keeps batches in flight switches it on. */
 int pipamd_engine_set_lean_big(pipamd_engine *e, int on);
-/* A tail launch of a 128-bit batch over at most 256 tableaux gives each a whole CU (sixteen waves): the hundreds of rows a
- * late pivot of a long tableau rewrites spread over four times the waves (built in; pipamd_engine_set_tail_waves or
- * _set_waves_per_job switch it off). */
 /* How pipamd_batch_solve waits for the device at its end: 0 (default) polls the stream, which is the
  * quickest for a few host threads; 1 naps 40 us between looks at the stream.  With more batches in flight
  * than the host has CPUs the spinning threads take turns on the cores: 48 batches of 1,250 tableaux on 16 CPUs ran
@@ -505,7 +505,8 @@ int pipamd_solve_tableaux_lockstep(pipamd_engine *e, int n, const pipamd_problem
 /* The lock-step scheduler of the overflow-safe flavour (piplib.h:42-88, funcall.h:37-41: the flavour is a type choice):
  * device tableaux, contexts, parametric cuts and tape cells are 128-bit, one launch sequence per step serves the whole
  * batch; the 128-bit instantiation of the device-resident traiter() runs in front of it (the problems in its box, see
- * pipamd_device_tree_fits), rare paths go to a TreeT<__int128>. */
+ * pipamd_device_tree_fits) and pipamd_last_device_tree reports what it served and handed back, as for the 64-bit entry;
+ * rare paths go to a TreeT<__int128>. */
 int pipamd_solve_tableaux_lockstep128(pipamd_engine *e, int n, const pipamd_problem *problems, int simplify,
                                       int deepest_cut, pipamd_sol_cell128 **cells, size_t *n_cells, int *rcs,
                                       int *statuses, int64_t *pivots);

@@ -29,11 +29,11 @@
 
 #include "pip_host.h"
 #include "pip_quast.h"
+#include "pip_tree_steps.h"
+
+using namespace pip_steps;  // the integer helpers, CellT, CtxT and the formulas both trees share
 
 namespace {
-
-typedef long long i64;
-typedef unsigned long long u64;
 
 #define HIPTHROW(call)                                                                              \
   do {                                                                                              \
@@ -43,120 +43,6 @@ typedef unsigned long long u64;
       throw (int)PIPAMD_E_HIP;                                                                      \
     }                                                                                               \
   } while (0)
-
-// ---- wrap-around integer helpers (piplib.h:128-169, integrer.c:43-74), host side, for both
-// entry widths: E = long long (the reference's int64 build) or __int128 (the overflow-safe one)
-typedef __int128 i128;
-template <class E> struct UT;
-template <> struct UT<i64> { typedef u64 type; };
-template <> struct UT<i128> { typedef unsigned __int128 type; };
-template <class E> inline E wadd(E a, E b) { return (E)((typename UT<E>::type)a + (typename UT<E>::type)b); }
-template <class E> inline E wsub(E a, E b) { return (E)((typename UT<E>::type)a - (typename UT<E>::type)b); }
-template <class E> inline E wneg(E a) { return (E)((typename UT<E>::type)0 - (typename UT<E>::type)a); }
-template <class E> inline E wabs(E a) { return a < 0 ? wneg(a) : a; }
-template <class E> inline E crem(E a, E b) { return (b == 0 || b == -1) ? (E)0 : a % b; }
-template <class E> inline E cquo(E a, E b) { return b == 0 ? (E)0 : (b == -1 ? wneg(a) : a / b); }
-template <class E> E gcd(E a, E b) {
-  while (b) {
-    E t = crem(a, b);
-    a = b;
-    b = t;
-  }
-  return wabs(a);
-}
-template <class E> inline E fmod_(E a, E b) {
-  E m = crem(a, b);
-  if (m < 0) m = wadd(m, wabs(b));
-  return m;
-}
-template <class E> inline E floordiv(E a, E b) { return cquo(wsub(a, fmod_(a, b)), b); }
-template <class E> inline E wmul(E a, E b) { return (E)((typename UT<E>::type)a * (typename UT<E>::type)b); }
-
-enum { S_FREE = 0, S_NIL, S_IF, S_LIST, S_FORM, S_NEW, S_DIV, S_VAL }; /* sol.c:42-50 */
-template <class E> struct CellT {
-  int kind;
-  E a, b;
-};
-typedef CellT<i64> Cell;
-
-// context: rows of (parameters | constant), traiter.c keeps it as a Tableau
-template <class E> struct CtxT {
-  int nc = 0, width = 0;  // rows in use, columns allocated per row
-  std::vector<E> v;
-  E &at(int r, int c) { return v[(size_t)r * width + c]; }
-  E at(int r, int c) const { return v[(size_t)r * width + c]; }
-  void reserve(int rows, int cols) {
-    if (cols > width) {
-      std::vector<E> nv((size_t)std::max(rows, nc + 4) * cols, 0);
-      for (int r = 0; r < nc; r++)
-        for (int c = 0; c < width; c++) nv[(size_t)r * cols + c] = v[(size_t)r * width + c];
-      v.swap(nv);
-      width = cols;
-    }
-    if ((size_t)rows * width > v.size()) v.resize((size_t)(rows + 8) * width, 0);
-  }
-
-  // ---- parameters introduced by parametric cuts (integrer.c:156-291) ----
-  // A cut with parameter part c.p + c0 over the denominator D needs q = floor(-(c.p + c0) / D),
-  // i.e. the parameter q with 0 <= -(c.p + c0) - D q <= D - 1.  The context stores such a
-  // definition as the two rows of that double inequality, with q in a column of its own:
-  //     lower:  -c.p - D q - c0          >= 0
-  //     upper:   c.p + D q + c0 + D - 1  >= 0
-  struct Quotient {
-    std::vector<E> c;  // coefficients of the nparm existing parameters
-    E c0, D;           // constant, divisor
-  };
-  // is there a row  sign * (c on the columns before p | D in column p | 0 behind it)  with constant cst?
-  bool has_row(int nparm, int p, const Quotient &k, bool negated, E cst) const {
-    for (int r = 0; r < nc; r++) {
-      if (at(r, p) != (negated ? wneg(k.D) : k.D) || at(r, nparm) != cst) continue;
-      bool same = true;
-      for (int col = p + 1; col < nparm && same; col++) same = at(r, col) == 0;
-      for (int col = 0; col < p && same; col++) same = at(r, col) == (negated ? wneg(k.c[col]) : k.c[col]);
-      if (same) return true;
-    }
-    return false;
-  }
-  // A parameter the cut does not use (trailing zero coefficients) whose two defining rows are the
-  // ones this quotient would get: its column, or -1 (find_parm, integrer.c:258-291).
-  int find_quotient(int nparm, const Quotient &k) const {
-    const E upper_cst = wsub(wadd(k.c0, k.D), (E)1);
-    for (int p = nparm - 1; p >= 0 && k.c[p] == 0; --p)
-      if (has_row(nparm, p, k, false, upper_cst) && has_row(nparm, p, k, true, wneg(k.c0))) return p;
-    return -1;
-  }
-  // The new parameter takes column nparm (the constants move one column right) and its two rows
-  // are appended (add_parm, integrer.c:194-224).  Returns its column.
-  int define_quotient(int nparm, const Quotient &k) {
-    const int nr = nc;
-    reserve(nr + 2, nparm + 2);
-    for (int r = 0; r < nr; r++) {
-      at(r, nparm + 1) = at(r, nparm);
-      at(r, nparm) = 0;
-    }
-    for (int j = 0; j < nparm; j++) {
-      at(nr, j) = wneg(k.c[j]);
-      at(nr + 1, j) = k.c[j];
-    }
-    at(nr, nparm) = wneg(k.D);
-    at(nr + 1, nparm) = k.D;
-    at(nr, nparm + 1) = wneg(k.c0);
-    at(nr + 1, nparm + 1) = wadd(wsub(k.c0, (E)1), k.D);
-    nc += 2;
-    return nparm;
-  }
-  // what the solution tape says about it (integrer.c:173-188): New k, Div, the form -c.p - c0, D
-  template <class PUSH>
-  static void announce_quotient(PUSH &&push, int nparm, const Quotient &k) {
-    push(S_NEW, (E)nparm, (E)0);
-    push(S_DIV, (E)0, (E)0);
-    push(S_FORM, (E)(nparm + 1), (E)0);
-    for (int j = 0; j < nparm; j++) push(S_VAL, wneg(k.c[j]), (E)1);
-    push(S_VAL, wneg(k.c0), (E)1);
-    push(S_VAL, k.D, (E)1);
-  }
-};
-typedef CtxT<i64> Ctx;
 
 // The block of a tree's job: a solution over every column the block has, and room for the bitmaps of any launch
 // geometry (8 words per slot: jobs of mixed widths share launches).
@@ -288,6 +174,9 @@ class TreeT {
     tape.push_back(Cell{kind, a, b});
     if (tape.size() >= 4096) fail(PIPAMD_ST_INTERNAL);  // "The solution is too complex", sol.c:97
   }
+  auto tape_out() {  // the tape as the shared formulas write to it
+    return [this](int kind, E a, E b) { push(kind, a, b); };
+  }
 
   // ---------------------------------------------------------------- arena
   void ensure_arena(size_t words) {
@@ -388,14 +277,14 @@ class TreeT {
   }
   // expanser(context, nparm, nc, nparm+1, nparm, extra?1:0, 0) (traiter.c:191,211,
   // maind.c:198): the context as a problem in the parameters, optionally one more row
-  HostJob make_context_job(const Ctx &ctx, int nparm, int nc, const std::vector<E> *extra) {
+  HostJob make_context_job(const Ctx &ctx, int nparm, int nc, const E *extra) {
     const int ni = nc + (extra ? 1 : 0), ncol = nparm + 1;
     HostJob j = alloc_job(nparm, 0, ni, -1, PIPAMD_T_INT, ni + 16, ncol);
     std::vector<E> r((size_t)ni * ncol);
     for (int i = 0; i < nc; i++)
       for (int c = 0; c < ncol; c++) r[(size_t)i * ncol + c] = ctx.at(i, c);
     if (extra)
-      for (int c = 0; c < ncol; c++) r[(size_t)nc * ncol + c] = (*extra)[c];
+      for (int c = 0; c < ncol; c++) r[(size_t)nc * ncol + c] = extra[c];
     upload_fresh(j, r);
     return j;
   }
@@ -542,6 +431,7 @@ class TreeT {
     const size_t mark = top_;
     std::vector<HostJob> sub;
     std::vector<int> critic(rows.size());
+    std::vector<E> ex_plus(nparm + 1), ex_minus(nparm + 1);
     sub.reserve(2 * rows.size());
     for (size_t t = 0; t < rows.size(); t++) {
       const E *r = s.row(rows[t]);
@@ -552,13 +442,9 @@ class TreeT {
           break;
         }
       critic[t] = cr;
-      std::vector<E> ex(nparm + 1);
-      for (int j = 0; j < nparm; j++) ex[j] = r[j + nvar + 1];  // "row >= 1" (>= 0 if critical)
-      ex[nparm] = cr ? r[nvar] : wsub(r[nvar], (E)1);
-      sub.push_back(make_context_job(ctx, nparm, nc, &ex));
-      for (int j = 0; j < nparm; j++) ex[j] = wneg(r[j + nvar + 1]);  // "-row >= 1"
-      ex[nparm] = wsub(wneg(r[nvar]), (E)1);
-      sub.push_back(make_context_job(ctx, nparm, nc, &ex));
+      compa_rows(r[nvar], r + nvar + 1, nparm, cr != 0, ex_plus.data(), ex_minus.data());
+      sub.push_back(make_context_job(ctx, nparm, nc, ex_plus.data()));
+      sub.push_back(make_context_job(ctx, nparm, nc, ex_minus.data()));
     }
     std::vector<HostJob *> ptr;
     for (auto &h : sub) ptr.push_back(&h);
@@ -581,36 +467,11 @@ class TreeT {
       pivots += jp.pj.npiv + jm.pj.npiv;
       check_final(jp);
       check_final(jm);
-      const bool cp = jp.pj.status != PIPAMD_ST_NIL, cm = jm.pj.status != PIPAMD_ST_NIL;
-      int f;
-      if (cp && cm)
-        f = critic[t] ? PIPAMD_F_CRITIC : PIPAMD_F_UNKNOWN;
-      else if (cm)
-        f = PIPAMD_F_MINUS;
-      else
-        f = cp ? PIPAMD_F_PLUS : PIPAMD_F_ZERO;
+      const int f = compa_flag(jp.pj.status == PIPAMD_ST_NIL, jm.pj.status == PIPAMD_ST_NIL, critic[t] != 0);
       set_flag(job, rows[t], f);
       if (f == PIPAMD_F_MINUS) break;
     }
     top_ = mark;
-  }
-
-  // (find_parm / add_parm, integrer.c:156-291: CtxT::find_quotient / define_quotient)
-  static E bezout(E x, E y, E delta) {  // integrer.c:98-150
-    E a = 1, b = 0, c = 0, d = 1, u = y, v = delta;
-    for (;;) {
-      E q = floordiv(u, v), r = fmod_(u, v);
-      if (r == 0) break;
-      u = v;
-      v = r;
-      E e = wsub(a, wmul(q, c)), f = wsub(b, wmul(q, d));
-      a = c;
-      b = d;
-      c = e;
-      d = f;
-    }
-    if (v != 1) return 0;
-    return fmod_(wmul(c, x), delta);
   }
 
   // integrer() for the row the kernel stopped at (integrer.c:342-520): the kernel hands over
@@ -619,62 +480,20 @@ class TreeT {
   bool host_cut(HostJob &job, Ctx &ctx, int nvar, int &nparm, int &ni, int bigparm) {
     const int ci = job.pj.aux;
     Snap s = download(job);
-    const int ncol = nvar + nparm + 1, nligne = nvar + ni;
-    if (ncol >= PIPAMD_MAXCOL) fail(PIPAMD_ST_MAXCOL);
-    const E *r = s.row(ci);
+    const int nligne = nvar + ni;
+    if (nvar + nparm + 1 >= PIPAMD_MAXCOL) fail(PIPAMD_ST_MAXCOL);
     const E D = s.den[ci];
-    std::vector<E> cut(ncol + 1);
-    bool ok_var = false, ok_parm = false;
-    for (int j = 0; j < nvar; j++) {
-      cut[j] = fmod_(r[j], D);
-      if (cut[j] > 0) ok_var = true;
-    }
-    cut[nvar] = wneg(fmod_(wneg(r[nvar]), D));
-    for (int j = nvar + 1; j < ncol; j++) {
-      if (j == bigparm) {
-        cut[j] = 0;
-        continue;
-      }
-      cut[j] = wneg(fmod_(wneg(r[j]), D));
-      if (cut[j] != 0) ok_parm = true;
-    }
-    cut[ncol] = D;
-    int newcol = -1;
-    if (!ok_parm) {
-      if (!ok_var) return false;
-      if (deepest_) {  // integrer.c:417-438
-        E t = wneg(cut[nvar]), delta = gcd(t, D), tau = cquo(t, delta), dd = cquo(D, delta);
-        t = wsub(dd, (E)1);
-        E lambda = bezout(t, tau, dd);
-        t = gcd(lambda, D);
-        while (t != 1) {
-          lambda = wadd(lambda, dd);
-          t = gcd(lambda, D);
-        }
-        for (int j = 0; j < nvar; j++) cut[j] = fmod_(wmul(lambda, cut[j]), D);
-        t = fmod_(wmul(cut[nvar], lambda), D);
-        t = wsub(D, t);
-        cut[nvar] = wneg(t);
-      }
-    } else {
-      typename Ctx::Quotient k{std::vector<E>(cut.begin() + nvar + 1, cut.begin() + ncol), cut[nvar], D};
-      int parm = ctx.find_quotient(nparm, k);
-      if (parm == -1) {
-        Ctx::announce_quotient([&](int kind, E a, E b) { push(kind, a, b); }, nparm, k);
-        parm = ctx.define_quotient(nparm, k);
-        nparm++;
-      }
-      if (!ok_var) fail(PIPAMD_ST_INTERNAL);  // assert(ok_var), integrer.c:499
-      newcol = nvar + 1 + parm;
-    }
+    std::vector<E> row;
+    int newcol;
+    const CutKind kind = parm_cut(s.row(ci), D, nvar, nparm, bigparm, deepest_ != 0, ctx, tape_out(), row, newcol);
+    if (kind == CUT_NONE) return false;
+    if (kind == CUT_NO_VAR) fail(PIPAMD_ST_INTERNAL);
     // append the cut as logical row nligne in slot ni
     const int need_w = nvar + nparm + 1;
     if (ni >= job.pj.S || nligne >= job.pj.L || need_w > job.pj.W)
       grow(job, std::max((int)job.pj.S, ni + 1) + 16, std::max((int)job.pj.W, need_w) + 4);
     const int W = job.pj.W, L = job.pj.L;
-    std::vector<E> row(W, 0);
-    for (int j = 0; j < ncol; j++) row[j] = cut[j];
-    if (newcol >= 0) row[newcol] = wadd(row[newcol], cut[ncol]);
+    row.resize(W, 0);
     copy((E *)(d_arena_ + job.pj.vals_off) + (size_t)ni * W, row.data(), W * sizeof(E), hipMemcpyHostToDevice);
     const auto [g_den, g_flag, g_ref] = pip_row_tables<E>(d_arena_ + job.pj.rows_off, L);
     const int fl = PIPAMD_F_MINUS;
@@ -694,11 +513,7 @@ class TreeT {
     std::vector<E> buf(n + nvar);
     if (n + nvar)
       copy(buf.data(), d_arena_ + job.pj.sol_off, (n + nvar) * sizeof(E), hipMemcpyDeviceToHost);
-    push(S_LIST, (E)nvar, 0);
-    for (int i = 0; i < nvar; i++) {
-      push(S_FORM, (E)(nparm + 1), 0);
-      for (int j = 0; j <= nparm; j++) push(S_VAL, buf[(size_t)i * (nparm + 1) + j], buf[n + i]);
-    }
+    push_solution(tape_out(), nvar, nparm, buf.data(), buf.data() + n);
   }
 
   // tab_sort_rows' bookkeeping for the dual (traiter.c:556-623): where each inequality of this
@@ -832,40 +647,25 @@ class TreeT {
            hipMemcpyDeviceToDevice);
       child.pj.ldet = job.pj.ldet;
       memcpy(child.pj.det, job.pj.det, sizeof job.pj.det);
-      push(S_IF, 0, 0);
-      push(S_FORM, (E)(nparm + 1), 0);
       const E *r = s.row(pivi);
-      E g = 0;
-      for (int j = 0; j < nparm; j++) g = gcd(g, r[j + nvar + 1]);
-      if (!(flags & PIPAMD_T_INT)) g = gcd(g, r[nvar]);
-      const int nc = ctx.nc;
-      ctx.reserve(nc + 1, nparm + 2);
-      for (int j = 0; j < nparm; j++) {
-        ctx.at(nc, j) = cquo(r[j + nvar + 1], g);
-        push(S_VAL, ctx.at(nc, j), 1);
-      }
-      ctx.at(nc, nparm) = (flags & PIPAMD_T_INT) ? floordiv(r[nvar], g) : cquo(r[nvar], g);
-      push(S_VAL, ctx.at(nc, nparm), 1);
+      fork_row(r[nvar], r + nvar + 1, nparm, (flags & PIPAMD_T_INT) != 0, ctx, tape_out());
       set_flag(child, pivi, PIPAMD_F_PLUS);
       {
         Ctx cc = ctx;
-        cc.nc = nc + 1;
+        cc.nc = ctx.nc + 1;
         node(child, cc, nvar, nparm, ni, bigparm, flags);
       }
       top_ = mark;
-      for (int j = 0; j < nparm; j++) ctx.at(nc, j) = wneg(ctx.at(nc, j));
-      ctx.at(nc, nparm) = wneg(wadd(ctx.at(nc, nparm), (E)1));
-      ctx.nc = nc + 1;
+      fork_else(ctx, nparm);
       set_flag(job, pivi, PIPAMD_F_MINUS);
     }
   }
 };
-typedef TreeT<i64> Tree;
 
 // tab_simplify (tab.c:396-427) on a row-major matrix
-void simplify_rows(i64 *m, int rows, int width, int cst) {
+void simplify_rows(std::vector<i64> &m, int rows, int width, int cst) {
   for (int i = 0; i < rows; i++) {
-    i64 *r = m + (size_t)i * width;
+    i64 *r = m.data() + (size_t)i * width;
     i64 g = 0;
     for (int j = 0; j < width; j++) {
       if (j == cst) continue;
@@ -876,58 +676,102 @@ void simplify_rows(i64 *m, int rows, int width, int cst) {
     for (int j = 0; j < width; j++) r[j] = (j == cst) ? floordiv(r[j], g) : cquo(r[j], g);
   }
 }
-void simplify_rows(std::vector<i64> &m, int rows, int width, int cst) { simplify_rows(m.data(), rows, width, cst); }
 
-}  // namespace
+// what a path hands back for one problem; rc == PIPAMD_E_TOOLARGE: not served, the next path takes it
+template <class E> struct FResultT {
+  int rc = PIPAMD_OK, status = 0;
+  long long pivots = 0;
+  bool is_void = false;
+  std::vector<CellT<E>> tape;
+};
 
-// One small 64-bit problem through the device-resident traiter() (defined with the device tree at the end
-// of this file): true when it was served there (tape / is_void / pivots filled), false: use the host tree.
-// (E: the entry type -- long long, or __int128 for the overflow-safe flavour: the kernel is a template over it)
+// the device-resident traiter() (defined with the device tree at the end of this file)
 template <class E>
-static bool device_tree_one(pipamd_engine *e, const pipamd_problem &p, int simplify, int deepest_cut, int qflags,
-                            std::vector<CellT<E>> &tape, bool *is_void, int64_t *pivots);
-// The same for many problems: fills the outputs of every problem it serves and marks it in `served`.
-template <class E, class CELL>
-static void device_tree_many(pipamd_engine *e, int n, const pipamd_problem *probs, int simplify, int deepest_cut,
-                             std::vector<char> &served, CELL **cells, size_t *n_cells, int *rcs, int *statuses,
-                             int64_t *pivots);
+void device_tree(pipamd_engine *e, int n, const pipamd_problem *probs, int simplify, int deepest_cut, std::vector<FResultT<E>> &res,
+                 int *served, int *handed_back, const int *qflags);
+
+// device bytes a chunk of problems may reserve, in the device tree and in the Forest (PIPAMD_FOREST_ARENA_MB, default 4096)
+size_t forest_arena_budget() {
+  if (const char *mb = getenv("PIPAMD_FOREST_ARENA_MB")) return (size_t)strtoull(mb, nullptr, 10) << 20;
+  return (size_t)4096 << 20;
+}
+
+// The device tree in front of an entry, over n problems (E: the entry type -- long long, or __int128 for the overflow-safe
+// flavour: the kernel is a template over it).  res[i].rc is PIPAMD_OK where it served problem i and PIPAMD_E_TOOLARGE
+// where the host schedulers have to.  qflags: QProb::flags of every problem (null: 0 for all), a negative entry keeps
+// its problem out.  pipamd_last_device_tree answers for the call: the one-problem entries leave its counts alone while
+// the device tree is switched off, the many-problem entries report 0 / 0 then.
+template <class E>
+void try_device_tree(pipamd_engine *e, int n, const pipamd_problem *probs, int simplify, int deepest_cut, const int *qflags,
+                     bool one_problem, std::vector<FResultT<E>> &res) {
+  res.assign(n > 0 ? n : 0, FResultT<E>());
+  for (auto &r : res) r.rc = PIPAMD_E_TOOLARGE;
+  if (!one_problem) e->dt_served = e->dt_fallback = 0;
+  if (e->no_device_tree || getenv("PIPAMD_NO_DEVICE_TREE") || n <= 0) return;
+  int served = 0, back = 0;
+  device_tree<E>(e, n, probs, simplify, deepest_cut, res, &served, &back, qflags);
+  pthread_mutex_lock(&e->dt_lock);
+  e->dt_served = served;
+  e->dt_fallback = back;
+  pthread_mutex_unlock(&e->dt_lock);
+}
 
 // the tape as the C ABI hands it out: (kind, param1, param2) cells, sol.c:52-59
-static int export_tape(const std::vector<Cell> &tape, pipamd_sol_cell **cells, size_t *n_cells) {
+void set_cell(pipamd_sol_cell &c, const CellT<i64> &t) {
+  c.param1 = t.a;
+  c.param2 = t.b;
+}
+void set_cell(pipamd_sol_cell128 &c, const CellT<i128> &t) {
+  c.param1_lo = (int64_t)(u64)(unsigned __int128)t.a;
+  c.param1_hi = (int64_t)(t.a >> 64);
+  c.param2_lo = (int64_t)(u64)(unsigned __int128)t.b;
+  c.param2_hi = (int64_t)(t.b >> 64);
+}
+template <class E, class CELL>
+int export_tape(const std::vector<CellT<E>> &tape, CELL **cells, size_t *n_cells) {
   *n_cells = tape.size();
   *cells = nullptr;
   if (tape.empty()) return PIPAMD_OK;
-  pipamd_sol_cell *c = (pipamd_sol_cell *)malloc(tape.size() * sizeof *c);
+  CELL *c = (CELL *)malloc(tape.size() * sizeof *c);
   if (!c) return PIPAMD_E_NOMEM;
   for (size_t i = 0; i < tape.size(); i++) {
     c[i].kind = tape[i].kind;
     c[i].reserved = 0;
-    c[i].param1 = tape[i].a;
-    c[i].param2 = tape[i].b;
+    set_cell(c[i], tape[i]);
   }
   *cells = c;
   return PIPAMD_OK;
 }
 
-static int export_tape(const std::vector<CellT<i128>> &tape, pipamd_sol_cell128 **cells, size_t *n_cells) {
-  *n_cells = tape.size();
-  *cells = nullptr;
-  if (tape.empty()) return PIPAMD_OK;
-  pipamd_sol_cell128 *c = (pipamd_sol_cell128 *)malloc(tape.size() * sizeof *c);
-  if (!c) return PIPAMD_E_NOMEM;
-  for (size_t i = 0; i < tape.size(); i++) {
-    c[i].kind = tape[i].kind;
-    c[i].reserved = 0;
-    c[i].param1_lo = (int64_t)(u64)(unsigned __int128)tape[i].a;
-    c[i].param1_hi = (int64_t)(tape[i].a >> 64);
-    c[i].param2_lo = (int64_t)(u64)(unsigned __int128)tape[i].b;
-    c[i].param2_hi = (int64_t)(tape[i].b >> 64);
+// The problems a path has served, in the C arrays of an entry (statuses and pivots may be null), each marked in `served`.
+// A problem already marked is left alone (pipamd_traiter_many marks those it refuses as PIPAMD_E_INVALID); a void
+// problem -- an empty context, which only the front ends test for -- is PIPAMD_OK with no cells.
+template <class E, class CELL>
+void export_results(const std::vector<FResultT<E>> &res, std::vector<char> &served, CELL **cells, size_t *n_cells, int *rcs,
+                    int *statuses, int64_t *pivots) {
+  for (size_t i = 0; i < res.size(); i++) {
+    if (res[i].rc != PIPAMD_OK || served[i]) continue;
+    served[i] = 1;
+    cells[i] = nullptr;
+    n_cells[i] = 0;
+    if (statuses) statuses[i] = 0;
+    if (pivots) pivots[i] = res[i].pivots;
+    rcs[i] = res[i].is_void ? PIPAMD_OK : export_tape(res[i].tape, &cells[i], &n_cells[i]);
   }
-  *cells = c;
-  return PIPAMD_OK;
 }
 
-static bool valid_shape(int nvar, int nparm, int ni, int nc, int bigparm, const void *ineq, const void *ctx) {
+// One problem through the device tree: true when it was served there (the outputs filled, *rc what the entry returns).
+template <class E, class CELL>
+bool device_tree_one(pipamd_engine *e, const pipamd_problem &p, int simplify, int deepest_cut, int qflags, CELL **cells,
+                     size_t *n_cells, int *rc, int *status, int64_t *pivots) {
+  std::vector<FResultT<E>> res;
+  std::vector<char> served(1, 0);
+  try_device_tree<E>(e, 1, &p, simplify, deepest_cut, &qflags, true, res);
+  export_results(res, served, cells, n_cells, rc, status, pivots);
+  return served[0] != 0;
+}
+
+bool valid_shape(int nvar, int nparm, int ni, int nc, int bigparm, const void *ineq, const void *ctx) {
   if (nvar < 0 || nparm < 0 || ni < 0 || nc < 0 || (ni && !ineq) || (nc && !ctx)) {
     pipamd_set_error("invalid tableau shape or missing rows");
     return false;
@@ -940,12 +784,28 @@ static bool valid_shape(int nvar, int nparm, int ni, int nc, int bigparm, const 
   return true;
 }
 
-// one problem on an existing tree (device buffers and stream are reused between problems);
-// an empty tape with PIPAMD_OK is the front ends' "void" (empty context)
+// One call on an existing tree (device buffers and stream are reused between problems): what it throws becomes the rc,
+// the PIPAMD_ST_* reason in *status and the error string; *pivots in either case (status and pivots may be null).
+template <class TREE, class CALL>
+int tree_call(TREE &t, int deepest_cut, int *status, int64_t *pivots, CALL &&call) {
+  t.reset(deepest_cut);
+  int rc = PIPAMD_OK;
+  try {
+    call();
+  } catch (int code) {
+    rc = code;
+    if (status) *status = t.fail_status;
+    if (rc == PIPAMD_E_SOLVER)
+      pipamd_set_error("solver stopped with status %d (5 = the reference's \"Integer overflow\" exit)", t.fail_status);
+  }
+  if (pivots) *pivots = t.pivots;
+  return rc;
+}
+
+// one problem of the front ends (maind.c:190-231) on a tree; an empty tape with PIPAMD_OK is their "void" (empty context)
 template <class TREE, class CELL>
-static int solve_one(TREE &t, int nvar, int nparm, int ni, int nc, int bigparm, int nq, const int64_t *ineq,
-                     const int64_t *ctx, int simplify, int deepest_cut, CELL **cells, size_t *n_cells,
-                     int *status, int64_t *pivots) {
+int solve_one(TREE &t, int nvar, int nparm, int ni, int nc, int bigparm, int nq, const int64_t *ineq, const int64_t *ctx,
+              int simplify, int deepest_cut, CELL **cells, size_t *n_cells, int *status, int64_t *pivots) {
   if (!cells || !n_cells || !valid_shape(nvar, nparm, ni, nc, bigparm, ineq, ctx)) return PIPAMD_E_INVALID;
   const int ncol = nvar + nparm + 1;
   *cells = nullptr;
@@ -958,155 +818,41 @@ static int solve_one(TREE &t, int nvar, int nparm, int ni, int nc, int bigparm, 
     simplify_rows(a, ni, ncol, nvar);
     simplify_rows(c, nc, nparm + 1, nparm);
   }
-  t.reset(deepest_cut);
-  int rc = PIPAMD_OK;
   bool non_void = false;
-  try {
-    non_void = t.front(nvar, nparm, ni, nc, bigparm, nq, a.data(), c.data());
-  } catch (int code) {
-    rc = code;
-    if (status) *status = t.fail_status;
-    if (rc == PIPAMD_E_SOLVER)
-      pipamd_set_error("solver stopped with status %d (5 = the reference's \"Integer overflow\" exit)", t.fail_status);
-  }
-  if (pivots) *pivots = t.pivots;
+  const int rc = tree_call(t, deepest_cut, status, pivots,
+                           [&] { non_void = t.front(nvar, nparm, ni, nc, bigparm, nq, a.data(), c.data()); });
   if (rc) return rc;
   return non_void ? export_tape(t.tape, cells, n_cells) : PIPAMD_OK;
 }
-
-extern "C" int pipamd_solve_tableau(pipamd_engine *e, int nvar, int nparm, int ni, int nc, int bigparm, int nq,
-                                    const int64_t *ineq, const int64_t *ctx, int simplify, int deepest_cut,
-                                    pipamd_sol_cell **cells, size_t *n_cells, int *status, int64_t *pivots) {
-  if (!e) return PIPAMD_E_INVALID;
-  if (hipSetDevice(e->device) != hipSuccess) return PIPAMD_E_HIP;
-  try {
-    if (cells && n_cells && valid_shape(nvar, nparm, ni, nc, bigparm, ineq, ctx)) {  // a small problem: wholly on the device
-      const pipamd_problem p{nvar, nparm, ni, nc, bigparm, nq, ineq, ctx};
-      std::vector<Cell> tape;
-      bool is_void = false;
-      int64_t pv = 0;
-      if (device_tree_one<i64>(e, p, simplify, deepest_cut, 0, tape, &is_void, &pv)) {
-        *cells = nullptr;
-        *n_cells = 0;
-        if (status) *status = 0;
-        if (pivots) *pivots = pv;
-        return is_void ? PIPAMD_OK : export_tape(tape, cells, n_cells);
-      }
-    }
-    Tree t(e, deepest_cut);
-    return solve_one(t, nvar, nparm, ni, nc, bigparm, nq, ineq, ctx, simplify, deepest_cut, cells, n_cells, status, pivots);
-  } catch (int code) {
-    return code;
-  }
-}
-
-// traiter() (traiter.c:628-791) behind the reference's own front ends: see include/piplib_amd.h
-template <class E, class CELL>
-static int traiter_any(pipamd_engine *e, int nvar, int nparm, int ni, int nc, int bigparm, int flags, int deepest_cut,
-                       const int64_t *tableau, const int64_t *context, CELL **cells, size_t *n_cells, int *status,
-                       int64_t *pivots) {
-  if (!e || !cells || !n_cells || !valid_shape(nvar, nparm, ni, nc, bigparm, tableau, context)) return PIPAMD_E_INVALID;
-  if ((flags & ~(PIPAMD_T_INT | PIPAMD_T_DUAL)) || ((flags & PIPAMD_T_INT) && (flags & PIPAMD_T_DUAL))) {
-    pipamd_set_error("pipamd_traiter: flags must be 0, PIPAMD_T_INT or PIPAMD_T_DUAL (the dual needs a rational solve)");
-    return PIPAMD_E_INVALID;
-  }
-  if (hipSetDevice(e->device) != hipSuccess) return PIPAMD_E_HIP;
-  *cells = nullptr;
-  *n_cells = 0;
-  if (status) *status = 0;
-  if (pivots) *pivots = 0;
-  int rc = PIPAMD_OK;
-  try {
-    {  // a small problem (with or without the dual): wholly on the device
-      const pipamd_problem p{nvar, nparm, ni, nc, bigparm, (flags & PIPAMD_T_INT) ? 1 : 0, tableau, context};
-      std::vector<CellT<E>> tape;
-      bool is_void = false;
-      int64_t pv = 0;
-      if (device_tree_one<E>(e, p, 0, deepest_cut, Q_NO_CONTEXT_TEST | ((flags & PIPAMD_T_DUAL) ? Q_DUAL : 0), tape, &is_void, &pv)) {
-        if (pivots) *pivots = pv;
-        return export_tape(tape, cells, n_cells);
-      }
-    }
-    TreeT<E> t(e, deepest_cut);
-    try {
-      t.traiter_call(nvar, nparm, ni, nc, bigparm, flags, (const i64 *)tableau, (const i64 *)context);
-    } catch (int code) {
-      rc = code;
-      if (status) *status = t.fail_status;
-      if (rc == PIPAMD_E_SOLVER)
-        pipamd_set_error("solver stopped with status %d (5 = the reference's \"Integer overflow\" exit)", t.fail_status);
-    }
-    if (pivots) *pivots = t.pivots;
-    if (!rc) rc = export_tape(t.tape, cells, n_cells);
-  } catch (int code) {
-    rc = code;
-  }
-  return rc;
-}
-extern "C" int pipamd_traiter(pipamd_engine *e, int nvar, int nparm, int ni, int nc, int bigparm, int flags,
-                              int deepest_cut, const int64_t *tableau, const int64_t *context,
-                              pipamd_sol_cell **cells, size_t *n_cells, int *status, int64_t *pivots) {
-  return traiter_any<i64>(e, nvar, nparm, ni, nc, bigparm, flags, deepest_cut, tableau, context, cells, n_cells, status,
-                          pivots);
-}
-// the overflow-safe flavour (include/piplib/piplib.h:42-88): 128-bit entries on the device and in
-// the host tree, inputs still int64, cells with 128-bit parameters
-extern "C" int pipamd_traiter128(pipamd_engine *e, int nvar, int nparm, int ni, int nc, int bigparm, int flags,
-                                 int deepest_cut, const int64_t *tableau, const int64_t *context,
-                                 pipamd_sol_cell128 **cells, size_t *n_cells, int *status, int64_t *pivots) {
-  return traiter_any<i128>(e, nvar, nparm, ni, nc, bigparm, flags, deepest_cut, tableau, context, cells, n_cells, status,
-                           pivots);
-}
-extern "C" int pipamd_solve_tableau128(pipamd_engine *e, int nvar, int nparm, int ni, int nc, int bigparm, int nq,
-                                       const int64_t *ineq, const int64_t *ctx, int simplify, int deepest_cut,
-                                       pipamd_sol_cell128 **cells, size_t *n_cells, int *status, int64_t *pivots) {
-  if (!e) return PIPAMD_E_INVALID;
-  if (hipSetDevice(e->device) != hipSuccess) return PIPAMD_E_HIP;
-  try {
-    if (cells && n_cells && valid_shape(nvar, nparm, ni, nc, bigparm, ineq, ctx)) {  // a small problem: wholly on the device
-      const pipamd_problem p{nvar, nparm, ni, nc, bigparm, nq, ineq, ctx};
-      std::vector<CellT<i128>> tape;
-      bool is_void = false;
-      int64_t pv = 0;
-      if (device_tree_one<i128>(e, p, simplify, deepest_cut, 0, tape, &is_void, &pv)) {
-        *cells = nullptr;
-        *n_cells = 0;
-        if (status) *status = 0;
-        if (pivots) *pivots = pv;
-        return is_void ? PIPAMD_OK : export_tape(tape, cells, n_cells);
-      }
-    }
-    TreeT<i128> t(e, deepest_cut);
-    return solve_one(t, nvar, nparm, ni, nc, bigparm, nq, ineq, ctx, simplify, deepest_cut, cells, n_cells, status, pivots);
-  } catch (int code) {
-    return code;
-  }
-}
-
-// Many independent problems: `nthreads` host threads, each with its own tree (device arena and
-// HIP stream), pull problems from a shared counter; their launches overlap on the GPU.
-// rc[i] receives what pipamd_solve_tableau would have returned for problem i.
-// TREE = Tree (64-bit entries; small problems go to the device-resident traiter() first) or TreeT<i128>.
 template <class TREE, class CELL>
-static int solve_many(pipamd_engine *e, int n, const pipamd_problem *probs, int simplify, int deepest_cut, int nthreads,
-                      CELL **cells, size_t *n_cells, int *rcs, int *statuses, int64_t *pivots, std::vector<char> &served) {
+int solve_one(TREE &t, const pipamd_problem &p, int simplify, int deepest_cut, CELL **cells, size_t *n_cells, int *status,
+              int64_t *pivots) {
+  return solve_one(t, p.nvar, p.nparm, p.ni, p.nc, p.bigparm, p.nq, p.ineq, p.ctx, simplify, deepest_cut, cells, n_cells, status,
+                   pivots);
+}
+// one traiter() call (traiter.c:628-791) on a tree: no context test, no tab_simplify; p.nq is not looked at
+template <class E, class CELL>
+int traiter_one(TreeT<E> &t, const pipamd_problem &p, int flags, int deepest_cut, CELL **cells, size_t *n_cells, int *status,
+                int64_t *pivots) {
+  const int rc = tree_call(t, deepest_cut, status, pivots, [&] {
+    t.traiter_call(p.nvar, p.nparm, p.ni, p.nc, p.bigparm, flags, (const i64 *)p.ineq, (const i64 *)p.ctx);
+  });
+  return rc ? rc : export_tape(t.tape, cells, n_cells);
+}
+
+// `nthreads` host threads, each with its own tree (device arena and HIP stream), pull the problems not yet served from a
+// shared counter; their launches overlap on the GPU.  per_problem(tree, i) fills problem i's outputs.
+template <class TREE, class F>
+void run_workers(pipamd_engine *e, int deepest_cut, int nthreads, int n, const std::vector<char> &served, F &&per_problem) {
   std::atomic<int> next(0);
-  const int device = e->device;
   auto worker = [&]() {
-    if (hipSetDevice(device) != hipSuccess) return;
+    if (hipSetDevice(e->device) != hipSuccess) return;
     try {
       TREE t(e, deepest_cut);
       for (;;) {
         const int i = next.fetch_add(1);
         if (i >= n) break;
-        if (served[i]) continue;
-        const pipamd_problem &p = probs[i];
-        int st = 0;
-        int64_t pv = 0;
-        rcs[i] = solve_one(t, p.nvar, p.nparm, p.ni, p.nc, p.bigparm, p.nq, p.ineq, p.ctx, simplify, deepest_cut,
-                           &cells[i], &n_cells[i], &st, &pv);
-        if (statuses) statuses[i] = st;
-        if (pivots) pivots[i] = pv;
+        if (!served[i]) per_problem(t, i);
       }
     } catch (int) {  // the tree could not be set up (stream creation failed): its problems stay E_HIP
     }
@@ -1114,12 +860,11 @@ static int solve_many(pipamd_engine *e, int n, const pipamd_problem *probs, int 
   std::vector<std::thread> th;
   for (int k = 0; k < nthreads; k++) th.emplace_back(worker);
   for (auto &x : th) x.join();
-  return PIPAMD_OK;
 }
 
 template <class CELL>
-static bool many_args(pipamd_engine *e, int n, const pipamd_problem *probs, int &nthreads, CELL **cells, size_t *n_cells,
-                      int *rcs, int *statuses, int64_t *pivots) {
+bool many_args(pipamd_engine *e, int n, const pipamd_problem *probs, int &nthreads, CELL **cells, size_t *n_cells, int *rcs,
+               int *statuses, int64_t *pivots) {
   if (!e || n < 0 || (n && (!probs || !cells || !n_cells || !rcs))) return false;
   if (nthreads < 1) nthreads = 1;
   if (nthreads > n) nthreads = n > 0 ? n : 1;
@@ -1133,39 +878,82 @@ static bool many_args(pipamd_engine *e, int n, const pipamd_problem *probs, int 
   return true;
 }
 
-extern "C" int pipamd_solve_tableaux(pipamd_engine *e, int n, const pipamd_problem *probs, int simplify, int deepest_cut,
-                                     int nthreads, pipamd_sol_cell **cells, size_t *n_cells, int *rcs, int *statuses,
-                                     int64_t *pivots) {
-  if (!many_args(e, n, probs, nthreads, cells, n_cells, rcs, statuses, pivots)) return PIPAMD_E_INVALID;
-  std::vector<char> served(n > 0 ? n : 1, 0);
-  if (hipSetDevice(e->device) == hipSuccess)  // small problems: wholly on the device, in one launch
-    device_tree_many<i64>(e, n, probs, simplify, deepest_cut, served, cells, n_cells, rcs, statuses, pivots);
-  return solve_many<Tree, pipamd_sol_cell>(e, n, probs, simplify, deepest_cut, nthreads, cells, n_cells, rcs, statuses, pivots,
-                                           served);
+// ---- the entries, one body for both widths: E = long long with pipamd_sol_cell, __int128 with pipamd_sol_cell128
+// (the overflow-safe flavour, include/piplib/piplib.h:42-88: 128-bit entries on the device and in the host tree, inputs
+// still int64, cells with 128-bit parameters)
+template <class E, class CELL>
+int solve_tableau_any(pipamd_engine *e, int nvar, int nparm, int ni, int nc, int bigparm, int nq, const int64_t *ineq,
+                      const int64_t *ctx, int simplify, int deepest_cut, CELL **cells, size_t *n_cells, int *status,
+                      int64_t *pivots) {
+  if (!e) return PIPAMD_E_INVALID;
+  if (hipSetDevice(e->device) != hipSuccess) return PIPAMD_E_HIP;
+  try {
+    int rc;
+    if (cells && n_cells && valid_shape(nvar, nparm, ni, nc, bigparm, ineq, ctx) &&  // a small problem: wholly on the device
+        device_tree_one<E>(e, pipamd_problem{nvar, nparm, ni, nc, bigparm, nq, ineq, ctx}, simplify, deepest_cut, 0, cells,
+                           n_cells, &rc, status, pivots))
+      return rc;
+    TreeT<E> t(e, deepest_cut);
+    return solve_one(t, nvar, nparm, ni, nc, bigparm, nq, ineq, ctx, simplify, deepest_cut, cells, n_cells, status, pivots);
+  } catch (int code) {
+    return code;
+  }
 }
 
-// The same on 128-bit entries (the overflow-safe flavour): one TreeT<__int128> per host thread.
-extern "C" int pipamd_solve_tableaux128(pipamd_engine *e, int n, const pipamd_problem *probs, int simplify, int deepest_cut,
-                                        int nthreads, pipamd_sol_cell128 **cells, size_t *n_cells, int *rcs, int *statuses,
-                                        int64_t *pivots) {
+// traiter() (traiter.c:628-791) behind the reference's own front ends: see include/piplib_amd.h
+template <class E, class CELL>
+int traiter_any(pipamd_engine *e, int nvar, int nparm, int ni, int nc, int bigparm, int flags, int deepest_cut,
+                const int64_t *tableau, const int64_t *context, CELL **cells, size_t *n_cells, int *status, int64_t *pivots) {
+  if (!e || !cells || !n_cells || !valid_shape(nvar, nparm, ni, nc, bigparm, tableau, context)) return PIPAMD_E_INVALID;
+  if ((flags & ~(PIPAMD_T_INT | PIPAMD_T_DUAL)) || ((flags & PIPAMD_T_INT) && (flags & PIPAMD_T_DUAL))) {
+    pipamd_set_error("pipamd_traiter: flags must be 0, PIPAMD_T_INT or PIPAMD_T_DUAL (the dual needs a rational solve)");
+    return PIPAMD_E_INVALID;
+  }
+  if (hipSetDevice(e->device) != hipSuccess) return PIPAMD_E_HIP;
+  *cells = nullptr;
+  *n_cells = 0;
+  if (status) *status = 0;
+  if (pivots) *pivots = 0;
+  try {
+    const pipamd_problem p{nvar, nparm, ni, nc, bigparm, (flags & PIPAMD_T_INT) ? 1 : 0, tableau, context};
+    int rc;  // a small problem (with or without the dual): wholly on the device
+    if (device_tree_one<E>(e, p, 0, deepest_cut, Q_NO_CONTEXT_TEST | ((flags & PIPAMD_T_DUAL) ? Q_DUAL : 0), cells, n_cells, &rc,
+                           status, pivots))
+      return rc;
+    TreeT<E> t(e, deepest_cut);
+    return traiter_one(t, p, flags, deepest_cut, cells, n_cells, status, pivots);
+  } catch (int code) {
+    return code;
+  }
+}
+
+// Many independent problems: the small ones wholly on the device, in one launch, then `nthreads` host trees for the rest.
+// rcs[i] receives what pipamd_solve_tableau would have returned for problem i.
+template <class E, class CELL>
+int solve_tableaux_any(pipamd_engine *e, int n, const pipamd_problem *probs, int simplify, int deepest_cut, int nthreads,
+                       CELL **cells, size_t *n_cells, int *rcs, int *statuses, int64_t *pivots) {
   if (!many_args(e, n, probs, nthreads, cells, n_cells, rcs, statuses, pivots)) return PIPAMD_E_INVALID;
   std::vector<char> served(n > 0 ? n : 1, 0);
-  if (hipSetDevice(e->device) == hipSuccess)  // small problems: wholly on the device, in one launch
-    device_tree_many<i128>(e, n, probs, simplify, deepest_cut, served, cells, n_cells, rcs, statuses, pivots);
-  return solve_many<TreeT<i128>, pipamd_sol_cell128>(e, n, probs, simplify, deepest_cut, nthreads, cells, n_cells, rcs, statuses,
-                                                     pivots, served);
+  if (hipSetDevice(e->device) == hipSuccess) {
+    std::vector<FResultT<E>> res;
+    try_device_tree<E>(e, n, probs, simplify, deepest_cut, nullptr, false, res);
+    export_results(res, served, cells, n_cells, rcs, statuses, pivots);
+  }
+  run_workers<TreeT<E>>(e, deepest_cut, nthreads, n, served, [&](TreeT<E> &t, int i) {  // (started even with nothing left)
+    int st = 0;
+    int64_t pv = 0;
+    rcs[i] = solve_one(t, probs[i], simplify, deepest_cut, &cells[i], &n_cells[i], &st, &pv);
+    if (statuses) statuses[i] = st;
+    if (pivots) pivots[i] = pv;
+  });
+  return PIPAMD_OK;
 }
 
 // traiter() for many problems: the device tree first, each problem with its own flags (no context test, no tab_simplify:
 // the semantics of pipamd_traiter, not maind.c's), then `nthreads` host trees for what it did not serve.
 template <class E, class CELL>
-static void device_traiter_many(pipamd_engine *e, int n, const pipamd_problem *probs, const int *qflags, int deepest_cut,
-                                std::vector<char> &served, CELL **cells, size_t *n_cells, int *rcs, int *statuses,
-                                int64_t *pivots);
-
-template <class E, class CELL>
-static int traiter_many_any(pipamd_engine *e, int n, const pipamd_problem *probs, const int *flags, int deepest_cut, int nthreads,
-                            CELL **cells, size_t *n_cells, int *rcs, int *statuses, int64_t *pivots) {
+int traiter_many_any(pipamd_engine *e, int n, const pipamd_problem *probs, const int *flags, int deepest_cut, int nthreads,
+                     CELL **cells, size_t *n_cells, int *rcs, int *statuses, int64_t *pivots) {
   if (!many_args(e, n, probs, nthreads, cells, n_cells, rcs, statuses, pivots)) return PIPAMD_E_INVALID;
   if (n <= 0) return PIPAMD_OK;
   // the problems as traiter_any hands them on: nq says integer or rational; QProb::flags carries the rest
@@ -1187,54 +975,64 @@ static int traiter_many_any(pipamd_engine *e, int n, const pipamd_problem *probs
     tp[i].nq = (f & PIPAMD_T_INT) ? 1 : 0;
     qfl[i] = Q_NO_CONTEXT_TEST | ((f & PIPAMD_T_DUAL) ? Q_DUAL : 0);
   }
-  if (hipSetDevice(e->device) == hipSuccess)
-    device_traiter_many<E>(e, n, tp.data(), qfl.data(), deepest_cut, served, cells, n_cells, rcs, statuses, pivots);
-  std::atomic<int> next(0);
-  const int device = e->device;
-  auto worker = [&]() {
-    if (hipSetDevice(device) != hipSuccess) return;
-    try {
-      TreeT<E> t(e, deepest_cut);
-      for (;;) {
-        const int i = next.fetch_add(1);
-        if (i >= n) break;
-        if (served[i]) continue;
-        const pipamd_problem &p = tp[i];
-        int rc = PIPAMD_OK;
-        t.reset(deepest_cut);
-        try {
-          t.traiter_call(p.nvar, p.nparm, p.ni, p.nc, p.bigparm, tfl[i], (const i64 *)p.ineq, (const i64 *)p.ctx);
-        } catch (int code) {
-          rc = code;
-          if (statuses) statuses[i] = t.fail_status;
-          if (rc == PIPAMD_E_SOLVER)
-            pipamd_set_error("solver stopped with status %d (5 = the reference's \"Integer overflow\" exit)", t.fail_status);
-        }
-        if (pivots) pivots[i] = t.pivots;
-        rcs[i] = rc ? rc : export_tape(t.tape, &cells[i], &n_cells[i]);
-      }
-    } catch (int) {  // the tree could not be set up (stream creation failed): its problems stay E_HIP
-    }
-  };
-  bool rest = false;
-  for (int i = 0; i < n && !rest; i++) rest = !served[i];
-  if (rest) {
-    std::vector<std::thread> th;
-    for (int k = 0; k < nthreads; k++) th.emplace_back(worker);
-    for (auto &x : th) x.join();
+  if (hipSetDevice(e->device) == hipSuccess) {
+    std::vector<FResultT<E>> res;
+    try_device_tree<E>(e, n, tp.data(), 0, deepest_cut, qfl.data(), false, res);
+    export_results(res, served, cells, n_cells, rcs, statuses, pivots);
   }
+  if (std::find(served.begin(), served.end(), 0) != served.end())  // (no threads when nothing is left)
+    run_workers<TreeT<E>>(e, deepest_cut, nthreads, n, served, [&](TreeT<E> &t, int i) {
+      rcs[i] = traiter_one(t, tp[i], tfl[i], deepest_cut, &cells[i], &n_cells[i], statuses ? &statuses[i] : nullptr,
+                           pivots ? &pivots[i] : nullptr);
+    });
   return PIPAMD_OK;
+}
+
+}  // namespace
+
+extern "C" int pipamd_solve_tableau(pipamd_engine *e, int nvar, int nparm, int ni, int nc, int bigparm, int nq,
+                                    const int64_t *ineq, const int64_t *ctx, int simplify, int deepest_cut,
+                                    pipamd_sol_cell **cells, size_t *n_cells, int *status, int64_t *pivots) {
+  return solve_tableau_any<i64>(e, nvar, nparm, ni, nc, bigparm, nq, ineq, ctx, simplify, deepest_cut, cells, n_cells, status,
+                                pivots);
+}
+extern "C" int pipamd_solve_tableau128(pipamd_engine *e, int nvar, int nparm, int ni, int nc, int bigparm, int nq,
+                                       const int64_t *ineq, const int64_t *ctx, int simplify, int deepest_cut,
+                                       pipamd_sol_cell128 **cells, size_t *n_cells, int *status, int64_t *pivots) {
+  return solve_tableau_any<i128>(e, nvar, nparm, ni, nc, bigparm, nq, ineq, ctx, simplify, deepest_cut, cells, n_cells, status,
+                                 pivots);
+}
+extern "C" int pipamd_traiter(pipamd_engine *e, int nvar, int nparm, int ni, int nc, int bigparm, int flags,
+                              int deepest_cut, const int64_t *tableau, const int64_t *context,
+                              pipamd_sol_cell **cells, size_t *n_cells, int *status, int64_t *pivots) {
+  return traiter_any<i64>(e, nvar, nparm, ni, nc, bigparm, flags, deepest_cut, tableau, context, cells, n_cells, status,
+                          pivots);
+}
+extern "C" int pipamd_traiter128(pipamd_engine *e, int nvar, int nparm, int ni, int nc, int bigparm, int flags,
+                                 int deepest_cut, const int64_t *tableau, const int64_t *context,
+                                 pipamd_sol_cell128 **cells, size_t *n_cells, int *status, int64_t *pivots) {
+  return traiter_any<i128>(e, nvar, nparm, ni, nc, bigparm, flags, deepest_cut, tableau, context, cells, n_cells, status,
+                           pivots);
+}
+extern "C" int pipamd_solve_tableaux(pipamd_engine *e, int n, const pipamd_problem *probs, int simplify, int deepest_cut,
+                                     int nthreads, pipamd_sol_cell **cells, size_t *n_cells, int *rcs, int *statuses,
+                                     int64_t *pivots) {
+  return solve_tableaux_any<i64>(e, n, probs, simplify, deepest_cut, nthreads, cells, n_cells, rcs, statuses, pivots);
+}
+extern "C" int pipamd_solve_tableaux128(pipamd_engine *e, int n, const pipamd_problem *probs, int simplify, int deepest_cut,
+                                        int nthreads, pipamd_sol_cell128 **cells, size_t *n_cells, int *rcs, int *statuses,
+                                        int64_t *pivots) {
+  return solve_tableaux_any<i128>(e, n, probs, simplify, deepest_cut, nthreads, cells, n_cells, rcs, statuses, pivots);
 }
 extern "C" int pipamd_traiter_many(pipamd_engine *e, int n, const pipamd_problem *probs, const int *flags, int deepest_cut,
                                    int nthreads, pipamd_sol_cell **cells, size_t *n_cells, int *rcs, int *statuses,
                                    int64_t *pivots) {
-  return traiter_many_any<i64, pipamd_sol_cell>(e, n, probs, flags, deepest_cut, nthreads, cells, n_cells, rcs, statuses, pivots);
+  return traiter_many_any<i64>(e, n, probs, flags, deepest_cut, nthreads, cells, n_cells, rcs, statuses, pivots);
 }
 extern "C" int pipamd_traiter_many128(pipamd_engine *e, int n, const pipamd_problem *probs, const int *flags, int deepest_cut,
                                       int nthreads, pipamd_sol_cell128 **cells, size_t *n_cells, int *rcs, int *statuses,
                                       int64_t *pivots) {
-  return traiter_many_any<i128, pipamd_sol_cell128>(e, n, probs, flags, deepest_cut, nthreads, cells, n_cells, rcs, statuses,
-                                                    pivots);
+  return traiter_many_any<i128>(e, n, probs, flags, deepest_cut, nthreads, cells, n_cells, rcs, statuses, pivots);
 }
 
 // =========================================================================== Forest
@@ -1246,14 +1044,6 @@ extern "C" int pipamd_traiter_many128(pipamd_engine *e, int n, const pipamd_prob
 //   (all runnable jobs of all problems) -> gather pass (undecided rows / cut rows / solutions).
 // Problems that hit a rare path (capacity growth, deepest cuts, dual) are handed to the Tree.
 namespace {
-
-template <class E> struct FResultT {
-  int rc = PIPAMD_OK, status = 0;
-  long long pivots = 0;
-  bool is_void = false;
-  std::vector<CellT<E>> tape;
-};
-typedef FResultT<i64> FResult;
 
 // E = the entry type of the device tableaux, of the contexts, cut rows and tape cells on the host: long long, or __int128
 // for the overflow-safe flavour (the same scheduler; blocks, patches and gathered records are EW = 1 or 2 int64 words a value).
@@ -1450,6 +1240,9 @@ class ForestT {
     P_[i].tape.push_back(Cell{kind, a, b});
     if (P_[i].tape.size() >= 4096) fail(i, PIPAMD_ST_INTERNAL);
   }
+  auto tape_out(int i) {  // problem i's tape as the shared formulas write to it
+    return [this, i](int kind, E a, E b) { tape_push(i, kind, a, b); };
+  }
 
   // ---- patches ------------------------------------------------------------
   void patch32(size_t dst32, const int *data, int n32) {
@@ -1514,12 +1307,12 @@ class ForestT {
       fresh_vals(&v, 1);
     }
   }
-  int context_job(int i, const Ctx &ctx, int nparm, int nc, const std::vector<E> *extra) {
+  int context_job(int i, const Ctx &ctx, int nparm, int nc, const E *extra) {
     const int ni = nc + (extra ? 1 : 0), ncol = nparm + 1;
     const int job = new_job(i, nparm, 0, ni, -1, PIPAMD_T_INT, ni + 16, ncol);
     fresh_begin(job);
     for (int k = 0; k < nc; k++) fresh_vals(&ctx.v[(size_t)k * ctx.width], ncol);
-    if (extra) fresh_vals(extra->data(), ncol);
+    if (extra) fresh_vals(extra, ncol);
     is_sub_[job] = 1;
     return job;
   }
@@ -1662,10 +1455,7 @@ class ForestT {
     }
     // the parent was waiting for its "then" branch: now the "else" branch (traiter.c:751-758)
     Frame &f = q.stack.back();
-    const int nc = f.ctx.nc;
-    for (int j = 0; j < f.nparm; j++) f.ctx.at(nc, j) = wneg(f.ctx.at(nc, j));
-    f.ctx.at(nc, f.nparm) = wneg(wadd(f.ctx.at(nc, f.nparm), (E)1));
-    f.ctx.nc = nc + 1;
+    fork_else(f.ctx, f.nparm);
     patch_flag(jobs_[f.job], f.split_row, PIPAMD_F_MINUS);
     jobs_[f.job].status = PIPAMD_ST_RUN;
     f.split_row = -1;
@@ -1700,13 +1490,7 @@ class ForestT {
     switch (st) {
       case PIPAMD_ST_SOLUTION: {
         const E *g = gathered(f.job);
-        const int nvar = q.nvar, np = f.nparm;
-        const size_t nn = (size_t)nvar * (np + 1);
-        tape_push(i, S_LIST, (E)nvar, (E)0);
-        for (int r = 0; r < nvar; r++) {
-          tape_push(i, S_FORM, (E)(np + 1), (E)0);
-          for (int j = 0; j <= np; j++) tape_push(i, S_VAL, g[(size_t)r * (np + 1) + j], g[nn + r]);
-        }
+        push_solution(tape_out(i), q.nvar, f.nparm, g, g + (size_t)q.nvar * (f.nparm + 1));
         pop_frame(i);
         return;
       }
@@ -1733,19 +1517,15 @@ class ForestT {
     f.rowvals.clear();
     f.sub_begin = (int)jobs_.size();
     f.sub_count = 0;
+    std::vector<E> ex_plus(np + 1), ex_minus(np + 1);
     for (int t = 0; t < nrec; t++) {
       const E *r = g + 1 + (size_t)t * rec;
       f.rows.push_back((int)r[0]);
       f.critic.push_back((int)r[1]);
-      std::vector<E> rv(r + 2, r + 3 + np);  // constant | parameters
-      f.rowvals.push_back(rv);
-      std::vector<E> ex(np + 1);
-      for (int j = 0; j < np; j++) ex[j] = rv[1 + j];
-      ex[np] = r[1] != 0 ? rv[0] : wsub(rv[0], (E)1);
-      context_job(i, f.ctx, np, f.ctx.nc, &ex);
-      for (int j = 0; j < np; j++) ex[j] = wneg(rv[1 + j]);
-      ex[np] = wsub(wneg(rv[0]), (E)1);
-      context_job(i, f.ctx, np, f.ctx.nc, &ex);
+      f.rowvals.emplace_back(r + 2, r + 3 + np);  // constant | parameters
+      compa_rows(r[2], r + 3, np, r[1] != 0, ex_plus.data(), ex_minus.data());
+      context_job(i, f.ctx, np, f.ctx.nc, ex_plus.data());
+      context_job(i, f.ctx, np, f.ctx.nc, ex_minus.data());
       f.sub_count += 2;
     }
     f.phase = PH_COMPA;
@@ -1769,14 +1549,7 @@ class ForestT {
         if (s->status == PIPAMD_ST_CAPACITY || s->status == PIPAMD_ST_NEED_PARMCUT) throw (int)PIPAMD_E_TOOLARGE;
         if (s->status != PIPAMD_ST_SOLUTION && s->status != PIPAMD_ST_NIL) fail(i, s->status);
       }
-      const bool cp = jp.status != PIPAMD_ST_NIL, cm = jm.status != PIPAMD_ST_NIL;
-      int fl;
-      if (cp && cm)
-        fl = f.critic[t] ? PIPAMD_F_CRITIC : PIPAMD_F_UNKNOWN;
-      else if (cm)
-        fl = PIPAMD_F_MINUS;
-      else
-        fl = cp ? PIPAMD_F_PLUS : PIPAMD_F_ZERO;
+      const int fl = compa_flag(jp.status == PIPAMD_ST_NIL, jm.status == PIPAMD_ST_NIL, f.critic[t] != 0);
       newflag[t] = fl;
       patch_flag(pj, f.rows[t], fl);
       if (fl == PIPAMD_F_MINUS) break;
@@ -1828,26 +1601,14 @@ class ForestT {
     clones_.push_back(pj.rows_off);
     clones_.push_back(cj.rows_off);
     clones_.push_back(pj.sol_off - pj.rows_off);  // row tables and rows
-    tape_push(i, S_IF, (E)0, (E)0);
-    tape_push(i, S_FORM, (E)(np + 1), (E)0);
-    E g = 0;
-    for (int j = 0; j < np; j++) g = gcd(g, rv[1 + j]);
-    if (!(f.flags & PIPAMD_T_INT)) g = gcd(g, rv[0]);
-    const int nc = f.ctx.nc;
-    f.ctx.reserve(nc + 1, np + 2);
-    for (int j = 0; j < np; j++) {
-      f.ctx.at(nc, j) = cquo(rv[1 + j], g);
-      tape_push(i, S_VAL, f.ctx.at(nc, j), (E)1);
-    }
-    f.ctx.at(nc, np) = (f.flags & PIPAMD_T_INT) ? floordiv(rv[0], g) : cquo(rv[0], g);
-    tape_push(i, S_VAL, f.ctx.at(nc, np), (E)1);
+    fork_row(rv[0], rv.data() + 1, np, (f.flags & PIPAMD_T_INT) != 0, f.ctx, tape_out(i));
     // the clone pass runs before the patch pass, so the copy still has the flags from before this
     // compa_test: give it the refreshed ones (expanser copies them, traiter.c:717), then Plus
     for (size_t k = 0; k < f.rows.size(); k++)
       if ((int)k != t && newflag[k] >= 0) patch_flag(cj, f.rows[k], newflag[k]);
     patch_flag(cj, pivi, PIPAMD_F_PLUS);
     c.ctx = f.ctx;
-    c.ctx.nc = nc + 1;
+    c.ctx.nc = f.ctx.nc + 1;
     f.split_row = pivi;
     q.stack.push_back(c);  // (f is invalid from here on)
   }
@@ -1861,40 +1622,17 @@ class ForestT {
     const E *g = gathered(f.job);
     const int nvar = q.nvar, ni = f.ni;
     int nparm = f.nparm;
-    const int ncol = nvar + nparm + 1, nligne = nvar + ni;
-    if (ncol >= PIPAMD_MAXCOL) fail(i, PIPAMD_ST_MAXCOL);
+    const int nligne = nvar + ni;
+    if (nvar + nparm + 1 >= PIPAMD_MAXCOL) fail(i, PIPAMD_ST_MAXCOL);
     const E D = g[1];
-    const E *r = g + 2;
-    std::vector<E> cut(ncol + 1);
-    bool ok_var = false, ok_parm = false;
-    for (int j = 0; j < nvar; j++) {
-      cut[j] = fmod_(r[j], D);
-      if (cut[j] > 0) ok_var = true;
-    }
-    cut[nvar] = wneg(fmod_(wneg(r[nvar]), D));
-    for (int j = nvar + 1; j < ncol; j++) {
-      if (j == f.bigparm) {
-        cut[j] = 0;
-        continue;
-      }
-      cut[j] = wneg(fmod_(wneg(r[j]), D));
-      if (cut[j] != 0) ok_parm = true;
-    }
-    cut[ncol] = D;
-    if (!ok_parm) throw (int)PIPAMD_E_TOOLARGE;  // only reached with options the Tree handles
-    typename Ctx::Quotient k{std::vector<E>(cut.begin() + nvar + 1, cut.begin() + ncol), cut[nvar], D};
-    int parm = f.ctx.find_quotient(nparm, k);
-    if (parm == -1) {  // a new parameter on this problem's tape and context
-      Ctx::announce_quotient([&](int kind, E a, E b) { tape_push(i, kind, a, b); }, nparm, k);
-      parm = f.ctx.define_quotient(nparm, k);
-      nparm++;
-    }
-    if (!ok_var) fail(i, PIPAMD_ST_INTERNAL);  // assert(ok_var), integrer.c:499
-    const int newcol = nvar + 1 + parm;
+    std::vector<E> row;
+    int newcol;
+    // (a new parameter goes to this problem's tape and context)
+    const CutKind kind = pip_steps::parm_cut(g + 2, D, nvar, nparm, f.bigparm, false, f.ctx, tape_out(i), row, newcol);
+    if (kind == CUT_NONE || kind == CUT_CONST) throw (int)PIPAMD_E_TOOLARGE;  // only reached with options the Tree handles
+    if (kind == CUT_NO_VAR) fail(i, PIPAMD_ST_INTERNAL);
     if (ni >= pj.S || nligne >= pj.L || nvar + nparm + 1 > pj.W) throw (int)PIPAMD_E_TOOLARGE;
-    std::vector<E> row(pj.W, 0);
-    for (int j = 0; j < ncol; j++) row[j] = cut[j];
-    row[newcol] = wadd(row[newcol], cut[ncol]);
+    row.resize(pj.W, 0);
     patch_vals((size_t)pj.vals_off + (size_t)ni * pj.W * EW, row.data(), row.size());
     patch_vals((size_t)pj.rows_off + (size_t)nligne * EW, &D, 1);
     patch_flag(pj, nligne, PIPAMD_F_MINUS);
@@ -1909,7 +1647,6 @@ class ForestT {
     pj.status = PIPAMD_ST_RUN;
   }
 };
-typedef ForestT<i64> Forest;
 
 }  // namespace
 
@@ -2098,16 +1835,14 @@ void device_tree_chunk(pipamd_engine *e, const std::vector<int> &idx, const pipa
 // qflags: QProb::flags of every problem (null: 0 for all); a negative entry keeps its problem out of the device tree
 template <class E>
 void device_tree(pipamd_engine *e, int n, const pipamd_problem *probs, int simplify, int deepest_cut, std::vector<FResultT<E>> &res,
-                 int *served, int *handed_back, const int *qflags = nullptr) {
+                 int *served, int *handed_back, const int *qflags) {
   constexpr int EBITS = 64 * (int)(sizeof(E) / 8);
   struct Hold {  // the engine's device-tree buffers serve one call at a time
     pthread_mutex_t *m;
     explicit Hold(pthread_mutex_t *mm) : m(mm) { pthread_mutex_lock(m); }
     ~Hold() { pthread_mutex_unlock(m); }
   } hold(&e->dt_lock);
-  // chunks of problems whose stack + tape regions fit the budget (PIPAMD_FOREST_ARENA_MB, default 4096)
-  size_t budget = (size_t)4096 << 20;
-  if (const char *mb = getenv("PIPAMD_FOREST_ARENA_MB")) budget = (size_t)strtoull(mb, nullptr, 10) << 20;
+  const size_t budget = forest_arena_budget();  // chunks of problems whose stack + tape regions fit it
   std::vector<int> idx;
   QCaps cap;
   memset(&cap, 0, sizeof cap);
@@ -2169,72 +1904,8 @@ extern "C" int pipamd_device_tree_fits(const pipamd_problem *p, int entier_bits)
   return device_tree_caps(*p, entier_bits, c) ? 1 : 0;
 }
 
-template <class E>
-static bool device_tree_one(pipamd_engine *e, const pipamd_problem &p, int simplify, int deepest_cut, int qflags,
-                            std::vector<CellT<E>> &tape, bool *is_void, int64_t *pivots) {
-  if (e->no_device_tree || getenv("PIPAMD_NO_DEVICE_TREE")) return false;
-  std::vector<FResultT<E>> res(1);
-  res[0].rc = PIPAMD_E_TOOLARGE;
-  int served = 0, back = 0;
-  device_tree<E>(e, 1, &p, simplify, deepest_cut, res, &served, &back, &qflags);
-  pthread_mutex_lock(&e->dt_lock);
-  e->dt_served = served;  // (pipamd_last_device_tree also answers for the one-problem entries)
-  e->dt_fallback = back;
-  pthread_mutex_unlock(&e->dt_lock);
-  if (res[0].rc != PIPAMD_OK) return false;
-  tape.swap(res[0].tape);
-  *is_void = res[0].is_void;
-  *pivots = res[0].pivots;
-  return true;
-}
-
-template <class E, class CELL>
-static void device_tree_many(pipamd_engine *e, int n, const pipamd_problem *probs, int simplify, int deepest_cut,
-                             std::vector<char> &served, CELL **cells, size_t *n_cells, int *rcs, int *statuses,
-                             int64_t *pivots) {
-  e->dt_served = e->dt_fallback = 0;
-  if (e->no_device_tree || getenv("PIPAMD_NO_DEVICE_TREE") || n <= 0) return;
-  std::vector<FResultT<E>> res(n);
-  for (auto &r : res) r.rc = PIPAMD_E_TOOLARGE;
-  device_tree<E>(e, n, probs, simplify, deepest_cut, res, &e->dt_served, &e->dt_fallback);
-  for (int i = 0; i < n; i++) {
-    if (res[i].rc != PIPAMD_OK) continue;
-    served[i] = 1;
-    cells[i] = nullptr;
-    n_cells[i] = 0;
-    if (statuses) statuses[i] = 0;
-    if (pivots) pivots[i] = res[i].pivots;
-    rcs[i] = res[i].is_void ? PIPAMD_OK : export_tape(res[i].tape, &cells[i], &n_cells[i]);
-  }
-}
-
-template <class E, class CELL>
-static void device_traiter_many(pipamd_engine *e, int n, const pipamd_problem *probs, const int *qflags, int deepest_cut,
-                                std::vector<char> &served, CELL **cells, size_t *n_cells, int *rcs, int *statuses,
-                                int64_t *pivots) {
-  e->dt_served = e->dt_fallback = 0;
-  if (e->no_device_tree || getenv("PIPAMD_NO_DEVICE_TREE") || n <= 0) return;
-  std::vector<FResultT<E>> res(n);
-  for (auto &r : res) r.rc = PIPAMD_E_TOOLARGE;
-  device_tree<E>(e, n, probs, 0, deepest_cut, res, &e->dt_served, &e->dt_fallback, qflags);
-  for (int i = 0; i < n; i++) {
-    if (res[i].rc != PIPAMD_OK || served[i]) continue;
-    served[i] = 1;
-    if (statuses) statuses[i] = 0;
-    if (pivots) pivots[i] = res[i].pivots;
-    rcs[i] = export_tape(res[i].tape, &cells[i], &n_cells[i]);
-  }
-}
-
 // Many problems: the device tree first (small problems), then the lock-step Forest; the few that need
 // a rare path are finished by the Tree.
-template <class E>
-static void lockstep_device_tree(pipamd_engine *e, int n, const pipamd_problem *probs, int simplify, int deepest_cut,
-                                 std::vector<FResultT<E>> &res) {
-  if (!e->no_device_tree && !getenv("PIPAMD_NO_DEVICE_TREE"))
-    device_tree<E>(e, n, probs, simplify, deepest_cut, res, &e->dt_served, &e->dt_fallback);
-}
-
 template <class E, class CELL>
 static int lockstep_any(pipamd_engine *e, int n, const pipamd_problem *probs, int simplify, int deepest_cut, CELL **cells,
                         size_t *n_cells, int *rcs, int *statuses, int64_t *pivots) {
@@ -2243,10 +1914,8 @@ static int lockstep_any(pipamd_engine *e, int n, const pipamd_problem *probs, in
   typedef TreeT<E> Tree;
   if (!e || n < 0 || (n && (!probs || !cells || !n_cells || !rcs))) return PIPAMD_E_INVALID;
   if (hipSetDevice(e->device) != hipSuccess) return PIPAMD_E_HIP;
-  std::vector<FResult> res(n);
-  for (auto &r : res) r.rc = PIPAMD_E_TOOLARGE;  // until a path has served it
-  e->dt_served = e->dt_fallback = 0;
-  lockstep_device_tree<E>(e, n, probs, simplify, deepest_cut, res);
+  std::vector<FResult> res;  // rc == PIPAMD_E_TOOLARGE until a path has served the problem
+  try_device_tree<E>(e, n, probs, simplify, deepest_cut, nullptr, false, res);
   std::vector<int> rest;
   for (int i = 0; i < n; i++)
     if (res[i].rc == PIPAMD_E_TOOLARGE) rest.push_back(i);
@@ -2255,9 +1924,8 @@ static int lockstep_any(pipamd_engine *e, int n, const pipamd_problem *probs, in
     for (size_t k = 0; k < rest.size(); k++) rp[k] = probs[rest[k]];
     const int nr = (int)rest.size();
     // The forest reserves a worst-case region per problem; batches whose regions add up to more
-    // than the arena budget go through it in chunks (PIPAMD_FOREST_ARENA_MB, default 4096).
-    size_t budget = (size_t)4096 << 20;
-    if (const char *mb = getenv("PIPAMD_FOREST_ARENA_MB")) budget = (size_t)strtoull(mb, nullptr, 10) << 20;
+    // than the arena budget go through it in chunks.
+    const size_t budget = forest_arena_budget();
     try {
       Forest f(e->device);
       for (int lo = 0; lo < nr;) {
@@ -2287,11 +1955,9 @@ static int lockstep_any(pipamd_engine *e, int n, const pipamd_problem *probs, in
     if (res[i].rc == PIPAMD_E_TOOLARGE) {
       int st = 0;
       int64_t pv = 0;
-      const pipamd_problem &p = probs[i];
       try {
         if (!fallback) fallback = new Tree(e, deepest_cut);
-        rcs[i] = solve_one(*fallback, p.nvar, p.nparm, p.ni, p.nc, p.bigparm, p.nq, p.ineq, p.ctx, simplify, deepest_cut,
-                           &cells[i], &n_cells[i], &st, &pv);
+        rcs[i] = solve_one(*fallback, probs[i], simplify, deepest_cut, &cells[i], &n_cells[i], &st, &pv);
       } catch (int code) {
         rcs[i] = code;
       }
@@ -2314,8 +1980,9 @@ extern "C" int pipamd_solve_tableaux_lockstep(pipamd_engine *e, int n, const pip
                                               int *statuses, int64_t *pivots) {
   return lockstep_any<i64, pipamd_sol_cell>(e, n, probs, simplify, deepest_cut, cells, n_cells, rcs, statuses, pivots);
 }
-// The same on 128-bit entries (the overflow-safe flavour, include/piplib/piplib.h:42-88): ForestT<__int128> -- device tableaux,
-// contexts, cut rows and tape cells 128-bit --, the rare paths finished by a TreeT<__int128>.
+// The same on 128-bit entries (the overflow-safe flavour, include/piplib/piplib.h:42-88): the device tree's 128-bit instantiation
+// in front, then ForestT<__int128> -- device tableaux, contexts, cut rows and tape cells 128-bit --, the rare paths finished
+// by a TreeT<__int128>.
 extern "C" int pipamd_solve_tableaux_lockstep128(pipamd_engine *e, int n, const pipamd_problem *probs, int simplify,
                                                  int deepest_cut, pipamd_sol_cell128 **cells, size_t *n_cells, int *rcs,
                                                  int *statuses, int64_t *pivots) {

@@ -691,11 +691,12 @@ class PreparedProblems:
         self.sts = (C.c_int * max(1, n))()
         self.piv = (C.c_int64 * max(1, n))()
 
-    def results(self):
-        """[(text | None, rc, status, pivots)]; frees the cells"""
+    def results(self, bits=64):
+        """[(text | None, rc, status, pivots)]; frees the cells (bits=128: they are pipamd_sol_cell128)"""
+        take = _take_cells128 if bits == 128 else _take_cells
         out = []
         for i in range(self.n):
-            t = tape_text(_take_cells(self.cells[i], self.ncell[i])) if self.rcs[i] == 0 else None
+            t = tape_text(take(self.cells[i], self.ncell[i])) if self.rcs[i] == 0 else None
             out.append((t, self.rcs[i], self.sts[i], self.piv[i]))
         return out
 
@@ -711,51 +712,35 @@ def device_tree_fits(problem, bits=64):
     return rc
 
 
+def _many(fn_name, engine, prep, *ints):
+    """one pipamd_solve_tableaux* call on prepared problems: (engine, n, problems, ints ..., the five result arrays)"""
+    fn = getattr(lib(), fn_name)
+    fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * len(ints) + [C.c_void_p] * 5
+    _check(fn(engine._h, prep.n, prep.arr, *[int(x) for x in ints], prep.cells, prep.ncell, prep.rcs, prep.sts, prep.piv))
+
+
 def solve_tableaux128(engine, problems, simplify=True, deepest_cut=False, nthreads=8):
     """Many problems through pipamd_solve_tableaux128 (128-bit entries, a host thread and a TreeT<__int128> each).
     Returns a list of (text | None, rc, status, pivots)."""
     prep = PreparedProblems(problems)
-    L = lib()
-    L.pipamd_solve_tableaux128.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    _check(L.pipamd_solve_tableaux128(engine._h, prep.n, prep.arr, int(bool(simplify)), int(bool(deepest_cut)), int(nthreads),
-                                      prep.cells, prep.ncell, prep.rcs, prep.sts, prep.piv))
-    out = []
-    for i in range(prep.n):
-        t = tape_text(_take_cells128(prep.cells[i], prep.ncell[i])) if prep.rcs[i] == 0 else None
-        out.append((t, prep.rcs[i], prep.sts[i], prep.piv[i]))
-    return out
+    _many("pipamd_solve_tableaux128", engine, prep, bool(simplify), bool(deepest_cut), nthreads)
+    return prep.results(bits=128)
 
 
 def solve_tableaux_lockstep128(engine, problems, simplify=True, deepest_cut=False):
     """Many problems through pipamd_solve_tableaux_lockstep128 (128-bit entries, the lock-step scheduler).
     Returns a list of (text | None, rc, status, pivots)."""
     prep = PreparedProblems(problems)
-    L = lib()
-    L.pipamd_solve_tableaux_lockstep128.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
-                                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    _check(L.pipamd_solve_tableaux_lockstep128(engine._h, prep.n, prep.arr, int(bool(simplify)), int(bool(deepest_cut)),
-                                               prep.cells, prep.ncell, prep.rcs, prep.sts, prep.piv))
-    out = []
-    for i in range(prep.n):
-        t = tape_text(_take_cells128(prep.cells[i], prep.ncell[i])) if prep.rcs[i] == 0 else None
-        out.append((t, prep.rcs[i], prep.sts[i], prep.piv[i]))
-    return out
+    _many("pipamd_solve_tableaux_lockstep128", engine, prep, bool(simplify), bool(deepest_cut))
+    return prep.results(bits=128)
 
 
 def solve_prepared(engine, prep, simplify=True, deepest_cut=False, nthreads=8, lockstep=False):
     """the bare C call on prepared problems (what a C caller pays); prep.results() turns the cells into text"""
-    L = lib()
-    L.pipamd_solve_tableaux.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
-                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     if lockstep:
-        L.pipamd_solve_tableaux_lockstep.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
-                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        _check(L.pipamd_solve_tableaux_lockstep(engine._h, prep.n, prep.arr, int(bool(simplify)), int(bool(deepest_cut)),
-                                                prep.cells, prep.ncell, prep.rcs, prep.sts, prep.piv))
+        _many("pipamd_solve_tableaux_lockstep", engine, prep, bool(simplify), bool(deepest_cut))
     else:
-        _check(L.pipamd_solve_tableaux(engine._h, prep.n, prep.arr, int(bool(simplify)), int(bool(deepest_cut)),
-                                       int(nthreads), prep.cells, prep.ncell, prep.rcs, prep.sts, prep.piv))
+        _many("pipamd_solve_tableaux", engine, prep, bool(simplify), bool(deepest_cut), nthreads)
 
 
 def solve_tableaux(engine, problems, simplify=True, deepest_cut=False, nthreads=8, lockstep=False):

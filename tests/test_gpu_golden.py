@@ -359,3 +359,36 @@ def test_dual_on_the_device_tree_vs_host_tree(seed, shape):
         assert got == want
         compared += 1
     assert compared >= 30 and served >= 0.9 * compared, (compared, served)
+
+
+@pytest.mark.parametrize("bits", [64, 128])
+def test_four_host_entries_agree_entry_by_entry(bits):
+    """One small family through the four entries of the host schedulers with the device tree off -- the one-problem entry
+    (a Tree), the threaded one (a Tree per thread), the lock-step one (the Forest) and pipamd_traiter_many with T_INT (a
+    Tree per thread, no front end) -- in both widths: the same tape and the same pivot count, problem by problem.  The
+    problems are the reference's own parametric integer inputs without a context (so that traiter() alone is the whole
+    of the front end's work); three of them take a parametric cut and a fork, whose formulas Tree and Forest share
+    (csrc/pip_tree_steps.h).  The goldens pin the one-problem entry: test_dat_golden_on_gpu[host-tree]."""
+    from types import SimpleNamespace
+    from piplib_amd import engine as eng
+    names = ["max", "pairi", "rairoi", "equus", "loz"]
+    probs = [SimpleNamespace(**next(iter(read_dat(os.path.join(G, "test", n + ".dat"))))) for n in names]
+    assert all(p.nq == 1 and p.nc == 0 and p.nparm > 0 for p in probs)
+    e = eng.Engine(0)
+    e.set_device_tree(False)
+    one = [eng.solve_tableau_cells(e, p.nvar, p.nparm, p.ni, p.nc, p.bigparm, p.nq, p.ineq, p.ctx, simplify=False, bits=bits)
+           for p in probs]
+    assert sum(any(c[0] == eng.SOL_NEW for c in cells) for cells, _ in one) >= 3
+    assert sum(any(c[0] == eng.SOL_IF for c in cells) for cells, _ in one) >= 3
+    want = [(eng.tape_text(cells), 0, 0, piv) for cells, piv in one]
+    if bits == 128:
+        threaded = eng.solve_tableaux128(e, probs, simplify=False, nthreads=3)
+        lockstep = eng.solve_tableaux_lockstep128(e, probs, simplify=False)
+    else:
+        threaded = eng.solve_tableaux(e, probs, simplify=False, nthreads=3)
+        lockstep = eng.solve_tableaux(e, probs, simplify=False, lockstep=True)
+    many = eng.traiter_many(e, probs, flags=[eng.T_INT] * len(probs), nthreads=3, bits=bits)
+    assert e.last_device_tree() == (0, 0)
+    assert threaded == want
+    assert lockstep == want
+    assert many == [(cells, 0, 0, piv) for cells, piv in one]
