@@ -128,6 +128,12 @@ int pipamd_engine_set_tail_waves(pipamd_engine *e, int waves);
  * launches run beside it; for a lone batch it is a long, nearly empty launch, and the tableaux go straight to the
  * tail launches instead (a lone 10k batch: 4.7 ms instead of 6.3 ms; 14 batches in flight: 10 % fewer pivots/s). */
 int pipamd_engine_set_lone_batches(pipamd_engine *e, int on);
+/* The second lean launch of a bulk batch has a block per tableau over a list of the few hundred the first one paused.
+ * 1 (default): its blocks beyond the list replay the determinant logs of the tableaux the first launch finished, beside
+ * the launch's own tableaux, and the replay behind the launches, which then finds most logs empty, goes out a wave per
+ * tableau.  0: that replay does all the work, a lane per tableau (the sequence of rounds 3 to 5).  Same statuses, pivot
+ * counts and solutions either way; the switch is for measurements. */
+int pipamd_engine_set_spare_replay(pipamd_engine *e, int on);
 /* 128-bit batches without parameters of 129 ... 256 columns (at least 128 tableaux): 1 = the first launch of
  * pipamd_batch_solve is pip_lean64_kernel (csrc/pip_lean.h, long long rows) -- one wave per tableau, rows held as long longs while every
  * entry fits 63 bits (half the traffic and registers), tableaux with a wider entry handed over to the 128-bit kernel.
@@ -387,7 +393,7 @@ int pipamd_engine_set_timing(pipamd_engine *e, int on);
 int pipamd_last_solve_launches(pipamd_engine *e);
 /* pipamd_batch_solve serves a batch of >= 2048 tableaux with two queue-fed launches and no host
  * round trip in between: a bulk launch of persistent one-wave workgroups that draw tableaux from
- * a device queue and give one up when it is finished, has used `pivots` pivots (default 96) or
+ * a device queue and give one up when it is finished, has used `pivots` pivots (default 96; 128 where a second lean launch follows the first) or
  * `rows` Gomory-cut rows (default 48: the bulk launch's LDS image holds the input rows plus that
  * many, so that 24 tableaux fit a CU), and a tail launch that runs what is left to completion
  * with four waves per tableau. */

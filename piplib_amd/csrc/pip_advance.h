@@ -1254,6 +1254,69 @@ __device__ __forceinline__ bool det_step(T &det0, T &det1, T &det2, T &det3, int
   return true;
 }
 
+// (a determinant limb of a job header: det[i], or det[2i] | det[2i+1] << 64 with 128-bit entries)
+template <class T>
+__device__ __forceinline__ T det_limb(const PipJob *J, int i) {
+  if constexpr (sizeof(T) == 16)
+    return (T)(((u128)(u64)J->det[2 * i + 1] << 64) | (u64)J->det[2 * i]);
+  else
+    return (T)J->det[i];
+}
+template <class T>
+__device__ __forceinline__ void det_limb_store(PipJob *J, int i, T x) {
+  if constexpr (sizeof(T) == 16) {
+    J->det[2 * i] = (i64)(u64)(u128)x;
+    J->det[2 * i + 1] = (i64)(u64)((u128)x >> 64);
+  } else
+    J->det[i] = (i64)x;
+}
+// The determinant replay of ONE job by ONE lane (traiter.c:394-446 for the pivots the job's launches logged; the text on
+// the replay kernels, pip_kernels.hip): the lane walks the job's log alone, CH entries loaded at a time.  The body of
+// pip_det_replay_lanes_kernel, and of the lean kernel's spare blocks (pip_lean.h), which run it beside the launch's
+// own jobs.  Nothing else may write the job meanwhile.
+template <class T, int CH>
+__device__ __forceinline__ void det_replay_lane(PipJob *J, i64 *arena) {
+  const int nlog = J->nlog;
+  if (nlog <= 0 || (J->ebits == 128) != (sizeof(T) == 16)) return;
+  const T *lg = (const T *)(arena + J->log_off);
+  T det0 = det_limb<T>(J, 0), det1 = det_limb<T>(J, 1), det2 = det_limb<T>(J, 2), det3 = det_limb<T>(J, 3);
+  int ldet = J->ldet;
+  bool stop = false;
+  for (int k0 = 0; k0 < nlog && !stop; k0 += CH) {
+    T ev[CH][2];
+#pragma unroll
+    for (int u = 0; u < CH; u++) {
+      const bool in = k0 + u < nlog;
+      ev[u][0] = in ? lg[2 * (k0 + u)] : (T)1;
+      ev[u][1] = in ? lg[2 * (k0 + u) + 1] : (T)1;
+    }
+#pragma unroll
+    for (int u = 0; u < CH; u++) {
+      const int k = k0 + u;
+      if (k >= nlog || stop) break;
+      T ppivot = ev[u][0], dppiv = ev[u][1];
+      if (dppiv != 1) {
+        const T d = gcd_i64(ppivot, dppiv);
+        if (d != 1) {
+          ppivot = exact_quo(ppivot, d);
+          dppiv = exact_quo(dppiv, d);
+        }
+      }
+      if (!det_step<T>(det0, det1, det2, det3, ldet, ppivot, dppiv)) {
+        J->status = PIPAMD_ST_OVERFLOW;
+        J->npiv = J->npiv - nlog + k + 1;
+        stop = true;
+      }
+    }
+  }
+  det_limb_store<T>(J, 0, det0);
+  det_limb_store<T>(J, 1, det1);
+  det_limb_store<T>(J, 2, det2);
+  det_limb_store<T>(J, 3, det3);
+  J->ldet = ldet;
+  J->nlog = 0;
+}
+
 // flag exam_coef (traiter.c:121-154) gives an Unknown row, from its sign summary
 __device__ __forceinline__ int exam_class(int sg) {
   const int fc = SIG_CONST(sg) == 1 ? PIPAMD_F_PLUS : (SIG_CONST(sg) == 2 ? PIPAMD_F_MINUS : PIPAMD_F_ZERO);
@@ -1613,6 +1676,8 @@ struct PipQueue {
   int *out_list;
   int *out_count;
   int *out_maxni;
+  int replay_spare;  // pip_lean_kernel with an input list: the workgroups beyond *in_count replay the determinant
+                     // logs of the jobs that are NOT on the list, 64 jobs each (lean_spare_replay, pip_lean.h)
 };
 
 // ---------------------------------------------------------------- pieces of a pivot that work on the tables alone

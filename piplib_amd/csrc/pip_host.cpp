@@ -48,6 +48,8 @@ extern "C" int pipamd_engine_create(pipamd_engine **out, int device) {
     e->no_lean = nl && nl[0] == '1';
     const char *n2 = getenv("PIPAMD_NO_LEAN2");  // measurement aid: the general one-wave kernel as the second bulk launch
     e->no_lean2 = n2 && n2[0] == '1';
+    const char *sr = getenv("PIPAMD_NO_SPARE_REPLAY");  // measurement aid, like pipamd_engine_set_spare_replay(e, 0)
+    e->no_spare_replay = sr && sr[0] == '1';
   }
   pthread_mutex_init(&e->dt_lock, nullptr);
   *out = e;
@@ -188,6 +190,16 @@ extern "C" int pipamd_batch_load(pipamd_engine *e, void *d_ws, const pipamd_batc
 //         little parallelism is left, so the latency of a pivot is what counts.
 // Only then the host looks at the number of tableaux still running (normally 0; tableaux that
 // hit the per-launch pivot limit `iter_limit` go through further tail launches).
+/* Pivot budget per tableau of the first bulk launch where a second lean launch follows it (begin() takes it for that
+ * sequence alone, every other bulk launch has 96; pipamd_engine_set_round_pivots overrides both).  A tableau that has
+ * spent it waits for the whole launch to end, is widened, listed and re-packed by the second lean launch; of 256
+ * headline tableaux nine spend a budget of 96 and one a budget of 128 (tests/test_gpu_first_launch_budget.py).  Measured
+ * against 96, 160 and 256 with 16 batches in flight on 4 and on 16 hardware queues (DESIGN.md section 5 round 6,
+ * profiles/r06_ab.txt): 128 is ahead of 96 in every round; 160 and 256 are no better with batches in flight and lose
+ * 8-11 % for a batch on its own. */
+#ifndef PIPAMD_ROUND_PIVOTS
+#define PIPAMD_ROUND_PIVOTS 128
+#endif
 #define Q_CTRL 3 /* control words per launch: out_count, out_maxni, the number of listed jobs that are out of rows */
 // Control words (out_count, out_maxni per launch) must be zero when a launch starts.  They come
 // from a pool of Q_POOL solves x Q_FAST launches that one memset zeroes every Q_POOL solves (a
@@ -207,6 +219,7 @@ struct BatchRun {
   hipStream_t st;
   int *pool, *over, *list[2];
   bool over_zeroed, have_list, active, finishing, replay_pending;
+  bool spare_went;  // the second lean launch's spare blocks replayed the logs of the jobs the first one finished
   int stage;       // launches issued
   int curS;        // row capacity of the largest block in play (grows when tableaux are re-housed)
   int grow_round;
@@ -304,7 +317,7 @@ struct BatchRun {
     return PIPAMD_OK;
   }
 
-  int launch(int waves, int budget, int smax, int grid, bool lean = false, bool replay = true) {
+  int launch(int waves, int budget, int smax, int grid, bool lean = false, bool replay = true, bool spare = false) {
     int rcs = next_stage();
     if (rcs) return rcs;
     if (smax > curS) smax = curS;
@@ -325,7 +338,8 @@ struct BatchRun {
     void *big[2] = {&e->d_scratch, &e->scratch_bytes};
     // a uniform batch without parameters whose rows fill a wave's 128 columns exactly: FULL kernels
     const int hints = ((lay.nparm == 0 && lay.bigparm < 0 && lay.nvar + 1 == 128 && lay.W == 128) ? 1 : 0) |
-                      (lean ? (lay.ebits == 128 ? 8 : (lay.bigparm >= 0 ? 2 | 16 : 2)) : 0) | (replay ? 0 : 4);
+                      (lean ? (lay.ebits == 128 ? 8 : (lay.bigparm >= 0 ? 2 | 16 : 2)) : 0) | (replay ? 0 : 4) |
+                      (spare ? 32 : 0);
     HIPCHK(pipk_launch_advance_q(jobs, arena, lay.batch, lay.nvar + smax, smax, lay.W, budget, waves, lay.ebits, q5, grid,
                                  big, hints, e->d_prof, st));
     if (!e->no_timing) HIPCHK(hipEventRecord(e->ev[2 * e->nlaunch + 1], st));
@@ -341,14 +355,20 @@ struct BatchRun {
     // (pipk_launch_replay_all): a replay kernel between two launches is a tiny launch that waits milliseconds for a
     // turn on a device busy with other batches' bulk launches, and nothing in the pivot launches depends on it -- a
     // tableau that overflowed goes on pivoting until the replay says so, its status and pivot count are the same.
-    // The bulk launches log at most 2 x 96 pivots per tableau, the log holds PIPAMD_DETLOG.
+    // The bulk launches together log fewer pivots per tableau than the log holds (`defer` in begin()).
+    // Where the second lean launch's spare blocks have replayed the logs of the jobs the first one finished
+    // (spare_went), this replay is the catch-all for what is left -- the few hundred tableaux of the second launch and the
+    // tail, every other log is empty -- and goes out a wave per job, the form with the shortest latency.  It does so
+    // whenever spare blocks went, also where they could reach little or nothing because the list covers most of the
+    // batch (a first-launch budget of a few pivots): correct, since this replay takes every log that is left, but that
+    // case was not measured.
     // (128-bit entries: a list shorter than the GPU has CUs gets a CU per tableau -- sixteen waves; what is left after the
     // first tail launch are the few tableaux of hundreds of pivots and rows, each a latency chain of its own)
     const bool wide16 = lay.ebits == 128 && lay.W <= 256 && upper <= 256 && !e->waves_per_job && !e->tail_waves;
     int rc = launch(wide16 ? 16 : tail_waves, e->iter_limit, curS, upper, false, !replay_pending);
     if (rc) return rc;
     if (replay_pending) {
-      HIPCHK(pipk_launch_replay_all(jobs, arena, lay.batch, lay.ebits, e->lone_batches, st));
+      HIPCHK(pipk_launch_replay_all(jobs, arena, lay.batch, lay.ebits, e->lone_batches || spare_went, st));
       replay_pending = false;
     }
     HIPCHK(hipMemcpyAsync(e->h_run, ctrl_of(stage - 1), Q_CTRL * sizeof(int), hipMemcpyDeviceToHost, st));
@@ -389,10 +409,14 @@ struct BatchRun {
     have_list = false;
     finishing = false;
     replay_pending = false;
+    spare_went = false;
     curS = lay.S;
     grow_round = 0;
     const bool integer = (lay.tflags & PIPAMD_T_INT) != 0;
-    const int K1 = e->round_pivots > 0 ? e->round_pivots : 96;
+    // (the default budget of the first bulk launch is 96; only where a second lean launch takes what the first leaves it
+    // is PIPAMD_ROUND_PIVOTS, chosen below once `lean2` is known -- the general one-wave launches of 128-bit batches and
+    // of batches with parameters, and an engine in lone-batches mode, keep 96)
+    int K1 = e->round_pivots > 0 ? e->round_pivots : 96;
     const int KA = !integer ? 0 : (e->round_rows > 0 ? e->round_rows : 48);
     tail_waves = e->waves_per_job ? e->waves_per_job : (e->tail_waves ? e->tail_waves : 4);
     upper = lay.batch;
@@ -420,9 +444,8 @@ struct BatchRun {
       }
     }
     if (!took64 && lay.batch >= (e->bulk_min > 0 ? e->bulk_min : 2048) && e->waves_per_job != 4 && e->waves_per_job != 8) {
-      const int budget = e->iter_limit < K1 ? e->iter_limit : K1;
-      int smax = lay.ni + (KA < budget ? KA : budget);
-      if (smax > curS) smax = curS;
+      int budget, smax;
+      bool lean, lean2;
       // no parameters, at most 128 columns of 64-bit entries, rows skipped, plain cuts: the lean kernel (pip_lean.h) goes
       // first -- it finishes the tableaux whose entries stay below 2^15 and leaves the others to the general kernel's launch
       // ... and its BIG flavour for the batches whose one parameter is the big one (lexicographic maxima, unknowns of either
@@ -430,11 +453,24 @@ struct BatchRun {
       // measured, it is ahead by 13-35 % except for a lone Urs_unknowns batch, where it is 3 % behind
       const bool plain = lay.nparm == 0 && lay.bigparm < 0;
       const bool bigone = e->lean_big && lay.nparm == 1 && lay.bigparm == lay.nvar + 1 && lay.nvar + 2 <= lay.W;
-      const bool lean = !dual && !e->no_lean && lay.ebits != 128 && (plain || bigone) && lay.W <= 128 && !(lay.W & 1) &&
-                        !(lay.tflags & (PIPAMD_T_NOSKIP | PIPAMD_T_DEEPEST)) && pipk_lean_class(smax) != 0;
-      // (the bulk launches leave their determinant logs to the replay behind the first tail launch; two of them log at
-      // most 2 * budget pivots per tableau)
-      const bool defer = 2 * budget <= PIPAMD_DETLOG / 2;
+      // The second one-wave launch: the lean kernel again where it can resume its own paused jobs (below), with a budget
+      // of its own; else the general kernel with the first launch's.
+      // The first launch's budget: PIPAMD_ROUND_PIVOTS is tried first and kept only if the two lean launches go out with
+      // it; every other sequence is shaped with 96.
+      for (int k = e->round_pivots > 0 ? K1 : PIPAMD_ROUND_PIVOTS;; k = K1) {
+        budget = e->iter_limit < k ? e->iter_limit : k;
+        smax = lay.ni + (KA < budget ? KA : budget);
+        if (smax > curS) smax = curS;
+        lean = !dual && !e->no_lean && lay.ebits != 128 && (plain || bigone) && lay.W <= 128 && !(lay.W & 1) &&
+               !(lay.tflags & (PIPAMD_T_NOSKIP | PIPAMD_T_DEEPEST)) && pipk_lean_class(smax) != 0;
+        lean2 = lean && !e->lone_batches && !e->no_lean2 && pipk_lean_class(lay.ni + 96 < curS ? lay.ni + 96 : curS) != 0;
+        if (lean2 || k == K1) break;
+      }
+      const int b2 = lean2 ? (e->iter_limit < 160 ? e->iter_limit : 160) : budget;
+      // The bulk launches leave their determinant logs to the replay behind the first tail launch when the two of them
+      // together cannot fill a tableau's log: budget + b2 pivots against the PIPAMD_DETLOG entries it holds.  (A kernel
+      // pauses a tableau whose log is full, so nothing is lost beyond that either: the launch then replays behind itself.)
+      const bool defer = budget + b2 <= PIPAMD_DETLOG;
       if (lean) {
         rc = launch(1, budget, smax, lay.batch, true, !defer);
         if (rc) return rc;
@@ -453,11 +489,12 @@ struct BatchRun {
       // image) to the tail.  Where the shape has no lean kernel: the general one-wave kernel.  (Measured with 14 batches
       // in flight: sending those tableaux straight to the four-wave tail instead costs 10 % of the throughput.)
       if (!(lean && e->lone_batches)) {  // (pipamd_engine_set_lone_batches: straight to the tail launches)
-        const bool lean2 = lean && !e->no_lean2 && pipk_lean_class(lay.ni + 96 < curS ? lay.ni + 96 : curS) != 0;
         if (lean2) {
           int smax2 = lay.ni + 96 < curS ? lay.ni + 96 : curS;
-          const int b2 = e->iter_limit < 160 ? e->iter_limit : 160;
-          rc = launch(1, b2, smax2, lay.batch, true, false);
+          // (a block per tableau of the batch over the list of the paused ones: the blocks beyond the list replay the
+          // logs the first launch left behind its finished tableaux, pip_lean.h lean_spare_replay)
+          spare_went = replay_pending && !e->no_spare_replay;
+          rc = launch(1, b2, smax2, lay.batch, true, false, spare_went);
           replay_pending = true;
         } else {
           rc = launch(1, budget, smax, lay.batch, false, !defer);
@@ -466,7 +503,9 @@ struct BatchRun {
         if (rc) return rc;
       }
       if (e->single_launch) {  // measurement aid: the bulk launch on its own (its tableaux stay PIPAMD_ST_RUN)
-        if (replay_pending) HIPCHK(pipk_launch_replay_all(jobs, arena, lay.batch, lay.ebits, e->lone_batches, st));
+        // (3: without the catch-all replay -- the logs stay as the launches left them, so that a test sees which of them
+        // the second lean launch's spare blocks replayed)
+        if (replay_pending && e->single_launch != 3) HIPCHK(pipk_launch_replay_all(jobs, arena, lay.batch, lay.ebits, e->lone_batches || spare_went, st));
         replay_pending = false;
         HIPCHK(hipMemcpyAsync(e->h_run, ctrl_of(stage - 1), Q_CTRL * sizeof(int), hipMemcpyDeviceToHost, st));
         active = true;
@@ -609,7 +648,9 @@ extern "C" int pipamd_debug_grow_step(pipamd_engine *e, int rows) {
 // what that launch alone did.
 extern "C" int pipamd_debug_single_launch(pipamd_engine *e, int on) {
   if (!e) return PIPAMD_E_INVALID;
-  e->single_launch = on < 0 ? 0 : (on > 2 ? 1 : on);  // 1: after the bulk launches, 2: after the lean launch alone
+  // 1: after the bulk launches, 2: after the lean launch alone, 3: as 1 but without the determinant replay behind them
+  // (testing aid: statuses are then not final, an overflow the replay would find is not reported)
+  e->single_launch = on < 0 ? 0 : (on > 3 ? 1 : on);
   return PIPAMD_OK;
 }
 
@@ -683,6 +724,12 @@ extern "C" int pipamd_engine_set_tail_waves(pipamd_engine *e, int waves) {
 extern "C" int pipamd_engine_set_lone_batches(pipamd_engine *e, int on) {
   if (!e) return PIPAMD_E_INVALID;
   e->lone_batches = on ? 1 : 0;
+  return PIPAMD_OK;
+}
+
+extern "C" int pipamd_engine_set_spare_replay(pipamd_engine *e, int on) {
+  if (!e) return PIPAMD_E_INVALID;
+  e->no_spare_replay = on ? 0 : 1;
   return PIPAMD_OK;
 }
 

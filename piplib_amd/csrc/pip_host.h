@@ -19,6 +19,7 @@ struct pipamd_engine {
   int bulk_min;      /* batches of at least this many tableaux start with the one-wave bulk launch (0 = default 2048) */
   int single_launch; /* debug: stop after one launch */
   int lone_batches;  /* 1: no general one-wave launch between the lean launch and the tail (pipamd_engine_set_lone_batches) */
+  int no_spare_replay; /* 1: the second lean launch's spare blocks replay no determinant logs (pipamd_engine_set_spare_replay) */
   int no_lean;       /* 1: bulk launches without the lean kernel (pip_lean.h) */
   int lean64;        /* 1: 128-bit batches of 129 ... 256 columns start with pip_lean64_kernel (pip_lean.h; pipamd_engine_set_lean64) */
   int lean_big;      /* 1: bulk batches whose one parameter is the big one start with the lean kernel's BIG flavour (pipamd_engine_set_lean_big) */

@@ -30,21 +30,6 @@ PIP_LEAN_BIG_CLASSES(PIP_LEAN_BIG_EXTERN)
 // and sets the pivot count to the pivot that overflowed.  In the pivot loop itself this was
 // wave-uniform scalar work: ~12 % of all instructions with 64-bit entries, ~18 % of the run time
 // with 128-bit ones.
-template <class T>
-__device__ __forceinline__ T det_limb(const PipJob *J, int i) {
-  if constexpr (sizeof(T) == 16)
-    return (T)(((u128)(u64)J->det[2 * i + 1] << 64) | (u64)J->det[2 * i]);
-  else
-    return (T)J->det[i];
-}
-template <class T>
-__device__ __forceinline__ void det_limb_store(PipJob *J, int i, T x) {
-  if constexpr (sizeof(T) == 16) {
-    J->det[2 * i] = (i64)(u64)(u128)x;
-    J->det[2 * i + 1] = (i64)(u64)((u128)x >> 64);
-  } else
-    J->det[i] = (i64)x;
-}
 // One WAVE per job: gcd(pivot, dpiv) and the two quotients do not depend on the limbs, so the
 // lanes compute them for 64 pivots at once; only the walk over the limbs is sequential, on the
 // scalar unit.  Shortest latency: used where few jobs ran and someone waits for them.
@@ -106,46 +91,7 @@ __global__ __launch_bounds__(64) void pip_det_replay_lanes_kernel(PipJob *jobs, 
   const int nq = q.in_count ? *q.in_count : njobs;
   if (t >= nq) return;
   PipJob *J = &jobs[q.in_list ? q.in_list[t] : t];
-  const int nlog = J->nlog;
-  if (nlog <= 0 || (J->ebits == 128) != (sizeof(T) == 16)) return;
-  const T *lg = (const T *)(arena + J->log_off);
-  T det0 = det_limb<T>(J, 0), det1 = det_limb<T>(J, 1), det2 = det_limb<T>(J, 2), det3 = det_limb<T>(J, 3);
-  int ldet = J->ldet;
-  constexpr int CH = sizeof(T) == 16 ? 4 : 8;  // log entries per 128-byte line
-  bool stop = false;
-  for (int k0 = 0; k0 < nlog && !stop; k0 += CH) {
-    T ev[CH][2];
-#pragma unroll
-    for (int u = 0; u < CH; u++) {
-      const bool in = k0 + u < nlog;
-      ev[u][0] = in ? lg[2 * (k0 + u)] : (T)1;
-      ev[u][1] = in ? lg[2 * (k0 + u) + 1] : (T)1;
-    }
-#pragma unroll
-    for (int u = 0; u < CH; u++) {
-      const int k = k0 + u;
-      if (k >= nlog || stop) break;
-      T ppivot = ev[u][0], dppiv = ev[u][1];
-      if (dppiv != 1) {
-        const T d = gcd_i64(ppivot, dppiv);
-        if (d != 1) {
-          ppivot = exact_quo(ppivot, d);
-          dppiv = exact_quo(dppiv, d);
-        }
-      }
-      if (!det_step<T>(det0, det1, det2, det3, ldet, ppivot, dppiv)) {
-        J->status = PIPAMD_ST_OVERFLOW;
-        J->npiv = J->npiv - nlog + k + 1;
-        stop = true;
-      }
-    }
-  }
-  det_limb_store<T>(J, 0, det0);
-  det_limb_store<T>(J, 1, det1);
-  det_limb_store<T>(J, 2, det2);
-  det_limb_store<T>(J, 3, det3);
-  J->ldet = ldet;
-  J->nlog = 0;
+  det_replay_lane<T, sizeof(T) == 16 ? 4 : 8>(J, arena);  // (a chunk: the log entries of a 128-byte line)
 }
 
 // ---------------------------------------------------------------- batch load
@@ -1107,6 +1053,8 @@ static hipError_t launch_by_shape(const AdvanceLaunch &a, bool one, int wp, int 
 // entries, 129 ... 256 columns, pipk_lean64_lds_bytes(Smax, Lmax) within the LDS budget, else refused) = the lean kernel of
 // pip_lean.h on long long rows: it runs the jobs it can (no parameters, entries below 2^63) and leaves the others on the output list.
 // Bit 4 (with bit 1): every job has nparm == 1 and bigparm == nvar + 1 -- the lean kernel's BIG flavour.
+// Bit 5 (with bit 1 and an input list): the launch's workgroups beyond the list replay the determinant logs of the finished
+// jobs that are not on it (PipQueue.replay_spare; `grid` is then the batch, not the list's bound).
 extern "C" hipError_t pipk_launch_advance_q(PipJob *jobs, i64 *arena, int njobs, int Lmax, int Smax, int Wmax,
                                             int iter_limit, int waves_per_job, int ebits, void *const *q5, int grid,
                                             void **big, int hints, unsigned long long *prof, hipStream_t stream) {
@@ -1128,6 +1076,7 @@ extern "C" hipError_t pipk_launch_advance_q(PipJob *jobs, i64 *arena, int njobs,
   if (q5) {
     a.q = PipQueue{(const int *)q5[0], (const int *)q5[1], (int *)q5[2], (int *)q5[3], (int *)q5[4]};
     a.grid = grid;
+    a.q.replay_spare = (hints & 2) && (hints & 32) ? 1 : 0;
   }
   a.prof = prof;
   a.waves = waves_per_job;

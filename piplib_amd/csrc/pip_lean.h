@@ -81,6 +81,9 @@
 #ifndef PIP_LEAN_KEEPCUT
 #define PIP_LEAN_KEEPCUT 1  // (A/B switch) a cut that integrer() has just built stays in registers as the pivot row
 #endif
+#ifndef PIP_LEAN_REPLAY_CH
+#define PIP_LEAN_REPLAY_CH 4  // log entries a lane of a spare block loads at a time (lean_spare_replay; within the 64 VGPRs)
+#endif
 #ifndef PIP_LEAN_WAVES
 #define PIP_LEAN_WAVES 8  // waves per SIMD pip_lean_kernel is bounded to (64 VGPRs)
 #endif
@@ -602,6 +605,36 @@ last_unit_wins:
   return sc->tmp2 & 1023;
 }
 
+// ---- the determinant replay in a lean launch's spare workgroups.  pipamd_batch_solve's second lean launch has a block
+// per tableau of the batch and a list of the few the first launch paused: block nq + r (r = 0 .. ceil(njobs / 64) - 1) takes
+// the jobs 64 r .. 64 r + 63, a lane each, and replays the logs of those that are finished (PIPAMD_ST_SOLUTION, _NIL)
+// with the one-lane walk of pip_det_replay_lanes_kernel -- beside the launch's own jobs, not behind them on the queue.
+// The jobs on the launch's list belong to its list blocks, which may finish them at any moment: the block reads the
+// whole list first (it does not change during the launch) and leaves every listed job alone, whatever its status says
+// by now.  So no job has two writers.  What the spare blocks do not reach (a list longer than the batch minus the
+// blocks needed) is left to the replay behind the launches, for which an empty log is a no-op.
+// `lds`: 8 bytes of the block's LDS image, which a spare block does not use otherwise.
+template <class T>
+__device__ __forceinline__ void lean_spare_replay(PipJob *jobs, i64 *arena, int njobs, const int *in_list, int nq, int r,
+                                                  unsigned char *lds) {
+  if (r >= (njobs + 63) / 64) return;
+  const int lane = threadIdx.x;
+  u64 *listed = (u64 *)lds;
+  if (lane == 0) *listed = 0;
+  __builtin_amdgcn_wave_barrier();
+  for (int i = lane; i < nq; i += 64) {
+    const int v = in_list[i];
+    if ((v >> 6) == r) atomicOr((unsigned long long *)listed, 1ull << (v & 63));
+  }
+  __builtin_amdgcn_wave_barrier();
+  const int j = 64 * r + lane;
+  if (j >= njobs || ((*listed >> lane) & 1)) return;
+  PipJob *J = &jobs[j];
+  const int st = J->status;
+  if (st != PIPAMD_ST_SOLUTION && st != PIPAMD_ST_NIL) return;
+  det_replay_lane<T, PIP_LEAN_REPLAY_CH>(J, arena);
+}
+
 #ifdef PIP_PROFILE
 #define PIP_LEAN_PROF_PARAM , u64 *prof
 #else
@@ -661,7 +694,13 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ Scalars sc;
   const int nq = q.in_count ? *q.in_count : njobs;
-  if ((int)blockIdx.x >= nq) return;
+  if ((int)blockIdx.x >= nq) {
+    // a launch sized by the batch over a shorter list: the first blocks beyond the list do the determinant bookkeeping
+    // of the jobs the earlier launch finished, beside this launch's own jobs (PipQueue.replay_spare)
+    if constexpr (sizeof(T) == 8)
+      if (q.replay_spare && q.in_list) lean_spare_replay<T>(jobs, arena, njobs, q.in_list, nq, (int)blockIdx.x - nq, smem);
+    return;
+  }
   const int jb = q.in_list ? q.in_list[blockIdx.x] : (int)blockIdx.x;
   PipJob *J = &jobs[jb];
   const int lane = threadIdx.x;

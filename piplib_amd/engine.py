@@ -144,6 +144,12 @@ class Engine:
         lib().pipamd_engine_set_lone_batches.argtypes = [C.c_void_p, C.c_int]
         _check(lib().pipamd_engine_set_lone_batches(self._h, int(bool(on))))
 
+    def set_spare_replay(self, on):
+        """the second lean launch's spare blocks replay the determinant logs of the finished tableaux (default on;
+        pipamd_engine_set_spare_replay)"""
+        lib().pipamd_engine_set_spare_replay.argtypes = [C.c_void_p, C.c_int]
+        _check(lib().pipamd_engine_set_spare_replay(self._h, int(bool(on))))
+
     def set_lean64(self, on):
         """128-bit batches of 129 ... 256 columns start with pip_lean64_kernel (csrc/pip_lean.h; default off)"""
         lib().pipamd_engine_set_lean64.argtypes = [C.c_void_p, C.c_int]
@@ -174,7 +180,8 @@ class Engine:
 
     def debug_single_launch(self, on):
         """measurement aid: the next solves stop after their bulk launches (True / 1: the one-wave launches of a large
-        batch; 2: after the lean launch alone, when the batch has one) -- unfinished tableaux stay PIPAMD_ST_RUN"""
+        batch; 2: after the lean launch alone, when the batch has one; 3: as 1, but without the determinant replay
+        behind the launches, for tests that look at the logs) -- unfinished tableaux stay PIPAMD_ST_RUN"""
         lib().pipamd_debug_single_launch.argtypes = [C.c_void_p, C.c_int]
         _check(lib().pipamd_debug_single_launch(self._h, int(on)))
 
