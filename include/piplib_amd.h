@@ -500,6 +500,69 @@ int pipamd_traiter_many128(pipamd_engine *e, int n, const pipamd_problem *proble
                            int nthreads, pipamd_sol_cell128 **cells, size_t *n_cells, int *rcs, int *statuses,
                            int64_t *pivots);
 
+/* pip_solve(inequnk, ineqpar, Bg, options) (piplib.c:722-880) for `n` independent calls at once, straight from the PolyLib
+ * matrices (added since interface version 500).  A front end that has the matrices need not build a tableau: the engine
+ * does the integer bookkeeping of piplib.c:758-797 on the host, uploads the matrices in one copy, and a kernel
+ * (csrc/pip_m2t.hip) writes, for every problem, what tab_Matrix2Tableau (tab.c:292-393) returns at piplib.c:813 (the
+ * context) and piplib.c:846 (the domain): the constant moved behind the first series of columns, the unknowns negated
+ * under Maximize, the sum of the unknowns' coefficients in the big column (a fresh column when Bg is -1, added to the
+ * given one otherwise; sums wrap in 64 bits as in the reference's long long build), the negated copies of the parameters
+ * for Urs_parms with the `pos <= Bg` skip of tab.c:358-365, a zero column in the context where a new big parameter goes,
+ * and the negated twin behind every equality (marker 0; Nl and Nm count those twice, piplib.c:767-770, 808-811).  The
+ * device-resident traiter() then solves the problems of its box from that device buffer; the others, and those it hands
+ * back, have their built rows copied back and go to `nthreads` host trees.  Either side does what pip_solve does:
+ * tab_simplify on both tableaux when Nq, the context test as a TRAITER_INT call of its own (piplib.c:818-826), then
+ * traiter() with the problem's flags. */
+#define PIPAMD_PIP_NQ 1           /* options->Nq: integer solution (tab_simplify, TRAITER_INT: piplib.c:815, 848-853) */
+#define PIPAMD_PIP_MAXIMIZE 2     /* options->Maximize: Shift = 1, SOL_MAX (piplib.c:777-779) */
+#define PIPAMD_PIP_URS_PARMS 4    /* options->Urs_parms: Np - (Bg >= 0) negated parameter copies (piplib.c:785-788) */
+#define PIPAMD_PIP_URS_UNKNOWNS 8 /* options->Urs_unknowns: Shift = -1, SOL_SHIFT; ignored under MAXIMIZE (piplib.c:777-783) */
+#define PIPAMD_PIP_DUAL 16        /* options->Compute_dual: TRAITER_DUAL, SOL_DUAL; ignored under NQ (piplib.c:852-857) */
+typedef struct pipamd_pip_problem {
+  int32_t nrows, ncols;       /* inequnk: NbRows, NbColumns = 1 + Nn + Np + 1 (marker | unknowns | parameters | constant) */
+  int32_t ctx_rows, ctx_cols; /* ineqpar: NbRows, NbColumns = Np + 2; ctx_cols == 0: ineqpar is NULL, Np = 0 (piplib.c:758) */
+  int32_t bg;                 /* Bg as pip_solve takes it: a tableau column Nn+1 .. Nn+Np, or -1 (then Maximize and
+                                 Urs_unknowns make one at NbColumns - 1 and count it as a parameter, piplib.c:791-797) */
+  int32_t options;            /* PIPAMD_PIP_* */
+  const int64_t *inequnk;     /* host, row-major, marker column first; NULL: the answer is void (piplib.c:753-754) */
+  const int64_t *ineqpar;     /* host, row-major; may be NULL when ctx_rows == 0 */
+} pipamd_pip_problem;         /* 40 bytes, offsets 0 4 8 12 16 20 24 32 */
+/* what traiter() was called with (piplib.c:858), and what sol_quast_edit (piplib.c:866) takes */
+typedef struct pipamd_pip_info {
+  int32_t nvar, nparm, ni, nc, bigparm, flags;   /* Nn, Np, Nl, Nm, Bg as traiter() gets them; flags: 0, PIPAMD_T_INT or
+                                                    PIPAMD_T_DUAL (TRAITER_*, funcall.h:32-33) */
+  int32_t sol_bg, urs_parms, sol_flags, is_void; /* Bg - Nn - 1, Urs_parms, the SOL_* bits as sol.h:36-50 numbers them
+                                                    (SOL_SHIFT 1, SOL_NEGATE 2, SOL_REMOVE 4, SOL_DUAL 8); is_void: pip_solve
+                                                    returns NULL (inequnk NULL, or the context is empty) */
+  int64_t row_off;                               /* pipamd_pip_tableaux: where this problem's rows start in *rows */
+} pipamd_pip_info;                               /* 48 bytes, offsets 0 .. 36 in steps of 4, 40 */
+/* The many-problem form of tab_Matrix2Tableau: validation, upload and the build kernel only.  *rows is a malloc'ed array
+ * of *n_words int64 (free with pipamd_free; NULL when there are none): problem i has its ni x (nvar + nparm + 1) domain
+ * rows at info[i].row_off, then its nc x (nparm + 1) context rows -- the kernel's output bit for bit, not simplified.  A
+ * problem that is void or malformed (info[i].nvar < 0) has no rows.  Returns PIPAMD_E_INVALID for a null array or n < 0
+ * and when any problem is malformed (the others are still built). */
+int pipamd_pip_tableaux(pipamd_engine *e, int n, const pipamd_pip_problem *p, pipamd_pip_info *info, int64_t **rows,
+                        size_t *n_words);
+/* cells[i] / n_cells[i]: the tape pip_solve has when traiter() returns at piplib.c:858 -- the cells the one-call hook
+ * (bindings/piplib_traiter_hook.c) would replay, so a caller replays them into sol.c and calls sol_simplify /
+ * sol_quast_edit(&xq, NULL, info[i].sol_bg, info[i].urs_parms, info[i].sol_flags) unchanged.  A void
+ * answer is PIPAMD_OK with no cells and info[i].is_void = 1.  pivots[i] counts the context test's pivots too; statuses
+ * and pivots may be NULL; deepest_cut and nthreads as in pipamd_traiter_many; pipamd_last_device_tree answers for the
+ * call.  A malformed problem gets PIPAMD_E_INVALID in its own rcs[i] (before any HIP call) and does not fail the call:
+ * unknown option bits, a negative count, ncols < 2, ctx_cols of 1, ctx_cols == 0 with ctx_rows > 0, Nn < 0, bg outside
+ * -1 / Nn+1 .. Nn+Np, ineqpar NULL with ctx_rows > 0, a built tableau of more than 512 columns (MAXCOL).  The call
+ * itself fails only for a null array or n < 0; n == 0 is PIPAMD_OK. */
+int pipamd_pip_solve_many(pipamd_engine *e, int n, const pipamd_pip_problem *p, int deepest_cut, int nthreads,
+                          pipamd_pip_info *info, pipamd_sol_cell **cells, size_t *n_cells, int *rcs, int *statuses,
+                          int64_t *pivots);
+/* The overflow-safe flavour on the same int64 tableaux (the kernel's 128-bit instantiation, TreeT<__int128>; cells as
+ * pipamd_traiter128 hands them out).  A problem whose big column -- the sum, or its negation under an equality -- leaves
+ * 64 bits gets rcs[i] = PIPAMD_E_SOLVER and statuses[i] = PIPAMD_ST_RANGE instead of a wrapped column (the build kernel
+ * raises a flag per problem). */
+int pipamd_pip_solve_many128(pipamd_engine *e, int n, const pipamd_pip_problem *p, int deepest_cut, int nthreads,
+                             pipamd_pip_info *info, pipamd_sol_cell128 **cells, size_t *n_cells, int *rcs, int *statuses,
+                             int64_t *pivots);
+
 /* The same results from a lock-step scheduler: one explicit traiter() state machine per problem
  * and, per step, ONE clone / patch / pivot-kernel / gather sequence for the whole batch, so the
  * host <-> device latency is paid once per step instead of once per problem.  Problems that need

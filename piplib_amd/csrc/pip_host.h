@@ -35,9 +35,10 @@ struct pipamd_engine {
   int tail_waves;    /* waves per tableau of the tail launch when waves_per_job is 0 (0 = default 4) */
   int blocking_wait;   /* 1: pipamd_batch_solve naps between looks at its stream instead of spinning on it */
   int no_device_tree; /* 1: pipamd_solve_tableaux_lockstep skips the device-resident traiter() (pip_quast.hip) */
-  void *dt_buf[8];     /* device tree: device buffers kept between calls (problems, rows, stacks, tapes, results, ...) */
-  size_t dt_cap[8];
-  int dt_small[8];     /* calls in a row that needed less than a quarter of the buffer (it is given back after eight) */
+  void *dt_buf[10];    /* device tree: device buffers kept between calls (problems, rows, stacks, tapes, results, ...;
+                          7-9: pipamd_pip_*: built tableaux, uploaded matrices, range flags) */
+  size_t dt_cap[10];
+  int dt_small[10];     /* calls in a row that needed less than a quarter of the buffer (it is given back after eight) */
   pthread_mutex_t dt_lock; /* the device-tree buffers below serve one call at a time */
   void *dt_host;       /* device tree: pinned staging buffer for the problems' rows */
   size_t dt_host_cap;

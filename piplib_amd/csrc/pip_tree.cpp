@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "pip_host.h"
+#include "pip_m2t.h"
 #include "pip_quast.h"
 #include "pip_tree_steps.h"
 
@@ -688,7 +689,8 @@ template <class E> struct FResultT {
 // the device-resident traiter() (defined with the device tree at the end of this file)
 template <class E>
 void device_tree(pipamd_engine *e, int n, const pipamd_problem *probs, int simplify, int deepest_cut, std::vector<FResultT<E>> &res,
-                 int *served, int *handed_back, const int *qflags);
+                 int *served, int *handed_back, const int *qflags, const i64 *d_built = nullptr,
+                 const long long *built_off = nullptr);
 
 // device bytes a chunk of problems may reserve, in the device tree and in the Forest (PIPAMD_FOREST_ARENA_MB, default 4096)
 size_t forest_arena_budget() {
@@ -1739,9 +1741,25 @@ void quast_caps_max(QCaps &a, const QCaps &b) {
   a.cells = std::max(a.cells, b.cells);
 }
 
+// the engine's pinned staging buffer, at least `bytes` large (kept between calls)
+void *dt_staging(pipamd_engine *e, size_t bytes) {
+  if (bytes > e->dt_host_cap) {
+    if (e->dt_host) hipHostFree(e->dt_host);
+    e->dt_host = nullptr;
+    e->dt_host_cap = 0;
+    const size_t want = bytes + bytes / 4 + 4096;
+    HIPTHROW(hipHostMalloc(&e->dt_host, want, hipHostMallocDefault));
+    e->dt_host_cap = want;
+  }
+  return e->dt_host;
+}
+
+// d_built: the problems' rows are on the device already, problem i's at d_built[built_off[i]] (pipamd_pip_solve_many:
+// pip_m2t.hip wrote them); null: they are packed from probs[i].ineq / .ctx and uploaded
 template <class E>
 void device_tree_chunk(pipamd_engine *e, const std::vector<int> &idx, const pipamd_problem *probs, const QCaps &cap, const int *qflags,
-                       std::vector<FResultT<E>> &res, int *served, int *handed_back) {
+                       std::vector<FResultT<E>> &res, int *served, int *handed_back, const i64 *d_built,
+                       const long long *built_off) {
   constexpr int EW = (int)(sizeof(E) / 8), EBITS = 64 * EW;
   const int n = (int)idx.size();
   const bool stats = getenv("PIPAMD_FOREST_STATS") != nullptr;
@@ -1751,19 +1769,11 @@ void device_tree_chunk(pipamd_engine *e, const std::vector<int> &idx, const pipa
   size_t words = 0;
   for (int k = 0; k < n; k++) {
     const pipamd_problem &p = probs[idx[k]];
-    qp[k] = QProb{(long long)words, p.nvar, p.nparm, p.ni, p.nc, p.bigparm, p.nq, qflags ? qflags[idx[k]] : 0, 0};
+    qp[k] = QProb{d_built ? built_off[idx[k]] : (long long)words, p.nvar, p.nparm, p.ni, p.nc, p.bigparm, p.nq, qflags ? qflags[idx[k]] : 0, 0};
     words += (size_t)p.ni * (p.nvar + p.nparm + 1) + (size_t)p.nc * (p.nparm + 1);
   }
-  if (words * sizeof(i64) > e->dt_host_cap) {  // pinned staging buffer, kept between calls
-    if (e->dt_host) hipHostFree(e->dt_host);
-    e->dt_host = nullptr;
-    e->dt_host_cap = 0;
-    const size_t want = words * sizeof(i64) + words * sizeof(i64) / 4 + 4096;
-    HIPTHROW(hipHostMalloc(&e->dt_host, want, hipHostMallocDefault));
-    e->dt_host_cap = want;
-  }
-  i64 *in = (i64 *)e->dt_host;
-  for (int k = 0; k < n; k++) {
+  i64 *in = d_built ? nullptr : (i64 *)dt_staging(e, words * sizeof(i64));
+  for (int k = 0; k < n && !d_built; k++) {
     const pipamd_problem &p = probs[idx[k]];
     const size_t na = (size_t)p.ni * (p.nvar + p.nparm + 1), ncx = (size_t)p.nc * (p.nparm + 1);
     if (na) memcpy(in + qp[k].in_off, p.ineq, na * sizeof(i64));
@@ -1771,13 +1781,13 @@ void device_tree_chunk(pipamd_engine *e, const std::vector<int> &idx, const pipa
   }
   const size_t frame = pipk_quast_frame_words(&cap, EBITS);  // entries
   QProb *d_prob = dt_buffer<QProb>(e, 0, sizeof(QProb) * n);
-  i64 *d_in = dt_buffer<i64>(e, 1, sizeof(i64) * words);
+  const i64 *d_in = d_built ? d_built : dt_buffer<i64>(e, 1, sizeof(i64) * words);
   i64 *d_stack = dt_buffer<i64>(e, 2, sizeof(E) * frame * (size_t)cap.depth * n);
   i64 *d_cells = dt_buffer<i64>(e, 3, sizeof(E) * 3 * (size_t)cap.cells * n);
   int *d_out = dt_buffer<int>(e, 4, sizeof(int) * Q_OUT * n);
   const double t1 = now();
   HIPTHROW(hipMemcpy(d_prob, qp.data(), sizeof(QProb) * n, hipMemcpyHostToDevice));
-  HIPTHROW(hipMemcpyAsync(d_in, in, sizeof(i64) * words, hipMemcpyHostToDevice, 0));
+  if (!d_built) HIPTHROW(hipMemcpyAsync((void *)d_in, in, sizeof(i64) * words, hipMemcpyHostToDevice, 0));
   HIPTHROW(pipk_launch_quast(d_prob, d_in, d_stack, d_cells, d_out, n, &cap, EBITS, 0));
   std::vector<int> out(Q_OUT * (size_t)n);
   HIPTHROW(hipMemcpy(out.data(), d_out, sizeof(int) * Q_OUT * n, hipMemcpyDeviceToHost));
@@ -1832,16 +1842,21 @@ void device_tree_chunk(pipamd_engine *e, const std::vector<int> &idx, const pipa
   }
 }
 
-// qflags: QProb::flags of every problem (null: 0 for all); a negative entry keeps its problem out of the device tree
+// qflags: QProb::flags of every problem (null: 0 for all); a negative entry keeps its problem out of the device tree.
+// d_built / built_off: see device_tree_chunk; that caller holds the engine's device-tree buffers already.
 template <class E>
 void device_tree(pipamd_engine *e, int n, const pipamd_problem *probs, int simplify, int deepest_cut, std::vector<FResultT<E>> &res,
-                 int *served, int *handed_back, const int *qflags) {
+                 int *served, int *handed_back, const int *qflags, const i64 *d_built, const long long *built_off) {
   constexpr int EBITS = 64 * (int)(sizeof(E) / 8);
   struct Hold {  // the engine's device-tree buffers serve one call at a time
     pthread_mutex_t *m;
-    explicit Hold(pthread_mutex_t *mm) : m(mm) { pthread_mutex_lock(m); }
-    ~Hold() { pthread_mutex_unlock(m); }
-  } hold(&e->dt_lock);
+    explicit Hold(pthread_mutex_t *mm) : m(mm) {
+      if (m) pthread_mutex_lock(m);
+    }
+    ~Hold() {
+      if (m) pthread_mutex_unlock(m);
+    }
+  } hold(d_built ? nullptr : &e->dt_lock);
   const size_t budget = forest_arena_budget();  // chunks of problems whose stack + tape regions fit it
   std::vector<int> idx;
   QCaps cap;
@@ -1851,7 +1866,7 @@ void device_tree(pipamd_engine *e, int n, const pipamd_problem *probs, int simpl
     cap.deepest = deepest_cut ? 1 : 0;
     cap.simplify = simplify ? 1 : 0;  // the kernel simplifies the rows as it loads them
     try {
-      device_tree_chunk<E>(e, idx, probs, cap, qflags, res, served, handed_back);
+      device_tree_chunk<E>(e, idx, probs, cap, qflags, res, served, handed_back, d_built, built_off);
     } catch (int) {  // allocation or launch failure: the chunk's problems go to the next path
       (void)hipGetLastError();
     }
@@ -1987,4 +2002,280 @@ extern "C" int pipamd_solve_tableaux_lockstep128(pipamd_engine *e, int n, const 
                                                  int deepest_cut, pipamd_sol_cell128 **cells, size_t *n_cells, int *rcs,
                                                  int *statuses, int64_t *pivots) {
   return lockstep_any<i128, pipamd_sol_cell128>(e, n, probs, simplify, deepest_cut, cells, n_cells, rcs, statuses, pivots);
+}
+
+// =========================================================================== pip_solve for many problems
+// pipamd_pip_tableaux / pipamd_pip_solve_many: the PolyLib matrices of many pip_solve() calls (piplib.c:722-880) to
+// tableaux on the device (pip_m2t.hip), the device tree from that buffer, host trees for the rest.
+namespace {
+enum { SOL_SHIFT = 1, SOL_NEGATE = 2, SOL_REMOVE = 4, SOL_MAX = SOL_SHIFT | SOL_NEGATE, SOL_DUAL = 8 };  // sol.h:36-50
+
+// The integer bookkeeping of piplib.c:758-797 for one problem: PIPAMD_E_INVALID for a malformed one (info->nvar = -1),
+// else info and, unless the answer is void already (inequnk NULL), the build kernel's descriptor without its offsets.
+int pip_plan(const pipamd_pip_problem &p, pipamd_pip_info *info, M2TProb *d) {
+  memset(info, 0, sizeof *info);
+  memset(d, 0, sizeof *d);
+  info->nvar = -1;
+  auto bad = [](const char *what) {
+    pipamd_set_error("pipamd_pip_solve_many: %s", what);
+    return (int)PIPAMD_E_INVALID;
+  };
+  const int all = PIPAMD_PIP_NQ | PIPAMD_PIP_MAXIMIZE | PIPAMD_PIP_URS_PARMS | PIPAMD_PIP_URS_UNKNOWNS | PIPAMD_PIP_DUAL;
+  if (p.options & ~all) return bad("unknown option bits");
+  if (p.nrows < 0 || p.ncols < 0 || p.ctx_rows < 0 || p.ctx_cols < 0) return bad("a negative count");
+  if (!p.inequnk) {  // piplib.c:753-754
+    info->nvar = 0;
+    info->bigparm = info->sol_bg = -1;
+    info->is_void = 1;
+    return PIPAMD_OK;
+  }
+  if (p.ncols < 2) return bad("inequnk needs at least the marker and the constant column");
+  if (p.ctx_cols == 1 || (p.ctx_cols == 0 && p.ctx_rows > 0)) return bad("ineqpar has Np + 2 columns (0: no ineqpar)");
+  if (p.ctx_rows > 0 && !p.ineqpar) return bad("ineqpar is NULL but ctx_rows > 0");
+  const int np0 = p.ctx_cols ? p.ctx_cols - 2 : 0, nn = p.ncols - np0 - 2;  // piplib.c:758, 762
+  if (nn < 0) return bad("inequnk has fewer columns than ineqpar's parameters need");
+  if (p.bg != -1 && (p.bg < nn + 1 || p.bg > nn + np0)) return bad("bg must be -1 or a parameter column Nn+1 .. Nn+Np");
+  long long nl = p.nrows, nm = p.ctx_rows;  // piplib.c:767-770, 808-811
+  for (int i = 0; i < p.nrows; i++) nl += p.inequnk[(size_t)i * p.ncols] == 0;
+  for (int i = 0; i < p.ctx_rows; i++) nm += p.ineqpar[(size_t)i * p.ctx_cols] == 0;
+  int np = np0, bg = p.bg, shift = 0, urs = 0, sol_flags = 0, isnew = 0;
+  if (p.options & PIPAMD_PIP_MAXIMIZE) {  // piplib.c:777-783
+    sol_flags |= SOL_MAX;
+    shift = 1;
+  } else if (p.options & PIPAMD_PIP_URS_UNKNOWNS) {
+    sol_flags |= SOL_SHIFT;
+    shift = -1;
+  }
+  if (p.options & PIPAMD_PIP_URS_PARMS) {  // piplib.c:785-788
+    urs = np - (bg >= 0);
+    np += urs;
+  }
+  if (shift && bg < 0) {  // piplib.c:791-797; then bignum_is_new, tab.c:311-313
+    bg = p.ncols - 1;
+    np++;
+    sol_flags |= SOL_REMOVE;
+    isnew = 1;
+  }
+  if (nn + np + 1 > M2T_MAXCOL) return bad("the built tableau has more than 512 columns");
+  if (nl > (1 << 24) || nm > (1 << 24)) return bad("more than 2^24 rows");
+  int tfl = 0;  // piplib.c:852-857
+  if (p.options & PIPAMD_PIP_NQ)
+    tfl = PIPAMD_T_INT;
+  else if (p.options & PIPAMD_PIP_DUAL) {
+    tfl = PIPAMD_T_DUAL;
+    sol_flags |= SOL_DUAL;
+  }
+  *info = pipamd_pip_info{nn, np, (int)nl, (int)nm, bg, tfl, bg - nn - 1, urs, sol_flags, 0, 0};
+  *d = M2TProb{0, 0, p.nrows, p.ncols, p.ctx_rows, p.ctx_cols, nn, np0, bg, shift, urs, isnew, (int)nl, (int)nm};
+  return PIPAMD_OK;
+}
+
+// The plans of a call and where its built rows are.  build() fills the device buffer (the engine's slot 7); the caller
+// holds e->dt_lock from build() until it has no more use for that buffer.
+struct PipBuild {
+  std::vector<M2TProb> desc;   // one per problem (zeroed where nothing is built)
+  std::vector<char> todo;      // 1: the problem has tableaux to build
+  std::vector<int> range;      // 1: its big column left 64 bits
+  size_t src_words = 0, out_words = 0;
+  i64 *d_out = nullptr;
+
+  // validation and sizes; rcs may be null.  Returns the number of malformed problems.  No HIP call.
+  int plan(int n, const pipamd_pip_problem *p, pipamd_pip_info *info, int *rcs) {
+    int nbad = 0;
+    desc.resize(n);
+    todo.assign(n, 0);
+    range.assign(n, 0);
+    for (int i = 0; i < n; i++) {
+      const int rc = pip_plan(p[i], &info[i], &desc[i]);
+      if (rcs) rcs[i] = rc;
+      nbad += rc != PIPAMD_OK;
+      info[i].row_off = (int64_t)out_words;
+      if (rc != PIPAMD_OK || info[i].is_void) continue;
+      todo[i] = 1;
+      desc[i].src_off = (long long)src_words;
+      desc[i].out_off = (long long)out_words;
+      src_words += (size_t)p[i].nrows * p[i].ncols + (size_t)p[i].ctx_rows * p[i].ctx_cols;
+      out_words += (size_t)info[i].ni * (info[i].nvar + info[i].nparm + 1) + (size_t)info[i].nc * (info[i].nparm + 1);
+    }
+    return nbad;
+  }
+  // descriptors and matrices into the pinned staging buffer, one H2D copy, the build kernel; want_range: fetch the flags
+  void build(pipamd_engine *e, int n, const pipamd_pip_problem *p, bool want_range) {
+    std::vector<int> which;
+    for (int i = 0; i < n; i++)
+      if (todo[i]) which.push_back(i);
+    const int nb = (int)which.size();
+    if (!nb) return;
+    const size_t dbytes = sizeof(M2TProb) * (size_t)nb, bytes = dbytes + sizeof(i64) * src_words;
+    char *h = (char *)dt_staging(e, bytes);
+    i64 *hm = (i64 *)(h + dbytes);
+    for (int k = 0; k < nb; k++) {
+      const pipamd_pip_problem &q = p[which[k]];
+      const M2TProb &d = desc[which[k]];
+      memcpy(h + sizeof(M2TProb) * (size_t)k, &d, sizeof d);
+      const size_t na = (size_t)q.nrows * q.ncols, nc = (size_t)q.ctx_rows * q.ctx_cols;
+      if (na) memcpy(hm + d.src_off, q.inequnk, na * sizeof(i64));
+      if (nc) memcpy(hm + d.src_off + na, q.ineqpar, nc * sizeof(i64));
+    }
+    char *d_in = dt_buffer<char>(e, 8, bytes);
+    d_out = dt_buffer<i64>(e, 7, sizeof(i64) * std::max<size_t>(out_words, 1));
+    int *d_range = dt_buffer<int>(e, 9, sizeof(int) * (size_t)nb);
+    HIPTHROW(hipMemcpyAsync(d_in, h, bytes, hipMemcpyHostToDevice, 0));
+    HIPTHROW(pipk_launch_m2t((const M2TProb *)d_in, (const i64 *)(d_in + dbytes), d_out, d_range, nb, 0));
+    if (want_range) {
+      std::vector<int> r(nb);
+      HIPTHROW(hipMemcpy(r.data(), d_range, sizeof(int) * (size_t)nb, hipMemcpyDeviceToHost));
+      for (int k = 0; k < nb; k++) range[which[k]] = r[k];
+    }
+  }
+  // the built rows back on the host (one copy; it also waits for the kernel)
+  void fetch(i64 *dst) const {
+    if (out_words) HIPTHROW(hipMemcpy(dst, d_out, sizeof(i64) * out_words, hipMemcpyDeviceToHost));
+  }
+};
+
+struct DtHold {
+  pthread_mutex_t *m;
+  explicit DtHold(pthread_mutex_t *mm) : m(mm) { pthread_mutex_lock(m); }
+  void release() {
+    if (m) pthread_mutex_unlock(m);
+    m = nullptr;
+  }
+  ~DtHold() { release(); }
+};
+
+// one problem of pipamd_pip_solve_many on a host tree, from its built rows: piplib.c:815-858
+template <class E, class CELL>
+int pip_one(TreeT<E> &t, const pipamd_problem &p, bool dual, int deepest_cut, CELL **cells, size_t *n_cells, int *status,
+            int64_t *pivots, bool *is_void) {
+  const int ncol = p.nvar + p.nparm + 1;
+  std::vector<i64> a((const i64 *)p.ineq, (const i64 *)p.ineq + (size_t)p.ni * ncol);
+  std::vector<i64> c((const i64 *)p.ctx, (const i64 *)p.ctx + (size_t)p.nc * (p.nparm + 1));
+  if (p.nq) {
+    simplify_rows(a, p.ni, ncol, p.nvar);
+    simplify_rows(c, p.nc, p.nparm + 1, p.nparm);
+  }
+  bool non_void = false;
+  const int rc = tree_call(t, deepest_cut, status, pivots, [&] {
+    t.dual_ = dual;
+    non_void = t.front(p.nvar, p.nparm, p.ni, p.nc, p.bigparm, p.nq, a.data(), c.data());
+  });
+  if (rc) return rc;
+  *is_void = !non_void;
+  return non_void ? export_tape(t.tape, cells, n_cells) : PIPAMD_OK;
+}
+
+template <class E, class CELL>
+int pip_solve_many_any(pipamd_engine *e, int n, const pipamd_pip_problem *p, int deepest_cut, int nthreads, pipamd_pip_info *info,
+                       CELL **cells, size_t *n_cells, int *rcs, int *statuses, int64_t *pivots) {
+  constexpr bool WIDE = sizeof(E) == 16;
+  if (!e || n < 0 || (n && (!p || !info || !cells || !n_cells || !rcs))) return PIPAMD_E_INVALID;
+  e->dt_served = e->dt_fallback = 0;
+  if (n == 0) return PIPAMD_OK;
+  if (nthreads < 1) nthreads = 1;
+  if (nthreads > n) nthreads = n;
+  for (int i = 0; i < n; i++) {
+    cells[i] = nullptr;
+    n_cells[i] = 0;
+    if (statuses) statuses[i] = 0;
+    if (pivots) pivots[i] = 0;
+  }
+  PipBuild b;
+  b.plan(n, p, info, rcs);  // (validation: before any HIP call)
+  std::vector<char> served(n, 0);
+  bool any = false;
+  for (int i = 0; i < n; i++) {
+    served[i] = !b.todo[i];  // malformed (rcs[i] says so) or void already
+    any |= b.todo[i] != 0;
+  }
+  if (!any) return PIPAMD_OK;
+  for (int i = 0; i < n; i++)
+    if (b.todo[i]) rcs[i] = PIPAMD_E_HIP;  // until a path has served it
+  if (hipSetDevice(e->device) != hipSuccess) return PIPAMD_OK;
+  std::vector<i64> rows(b.out_words + 1);  // the built rows, fetched only when a host tree needs them
+  std::vector<pipamd_problem> tp(n);
+  std::vector<int> qfl(n, -1);
+  std::vector<long long> off(n, 0);
+  for (int i = 0; i < n; i++) {
+    if (!b.todo[i]) continue;
+    const pipamd_pip_info &f = info[i];
+    const i64 *r = rows.data() + b.desc[i].out_off;
+    tp[i] = pipamd_problem{f.nvar, f.nparm, f.ni, f.nc, f.bigparm, (f.flags & PIPAMD_T_INT) ? 1 : 0, (const int64_t *)r,
+                           (const int64_t *)(r + (size_t)f.ni * (f.nvar + f.nparm + 1))};
+    qfl[i] = (f.flags & PIPAMD_T_DUAL) ? Q_DUAL : 0;
+    off[i] = b.desc[i].out_off;
+  }
+  try {
+    DtHold hold(&e->dt_lock);
+    b.build(e, n, p, WIDE);
+    if (WIDE)
+      for (int i = 0; i < n; i++)
+        if (b.range[i]) {  // the big column does not fit the int64 tableau: no wrapped column in this flavour
+          pipamd_set_error("pipamd_pip_solve_many128: the big column of problem %d leaves 64 bits", i);
+          rcs[i] = PIPAMD_E_SOLVER;
+          if (statuses) statuses[i] = PIPAMD_ST_RANGE;
+          served[i] = 1;
+          qfl[i] = -1;
+        }
+    if (!e->no_device_tree && !getenv("PIPAMD_NO_DEVICE_TREE")) {
+      std::vector<FResultT<E>> res(n);
+      for (auto &r : res) r.rc = PIPAMD_E_TOOLARGE;
+      int nserved = 0, back = 0;
+      device_tree<E>(e, n, tp.data(), 1, deepest_cut, res, &nserved, &back, qfl.data(), b.d_out, off.data());
+      e->dt_served = nserved;
+      e->dt_fallback = back;
+      for (int i = 0; i < n; i++)
+        if (!served[i] && res[i].rc == PIPAMD_OK) info[i].is_void = res[i].is_void;
+      export_results(res, served, cells, n_cells, rcs, statuses, pivots);
+    }
+    if (std::find(served.begin(), served.end(), 0) != served.end()) b.fetch(rows.data());
+  } catch (int) {  // allocation, copy or launch failure: what is not served keeps PIPAMD_E_HIP
+    (void)hipGetLastError();
+    return PIPAMD_OK;
+  }
+  if (std::find(served.begin(), served.end(), 0) != served.end())
+    run_workers<TreeT<E>>(e, deepest_cut, nthreads, n, served, [&](TreeT<E> &t, int i) {
+      bool is_void = false;
+      rcs[i] = pip_one(t, tp[i], (info[i].flags & PIPAMD_T_DUAL) != 0, deepest_cut, &cells[i], &n_cells[i],
+                       statuses ? &statuses[i] : nullptr, pivots ? &pivots[i] : nullptr, &is_void);
+      info[i].is_void = is_void;
+    });
+  return PIPAMD_OK;
+}
+}  // namespace
+
+extern "C" int pipamd_pip_tableaux(pipamd_engine *e, int n, const pipamd_pip_problem *p, pipamd_pip_info *info, int64_t **rows,
+                                   size_t *n_words) {
+  if (!e || n < 0 || !rows || !n_words || (n && (!p || !info))) return PIPAMD_E_INVALID;
+  *rows = nullptr;
+  *n_words = 0;
+  PipBuild b;
+  const int nbad = b.plan(n, p, info, nullptr);
+  if (b.out_words) {
+    if (hipSetDevice(e->device) != hipSuccess) return PIPAMD_E_HIP;
+    int64_t *r = (int64_t *)malloc(sizeof(int64_t) * b.out_words);
+    if (!r) return PIPAMD_E_NOMEM;
+    try {
+      DtHold hold(&e->dt_lock);
+      b.build(e, n, p, false);
+      b.fetch((i64 *)r);
+    } catch (int code) {
+      (void)hipGetLastError();
+      free(r);
+      return code;
+    }
+    *rows = r;
+    *n_words = b.out_words;
+  }
+  return nbad ? PIPAMD_E_INVALID : PIPAMD_OK;
+}
+extern "C" int pipamd_pip_solve_many(pipamd_engine *e, int n, const pipamd_pip_problem *p, int deepest_cut, int nthreads,
+                                     pipamd_pip_info *info, pipamd_sol_cell **cells, size_t *n_cells, int *rcs, int *statuses,
+                                     int64_t *pivots) {
+  return pip_solve_many_any<i64>(e, n, p, deepest_cut, nthreads, info, cells, n_cells, rcs, statuses, pivots);
+}
+extern "C" int pipamd_pip_solve_many128(pipamd_engine *e, int n, const pipamd_pip_problem *p, int deepest_cut, int nthreads,
+                                        pipamd_pip_info *info, pipamd_sol_cell128 **cells, size_t *n_cells, int *rcs,
+                                        int *statuses, int64_t *pivots) {
+  return pip_solve_many_any<i128>(e, n, p, deepest_cut, nthreads, info, cells, n_cells, rcs, statuses, pivots);
 }

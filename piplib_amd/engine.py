@@ -756,3 +756,105 @@ def solve_tableaux(engine, problems, simplify=True, deepest_cut=False, nthreads=
     prep = PreparedProblems(problems)
     solve_prepared(engine, prep, simplify, deepest_cut, nthreads, lockstep)
     return prep.results()
+
+
+# ---- pip_solve(inequnk, ineqpar, Bg, options) for many problems, from the PolyLib matrices (pipamd_pip_*)
+PIP_NQ, PIP_MAXIMIZE, PIP_URS_PARMS, PIP_URS_UNKNOWNS, PIP_DUAL = 1, 2, 4, 8, 16
+
+
+class PipSolveProblem(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("nrows", "ncols", "ctx_rows", "ctx_cols", "bg", "options")] + \
+               [("inequnk", C.c_void_p), ("ineqpar", C.c_void_p)]
+
+
+class PipInfo(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("nvar", "nparm", "ni", "nc", "bigparm", "flags", "sol_bg", "urs_parms",
+                                         "sol_flags", "is_void")] + [("row_off", C.c_int64)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class PipInput:
+    """One pip_solve call: inequnk / ineqpar are 2-D int64 arrays in PolyLib form (marker column first) or None, bg the
+    big parameter's tableau column or -1, options a sum of PIP_*.  shape = (nrows, ncols, ctx_rows, ctx_cols) overrides
+    what the arrays say (tests of malformed problems)."""
+
+    def __init__(self, inequnk, ineqpar=None, bg=-1, options=PIP_NQ, shape=None):
+        self.inequnk, self.ineqpar, self.bg, self.options, self.shape = inequnk, ineqpar, bg, options, shape
+
+
+class _PipPrepared:
+    def __init__(self, problems):
+        import numpy as np
+        self.n = n = len(problems)
+        self.arr = (PipSolveProblem * max(1, n))()
+        self.info = (PipInfo * max(1, n))()
+        self.keep = []
+        for i, p in enumerate(problems):
+            a = None if p.inequnk is None else np.ascontiguousarray(p.inequnk, dtype=np.int64)
+            c = None if p.ineqpar is None else np.ascontiguousarray(p.ineqpar, dtype=np.int64)
+            if (a is not None and a.ndim != 2) or (c is not None and c.ndim != 2):
+                raise ValueError("pip problems take 2-D matrices")
+            self.keep += [a, c]
+            shape = p.shape or ((a.shape if a is not None else (0, 0)) + (c.shape if c is not None else (0, 0)))
+            self.arr[i] = PipSolveProblem(*[int(x) for x in shape], int(p.bg), int(p.options),
+                                          a.ctypes.data if a is not None else None,
+                                          c.ctypes.data if c is not None and c.size else None)
+
+
+def pip_tableaux(engine, problems):
+    """pipamd_pip_tableaux: tab_Matrix2Tableau for many problems (PipInput-like objects), built on the device.
+    Returns (infos, tableaux): infos[i] a dict of pipamd_pip_info, tableaux[i] = (domain rows, context rows) as int64
+    arrays, or None for a void or malformed problem (infos[i]["nvar"] < 0: malformed)."""
+    import numpy as np
+    L = lib()
+    if not hasattr(L, "pipamd_pip_tableaux"):
+        raise RuntimeError("libpipamd has no pipamd_pip_tableaux: rebuild the library")
+    prep = _PipPrepared(problems)
+    fn = L.pipamd_pip_tableaux
+    fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]
+    rows, nw = C.c_void_p(), C.c_size_t(0)
+    rc = fn(engine._h, prep.n, prep.arr, prep.info, C.byref(rows), C.byref(nw))
+    if rc != -1:  # PIPAMD_E_INVALID with rows: some problem is malformed, the others are built
+        _check(rc)
+    flat = np.zeros(0, dtype=np.int64)
+    if rows and nw.value:
+        flat = np.ctypeslib.as_array(C.cast(rows, C.POINTER(C.c_int64)), shape=(nw.value,)).copy()
+        L.pipamd_free(rows)
+    infos, tabs = [], []
+    for i in range(prep.n):
+        f = prep.info[i].as_dict()
+        infos.append(f)
+        if f["nvar"] < 0 or f["is_void"]:
+            tabs.append(None)
+            continue
+        w, cw = f["nvar"] + f["nparm"] + 1, f["nparm"] + 1
+        o = f["row_off"]
+        dom = flat[o:o + f["ni"] * w].reshape(f["ni"], w)
+        o += f["ni"] * w
+        tabs.append((dom, flat[o:o + f["nc"] * cw].reshape(f["nc"], cw)))
+    return infos, tabs
+
+
+def pip_solve_many(engine, problems, deepest_cut=False, nthreads=8, bits=64):
+    """pipamd_pip_solve_many / pipamd_pip_solve_many128: pip_solve for many problems (PipInput-like objects) in one call.
+    Returns a list of (cells | None, rc, status, pivots, info): the tape as pip_solve has it when traiter() returns (empty
+    for a void answer, info["is_void"] = 1; None where rc != 0) and info, the dict of pipamd_pip_info."""
+    L = lib()
+    name = "pipamd_pip_solve_many128" if bits == 128 else "pipamd_pip_solve_many"
+    if not hasattr(L, name):
+        raise RuntimeError(f"libpipamd has no {name}: rebuild the library")
+    prep = _PipPrepared(problems)
+    n = prep.n
+    cells, ncell = (C.c_void_p * max(1, n))(), (C.c_size_t * max(1, n))()
+    rcs, sts, piv = (C.c_int * max(1, n))(), (C.c_int * max(1, n))(), (C.c_int64 * max(1, n))()
+    fn = getattr(L, name)
+    fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6
+    _check(fn(engine._h, n, prep.arr, int(bool(deepest_cut)), int(nthreads), prep.info, cells, ncell, rcs, sts, piv))
+    take = _take_cells128 if bits == 128 else _take_cells
+    out = []
+    for i in range(n):
+        got = take(cells[i], ncell[i])
+        out.append((got if rcs[i] == 0 else None, rcs[i], sts[i], piv[i], prep.info[i].as_dict()))
+    return out
