@@ -49,7 +49,9 @@ extern "C" {
  * layer 1; pipamd_batch_load_system / pipamd_batch_dual_system and their _part forms -- layer 1 from the plain system
  * pip_solve takes (equalities, tab_simplify, the dual under Maximize / Urs_unknowns and of equalities);
  * pipamd_batch_load_matrices / pipamd_batch_dual_matrices and their _part forms -- the same from PolyLib matrices, each
- * system with its own row count and its equalities where its marker column has them (PIPAMD_ST_BADINPUT). */
+ * system with its own row count and its equalities where its marker column has them (PIPAMD_ST_BADINPUT);
+ * pipamd_batch_load_sparse / pipamd_batch_dual_sparse and their _part forms -- the plain system as sparse rows (CSR on
+ * the device), the tableaux built from them as from the dense expansion. */
 #define PIPAMD_VERSION 500
 
 /* ---- error codes (return values) ---- */
@@ -87,7 +89,7 @@ extern "C" {
 #define PIPAMD_ST_RANGE 7        /* entries too large for the exact fast pivot-column choice */
 #define PIPAMD_ST_INTERNAL 8
 #define PIPAMD_ST_MAXCOL 9       /* "Too many variables" (integrer.c:324) */
-#define PIPAMD_ST_BADINPUT 10    /* a system the load could not take (see pipamd_batch_load_matrices) */
+#define PIPAMD_ST_BADINPUT 10    /* a system the load could not take (see pipamd_batch_load_matrices, _sparse) */
 
 /* ---- row flags (reference tab.h:55-62) ---- */
 #define PIPAMD_F_UNIT 1
@@ -369,6 +371,49 @@ int pipamd_batch_dual_matrices(pipamd_engine *e, const void *d_workspace, const 
 int pipamd_batch_dual_matrices_part(pipamd_engine *e, const void *d_workspace, const pipamd_batch_desc *d,
                                     const pipamd_matrices *m, const int64_t *d_rows, int first, int count, int64_t *d_dual_num,
                                     int64_t *d_dual_den, void *stream);
+
+/* The plain system of pipamd_batch_load_system as SPARSE rows: the constraint matrix a front end has, column / value pairs
+ * with a row-pointer array (CSR), all three on the device.  `sys` is exactly the pipamd_system of the system entries
+ * (nrows, neq, the HOST list eq_rows, shift, simplify) and the descriptor is theirs: d->ni == nrows + neq; shift == 0:
+ * nparm == 0, bigparm == -1; shift == +-1: nparm == 1, bigparm == nvar + 1.  Row r of system s owns the entries
+ * d_row_ptr[s * nrows + r] .. d_row_ptr[s * nrows + r + 1] - 1 of d_cols / d_vals; a column is 0 .. nvar - 1 for an
+ * unknown and nvar for the constant; a row's columns are strictly increasing (canonical CSR); a stored 0 is allowed and
+ * equals an absent entry.  Values are int64 for either entry width, as for the dense loads.
+ * pipamd_batch_load_sparse: for every system the tableau, row tables, spare slots and job header are bit for bit what
+ * pipamd_batch_load_system builds from the system's dense expansion (nrows x (nvar + 1), zero where nothing is stored):
+ * the row order with an equality's negated twin, the shift, the big column summed in the entry type, tab_simplify.
+ * PIPAMD_T_ROWS_STAY is ignored; the three arrays may be released once the load's work on `stream` is done.  The solve
+ * and the result entries are the existing ones.
+ * A system the load cannot take is BAD and handled as pipamd_batch_load_matrices handles its bad systems: the load
+ * finishes it itself -- an empty tableau (ni = 0) with status PIPAMD_ST_BADINPUT --, pipamd_batch_solve skips it, the
+ * result and dual entries give it zeros, and the other systems are not disturbed.  Bad is: a row pointer of the system
+ * outside [0, nnz] or below its predecessor; a row of more than nvar + 1 entries; a column outside 0 .. nvar; a row whose
+ * columns are not strictly increasing.  A system's pointers are checked before any entry is read through them, and
+ * nothing of d_cols / d_vals is read outside [0, nnz).
+ * pipamd_batch_dual_sparse: pipamd_batch_dual_system for a batch loaded this way, callable where that is; one kernel on
+ * `stream`, no synchronisation; `s` names the arrays the batch was loaded from.  d_dual_num[b][r], d_dual_den[b][r],
+ * r < nrows: one reduced pair per input row, an equality's two values merged (u if u != 0, else -v); (0, 0) throughout
+ * for a tableau that is not PIPAMD_ST_SOLUTION, a bad system among them.
+ * _part: the tableaux first .. first + count - 1; the three arrays and nnz describe the `count` systems of the part
+ * (d_row_ptr has count * nrows + 1 offsets into the part's d_cols / d_vals), the dual arrays are the whole batch's.
+ * PIPAMD_E_INVALID, before any HIP call: everything pipamd_batch_load_system / pipamd_batch_dual_system refuse, with the
+ * same rules on `sys`, the descriptor and first / count; a null `s` or d_row_ptr; nnz < 0; null d_cols or d_vals with
+ * nnz > 0.  PIPAMD_E_TOOLARGE as for the system entries. */
+typedef struct pipamd_sparse {
+  pipamd_system sys;        /* nrows, neq, eq_rows (HOST list), shift, simplify: exactly as pipamd_batch_load_system */
+  int64_t nnz;              /* entries in d_cols / d_vals (of the call: the whole batch, or the part) */
+  const int64_t *d_row_ptr; /* DEVICE, systems * nrows + 1 offsets */
+  const int32_t *d_cols;    /* DEVICE: column of each entry, 0 .. nvar-1 an unknown, nvar the constant */
+  const int64_t *d_vals;    /* DEVICE: its value */
+} pipamd_sparse;            /* 56 bytes, offsets 0 24 32 40 48 */
+int pipamd_batch_load_sparse(pipamd_engine *e, void *d_workspace, const pipamd_batch_desc *d, const pipamd_sparse *s,
+                             void *stream);
+int pipamd_batch_load_sparse_part(pipamd_engine *e, void *d_workspace, const pipamd_batch_desc *d, const pipamd_sparse *s,
+                                  int first, int count, void *stream);
+int pipamd_batch_dual_sparse(pipamd_engine *e, const void *d_workspace, const pipamd_batch_desc *d, const pipamd_sparse *s,
+                             int64_t *d_dual_num, int64_t *d_dual_den, void *stream);
+int pipamd_batch_dual_sparse_part(pipamd_engine *e, const void *d_workspace, const pipamd_batch_desc *d, const pipamd_sparse *s,
+                                  int first, int count, int64_t *d_dual_num, int64_t *d_dual_den, void *stream);
 
 /* Batch totals, device memory, 4 x uint64: [0] pivots (calls of pivoter), [1] Gomory cuts,
  * [2] rows rewritten by pivots (rows whose pivot-column entry is zero and that are already

@@ -982,6 +982,63 @@ extern "C" int pipamd_batch_dual_system(pipamd_engine *e, const void *d_ws, cons
   return pipamd_batch_dual_system_part(e, d_ws, d, sys, d_rows, 0, d ? d->batch : 0, d_dual_num, d_dual_den, stream);
 }
 
+// The plain system as sparse rows (header comment: include/piplib_amd.h): the system entries' checks on `sys` and the
+// descriptor, with the row pointers in the place of the rows; what the arrays hold is checked on the device.
+static int sparse_check(const char *who, const void *e, const void *d_ws, const pipamd_batch_desc *d, const pipamd_sparse *s,
+                        PipEqMask *eq, PipCsrRows *cs) {
+  int rc = system_check(who, e, d_ws, d, s ? &s->sys : nullptr, s ? s->d_row_ptr : nullptr, eq);
+  if (rc) return rc;
+  if (s->nnz < 0 || (s->nnz > 0 && (!s->d_cols || !s->d_vals))) {
+    pipamd_set_error("%s: nnz (%lld) below 0, or entries without a column or a value array", who, (long long)s->nnz);
+    return PIPAMD_E_INVALID;
+  }
+  cs->row_ptr = s->d_row_ptr;
+  cs->cols = s->d_cols;
+  cs->vals = s->d_vals;
+  cs->nnz = s->nnz;
+  return PIPAMD_OK;
+}
+
+extern "C" int pipamd_batch_load_sparse_part(pipamd_engine *e, void *d_ws, const pipamd_batch_desc *d, const pipamd_sparse *s,
+                                             int first, int count, void *stream) {
+  PipEqMask eq;
+  PipCsrRows cs;
+  int rc = sparse_check("batch_load_sparse", e, d_ws, d, s, &eq, &cs);
+  if (rc) return rc;
+  BatchView v;
+  rc = batch_view("batch_load_sparse", e, d_ws, d, first, count, &v);
+  if (rc) return rc;
+  HIPCHK(pipk_launch_batch_load_sparse(v.jobs, v.arena, &cs, v.lay, s->sys.shift, s->sys.simplify, s->sys.nrows, &eq, first, count,
+                                       (hipStream_t)stream));
+  return PIPAMD_OK;
+}
+
+extern "C" int pipamd_batch_load_sparse(pipamd_engine *e, void *d_ws, const pipamd_batch_desc *d, const pipamd_sparse *s,
+                                        void *stream) {
+  return pipamd_batch_load_sparse_part(e, d_ws, d, s, 0, d ? d->batch : 0, stream);
+}
+
+extern "C" int pipamd_batch_dual_sparse_part(pipamd_engine *e, const void *d_ws, const pipamd_batch_desc *d, const pipamd_sparse *s,
+                                             int first, int count, int64_t *d_dual_num, int64_t *d_dual_den, void *stream) {
+  PipEqMask eq;
+  PipCsrRows cs;
+  int rc = sparse_check("batch_dual_sparse", e, d_ws, d, s, &eq, &cs);
+  if (rc) return rc;
+  rc = dual_check("batch_dual_sparse", d, cs.row_ptr, d_dual_num, d_dual_den);
+  if (rc) return rc;
+  BatchView v;
+  rc = batch_view("batch_dual_sparse", e, d_ws, d, first, count, &v);
+  if (rc) return rc;
+  HIPCHK(pipk_launch_batch_dual_sparse(v.jobs, v.arena, &cs, v.lay, s->sys.nrows, &eq, first, count, (void *)d_dual_num,
+                                       (void *)d_dual_den, (hipStream_t)stream));
+  return PIPAMD_OK;
+}
+
+extern "C" int pipamd_batch_dual_sparse(pipamd_engine *e, const void *d_ws, const pipamd_batch_desc *d, const pipamd_sparse *s,
+                                        int64_t *d_dual_num, int64_t *d_dual_den, void *stream) {
+  return pipamd_batch_dual_sparse_part(e, d_ws, d, s, 0, d ? d->batch : 0, d_dual_num, d_dual_den, stream);
+}
+
 // PolyLib matrices with a row count and markers per system (header comment: include/piplib_amd.h).  Which rows are
 // equalities and how many rows a system has is found on the device; what is left to refuse here is the description.
 static int matrices_check(const char *who, const void *e, const void *d_ws, const pipamd_batch_desc *d, const pipamd_matrices *m,

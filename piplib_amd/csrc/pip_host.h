@@ -93,6 +93,12 @@ hipError_t pipk_launch_batch_dual(const PipJob *jobs, const long long *arena, co
 hipError_t pipk_launch_batch_load_system(PipJob *jobs, long long *arena, const long long *rows, PipBatchLayout lay, int shift,
                                          int simplify, int nrows, const PipEqMask *eq, const PipEqMarkers *mk, int first,
                                          int count, hipStream_t stream);
+/* pipamd_batch_load_sparse / pipamd_batch_dual_sparse: the system launches with the rows in the CSR arrays of `cs` */
+hipError_t pipk_launch_batch_load_sparse(PipJob *jobs, long long *arena, const PipCsrRows *cs, PipBatchLayout lay, int shift,
+                                         int simplify, int nrows, const PipEqMask *eq, int first, int count, hipStream_t stream);
+hipError_t pipk_launch_batch_dual_sparse(const PipJob *jobs, const long long *arena, const PipCsrRows *cs, PipBatchLayout lay,
+                                         int nrows, const PipEqMask *eq, int first, int count, void *dual_num, void *dual_den,
+                                         hipStream_t stream);
 hipError_t pipk_launch_rehouse(PipJob *jobs, long long *arena, void *const *q5, int grid, PipBatchLayout nl, int *side_count,
                                int side_cap, hipStream_t stream);
 hipError_t pipk_launch_rehouse_finish(PipJob *jobs, long long *arena, int njobs, int sol_words, hipStream_t stream);

@@ -74,6 +74,17 @@ typedef struct PipEqMarkers {
   int32_t max_rows;
 } PipEqMarkers;
 
+/* Where a system's input rows come from when they are not dense (pipamd_sparse): CSR over the systems of the launch, all
+ * three arrays on the DEVICE.  Row r of system s (nrows rows each) owns the entries row_ptr[s * nrows + r] ..
+ * row_ptr[s * nrows + r + 1] - 1 of cols / vals; a column is 0 .. nvar - 1 for an unknown and nvar for the constant.
+ * The kernels check a system's pointers against [0, nnz] before they read an entry through them. */
+typedef struct PipCsrRows {
+  const int64_t *row_ptr;
+  const int32_t *cols;
+  const int64_t *vals;
+  int64_t nnz;
+} PipCsrRows;
+
 #ifdef __HIPCC__
 #define PIP_HD __host__ __device__
 #else

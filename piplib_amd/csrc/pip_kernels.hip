@@ -265,11 +265,69 @@ __device__ __forceinline__ int eq_from_markers(const PipEqMarkers &mk, int sys, 
   return n;
 }
 
-template <class T, int CPL, class EQ>
+// Where a lane's input value comes from is the kernel's SRC policy (pip_batch_dual_kernel has the same ones):
+//   PipDenseRows: `rows`, nvar + 1 (+ marker) int64 a row; the lane reads its columns.  Nothing travels with the launch.
+//   PipCsrRows (pipamd_batch_load_sparse; with PipEqMask): a row's stored entries, column and value, strictly
+//     increasing columns, the constant as column nvar.  The wave reads them 64 at a time, an entry per lane, and a
+//     readlane loop over the entries hands each value to the lane that owns its column: a sparse row has a few
+//     entries, the loop costs as many steps, and neither LDS nor a register is added to the dense instantiations.
+//     Before anything is stored the block checks the system (csr_system_ok); a bad one is finished here as the
+//     markers policy finishes its bad systems: an empty tableau, PIPAMD_ST_BADINPUT.
+struct PipDenseRows {};
+
+// PipCsrRows, by all waves of a block: may system `sys` of the launch (`nrows` rows) be read?  First its nrows + 1
+// pointers: within [0, nnz], not decreasing, at most nvar + 1 entries a row; then, only if they hold, its entries: every
+// column strictly above its predecessor in the row (above -1 for the first: none is negative) and at most nvar.
+// Nothing of cols is read outside [0, nnz) and nothing of vals at all.  Every thread gets the same answer.
+__device__ __forceinline__ bool csr_system_ok(const PipCsrRows &cs, int sys, int nrows, int nvar) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwave = (int)blockDim.x >> 6;
+  const i64 *rp = (const i64 *)cs.row_ptr + (size_t)sys * nrows;
+  bool ok = true;
+  for (int r = tid; r < nrows; r += blockDim.x) {
+    const i64 p0 = rp[r], p1 = rp[r + 1];
+    ok = ok && p0 >= 0 && p1 >= p0 && p1 <= cs.nnz && p1 - p0 <= nvar + 1;
+  }
+  if (!__syncthreads_and(ok)) return false;
+  for (int r = wave; r < nrows; r += nwave) {
+    const i64 p0 = rp[r], p1 = rp[r + 1];
+    for (i64 e = p0 + lane; e < p1; e += 64) {
+      const int c = cs.cols[e], prev = e > p0 ? cs.cols[e - 1] : -1;
+      ok = ok && c > prev && c <= nvar;
+    }
+  }
+  return __syncthreads_and(ok);
+}
+
+// PipCsrRows: the values of the row whose entries are p0 .. p1 - 1 (checked), to the lanes that own their columns:
+// a[c] of lane l is column l + 64 * c, zero where nothing is stored
+template <int CPL>
+__device__ __forceinline__ void csr_row_to_lanes(const PipCsrRows &cs, i64 p0, i64 p1, int lane, i64 (&a)[CPL]) {
+#pragma unroll
+  for (int c = 0; c < CPL; c++) a[c] = 0;
+  for (i64 e0 = p0; e0 < p1; e0 += 64) {
+    const int n = p1 - e0 < 64 ? (int)(p1 - e0) : 64;
+    const int col = lane < n ? cs.cols[e0 + lane] : 0;
+    const i64 val = lane < n ? cs.vals[e0 + lane] : 0;
+    for (int i = 0; i < n; i++) {
+      const int ci = __builtin_amdgcn_readlane(col, i);
+      const i64 vi = readlane64(val, i);
+      if (lane == (ci & 63)) {
+#pragma unroll
+        for (int c = 0; c < CPL; c++)
+          if (c == (ci >> 6)) a[c] = vi;
+      }
+    }
+  }
+}
+
+template <class T, int CPL, class EQ, class SRC>
 __global__ __launch_bounds__(256) void pip_batch_load_system_kernel(PipJob *jobs, i64 *arena, const i64 *rows, PipBatchLayout lay,
-                                                                    int first, int shift, int simplify, int nrows, EQ eq) {
+                                                                    int first, int shift, int simplify, int nrows, EQ eq,
+                                                                    SRC rs) {
   typedef typename ET<T>::U U;
   constexpr bool MARKED = std::is_same<EQ, PipEqMarkers>::value;
+  constexpr bool CSR = std::is_same<SRC, PipCsrRows>::value;
+  static_assert(!(MARKED && CSR), "sparse rows come with the launch's equality mask");
   constexpr int MK = MARKED ? 1 : 0;  // words of a source row before its unknowns
   const int b = first + blockIdx.x;  // `rows` holds the systems first, first + 1, ... of the batch
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -285,8 +343,13 @@ __global__ __launch_bounds__(256) void pip_batch_load_system_kernel(PipJob *jobs
     nrows = eq_from_markers<4>(eq, blockIdx.x, src, srcrow, lay.ni, words, ni);
     eqw = words;
   }
+  bool bad = false;  // (PipCsrRows)
+  if constexpr (CSR) {
+    bad = !csr_system_ok(rs, blockIdx.x, nrows, nvar);
+    if (bad) nrows = ni = 0;
+  }
   load_row_tables<T>(arena + base, lay, ni, tid);
-  if constexpr (!MARKED) src = rows + (size_t)blockIdx.x * nrows * srccol;
+  if constexpr (!MARKED && !CSR) src = rows + (size_t)blockIdx.x * nrows * srccol;
   int wcur = 0, before = 0;  // equalities among the rows below 64 * wcur
   for (int r = wave; r < nrows; r += 4) {
     for (; wcur < (r >> 6); wcur++) before += __popcll(eq_word(eq, eqw, wcur));
@@ -294,13 +357,22 @@ __global__ __launch_bounds__(256) void pip_batch_load_system_kernel(PipJob *jobs
     const int k = r + before + __popcll(word & ((1ull << (r & 63)) - 1));
     const bool twin = (word >> (r & 63)) & 1;
     if (k + (int)twin >= ni) break;  // (the host has held the list against ni; the markers' count gave ni)
-    const i64 *in = src + (size_t)r * srcrow + MK;
+    const i64 *in = CSR ? nullptr : src + (size_t)r * srcrow + MK;
+    i64 sp[CSR ? CPL : 1];  // PipCsrRows: the row's values, each in the lane of its column
+    if constexpr (CSR) {
+      const i64 *rp = (const i64 *)rs.row_ptr + (size_t)blockIdx.x * nrows + r;
+      csr_row_to_lanes<CPL>(rs, uni64(rp[0]), uni64(rp[1]), lane, sp);
+    }
     T v[CPL], sum = 0;
     u64 g = 0;
 #pragma unroll
     for (int c = 0; c < CPL; c++) {
       const int j = lane + 64 * c;
-      const i64 a = j < srccol ? in[j] : 0;
+      i64 a;
+      if constexpr (CSR)
+        a = sp[c];
+      else
+        a = j < srccol ? in[j] : 0;
       v[c] = (T)a;  // the constant as it is, zero beyond it
       if (j < nvar) {
         sum = wadd(sum, (T)a);
@@ -343,7 +415,8 @@ __global__ __launch_bounds__(256) void pip_batch_load_system_kernel(PipJob *jobs
   }
   load_clear_spare(vals, lay, ni, tid);
   if (tid == 0)
-    load_job_header<T>(&jobs[b], base, lay, ni, MARKED && nrows == 0 ? PIPAMD_ST_BADINPUT : PIPAMD_ST_RUN, false, nullptr);
+    load_job_header<T>(&jobs[b], base, lay, ni, (MARKED && nrows == 0) || bad ? PIPAMD_ST_BADINPUT : PIPAMD_ST_RUN, false,
+                       nullptr);
 }
 
 // sol_vector_edit (sol.c:435-512) with SOL_REMOVE and SOL_MAX / SOL_SHIFT for a batch solved under a big parameter
@@ -509,12 +582,17 @@ __device__ void dual_sort_pairs(float *key, u16 *ineq, int n, double smax, int l
 //     The tableau at hand has ni_b = rows + equalities rows, which its header must agree with, and ni_b pairs are
 //     sorted; the LDS tables keep the room of lay.ni.  [batch][max_rows] pairs are written, (0, 0) from the system's
 //     row count on, and throughout for a bad system.
-template <class T, class EQ>
+//   SRC == PipCsrRows (pipamd_batch_dual_sparse, with PipEqMask): the rows are the CSR arrays the batch was loaded
+//     from.  A row's key is the maximum over its stored entries with a column below nvar -- an absent entry is a zero
+//     and adds nothing.  A system csr_system_ok refuses was bad for the load: (0, 0) throughout.
+template <class T, class EQ, class SRC>
 __global__ __launch_bounds__(64) void pip_batch_dual_kernel(const PipJob *jobs, const i64 *arena, const i64 *rows,
                                                             PipBatchLayout lay, int first, int nrows, EQ eq, T *dual_num,
-                                                            T *dual_den) {
+                                                            T *dual_den, SRC rs) {
   constexpr bool SYSTEM = !std::is_same<EQ, PipNoEq>::value;
   constexpr bool MARKED = std::is_same<EQ, PipEqMarkers>::value;
+  constexpr bool CSR = std::is_same<SRC, PipCsrRows>::value;
+  static_assert(!CSR || std::is_same<EQ, PipEqMask>::value, "sparse rows come with the launch's equality mask");
   constexpr int MK = MARKED ? 1 : 0;  // words of a source row before its unknowns
   extern __shared__ __align__(16) unsigned char dual_lds[];
   const int lane = threadIdx.x;
@@ -535,6 +613,9 @@ __global__ __launch_bounds__(64) void pip_batch_dual_kernel(const PipJob *jobs, 
     src = rows + (size_t)blockIdx.x * eq.max_rows * srcrow;
     nrows = eq_from_markers<1>(eq, blockIdx.x, src, srcrow, lay.ni, words, ni);
     eqw = words;
+  } else if constexpr (CSR) {
+    src = nullptr;
+    if (!csr_system_ok(rs, blockIdx.x, nrows, nvar)) nrows = 0;  // no key, k stays 0: not ok below
   } else {
     src = rows + (size_t)blockIdx.x * nrows * srccol;
   }
@@ -542,7 +623,18 @@ __global__ __launch_bounds__(64) void pip_batch_dual_kernel(const PipJob *jobs, 
   int k = 0;  // tableau row of the input row at hand
   for (int i0 = 0; i0 < nrows; i0 += 4) {
     int sz[4] = {0, 0, 0, 0};
-    for (int j = 2 * lane; j < nvar; j += 128) {
+    if constexpr (CSR) {  // a lane per stored entry
+      const i64 *rp = (const i64 *)rs.row_ptr + (size_t)blockIdx.x * nrows + i0;
+#pragma unroll
+      for (int q = 0; q < 4; q++) {
+        if (i0 + q >= nrows) break;
+        for (i64 e = rp[q] + lane; e < rp[q + 1]; e += 64) {
+          const int a = rs.cols[e] < nvar ? dual_key_term(rs.vals[e]) : 0;
+          sz[q] = sz[q] > a ? sz[q] : a;
+        }
+      }
+    }
+    for (int j = 2 * lane; !CSR && j < nvar; j += 128) {
 #pragma unroll
       for (int q = 0; q < 4; q++) {
         if (i0 + q >= nrows) break;
@@ -640,35 +732,55 @@ __global__ __launch_bounds__(64) void pip_batch_dual_kernel(const PipJob *jobs, 
 }
 
 // mk != nullptr: pipamd_batch_dual_matrices (nrows is not looked at: mk->max_rows pairs a system); otherwise
-// eq == nullptr: pipamd_batch_dual (the caller has checked lay.nparm == 0), or pipamd_batch_dual_system
-extern "C" hipError_t pipk_launch_batch_dual(const PipJob *jobs, const i64 *arena, const i64 *rows, PipBatchLayout lay,
-                                             int nrows, const PipEqMask *eq, const PipEqMarkers *mk, int first, int count,
-                                             void *dual_num, void *dual_den, hipStream_t stream) {
+// eq == nullptr: pipamd_batch_dual (the caller has checked lay.nparm == 0), or pipamd_batch_dual_system.  cs != nullptr
+// (with eq): the rows are the launch's CSR arrays (pipamd_batch_dual_sparse; rows is not looked at)
+static hipError_t launch_batch_dual(const PipJob *jobs, const i64 *arena, const i64 *rows, PipBatchLayout lay, int nrows,
+                                    const PipEqMask *eq, const PipEqMarkers *mk, const PipCsrRows *cs, int first, int count,
+                                    void *dual_num, void *dual_den, hipStream_t stream) {
+  if (cs && (mk || !eq)) return hipErrorInvalidValue;
   if (mk) nrows = mk->max_rows;
   if (count <= 0 || lay.ni <= 0 || nrows <= 0) return hipSuccess;
   if (lay.ni > PIP_DUAL_MAXNI || (!mk && nrows > lay.ni) || (!mk && !eq && (nrows != lay.ni || lay.nparm != 0)))
     return hipErrorInvalidValue;
   const size_t shm = pipk_batch_dual_lds_bytes(lay.ni);
-#define PIP_DUAL(T, EQ, MASK)                                                                                          \
-  hipLaunchKernelGGL((pip_batch_dual_kernel<T, EQ>), dim3(count), dim3(64), shm, stream, jobs, arena, rows, lay, first, \
-                     nrows, MASK, (T *)dual_num, (T *)dual_den)
+#define PIP_DUAL(T, EQ, MASK, SRC, ROWS)                                                                                    \
+  hipLaunchKernelGGL((pip_batch_dual_kernel<T, EQ, SRC>), dim3(count), dim3(64), shm, stream, jobs, arena, rows, lay, first, \
+                     nrows, MASK, (T *)dual_num, (T *)dual_den, ROWS)
   if (lay.ebits == 128) {
-    if (mk)
-      PIP_DUAL(i128, PipEqMarkers, *mk);
+    if (cs)
+      PIP_DUAL(i128, PipEqMask, *eq, PipCsrRows, *cs);
+    else if (mk)
+      PIP_DUAL(i128, PipEqMarkers, *mk, PipDenseRows, PipDenseRows{});
     else if (eq)
-      PIP_DUAL(i128, PipEqMask, *eq);
+      PIP_DUAL(i128, PipEqMask, *eq, PipDenseRows, PipDenseRows{});
     else
-      PIP_DUAL(i128, PipNoEq, PipNoEq{});
+      PIP_DUAL(i128, PipNoEq, PipNoEq{}, PipDenseRows, PipDenseRows{});
   } else {
-    if (mk)
-      PIP_DUAL(i64, PipEqMarkers, *mk);
+    if (cs)
+      PIP_DUAL(i64, PipEqMask, *eq, PipCsrRows, *cs);
+    else if (mk)
+      PIP_DUAL(i64, PipEqMarkers, *mk, PipDenseRows, PipDenseRows{});
     else if (eq)
-      PIP_DUAL(i64, PipEqMask, *eq);
+      PIP_DUAL(i64, PipEqMask, *eq, PipDenseRows, PipDenseRows{});
     else
-      PIP_DUAL(i64, PipNoEq, PipNoEq{});
+      PIP_DUAL(i64, PipNoEq, PipNoEq{}, PipDenseRows, PipDenseRows{});
   }
 #undef PIP_DUAL
   return hipGetLastError();
+}
+
+extern "C" hipError_t pipk_launch_batch_dual(const PipJob *jobs, const i64 *arena, const i64 *rows, PipBatchLayout lay,
+                                             int nrows, const PipEqMask *eq, const PipEqMarkers *mk, int first, int count,
+                                             void *dual_num, void *dual_den, hipStream_t stream) {
+  return launch_batch_dual(jobs, arena, rows, lay, nrows, eq, mk, nullptr, first, count, dual_num, dual_den, stream);
+}
+
+// pipamd_batch_dual_sparse: the dual of a batch loaded from the CSR arrays of `cs` (those of the `count` systems)
+extern "C" hipError_t pipk_launch_batch_dual_sparse(const PipJob *jobs, const i64 *arena, const PipCsrRows *cs, PipBatchLayout lay,
+                                                    int nrows, const PipEqMask *eq, int first, int count, void *dual_num,
+                                                    void *dual_den, hipStream_t stream) {
+  if (!cs) return hipErrorInvalidValue;
+  return launch_batch_dual(jobs, arena, nullptr, lay, nrows, eq, nullptr, cs, first, count, dual_num, dual_den, stream);
 }
 
 // ---------------------------------------------------------------- expanser for the batch layer
@@ -1203,11 +1315,13 @@ extern "C" hipError_t pipk_launch_batch_load(PipJob *jobs, i64 *arena, const i64
 
 // the same from the caller's plain system: equalities expanded, shift 0 / +1 / -1, tab_simplify (the caller has held
 // the layout against the shift and the equality list against lay.ni).  mk != nullptr: the systems carry their markers
-// and row counts (pipamd_batch_load_matrices; nrows and eq are not looked at)
-extern "C" hipError_t pipk_launch_batch_load_system(PipJob *jobs, i64 *arena, const i64 *rows, PipBatchLayout lay, int shift,
-                                                    int simplify, int nrows, const PipEqMask *eq, const PipEqMarkers *mk,
-                                                    int first, int count, hipStream_t stream) {
+// and row counts (pipamd_batch_load_matrices; nrows and eq are not looked at).  cs != nullptr (with eq): the rows are
+// the launch's CSR arrays (pipamd_batch_load_sparse; rows is not looked at)
+static hipError_t launch_batch_load_system(PipJob *jobs, i64 *arena, const i64 *rows, PipBatchLayout lay, int shift, int simplify,
+                                           int nrows, const PipEqMask *eq, const PipEqMarkers *mk, const PipCsrRows *cs, int first,
+                                           int count, hipStream_t stream) {
   if (count <= 0) return hipSuccess;
+  if (cs && (mk || !eq)) return hipErrorInvalidValue;
   if (mk) nrows = mk->max_rows;
   if (shift < -1 || shift > 1 || lay.nparm != (shift ? 1 : 0) || (shift && lay.bigparm != lay.nvar + 1) ||
       lay.W < lay.nvar + lay.nparm + 1 || lay.W > 512 || nrows < 0 || (mk ? nrows > PIPAMD_SMAX : nrows > lay.ni))
@@ -1215,12 +1329,15 @@ extern "C" hipError_t pipk_launch_batch_load_system(PipJob *jobs, i64 *arena, co
   lay.pad = 0;
 #define PIP_LOAD_SYSTEM(T, CPL)                                                                                              \
   do {                                                                                                                       \
-    if (mk)                                                                                                                  \
-      hipLaunchKernelGGL((pip_batch_load_system_kernel<T, CPL, PipEqMarkers>), dim3(count), dim3(256), 0, stream, jobs, arena, \
-                         rows, lay, first, shift, simplify, nrows, *mk);                                                     \
+    if (cs)                                                                                                                  \
+      hipLaunchKernelGGL((pip_batch_load_system_kernel<T, CPL, PipEqMask, PipCsrRows>), dim3(count), dim3(256), 0, stream, jobs, \
+                         arena, nullptr, lay, first, shift, simplify, nrows, *eq, *cs);                                      \
+    else if (mk)                                                                                                             \
+      hipLaunchKernelGGL((pip_batch_load_system_kernel<T, CPL, PipEqMarkers, PipDenseRows>), dim3(count), dim3(256), 0, stream, \
+                         jobs, arena, rows, lay, first, shift, simplify, nrows, *mk, PipDenseRows{});                        \
     else                                                                                                                     \
-      hipLaunchKernelGGL((pip_batch_load_system_kernel<T, CPL, PipEqMask>), dim3(count), dim3(256), 0, stream, jobs, arena,    \
-                         rows, lay, first, shift, simplify, nrows, *eq);                                                     \
+      hipLaunchKernelGGL((pip_batch_load_system_kernel<T, CPL, PipEqMask, PipDenseRows>), dim3(count), dim3(256), 0, stream,   \
+                         jobs, arena, rows, lay, first, shift, simplify, nrows, *eq, PipDenseRows{});                        \
   } while (0)
   if (lay.ebits == 128) {
     if (lay.W <= 128)
@@ -1235,6 +1352,20 @@ extern "C" hipError_t pipk_launch_batch_load_system(PipJob *jobs, i64 *arena, co
   }
 #undef PIP_LOAD_SYSTEM
   return hipGetLastError();
+}
+
+extern "C" hipError_t pipk_launch_batch_load_system(PipJob *jobs, i64 *arena, const i64 *rows, PipBatchLayout lay, int shift,
+                                                    int simplify, int nrows, const PipEqMask *eq, const PipEqMarkers *mk,
+                                                    int first, int count, hipStream_t stream) {
+  return launch_batch_load_system(jobs, arena, rows, lay, shift, simplify, nrows, eq, mk, nullptr, first, count, stream);
+}
+
+// pipamd_batch_load_sparse: the same load with the rows of the `count` systems in the CSR arrays of `cs`
+extern "C" hipError_t pipk_launch_batch_load_sparse(PipJob *jobs, i64 *arena, const PipCsrRows *cs, PipBatchLayout lay, int shift,
+                                                    int simplify, int nrows, const PipEqMask *eq, int first, int count,
+                                                    hipStream_t stream) {
+  if (!cs) return hipErrorInvalidValue;
+  return launch_batch_load_system(jobs, arena, nullptr, lay, shift, simplify, nrows, eq, nullptr, cs, first, count, stream);
 }
 
 extern "C" hipError_t pipk_launch_batch_results_shifted(const PipJob *jobs, const i64 *arena, int njobs, int nvar, int ebits,

@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PIPAMD_LIB") or os.path.join(HERE, "libpipamd.so")
 
 ST_RUN, ST_SOLUTION, ST_NIL, ST_NEED_COMPA, ST_NEED_PARMCUT, ST_OVERFLOW, ST_CAPACITY, ST_RANGE, ST_INTERNAL, ST_MAXCOL = range(10)
-ST_BADINPUT = 10  # a system Batch(matrices=True).load_matrices() could not take (PIPAMD_ST_BADINPUT)
+ST_BADINPUT = 10  # a system load_matrices() or load_sparse() could not take (PIPAMD_ST_BADINPUT)
 T_INT, T_DUAL = 1, 2
 T_NOSKIP = 2048
 T_ROWS_STAY = 8192  # the rows of Batch.load stay valid until the next solve: no copy pass (include/piplib_amd.h)
@@ -34,6 +34,12 @@ class Matrices(C.Structure):
     array of the systems' row counts (NULL: max_rows each)"""
     _fields_ = [("max_rows", C.c_int32), ("shift", C.c_int32), ("simplify", C.c_int32), ("reserved", C.c_int32),
                 ("d_nrows", C.c_void_p)]
+
+
+class Sparse(C.Structure):
+    """pipamd_sparse: the plain system of Batch(sparse=True) -- the System, then the entry count and the device arrays of
+    row pointers (int64), columns (int32) and values (int64)"""
+    _fields_ = [("sys", System), ("nnz", C.c_int64), ("d_row_ptr", C.c_void_p), ("d_cols", C.c_void_p), ("d_vals", C.c_void_p)]
 
 
 ABI_VERSION = 500  # include/piplib_amd.h PIPAMD_VERSION
@@ -86,6 +92,11 @@ def lib():
                                                       C.c_int, C.c_int, C.c_void_p]
         L.pipamd_batch_dual_matrices_part.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BatchDesc), C.POINTER(Matrices), C.c_void_p,
                                                       C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(L, "pipamd_batch_load_sparse_part"):  # (added since 500: a PIPAMD_LIB build may be older)
+            L.pipamd_batch_load_sparse_part.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BatchDesc), C.POINTER(Sparse), C.c_int,
+                                                        C.c_int, C.c_void_p]
+            L.pipamd_batch_dual_sparse_part.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BatchDesc), C.POINTER(Sparse), C.c_int,
+                                                        C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.pipamd_batch_counters.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BatchDesc), C.c_void_p, C.c_void_p]
         L.pipamd_last_solve_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         L.pipamd_free.argtypes = [C.c_void_p]
@@ -215,7 +226,8 @@ class Batch:
     """A uniform batch of tableaux resident in HBM (layer 1 of the C ABI)."""
 
     def __init__(self, engine, rows, nvar, nparm, bigparm=-1, tflags=T_INT, cap_cuts=None, cap_newparm=0,
-                 entier_bits=64, shape=None, shift=0, system=False, eq_rows=(), simplify=0, matrices=False, nrows=None, ni=None):
+                 entier_bits=64, shape=None, shift=0, system=False, eq_rows=(), simplify=0, matrices=False, nrows=None, ni=None,
+                 sparse=False):
         """rows: (batch, ni, ncol) int64, host or device; or None with shape=(batch, ni, ncol) for a workspace whose
         tableaux come from load_parts().
         shift=SHIFT_MAX / SHIFT_URS: the lexicographic maximum / unknowns of either sign (pip_solve's Maximize,
@@ -231,10 +243,24 @@ class Batch:
         nrows: an int32 tensor or array of the systems' row counts (None: max_rows each), kept on the device with the
         rows; ni: the room for the tallest tableau (rows + equalities; default 2 * max_rows).  shift and simplify as for
         system=True; load_matrices() / dual_matrices() go through pipamd_batch_load_matrices / pipamd_batch_dual_matrices,
-        and a system the load cannot take ends ST_BADINPUT."""
+        and a system the load cannot take ends ST_BADINPUT.
+        sparse=True: the plain systems of system=True as sparse rows.  rows is (row_ptr, cols, vals) -- int64 offsets,
+        batch * nrows + 1 of them, int32 columns (nvar: the constant) and int64 values, strictly increasing columns in a
+        row --, or None for a workspace loaded with load_sparse_part(); shape=(batch, nrows, nvar + 1) is that of the dense
+        expansion.  eq_rows, shift and simplify as for system=True; load_sparse() / dual_sparse() go through
+        pipamd_batch_load_sparse / pipamd_batch_dual_sparse, and a system the load cannot take ends ST_BADINPUT."""
         import torch
         self.torch = torch
         self.e = engine
+        self.csr = None
+        self.sparse = bool(sparse)
+        if sparse:
+            assert shape is not None and not matrices, "Batch(sparse=True) takes shape=(batch, nrows, nvar + 1)"
+            dev = torch.device("cuda", engine.device)
+            if rows is not None:
+                self.csr = tuple((t if torch.is_tensor(t) else torch.as_tensor(t)).to(device=dev, dtype=dt).contiguous()
+                                 for t, dt in zip(rows, (torch.int64, torch.int32, torch.int64)))
+            rows, system = None, True
         B, ni_in, ncol = rows.shape if rows is not None else shape
         self.shift = int(shift)
         self.system = None
@@ -292,6 +318,8 @@ class Batch:
         return C.c_void_p(self.torch.cuda.current_stream(self.dev).cuda_stream)
 
     def load(self):
+        if self.sparse:
+            return self.load_sparse()
         if self.matrices is not None:
             return self.load_matrices()
         if self.shift or self.system is not None:
@@ -303,6 +331,7 @@ class Batch:
         """tableaux first .. first + len(rows) - 1 of the batch from a resident row array (pipamd_batch_load_part)"""
         assert rows.is_cuda and rows.is_contiguous()
         assert self.matrices is None, "a Batch(matrices=True) is loaded with load_matrices_part(rows, nrows, first)"
+        assert not self.sparse, "a Batch(sparse=True) is loaded with load_sparse_part(row_ptr, cols, vals, first)"
         st = C.c_void_p(stream) if stream is not None else self._stream()
         if self.system is not None:
             return self.load_system_part(rows, first, stream)
@@ -458,6 +487,46 @@ class Batch:
         _check(lib().pipamd_batch_dual_matrices_part(self.e._h, C.c_void_p(self.ws.data_ptr()), C.byref(self.desc), C.byref(m),
                                                      C.c_void_p(rows.data_ptr()), int(first), int(rows.shape[0]),
                                                      C.c_void_p(num.data_ptr()), C.c_void_p(den.data_ptr()), st))
+        return num, den
+
+    def _sparse_part(self, row_ptr, cols, vals):
+        """(the pipamd_sparse of a part: the batch's system with the part's own arrays, the part's systems)"""
+        t = self.torch
+        assert self.sparse and all(x.is_cuda and x.is_contiguous() and x.dim() == 1 for x in (row_ptr, cols, vals))
+        assert row_ptr.dtype == t.int64 and cols.dtype == t.int32 and vals.dtype == t.int64 and cols.numel() == vals.numel()
+        count, rest = divmod(row_ptr.numel() - 1, max(1, self.system.nrows))
+        assert rest == 0 and row_ptr.numel() >= 1, "row_ptr holds systems * nrows + 1 offsets"
+        nnz = cols.numel()
+        return Sparse(self.system, nnz, row_ptr.data_ptr(), cols.data_ptr() if nnz else None, vals.data_ptr() if nnz else None), count
+
+    def load_sparse(self, stream=None):
+        """pipamd_batch_load_sparse of a Batch(sparse=True): the whole batch from its resident CSR arrays"""
+        return self.load_sparse_part(*self.csr, 0, stream)
+
+    def load_sparse_part(self, row_ptr, cols, vals, first, stream=None):
+        """pipamd_batch_load_sparse_part: tableaux first .. first + count - 1 from the resident CSR arrays of those systems
+        (row_ptr: count * nrows + 1 offsets into cols / vals)"""
+        sp, count = self._sparse_part(row_ptr, cols, vals)
+        st = C.c_void_p(stream) if stream is not None else self._stream()
+        _check(lib().pipamd_batch_load_sparse_part(self.e._h, C.c_void_p(self.ws.data_ptr()), C.byref(self.desc), C.byref(sp),
+                                                   int(first), count, st))
+
+    def dual_sparse(self, stream=None):
+        """pipamd_batch_dual_sparse after a solve with T_DUAL of a Batch(sparse=True): device tensors (dual_num, dual_den)
+        of shape (batch, nrows) -- plus a trailing 2 for 128-bit entries --, as dual_system() gives them; (0, 0)
+        throughout for a tableau without a solution.  Does not synchronise."""
+        if self.csr is None:
+            raise RuntimeError("Batch.dual_sparse needs the arrays the batch was loaded from: use dual_sparse_part()")
+        return self.dual_sparse_part(*self.csr, 0, stream)
+
+    def dual_sparse_part(self, row_ptr, cols, vals, first, stream=None, out=None):
+        """pipamd_batch_dual_sparse_part for the tableaux first .. first + count - 1, loaded from these CSR arrays; returns
+        (dual_num, dual_den) of the whole batch's shape (pass the pair back as `out` to fill it part by part)."""
+        sp, count = self._sparse_part(row_ptr, cols, vals)
+        num, den = out if out is not None else self._dual_out(self.system.nrows)
+        st = C.c_void_p(stream) if stream is not None else self._stream()
+        _check(lib().pipamd_batch_dual_sparse_part(self.e._h, C.c_void_p(self.ws.data_ptr()), C.byref(self.desc), C.byref(sp),
+                                                   int(first), count, C.c_void_p(num.data_ptr()), C.c_void_p(den.data_ptr()), st))
         return num, den
 
     def counters(self):
