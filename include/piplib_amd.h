@@ -51,7 +51,9 @@ extern "C" {
  * pipamd_batch_load_matrices / pipamd_batch_dual_matrices and their _part forms -- the same from PolyLib matrices, each
  * system with its own row count and its equalities where its marker column has them (PIPAMD_ST_BADINPUT);
  * pipamd_batch_load_sparse / pipamd_batch_dual_sparse and their _part forms -- the plain system as sparse rows (CSR on
- * the device), the tableaux built from them as from the dense expansion. */
+ * the device), the tableaux built from them as from the dense expansion; pipamd_batch_load_instances /
+ * pipamd_batch_dual_instances and their _part forms -- one parametric system at many parameter points, substituted
+ * exactly on the device (a constant that does not fit the entry type: PIPAMD_ST_BADINPUT). */
 #define PIPAMD_VERSION 500
 
 /* ---- error codes (return values) ---- */
@@ -89,7 +91,7 @@ extern "C" {
 #define PIPAMD_ST_RANGE 7        /* entries too large for the exact fast pivot-column choice */
 #define PIPAMD_ST_INTERNAL 8
 #define PIPAMD_ST_MAXCOL 9       /* "Too many variables" (integrer.c:324) */
-#define PIPAMD_ST_BADINPUT 10    /* a system the load could not take (see pipamd_batch_load_matrices, _sparse) */
+#define PIPAMD_ST_BADINPUT 10    /* a system the load could not take (see pipamd_batch_load_matrices, _sparse, _instances) */
 
 /* ---- row flags (reference tab.h:55-62) ---- */
 #define PIPAMD_F_UNIT 1
@@ -414,6 +416,58 @@ int pipamd_batch_dual_sparse(pipamd_engine *e, const void *d_workspace, const pi
                              int64_t *d_dual_num, int64_t *d_dual_den, void *stream);
 int pipamd_batch_dual_sparse_part(pipamd_engine *e, const void *d_workspace, const pipamd_batch_desc *d, const pipamd_sparse *s,
                                   int first, int count, int64_t *d_dual_num, int64_t *d_dual_den, void *stream);
+
+/* INSTANCES of one parametric system: PipLib's native input -- one system whose right-hand sides depend on parameters --
+ * solved at many parameter points (tile sizes or loop bounds to explore, sample points to hold a quast against, many
+ * right-hand sides of one constraint matrix) without parameters in the tableaux.  d_matrix is ONE matrix on the device,
+ * nrows x (nvar + nparm + 1) int64: unknowns | parameters | constant, a PolyLib row of pip_solve's inequnk without its
+ * marker column; d_points gives system b its parameter values theta_b0 .. theta_b(nparm-1).  System b is the plain
+ * system whose row r is a_r0 .. a_r(nvar-1) | c_r + sum_k p_rk * theta_bk, substituted on the device: N instances cost
+ * nrows x (nvar + nparm + 1) + N x nparm words of input instead of N x nrows x (nvar + 1).  `sys` is exactly the
+ * pipamd_system of the system entries (nrows, neq, the HOST list eq_rows, shift, simplify) and the descriptor is theirs,
+ * the tableau as it is solved: d->ni == nrows + neq; shift == 0: d->nparm == 0, bigparm == -1; shift == +-1:
+ * d->nparm == 1, bigparm == nvar + 1.  in->nparm, the parameters of the shared system, is NOT d->nparm.
+ * pipamd_batch_load_instances: for every system the tableau, row tables, spare slots and job header are bit for bit what
+ * pipamd_batch_load_system builds from that system's dense rows: the row order with an equality's negated twin, the
+ * shift, the big column as the sum of the unknowns' coefficients only, tab_simplify.  PIPAMD_T_ROWS_STAY is ignored; the
+ * two arrays may be released once the load's work on `stream` is done.  The solve and the result entries are the
+ * existing ones.
+ * The constant is computed EXACTLY, not stepwise in the entry type: a system is good whenever every one of its constants
+ * fits the entry type (int64 for entier_bits 0 / 64, __int128 for 128), even when single products or partial sums do
+ * not; nothing wraps anywhere in the substitution.  A system with a constant that does not fit is BAD and handled as
+ * pipamd_batch_load_matrices and _sparse handle their bad systems: the load finishes it itself -- an empty tableau
+ * (ni = 0) with status PIPAMD_ST_BADINPUT, nothing of it stored before that is known --, pipamd_batch_solve skips it, the
+ * result and dual entries give it zeros, and the other systems are not disturbed.
+ * Points are any int64 values.  PIP's convention that parameters are non-negative, and any context on them, are the
+ * caller's business: they are the caller's choice of points, nothing here looks at them.
+ * pipamd_batch_dual_instances: pipamd_batch_dual_system for a batch loaded this way, callable where that is; one kernel on
+ * `stream`, no synchronisation; `in` names the arrays the batch was loaded from.  d_dual_num[b][r], d_dual_den[b][r],
+ * r < nrows: one reduced pair per input row, an equality's two values merged (u if u != 0, else -v); (0, 0) throughout
+ * for a tableau that is not PIPAMD_ST_SOLUTION, a bad system among them.
+ * _part: the tableaux first .. first + count - 1; d_points holds the `count` points of the part and d_matrix is the
+ * part's matrix -- parts of one batch may use different matrices of the same shape --, the dual arrays are the whole
+ * batch's.
+ * PIPAMD_E_INVALID, before any HIP call: everything pipamd_batch_load_system / pipamd_batch_dual_system refuse, with the
+ * same rules on `sys`, the descriptor and first / count; a null `in` or d_matrix; nparm < 0; reserved != 0; null d_points
+ * with nparm > 0.  PIPAMD_E_TOOLARGE as for the system entries, and for nvar + nparm + 1 above 512 (the reference's
+ * MAXCOL). */
+typedef struct pipamd_instances {
+  pipamd_system sys;       /* nrows, neq, eq_rows (HOST list), shift, simplify: exactly as pipamd_batch_load_system */
+  int32_t nparm;           /* parameters of the shared system that the points give values to (>= 0) */
+  int32_t reserved;        /* 0 */
+  const int64_t *d_matrix; /* DEVICE, nrows x (nvar + nparm + 1): unknowns | parameters | constant; ONE matrix for the
+                              batch (or the part) */
+  const int64_t *d_points; /* DEVICE, systems x nparm: the parameter values of each system; may be NULL when nparm == 0 */
+} pipamd_instances;        /* 48 bytes, offsets 0 24 28 32 40 */
+int pipamd_batch_load_instances(pipamd_engine *e, void *d_workspace, const pipamd_batch_desc *d, const pipamd_instances *in,
+                                void *stream);
+int pipamd_batch_load_instances_part(pipamd_engine *e, void *d_workspace, const pipamd_batch_desc *d, const pipamd_instances *in,
+                                     int first, int count, void *stream);
+int pipamd_batch_dual_instances(pipamd_engine *e, const void *d_workspace, const pipamd_batch_desc *d, const pipamd_instances *in,
+                                int64_t *d_dual_num, int64_t *d_dual_den, void *stream);
+int pipamd_batch_dual_instances_part(pipamd_engine *e, const void *d_workspace, const pipamd_batch_desc *d,
+                                     const pipamd_instances *in, int first, int count, int64_t *d_dual_num, int64_t *d_dual_den,
+                                     void *stream);
 
 /* Batch totals, device memory, 4 x uint64: [0] pivots (calls of pivoter), [1] Gomory cuts,
  * [2] rows rewritten by pivots (rows whose pivot-column entry is zero and that are already

@@ -1039,6 +1039,70 @@ extern "C" int pipamd_batch_dual_sparse(pipamd_engine *e, const void *d_ws, cons
   return pipamd_batch_dual_sparse_part(e, d_ws, d, s, 0, d ? d->batch : 0, d_dual_num, d_dual_den, stream);
 }
 
+// The instances of one parametric system (header comment: include/piplib_amd.h): the system entries' checks on `sys` and
+// the descriptor, with the shared matrix in the place of the rows; the substitution, and whether a system's constants
+// fit the entry type, is the device's business.
+static int instances_check(const char *who, const void *e, const void *d_ws, const pipamd_batch_desc *d, const pipamd_instances *in,
+                           PipEqMask *eq, PipInstanceRows *is) {
+  int rc = system_check(who, e, d_ws, d, in ? &in->sys : nullptr, in ? in->d_matrix : nullptr, eq);
+  if (rc) return rc;
+  if (in->nparm < 0 || in->reserved != 0 || (in->nparm > 0 && !in->d_points)) {
+    pipamd_set_error("%s: nparm (%d) below 0, reserved (%d) not 0, or parameters without an array of points", who, in->nparm,
+                     in->reserved);
+    return PIPAMD_E_INVALID;
+  }
+  if ((int64_t)d->nvar + in->nparm + 1 > PIPAMD_MAXCOL) {
+    pipamd_set_error("%s: a matrix row of %d unknowns, %d parameters and the constant, at most %d columns", who, d->nvar,
+                     in->nparm, PIPAMD_MAXCOL);
+    return PIPAMD_E_TOOLARGE;
+  }
+  is->matrix = in->d_matrix;
+  is->points = in->d_points;
+  is->nparm = in->nparm;
+  return PIPAMD_OK;
+}
+
+extern "C" int pipamd_batch_load_instances_part(pipamd_engine *e, void *d_ws, const pipamd_batch_desc *d, const pipamd_instances *in,
+                                                int first, int count, void *stream) {
+  PipEqMask eq;
+  PipInstanceRows is;
+  int rc = instances_check("batch_load_instances", e, d_ws, d, in, &eq, &is);
+  if (rc) return rc;
+  BatchView v;
+  rc = batch_view("batch_load_instances", e, d_ws, d, first, count, &v);
+  if (rc) return rc;
+  HIPCHK(pipk_launch_batch_load_instances(v.jobs, v.arena, &is, v.lay, in->sys.shift, in->sys.simplify, in->sys.nrows, &eq, first,
+                                          count, (hipStream_t)stream));
+  return PIPAMD_OK;
+}
+
+extern "C" int pipamd_batch_load_instances(pipamd_engine *e, void *d_ws, const pipamd_batch_desc *d, const pipamd_instances *in,
+                                           void *stream) {
+  return pipamd_batch_load_instances_part(e, d_ws, d, in, 0, d ? d->batch : 0, stream);
+}
+
+extern "C" int pipamd_batch_dual_instances_part(pipamd_engine *e, const void *d_ws, const pipamd_batch_desc *d,
+                                                const pipamd_instances *in, int first, int count, int64_t *d_dual_num,
+                                                int64_t *d_dual_den, void *stream) {
+  PipEqMask eq;
+  PipInstanceRows is;
+  int rc = instances_check("batch_dual_instances", e, d_ws, d, in, &eq, &is);
+  if (rc) return rc;
+  rc = dual_check("batch_dual_instances", d, is.matrix, d_dual_num, d_dual_den);
+  if (rc) return rc;
+  BatchView v;
+  rc = batch_view("batch_dual_instances", e, d_ws, d, first, count, &v);
+  if (rc) return rc;
+  HIPCHK(pipk_launch_batch_dual_instances(v.jobs, v.arena, &is, v.lay, in->sys.nrows, &eq, first, count, (void *)d_dual_num,
+                                          (void *)d_dual_den, (hipStream_t)stream));
+  return PIPAMD_OK;
+}
+
+extern "C" int pipamd_batch_dual_instances(pipamd_engine *e, const void *d_ws, const pipamd_batch_desc *d, const pipamd_instances *in,
+                                           int64_t *d_dual_num, int64_t *d_dual_den, void *stream) {
+  return pipamd_batch_dual_instances_part(e, d_ws, d, in, 0, d ? d->batch : 0, d_dual_num, d_dual_den, stream);
+}
+
 // PolyLib matrices with a row count and markers per system (header comment: include/piplib_amd.h).  Which rows are
 // equalities and how many rows a system has is found on the device; what is left to refuse here is the description.
 static int matrices_check(const char *who, const void *e, const void *d_ws, const pipamd_batch_desc *d, const pipamd_matrices *m,

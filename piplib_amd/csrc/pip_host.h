@@ -99,6 +99,12 @@ hipError_t pipk_launch_batch_load_sparse(PipJob *jobs, long long *arena, const P
 hipError_t pipk_launch_batch_dual_sparse(const PipJob *jobs, const long long *arena, const PipCsrRows *cs, PipBatchLayout lay,
                                          int nrows, const PipEqMask *eq, int first, int count, void *dual_num, void *dual_den,
                                          hipStream_t stream);
+/* pipamd_batch_load_instances / pipamd_batch_dual_instances: the system launches with the shared matrix and the points of `is` */
+hipError_t pipk_launch_batch_load_instances(PipJob *jobs, long long *arena, const PipInstanceRows *is, PipBatchLayout lay, int shift,
+                                            int simplify, int nrows, const PipEqMask *eq, int first, int count, hipStream_t stream);
+hipError_t pipk_launch_batch_dual_instances(const PipJob *jobs, const long long *arena, const PipInstanceRows *is, PipBatchLayout lay,
+                                            int nrows, const PipEqMask *eq, int first, int count, void *dual_num, void *dual_den,
+                                            hipStream_t stream);
 hipError_t pipk_launch_rehouse(PipJob *jobs, long long *arena, void *const *q5, int grid, PipBatchLayout nl, int *side_count,
                                int side_cap, hipStream_t stream);
 hipError_t pipk_launch_rehouse_finish(PipJob *jobs, long long *arena, int njobs, int sol_words, hipStream_t stream);

@@ -85,6 +85,16 @@ typedef struct PipCsrRows {
   int64_t nnz;
 } PipCsrRows;
 
+/* The same for the instances of ONE parametric system (pipamd_instances): `matrix` is nrows x (nvar + nparm + 1), unknowns |
+ * parameters | constant, shared by every system of the launch; `points` holds the launch's systems' parameter values,
+ * nparm each (not looked at when nparm == 0).  Both on the DEVICE.  The kernels substitute a system's point into the
+ * parameter columns: its row r is a_r0 .. a_r(nvar-1) | c_r + sum_k p_rk * theta_k, the sum exact. */
+typedef struct PipInstanceRows {
+  const int64_t *matrix;
+  const int64_t *points;
+  int32_t nparm;
+} PipInstanceRows;
+
 #ifdef __HIPCC__
 #define PIP_HD __host__ __device__
 #else

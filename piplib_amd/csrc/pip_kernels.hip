@@ -273,7 +273,16 @@ __device__ __forceinline__ int eq_from_markers(const PipEqMarkers &mk, int sys, 
 //     entries, the loop costs as many steps, and neither LDS nor a register is added to the dense instantiations.
 //     Before anything is stored the block checks the system (csr_system_ok); a bad one is finished here as the
 //     markers policy finishes its bad systems: an empty tableau, PIPAMD_ST_BADINPUT.
+//   PipInstanceRows (pipamd_batch_load_instances; with PipEqMask): ONE matrix for the launch, unknowns | parameters |
+//     constant, and a point per system.  The block reads its point once into LDS; a lane reads its unknown columns from
+//     the shared matrix (every block reads the same lines: they stay in L2) and the constant's lane gets c_r +
+//     sum_k p_rk * theta_k, summed exactly across the wave (inst_constant).  All constants are formed, and the system
+//     declared bad if one does not fit the entry type, before anything is stored; the main loop takes them from LDS.
 struct PipDenseRows {};
+// words of a source row between its unknowns and its constant
+__device__ __forceinline__ int src_parms(const PipDenseRows &) { return 0; }
+__device__ __forceinline__ int src_parms(const PipCsrRows &) { return 0; }
+__device__ __forceinline__ int src_parms(const PipInstanceRows &is) { return is.nparm; }
 
 // PipCsrRows, by all waves of a block: may system `sys` of the launch (`nrows` rows) be read?  First its nrows + 1
 // pointers: within [0, nnz], not decreasing, at most nvar + 1 entries a row; then, only if they hold, its entries: every
@@ -320,6 +329,61 @@ __device__ __forceinline__ void csr_row_to_lanes(const PipCsrRows &cs, i64 p0, i
   }
 }
 
+// PipInstanceRows, by one wave: the constant of a matrix row at the block's point.  `row` points at the row's parameter
+// columns (nparm of them, then c), `theta` at the point in LDS: c + sum_k p_k * theta_k, exactly.  A product of two int64
+// values is below 2^126 in magnitude; its signed high and its unsigned low 64-bit half go to 128-bit accumulators of
+// their own, the constant as one more term -- at most 512 terms, so either sum stays below 2^73 and nothing wraps --,
+// first within a lane, then over the lanes that hold a term (a butterfly from `top` down; inst_top below).  Only the
+// totals are joined, value = hi * 2^64 + low word with 0 <= low word < 2^64, and held against the entry type.  Returns
+// whether the value fits T; every lane gets the same answer and, if it fits, the value in `out`.
+__device__ __forceinline__ int inst_top(int nparm) {
+  int top = 1;
+  while (top < 64 && top < nparm + 1) top <<= 1;
+  return top >> 1;
+}
+template <class T>
+__device__ __forceinline__ bool inst_constant(const i64 *row, const i64 *theta, int nparm, int top, int lane, T &out) {
+  i128 hi = 0;
+  u128 lo = 0;
+  for (int k = lane; k < nparm; k += 64) {
+    const i128 p = (i128)row[k] * (i128)theta[k];
+    hi += (i128)(i64)(p >> 64);
+    lo += (u128)(u64)(u128)p;
+  }
+  if (lane == (nparm < 64 ? nparm : 0)) {
+    const i64 c = row[nparm];
+    hi += (i128)(c >> 63);
+    lo += (u128)(u64)c;
+  }
+  for (int o = top; o; o >>= 1) {
+    hi = wadd(hi, sys_shfl(hi, lane ^ o));
+    lo = (u128)wadd((i128)lo, sys_shfl((i128)lo, lane ^ o));
+  }
+  hi = uni64(hi);  // lane 0 has the totals
+  lo = (u128)uni64((i128)lo);
+  hi += (i128)(u64)(lo >> 64);
+  const u64 l0 = (u64)lo;
+  if constexpr (sizeof(T) == 8) {
+    out = (T)(i64)l0;
+    return hi == (i128)((i64)l0 >> 63);
+  } else {
+    out = (T)(((u128)hi << 64) | l0);
+    return fits64(hi);
+  }
+}
+// floor(c / g), g > 1, for a constant of PipInstanceRows: any value of the entry type.  Within 2^63 it is sys_floor.
+__device__ __forceinline__ i64 inst_floor(i64 c, u64 g) { return sys_floor(c, g); }
+__device__ __forceinline__ i128 inst_floor(i128 c, u64 g) {
+  const u128 uc = uabs64(c);  // (2^127 for the smallest value)
+  if ((uc >> 63) == 0) return sys_floor(c, g);
+  const u128 rem = umod128(uc, (u128)g);
+  const int s = __builtin_ctzll(g);
+  u128 q = ((uc - rem) >> s) * inv_odd64((u128)(g >> s));  // exact, and below 2^127: g >= 2
+  if (c < 0 && rem) q += 1;
+  return c < 0 ? wneg((i128)q) : (i128)q;
+}
+#define PIP_INST_KEEP 512 /* rows of a system whose constants the load kernel keeps in LDS; later rows are formed twice */
+
 template <class T, int CPL, class EQ, class SRC>
 __global__ __launch_bounds__(256) void pip_batch_load_system_kernel(PipJob *jobs, i64 *arena, const i64 *rows, PipBatchLayout lay,
                                                                     int first, int shift, int simplify, int nrows, EQ eq,
@@ -327,11 +391,13 @@ __global__ __launch_bounds__(256) void pip_batch_load_system_kernel(PipJob *jobs
   typedef typename ET<T>::U U;
   constexpr bool MARKED = std::is_same<EQ, PipEqMarkers>::value;
   constexpr bool CSR = std::is_same<SRC, PipCsrRows>::value;
+  constexpr bool INST = std::is_same<SRC, PipInstanceRows>::value;
   static_assert(!(MARKED && CSR), "sparse rows come with the launch's equality mask");
+  static_assert(!(MARKED && INST), "instances of one system come with the launch's equality mask");
   constexpr int MK = MARKED ? 1 : 0;  // words of a source row before its unknowns
   const int b = first + blockIdx.x;  // `rows` holds the systems first, first + 1, ... of the batch
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int nvar = lay.nvar, srccol = nvar + 1, srcrow = srccol + MK, W = lay.W;
+  const int nvar = lay.nvar, srccol = nvar + 1, srcrow = srccol + MK + src_parms(rs), W = lay.W;
   const int64_t base = lay.arena_off + (int64_t)b * lay.blk.words;
   T *vals = (T *)(arena + base + lay.blk.vals);
   int ni = lay.ni;  // rows of this tableau
@@ -343,13 +409,37 @@ __global__ __launch_bounds__(256) void pip_batch_load_system_kernel(PipJob *jobs
     nrows = eq_from_markers<4>(eq, blockIdx.x, src, srcrow, lay.ni, words, ni);
     eqw = words;
   }
-  bool bad = false;  // (PipCsrRows)
+  bool bad = false;  // (PipCsrRows, PipInstanceRows)
   if constexpr (CSR) {
     bad = !csr_system_ok(rs, blockIdx.x, nrows, nvar);
     if (bad) nrows = ni = 0;
   }
+  const i64 *theta = nullptr;  // (PipInstanceRows) the block's point and its rows' constants, in LDS
+  const T *konst = nullptr;
+  int top = 0;
+  if constexpr (INST) {
+    __shared__ i64 point[PIPAMD_MAXCOL];
+    __shared__ T kept[PIP_INST_KEEP];
+    const int np = rs.nparm;
+    for (int k = tid; k < np; k += 256) point[k] = (i64)rs.points[(size_t)blockIdx.x * np + k];
+    __syncthreads();
+    top = inst_top(np);
+    bool ok = true;
+    for (int r = wave; r < nrows; r += 4) {
+      T c;
+      ok = inst_constant<T>((const i64 *)rs.matrix + (size_t)r * srcrow + nvar, point, np, top, lane, c) && ok;
+      if (lane == 0 && r < PIP_INST_KEEP) kept[r] = c;
+    }
+    bad = !__syncthreads_and(ok);
+    if (bad) nrows = ni = 0;
+    theta = point;
+    konst = kept;
+  }
   load_row_tables<T>(arena + base, lay, ni, tid);
-  if constexpr (!MARKED && !CSR) src = rows + (size_t)blockIdx.x * nrows * srccol;
+  if constexpr (INST)
+    src = (const i64 *)rs.matrix;
+  else if constexpr (!MARKED && !CSR)
+    src = rows + (size_t)blockIdx.x * nrows * srccol;
   int wcur = 0, before = 0;  // equalities among the rows below 64 * wcur
   for (int r = wave; r < nrows; r += 4) {
     for (; wcur < (r >> 6); wcur++) before += __popcll(eq_word(eq, eqw, wcur));
@@ -363,6 +453,13 @@ __global__ __launch_bounds__(256) void pip_batch_load_system_kernel(PipJob *jobs
       const i64 *rp = (const i64 *)rs.row_ptr + (size_t)blockIdx.x * nrows + r;
       csr_row_to_lanes<CPL>(rs, uni64(rp[0]), uni64(rp[1]), lane, sp);
     }
+    T cst = 0;  // PipInstanceRows: the row's constant at the block's point
+    if constexpr (INST) {
+      if (r < PIP_INST_KEEP)
+        cst = konst[r];
+      else
+        inst_constant<T>(in + nvar, theta, rs.nparm, top, lane, cst);
+    }
     T v[CPL], sum = 0;
     u64 g = 0;
 #pragma unroll
@@ -371,9 +468,13 @@ __global__ __launch_bounds__(256) void pip_batch_load_system_kernel(PipJob *jobs
       i64 a;
       if constexpr (CSR)
         a = sp[c];
+      else if constexpr (INST)
+        a = j < nvar ? in[j] : 0;
       else
         a = j < srccol ? in[j] : 0;
       v[c] = (T)a;  // the constant as it is, zero beyond it
+      if constexpr (INST)
+        if (j == nvar) v[c] = cst;
       if (j < nvar) {
         sum = wadd(sum, (T)a);
         if (simplify) g = gcd_mag(g, uabs64(a));
@@ -402,8 +503,8 @@ __global__ __launch_bounds__(256) void pip_batch_load_system_kernel(PipJob *jobs
       T x = v[c], y = wneg(x);
       if (g > 1) {
         if (j == nvar) {
-          x = sys_floor(x, g);
-          y = sys_floor(y, g);
+          x = INST ? inst_floor(x, g) : sys_floor(x, g);
+          y = INST ? inst_floor(y, g) : sys_floor(y, g);
         } else {
           x = sys_exact(x, g);
           y = wneg(x);
@@ -585,6 +686,10 @@ __device__ void dual_sort_pairs(float *key, u16 *ineq, int n, double smax, int l
 //   SRC == PipCsrRows (pipamd_batch_dual_sparse, with PipEqMask): the rows are the CSR arrays the batch was loaded
 //     from.  A row's key is the maximum over its stored entries with a column below nvar -- an absent entry is a zero
 //     and adds nothing.  A system csr_system_ok refuses was bad for the load: (0, 0) throughout.
+//   SRC == PipInstanceRows (pipamd_batch_dual_instances, with PipEqMask): the rows are those of the launch's shared
+//     matrix; a key is taken over the unknown columns alone, which the point does not touch, so neither the point nor
+//     the parameter columns are read.  A system that was bad for the load has status PIPAMD_ST_BADINPUT and an empty
+//     tableau: (0, 0) throughout by the header check below.
 template <class T, class EQ, class SRC>
 __global__ __launch_bounds__(64) void pip_batch_dual_kernel(const PipJob *jobs, const i64 *arena, const i64 *rows,
                                                             PipBatchLayout lay, int first, int nrows, EQ eq, T *dual_num,
@@ -592,12 +697,14 @@ __global__ __launch_bounds__(64) void pip_batch_dual_kernel(const PipJob *jobs, 
   constexpr bool SYSTEM = !std::is_same<EQ, PipNoEq>::value;
   constexpr bool MARKED = std::is_same<EQ, PipEqMarkers>::value;
   constexpr bool CSR = std::is_same<SRC, PipCsrRows>::value;
+  constexpr bool INST = std::is_same<SRC, PipInstanceRows>::value;
   static_assert(!CSR || std::is_same<EQ, PipEqMask>::value, "sparse rows come with the launch's equality mask");
+  static_assert(!INST || std::is_same<EQ, PipEqMask>::value, "instances of one system come with the launch's equality mask");
   constexpr int MK = MARKED ? 1 : 0;  // words of a source row before its unknowns
   extern __shared__ __align__(16) unsigned char dual_lds[];
   const int lane = threadIdx.x;
   const int b = first + blockIdx.x;
-  const int nvar = lay.nvar, srccol = lay.nvar + 1, srcrow = srccol + MK;
+  const int nvar = lay.nvar, srccol = lay.nvar + 1, srcrow = srccol + MK + src_parms(rs);
   const int nout = nrows;  // pairs written per system
   int ni = lay.ni;         // rows of this tableau
   if (ni <= 0 || ni > PIP_DUAL_MAXNI || nrows <= 0 || (!MARKED && nrows > ni)) return;
@@ -616,6 +723,8 @@ __global__ __launch_bounds__(64) void pip_batch_dual_kernel(const PipJob *jobs, 
   } else if constexpr (CSR) {
     src = nullptr;
     if (!csr_system_ok(rs, blockIdx.x, nrows, nvar)) nrows = 0;  // no key, k stays 0: not ok below
+  } else if constexpr (INST) {
+    src = (const i64 *)rs.matrix;  // (a system that was bad for the load is not PIPAMD_ST_SOLUTION: nothing to decide here)
   } else {
     src = rows + (size_t)blockIdx.x * nrows * srccol;
   }
@@ -733,11 +842,12 @@ __global__ __launch_bounds__(64) void pip_batch_dual_kernel(const PipJob *jobs, 
 
 // mk != nullptr: pipamd_batch_dual_matrices (nrows is not looked at: mk->max_rows pairs a system); otherwise
 // eq == nullptr: pipamd_batch_dual (the caller has checked lay.nparm == 0), or pipamd_batch_dual_system.  cs != nullptr
-// (with eq): the rows are the launch's CSR arrays (pipamd_batch_dual_sparse; rows is not looked at)
+// (with eq): the rows are the launch's CSR arrays (pipamd_batch_dual_sparse; rows is not looked at); is != nullptr (with
+// eq): they are those of the launch's shared matrix (pipamd_batch_dual_instances; rows is not looked at)
 static hipError_t launch_batch_dual(const PipJob *jobs, const i64 *arena, const i64 *rows, PipBatchLayout lay, int nrows,
-                                    const PipEqMask *eq, const PipEqMarkers *mk, const PipCsrRows *cs, int first, int count,
-                                    void *dual_num, void *dual_den, hipStream_t stream) {
-  if (cs && (mk || !eq)) return hipErrorInvalidValue;
+                                    const PipEqMask *eq, const PipEqMarkers *mk, const PipCsrRows *cs, const PipInstanceRows *is,
+                                    int first, int count, void *dual_num, void *dual_den, hipStream_t stream) {
+  if ((cs || is) && (mk || !eq || (cs && is))) return hipErrorInvalidValue;
   if (mk) nrows = mk->max_rows;
   if (count <= 0 || lay.ni <= 0 || nrows <= 0) return hipSuccess;
   if (lay.ni > PIP_DUAL_MAXNI || (!mk && nrows > lay.ni) || (!mk && !eq && (nrows != lay.ni || lay.nparm != 0)))
@@ -747,7 +857,9 @@ static hipError_t launch_batch_dual(const PipJob *jobs, const i64 *arena, const 
   hipLaunchKernelGGL((pip_batch_dual_kernel<T, EQ, SRC>), dim3(count), dim3(64), shm, stream, jobs, arena, rows, lay, first, \
                      nrows, MASK, (T *)dual_num, (T *)dual_den, ROWS)
   if (lay.ebits == 128) {
-    if (cs)
+    if (is)
+      PIP_DUAL(i128, PipEqMask, *eq, PipInstanceRows, *is);
+    else if (cs)
       PIP_DUAL(i128, PipEqMask, *eq, PipCsrRows, *cs);
     else if (mk)
       PIP_DUAL(i128, PipEqMarkers, *mk, PipDenseRows, PipDenseRows{});
@@ -756,7 +868,9 @@ static hipError_t launch_batch_dual(const PipJob *jobs, const i64 *arena, const 
     else
       PIP_DUAL(i128, PipNoEq, PipNoEq{}, PipDenseRows, PipDenseRows{});
   } else {
-    if (cs)
+    if (is)
+      PIP_DUAL(i64, PipEqMask, *eq, PipInstanceRows, *is);
+    else if (cs)
       PIP_DUAL(i64, PipEqMask, *eq, PipCsrRows, *cs);
     else if (mk)
       PIP_DUAL(i64, PipEqMarkers, *mk, PipDenseRows, PipDenseRows{});
@@ -772,7 +886,7 @@ static hipError_t launch_batch_dual(const PipJob *jobs, const i64 *arena, const 
 extern "C" hipError_t pipk_launch_batch_dual(const PipJob *jobs, const i64 *arena, const i64 *rows, PipBatchLayout lay,
                                              int nrows, const PipEqMask *eq, const PipEqMarkers *mk, int first, int count,
                                              void *dual_num, void *dual_den, hipStream_t stream) {
-  return launch_batch_dual(jobs, arena, rows, lay, nrows, eq, mk, nullptr, first, count, dual_num, dual_den, stream);
+  return launch_batch_dual(jobs, arena, rows, lay, nrows, eq, mk, nullptr, nullptr, first, count, dual_num, dual_den, stream);
 }
 
 // pipamd_batch_dual_sparse: the dual of a batch loaded from the CSR arrays of `cs` (those of the `count` systems)
@@ -780,7 +894,15 @@ extern "C" hipError_t pipk_launch_batch_dual_sparse(const PipJob *jobs, const i6
                                                     int nrows, const PipEqMask *eq, int first, int count, void *dual_num,
                                                     void *dual_den, hipStream_t stream) {
   if (!cs) return hipErrorInvalidValue;
-  return launch_batch_dual(jobs, arena, nullptr, lay, nrows, eq, nullptr, cs, first, count, dual_num, dual_den, stream);
+  return launch_batch_dual(jobs, arena, nullptr, lay, nrows, eq, nullptr, cs, nullptr, first, count, dual_num, dual_den, stream);
+}
+
+// pipamd_batch_dual_instances: the dual of a batch loaded from the shared matrix of `is` (the points are not needed)
+extern "C" hipError_t pipk_launch_batch_dual_instances(const PipJob *jobs, const i64 *arena, const PipInstanceRows *is,
+                                                       PipBatchLayout lay, int nrows, const PipEqMask *eq, int first, int count,
+                                                       void *dual_num, void *dual_den, hipStream_t stream) {
+  if (!is || !is->matrix || is->nparm < 0 || lay.nvar + is->nparm + 1 > PIPAMD_MAXCOL) return hipErrorInvalidValue;
+  return launch_batch_dual(jobs, arena, nullptr, lay, nrows, eq, nullptr, nullptr, is, first, count, dual_num, dual_den, stream);
 }
 
 // ---------------------------------------------------------------- expanser for the batch layer
@@ -1316,12 +1438,13 @@ extern "C" hipError_t pipk_launch_batch_load(PipJob *jobs, i64 *arena, const i64
 // the same from the caller's plain system: equalities expanded, shift 0 / +1 / -1, tab_simplify (the caller has held
 // the layout against the shift and the equality list against lay.ni).  mk != nullptr: the systems carry their markers
 // and row counts (pipamd_batch_load_matrices; nrows and eq are not looked at).  cs != nullptr (with eq): the rows are
-// the launch's CSR arrays (pipamd_batch_load_sparse; rows is not looked at)
+// the launch's CSR arrays (pipamd_batch_load_sparse; rows is not looked at).  is != nullptr (with eq): the systems are the
+// launch's shared matrix at their points (pipamd_batch_load_instances; rows is not looked at)
 static hipError_t launch_batch_load_system(PipJob *jobs, i64 *arena, const i64 *rows, PipBatchLayout lay, int shift, int simplify,
-                                           int nrows, const PipEqMask *eq, const PipEqMarkers *mk, const PipCsrRows *cs, int first,
-                                           int count, hipStream_t stream) {
+                                           int nrows, const PipEqMask *eq, const PipEqMarkers *mk, const PipCsrRows *cs,
+                                           const PipInstanceRows *is, int first, int count, hipStream_t stream) {
   if (count <= 0) return hipSuccess;
-  if (cs && (mk || !eq)) return hipErrorInvalidValue;
+  if ((cs || is) && (mk || !eq || (cs && is))) return hipErrorInvalidValue;
   if (mk) nrows = mk->max_rows;
   if (shift < -1 || shift > 1 || lay.nparm != (shift ? 1 : 0) || (shift && lay.bigparm != lay.nvar + 1) ||
       lay.W < lay.nvar + lay.nparm + 1 || lay.W > 512 || nrows < 0 || (mk ? nrows > PIPAMD_SMAX : nrows > lay.ni))
@@ -1329,7 +1452,10 @@ static hipError_t launch_batch_load_system(PipJob *jobs, i64 *arena, const i64 *
   lay.pad = 0;
 #define PIP_LOAD_SYSTEM(T, CPL)                                                                                              \
   do {                                                                                                                       \
-    if (cs)                                                                                                                  \
+    if (is)                                                                                                                  \
+      hipLaunchKernelGGL((pip_batch_load_system_kernel<T, CPL, PipEqMask, PipInstanceRows>), dim3(count), dim3(256), 0, stream, \
+                         jobs, arena, nullptr, lay, first, shift, simplify, nrows, *eq, *is);                                \
+    else if (cs)                                                                                                             \
       hipLaunchKernelGGL((pip_batch_load_system_kernel<T, CPL, PipEqMask, PipCsrRows>), dim3(count), dim3(256), 0, stream, jobs, \
                          arena, nullptr, lay, first, shift, simplify, nrows, *eq, *cs);                                      \
     else if (mk)                                                                                                             \
@@ -1357,7 +1483,7 @@ static hipError_t launch_batch_load_system(PipJob *jobs, i64 *arena, const i64 *
 extern "C" hipError_t pipk_launch_batch_load_system(PipJob *jobs, i64 *arena, const i64 *rows, PipBatchLayout lay, int shift,
                                                     int simplify, int nrows, const PipEqMask *eq, const PipEqMarkers *mk,
                                                     int first, int count, hipStream_t stream) {
-  return launch_batch_load_system(jobs, arena, rows, lay, shift, simplify, nrows, eq, mk, nullptr, first, count, stream);
+  return launch_batch_load_system(jobs, arena, rows, lay, shift, simplify, nrows, eq, mk, nullptr, nullptr, first, count, stream);
 }
 
 // pipamd_batch_load_sparse: the same load with the rows of the `count` systems in the CSR arrays of `cs`
@@ -1365,7 +1491,19 @@ extern "C" hipError_t pipk_launch_batch_load_sparse(PipJob *jobs, i64 *arena, co
                                                     int simplify, int nrows, const PipEqMask *eq, int first, int count,
                                                     hipStream_t stream) {
   if (!cs) return hipErrorInvalidValue;
-  return launch_batch_load_system(jobs, arena, nullptr, lay, shift, simplify, nrows, eq, nullptr, cs, first, count, stream);
+  return launch_batch_load_system(jobs, arena, nullptr, lay, shift, simplify, nrows, eq, nullptr, cs, nullptr, first, count,
+                                  stream);
+}
+
+// pipamd_batch_load_instances: the same load with the `count` systems the shared matrix of `is` at their points (the point
+// array in the block's LDS has room for PIPAMD_MAXCOL values: held against the matrix row here)
+extern "C" hipError_t pipk_launch_batch_load_instances(PipJob *jobs, i64 *arena, const PipInstanceRows *is, PipBatchLayout lay,
+                                                       int shift, int simplify, int nrows, const PipEqMask *eq, int first,
+                                                       int count, hipStream_t stream) {
+  if (!is || !is->matrix || is->nparm < 0 || (is->nparm > 0 && !is->points) || lay.nvar + is->nparm + 1 > PIPAMD_MAXCOL)
+    return hipErrorInvalidValue;
+  return launch_batch_load_system(jobs, arena, nullptr, lay, shift, simplify, nrows, eq, nullptr, nullptr, is, first, count,
+                                  stream);
 }
 
 extern "C" hipError_t pipk_launch_batch_results_shifted(const PipJob *jobs, const i64 *arena, int njobs, int nvar, int ebits,

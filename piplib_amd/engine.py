@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PIPAMD_LIB") or os.path.join(HERE, "libpipamd.so")
 
 ST_RUN, ST_SOLUTION, ST_NIL, ST_NEED_COMPA, ST_NEED_PARMCUT, ST_OVERFLOW, ST_CAPACITY, ST_RANGE, ST_INTERNAL, ST_MAXCOL = range(10)
-ST_BADINPUT = 10  # a system load_matrices() or load_sparse() could not take (PIPAMD_ST_BADINPUT)
+ST_BADINPUT = 10  # a system load_matrices(), load_sparse() or load_instances() could not take (PIPAMD_ST_BADINPUT)
 T_INT, T_DUAL = 1, 2
 T_NOSKIP = 2048
 T_ROWS_STAY = 8192  # the rows of Batch.load stay valid until the next solve: no copy pass (include/piplib_amd.h)
@@ -40,6 +40,12 @@ class Sparse(C.Structure):
     """pipamd_sparse: the plain system of Batch(sparse=True) -- the System, then the entry count and the device arrays of
     row pointers (int64), columns (int32) and values (int64)"""
     _fields_ = [("sys", System), ("nnz", C.c_int64), ("d_row_ptr", C.c_void_p), ("d_cols", C.c_void_p), ("d_vals", C.c_void_p)]
+
+
+class Instances(C.Structure):
+    """pipamd_instances: the plain system of Batch(instances=True) -- the System, then the parameter count of the shared
+    matrix and the device arrays of the matrix (nrows x (nvar + nparm + 1) int64) and the points (systems x nparm int64)"""
+    _fields_ = [("sys", System), ("nparm", C.c_int32), ("reserved", C.c_int32), ("d_matrix", C.c_void_p), ("d_points", C.c_void_p)]
 
 
 ABI_VERSION = 500  # include/piplib_amd.h PIPAMD_VERSION
@@ -97,6 +103,11 @@ def lib():
                                                         C.c_int, C.c_void_p]
             L.pipamd_batch_dual_sparse_part.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BatchDesc), C.POINTER(Sparse), C.c_int,
                                                         C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(L, "pipamd_batch_load_instances_part"):  # (added since 500: a PIPAMD_LIB build may be older)
+            L.pipamd_batch_load_instances_part.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BatchDesc), C.POINTER(Instances),
+                                                           C.c_int, C.c_int, C.c_void_p]
+            L.pipamd_batch_dual_instances_part.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BatchDesc), C.POINTER(Instances),
+                                                           C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.pipamd_batch_counters.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BatchDesc), C.c_void_p, C.c_void_p]
         L.pipamd_last_solve_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         L.pipamd_free.argtypes = [C.c_void_p]
@@ -227,7 +238,7 @@ class Batch:
 
     def __init__(self, engine, rows, nvar, nparm, bigparm=-1, tflags=T_INT, cap_cuts=None, cap_newparm=0,
                  entier_bits=64, shape=None, shift=0, system=False, eq_rows=(), simplify=0, matrices=False, nrows=None, ni=None,
-                 sparse=False):
+                 sparse=False, instances=False):
         """rows: (batch, ni, ncol) int64, host or device; or None with shape=(batch, ni, ncol) for a workspace whose
         tableaux come from load_parts().
         shift=SHIFT_MAX / SHIFT_URS: the lexicographic maximum / unknowns of either sign (pip_solve's Maximize,
@@ -248,7 +259,14 @@ class Batch:
         batch * nrows + 1 of them, int32 columns (nvar: the constant) and int64 values, strictly increasing columns in a
         row --, or None for a workspace loaded with load_sparse_part(); shape=(batch, nrows, nvar + 1) is that of the dense
         expansion.  eq_rows, shift and simplify as for system=True; load_sparse() / dual_sparse() go through
-        pipamd_batch_load_sparse / pipamd_batch_dual_sparse, and a system the load cannot take ends ST_BADINPUT."""
+        pipamd_batch_load_sparse / pipamd_batch_dual_sparse, and a system the load cannot take ends ST_BADINPUT.
+        instances=True: the plain systems of system=True as ONE parametric system at many points.  rows is (matrix, points)
+        -- matrix (nrows, nvar + nparm_of_the_matrix + 1) int64, unknowns | parameters | constant, and points (batch,
+        nparm_of_the_matrix) int64 --; points may be an int, the batch size, for a workspace loaded with
+        load_instances_part().  The nparm argument stays 0 (the tableaux have no parameters).  System b has the constants
+        c_r + sum_k p_rk * points[b][k], computed exactly on the device; eq_rows, shift and simplify as for system=True;
+        load_instances() / dual_instances() go through pipamd_batch_load_instances / pipamd_batch_dual_instances, and a
+        system with a constant that does not fit the entry type ends ST_BADINPUT."""
         import torch
         self.torch = torch
         self.e = engine
@@ -260,6 +278,23 @@ class Batch:
             if rows is not None:
                 self.csr = tuple((t if torch.is_tensor(t) else torch.as_tensor(t)).to(device=dev, dtype=dt).contiguous()
                                  for t, dt in zip(rows, (torch.int64, torch.int32, torch.int64)))
+            rows, system = None, True
+        self.inst = None
+        self.instances = bool(instances)
+        if instances:
+            assert not sparse and not matrices and shape is None, "Batch(instances=True) takes rows=(matrix, points)"
+            dev = torch.device("cuda", engine.device)
+            matrix, points = rows
+            matrix = (matrix if torch.is_tensor(matrix) else torch.as_tensor(matrix)).to(device=dev, dtype=torch.int64).contiguous()
+            assert matrix.dim() == 2 and matrix.shape[1] >= nvar + 1, "matrix is (nrows, nvar + nparm + 1)"
+            self.inst_nparm = matrix.shape[1] - nvar - 1
+            if isinstance(points, int):
+                shape, points = (points, matrix.shape[0], nvar + 1), None
+            else:
+                points = (points if torch.is_tensor(points) else torch.as_tensor(points)).to(device=dev, dtype=torch.int64).contiguous()
+                points = points.reshape(points.shape[0], self.inst_nparm)
+                shape = (points.shape[0], matrix.shape[0], nvar + 1)
+            self.inst = (matrix, points)
             rows, system = None, True
         B, ni_in, ncol = rows.shape if rows is not None else shape
         self.shift = int(shift)
@@ -320,6 +355,8 @@ class Batch:
     def load(self):
         if self.sparse:
             return self.load_sparse()
+        if self.instances:
+            return self.load_instances()
         if self.matrices is not None:
             return self.load_matrices()
         if self.shift or self.system is not None:
@@ -332,6 +369,7 @@ class Batch:
         assert rows.is_cuda and rows.is_contiguous()
         assert self.matrices is None, "a Batch(matrices=True) is loaded with load_matrices_part(rows, nrows, first)"
         assert not self.sparse, "a Batch(sparse=True) is loaded with load_sparse_part(row_ptr, cols, vals, first)"
+        assert not self.instances, "a Batch(instances=True) is loaded with load_instances_part(points, first)"
         st = C.c_void_p(stream) if stream is not None else self._stream()
         if self.system is not None:
             return self.load_system_part(rows, first, stream)
@@ -527,6 +565,48 @@ class Batch:
         st = C.c_void_p(stream) if stream is not None else self._stream()
         _check(lib().pipamd_batch_dual_sparse_part(self.e._h, C.c_void_p(self.ws.data_ptr()), C.byref(self.desc), C.byref(sp),
                                                    int(first), count, C.c_void_p(num.data_ptr()), C.c_void_p(den.data_ptr()), st))
+        return num, den
+
+    def _instances_part(self, points, matrix):
+        """(the pipamd_instances of a part: the batch's system with the part's points and its matrix, the part's systems)"""
+        t = self.torch
+        assert self.instances
+        matrix = self.inst[0] if matrix is None else matrix
+        assert matrix.is_cuda and matrix.is_contiguous() and matrix.dtype == t.int64 and matrix.shape == self.inst[0].shape
+        assert points.is_cuda and points.is_contiguous() and points.dtype == t.int64
+        assert points.dim() == 2 and points.shape[1] == self.inst_nparm
+        return (Instances(self.system, self.inst_nparm, 0, matrix.data_ptr(), points.data_ptr() if self.inst_nparm else None),
+                int(points.shape[0]))
+
+    def load_instances(self, stream=None):
+        """pipamd_batch_load_instances of a Batch(instances=True): the whole batch from its resident matrix and points"""
+        return self.load_instances_part(self.inst[1], 0, stream)
+
+    def load_instances_part(self, points, first, stream=None, matrix=None):
+        """pipamd_batch_load_instances_part: tableaux first .. first + len(points) - 1, the systems of the resident `points`
+        ((count, nparm) int64) under the batch's matrix, or under `matrix`, a resident one of the same shape"""
+        ins, count = self._instances_part(points, matrix)
+        st = C.c_void_p(stream) if stream is not None else self._stream()
+        _check(lib().pipamd_batch_load_instances_part(self.e._h, C.c_void_p(self.ws.data_ptr()), C.byref(self.desc), C.byref(ins),
+                                                      int(first), count, st))
+
+    def dual_instances(self, stream=None):
+        """pipamd_batch_dual_instances after a solve with T_DUAL of a Batch(instances=True): device tensors (dual_num,
+        dual_den) of shape (batch, nrows) -- plus a trailing 2 for 128-bit entries --, as dual_system() gives them; (0, 0)
+        throughout for a tableau without a solution.  Does not synchronise."""
+        if self.inst[1] is None:
+            raise RuntimeError("Batch.dual_instances needs the points the batch was loaded from: use dual_instances_part()")
+        return self.dual_instances_part(self.inst[1], 0, stream)
+
+    def dual_instances_part(self, points, first, stream=None, out=None, matrix=None):
+        """pipamd_batch_dual_instances_part for the tableaux first .. first + len(points) - 1, loaded from these points (and
+        `matrix`, if not the batch's); returns (dual_num, dual_den) of the whole batch's shape (pass the pair back as `out`
+        to fill it part by part)."""
+        ins, count = self._instances_part(points, matrix)
+        num, den = out if out is not None else self._dual_out(self.system.nrows)
+        st = C.c_void_p(stream) if stream is not None else self._stream()
+        _check(lib().pipamd_batch_dual_instances_part(self.e._h, C.c_void_p(self.ws.data_ptr()), C.byref(self.desc), C.byref(ins),
+                                                      int(first), count, C.c_void_p(num.data_ptr()), C.c_void_p(den.data_ptr()), st))
         return num, den
 
     def counters(self):
