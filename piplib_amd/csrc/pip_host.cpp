@@ -70,6 +70,7 @@ extern "C" void pipamd_engine_destroy(pipamd_engine *e) {
   for (void *b : e->dt_buf)
     if (b) hipFree(b);
   if (e->dt_host) hipHostFree(e->dt_host);
+  free(e->dt_rec);
   pthread_mutex_destroy(&e->dt_lock);
   free(e);
 }

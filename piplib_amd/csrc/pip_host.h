@@ -43,6 +43,9 @@ struct pipamd_engine {
   void *dt_host;       /* device tree: pinned staging buffer for the problems' rows */
   size_t dt_host_cap;
   int dt_served, dt_fallback; /* problems the device tree finished / handed back in the last lock-step call */
+  int dt_record;       /* testing aid (pipamd_debug_device_tree_record): keep the device tree's result words of the last call */
+  int *dt_rec;         /* Q_OUT ints per problem of that call, by input index; -1 throughout where the device tree was not given it */
+  int dt_rec_n;
   unsigned long long *d_prof; /* diagnostic builds only (-DPIP_PROFILE) */
   void *d_scratch;
   size_t scratch_bytes;

@@ -1517,7 +1517,7 @@ static __device__ __forceinline__ void run(const QProb *probs, const w64 *input,
         next = PIVOT;  // traiter.c:758: the caller goes on with `pirouette` on the row now negative
       }
     }
-    if (!finished) w.bad |= Q_WHY_OTHER;
+    if (!finished && !BAD(w)) w.bad |= Q_WHY_OTHER;  // (the guard ran out; a problem that left with a reason keeps that reason alone)
   }
   int why = w.bad;
   for (int o = 32; o; o >>= 1) why |= __shfl_xor(why, o);

@@ -598,6 +598,10 @@ class TreeT {
       run(js);
       pivots += job.pj.npiv - piv0;
       ni = job.pj.ni;
+      // traiter() runs compa_test before it looks for a solution or a cut (traiter.c:682), rows to test or not: "Too much
+      // parameters" there (traiter.c:174) also where the kernel found every sign settled and asked for no compa_test
+      if ((job.pj.status == PIPAMD_ST_SOLUTION || job.pj.status == PIPAMD_ST_NEED_PARMCUT) && nparm >= PIPAMD_MAXPARM)
+        fail(PIPAMD_ST_INTERNAL);
       switch (job.pj.status) {
         case PIPAMD_ST_SOLUTION:
           emit_solution(job, nvar, nparm);
@@ -703,12 +707,28 @@ size_t forest_arena_budget() {
 // where the host schedulers have to.  qflags: QProb::flags of every problem (null: 0 for all), a negative entry keeps
 // its problem out.  pipamd_last_device_tree answers for the call: the one-problem entries leave its counts alone while
 // the device tree is switched off, the many-problem entries report 0 / 0 then.
+// Testing aid (pipamd_debug_device_tree_record): a call over n problems begins -- every record "not given to the device tree"
+// until device_tree_chunk has that problem's result words.  Recording off (the default): nothing.
+void dt_records_begin(pipamd_engine *e, int n) {
+  if (!e->dt_record) return;
+  pthread_mutex_lock(&e->dt_lock);
+  free(e->dt_rec);
+  e->dt_rec_n = 0;
+  e->dt_rec = n > 0 ? (int *)malloc(sizeof(int) * Q_OUT * (size_t)n) : nullptr;
+  if (e->dt_rec) {
+    e->dt_rec_n = n;
+    for (size_t k = 0; k < Q_OUT * (size_t)n; k++) e->dt_rec[k] = -1;
+  }
+  pthread_mutex_unlock(&e->dt_lock);
+}
+
 template <class E>
 void try_device_tree(pipamd_engine *e, int n, const pipamd_problem *probs, int simplify, int deepest_cut, const int *qflags,
                      bool one_problem, std::vector<FResultT<E>> &res) {
   res.assign(n > 0 ? n : 0, FResultT<E>());
   for (auto &r : res) r.rc = PIPAMD_E_TOOLARGE;
   if (!one_problem) e->dt_served = e->dt_fallback = 0;
+  dt_records_begin(e, n);
   if (e->no_device_tree || getenv("PIPAMD_NO_DEVICE_TREE") || n <= 0) return;
   int served = 0, back = 0;
   device_tree<E>(e, n, probs, simplify, deepest_cut, res, &served, &back, qflags);
@@ -1489,6 +1509,9 @@ class ForestT {
       begin_main(i);
       return;
     }
+    // traiter() runs compa_test before it looks for a solution or a cut (traiter.c:682), rows to test or not: "Too much
+    // parameters" there (traiter.c:174) also where the step found every sign settled and asked for no compa_test
+    if ((st == PIPAMD_ST_SOLUTION || st == PIPAMD_ST_NEED_PARMCUT) && f.nparm >= PIPAMD_MAXPARM) fail(i, PIPAMD_ST_INTERNAL);
     switch (st) {
       case PIPAMD_ST_SOLUTION: {
         const E *g = gathered(f.job);
@@ -1792,6 +1815,9 @@ void device_tree_chunk(pipamd_engine *e, const std::vector<int> &idx, const pipa
   std::vector<int> out(Q_OUT * (size_t)n);
   HIPTHROW(hipMemcpy(out.data(), d_out, sizeof(int) * Q_OUT * n, hipMemcpyDeviceToHost));
   const double t2 = now();
+  if (e->dt_record && e->dt_rec)
+    for (int k = 0; k < n; k++)
+      if (idx[k] < e->dt_rec_n) memcpy(e->dt_rec + Q_OUT * (size_t)idx[k], out.data() + Q_OUT * (size_t)k, sizeof(int) * Q_OUT);
   std::vector<i64> off(n + 1, 0);
   for (int k = 0; k < n; k++) off[k + 1] = off[k] + (out[Q_OUT * k] == Q_DONE ? out[Q_OUT * k + 1] : 0);
   std::vector<E> packed(3 * (size_t)off[n]);
@@ -1917,6 +1943,33 @@ extern "C" int pipamd_device_tree_fits(const pipamd_problem *p, int entier_bits)
   if (p->nvar < 0 || p->nparm < 0 || p->ni < 0 || p->nc < 0 || (p->ni && !p->ineq) || (p->nc && !p->ctx)) return PIPAMD_E_INVALID;
   QCaps c;
   return device_tree_caps(*p, entier_bits, c) ? 1 : 0;
+}
+
+// Testing aids, exported like pipamd_debug_lean and no part of the interface.  pipamd_debug_device_tree_record(e, 1): the
+// engine keeps, from its next call on, the Q_OUT result words (pip_quast.h: result, cells, pivots, Q_WHY_* bits, ticks,
+// tape cells) the device tree wrote for every problem of the call, by input index; default off.
+// pipamd_debug_device_tree_records copies those of the last call, at most `cap` problems' (Q_OUT ints each), and returns
+// how many problems that call had; a problem the device tree was not given (outside its box, or switched off) has -1
+// in all its words.
+extern "C" int pipamd_debug_device_tree_record(pipamd_engine *e, int on) {
+  if (!e) return PIPAMD_E_INVALID;
+  pthread_mutex_lock(&e->dt_lock);
+  e->dt_record = on ? 1 : 0;
+  if (!on) {
+    free(e->dt_rec);
+    e->dt_rec = nullptr;
+    e->dt_rec_n = 0;
+  }
+  pthread_mutex_unlock(&e->dt_lock);
+  return PIPAMD_OK;
+}
+extern "C" int pipamd_debug_device_tree_records(pipamd_engine *e, int *out, int cap) {
+  if (!e || cap < 0 || (cap && !out)) return PIPAMD_E_INVALID;
+  pthread_mutex_lock(&e->dt_lock);
+  const int n = e->dt_rec ? e->dt_rec_n : 0;
+  if (n && cap) memcpy(out, e->dt_rec, sizeof(int) * Q_OUT * (size_t)std::min(n, cap));
+  pthread_mutex_unlock(&e->dt_lock);
+  return n;
 }
 
 // Many problems: the device tree first (small problems), then the lock-step Forest; the few that need
@@ -2171,6 +2224,7 @@ int pip_solve_many_any(pipamd_engine *e, int n, const pipamd_pip_problem *p, int
   constexpr bool WIDE = sizeof(E) == 16;
   if (!e || n < 0 || (n && (!p || !info || !cells || !n_cells || !rcs))) return PIPAMD_E_INVALID;
   e->dt_served = e->dt_fallback = 0;
+  dt_records_begin(e, n);
   if (n == 0) return PIPAMD_OK;
   if (nthreads < 1) nthreads = 1;
   if (nthreads > n) nthreads = n;

@@ -153,6 +153,25 @@ class Engine:
         _check(lib().pipamd_last_device_tree(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def debug_device_tree_record(self, on):
+        """testing aid: keep the device tree's result words of every problem of a call (default off)"""
+        lib().pipamd_debug_device_tree_record.argtypes = [C.c_void_p, C.c_int]
+        _check(lib().pipamd_debug_device_tree_record(self._h, int(bool(on))))
+
+    def debug_device_tree_records(self):
+        """testing aid: (n, 6) int32 of the last call's problems, by input index -- result (Q_DONE 0, Q_VOID 1, Q_FALLBACK 2),
+        cells, pivots, Q_WHY_* bits, ticks, tape cells written (csrc/pip_quast.h); -1 throughout where the device tree was not
+        given the problem.  Recording must be on (debug_device_tree_record)."""
+        import numpy as np
+        L = lib()
+        L.pipamd_debug_device_tree_records.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        n = L.pipamd_debug_device_tree_records(self._h, None, 0)
+        _check(min(n, 0))
+        out = np.full((n, 6), -1, np.int32)
+        if n:
+            _check(min(L.pipamd_debug_device_tree_records(self._h, out.ctypes.data_as(C.c_void_p), n), 0))
+        return out
+
     def set_max_rows(self, rows):
         lib().pipamd_engine_set_max_rows.argtypes = [C.c_void_p, C.c_int]
         _check(lib().pipamd_engine_set_max_rows(self._h, int(rows)))

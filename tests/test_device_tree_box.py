@@ -72,3 +72,30 @@ def test_outside_the_box(shape):
 def test_bad_arguments():
     with pytest.raises(RuntimeError):
         eng.device_tree_fits(_one(5, 2, 7, 2), 32)
+
+
+def test_edge_members_in_the_box():
+    """the members of tests/device_tree_edges.py that sit on a limit of the box: 17 context rows with parameters (CR + 1 == SS
+    == 64), 127 and 128 columns, 104 inequalities, 49 parameters, a context of 64 columns with its spare ones"""
+    import device_tree_edges as dte
+    taken = [dte.member("chain24_new10_nc17"), dte.member("cols127_new1"), dte.widen(dte.chain(0, nnew=1), 128),
+             dte.member("cuts24_ni104"), dte.member("wide49_2_0")]
+    assert eng.device_tree_fits(_one(11, 53, 20, 1)) == 1  # (nparm + newp + 1 == 64; in 128 bits the LDS rule decides)
+    assert [(p.nc, p.nvar + p.nparm + 1, p.ni, p.nparm) for p in taken] == [
+        (17, 46, 35, 34), (0, 127, 2, 1), (0, 128, 2, 1), (0, 49, 104, 0), (0, 51, 3, 49)]
+    for p in taken:
+        assert eng.device_tree_fits(p) == 1 and eng.device_tree_fits(p, 128) == 1
+    for name in dte.MEMBERS:  # every member the GPU tests put at a reserve or one past it is given to the device tree
+        assert eng.device_tree_fits(dte.member(name)) == 1 and eng.device_tree_fits(dte.member(name), 128) == 1, name
+
+
+def test_edge_members_outside_the_box():
+    """18 context rows with parameters (CR + 1 > SS), 105 inequalities, nparm + newp + 1 > 64 (65 columns, 54 parameters:
+    two blocks leave 10 spare columns, the context would have 65)"""
+    import device_tree_edges as dte
+    out = [dte.chain(24, nnew=10, nc=18), dte.cuts(24, 81), dte.cuts(25, 80), _one(10, 54, 20, 1)]
+    assert (out[0].nc, out[1].ni, out[2].ni) == (18, 105, 105)
+    for p in out:
+        assert eng.device_tree_fits(p) == 0 and eng.device_tree_fits(p, 128) == 0
+    assert eng.device_tree_fits(dte.chain(0, nc=18, idle=20)) == 0  # (no fork or cut needed: the shape alone decides)
+    assert eng.device_tree_fits(dte.chain(0, nc=17, idle=20)) == 1
