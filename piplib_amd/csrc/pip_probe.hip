@@ -6,7 +6,11 @@
 //   pipamd_debug_arith(engine, op, in, out, n)            one case per lane, n cases
 //   pipamd_debug_row_update(engine, path, in, out, ncases) one wave per case (the row functions ballot and readlane)
 // and the lean kernel's per-lane preparation and its reductions from a given gcd (tests/test_gpu_lean_prep_probe.py):
-// pipamd_debug_arith op 128, pipamd_debug_row_update paths 32 ... 35.
+// pipamd_debug_arith op 128, pipamd_debug_row_update paths 32 ... 35;
+//   pipamd_debug_select(engine, fn, in, out, ncases)      one workgroup per case: the functions that decide which pivot is
+//     taken -- choose_column / choose_column_slow / lean_choose_column (choisir_piv), sort_rows (tab_sort_rows), exam_rows
+//     (exam_coef) -- on a small tableau, after row_publish / lean_publish have summarised its rows; the summaries are
+//     reported too (tests/test_gpu_select_probe.py; the case layout stands above the kernels).
 //
 // `in` / `out`: device pointers to int64 words, 16-byte aligned; a 128-bit value is two words, low then high (as
 // det_limb).  Exported, not declared in include/piplib_amd.h (like pipamd_debug_lean): no part of the interface.
@@ -240,6 +244,220 @@ __global__ __launch_bounds__(64) void pip_probe_lean_kernel(const i64 *in, i64 *
   }
 }
 
+// ---- pipamd_debug_select: one workgroup per case, the functions that decide WHICH pivot is taken (choisir_piv,
+// tab_sort_rows, exam_coef) on a small tableau the caller gives.  `in`: words 0, 1 the lengths of `in` and `out` in words,
+// then the cases' offsets into `in` (ncases words) and into `out` (ncases words), then the cases.  A case, in int64 words
+// (values of the flavour's Entier T: one word, or two, low then high):
+//   nvar, ncol, W, ni, nligne, pivi, bigparm, smax (the bits of a double)            8 words
+//   ref[nligne], urow[nvar], srow[ni], fl[ni], size[ni] (the bits of a float)        a word each
+//   the ni real rows of W entries, slot by slot, then den[ni]                        values of T, at an even word offset
+// out: status (1; 0 = the case does not fit the probe and nothing was run), the function's return value,
+// max_row_class, ref[nligne], fl[ni], then per slot sig, rcls, cst (a value of T) and the NM words of nzm; the lean
+// flavours append the packed image of the rows (ni slots of W values of T), which they read the rows back from.
+// Every real row is summarised by the shipped row_publish / lean_publish before the function under test runs.
+enum {
+  SEL_SLOTS = 192, SEL_ROWS = 256,          // row slots and logical rows the probe's tables hold ...
+  SEL_SLOTS_NW4 = 320, SEL_ROWS_NW4 = 384,  // ... and for exam_rows<i64, 4>, whose 256 threads wrap around at 257 rows
+  S_C64S_1 = 0, S_C64S_2, S_C64S_4, S_C64_1, S_C64_2, S_C64_4, S_C128_1, S_C128_4, S_C128_8, S_SLOW64, S_SLOW128,
+  S_LI_S, S_LI_M, S_LL_S, S_LL_M, S_SORT64, S_EXAM64_1, S_EXAM64_4, S_NFN
+};
+enum { SM_CHOOSE_SMALL, SM_CHOOSE, SM_SLOW, SM_SORT, SM_EXAM };
+
+template <class T, int WP, int NM, int SLOTS, int ROWS>
+struct SelectImage {
+  static constexpr int NS = SLOTS, NR = ROWS;
+  T den[SLOTS], prow[WP], cst[SLOTS];
+  u64 nzm[SLOTS * NM];
+  float size[SLOTS];
+  u16 sig[SLOTS], srow[SLOTS], work[SLOTS], ref[ROWS], urow[WP];
+  u8 fl[SLOTS], nf[SLOTS], rcls[SLOTS];
+  Scalars sc;
+  __device__ __forceinline__ Shared<T> shared() {
+    Shared<T> S = {den, prow, cst, nzm, size, sig, srow, work, ref, urow, fl, nf, rcls};
+    return S;
+  }
+};
+
+struct SelectCase {
+  int nvar, ncol, W, ni, nligne, pivi, bigparm;
+  double smax;
+  const i64 *ref, *urow, *srow, *fl, *size, *vals, *den;  // vals: the rows
+  i64 *out;
+  size_t nout;
+};
+
+// the case's header and extents, checked against the probe's tables and the two buffers; uniform over the workgroup
+template <class T>
+__device__ __forceinline__ bool select_case(const i64 *in, i64 *out, int cs, int ncases, int WP, int NM, int slots, int rows, bool lean,
+                                            SelectCase &c) {
+  constexpr size_t EW = ET<T>::EW;
+  const u64 nin = (u64)in[0], nall = (u64)in[1], oi = (u64)in[2 + cs], oo = (u64)in[2 + ncases + cs];
+  if (oo >= nall) return false;
+  c.out = out + oo;
+  c.out[0] = 0;
+  if (oi < 2 + 2 * (u64)ncases || oi + 8 > nin) return false;
+  const i64 *h = in + oi;
+  for (int k = 0; k < 7; k++)
+    if (h[k] < -1 || h[k] > 4096) return false;
+  c.nvar = (int)h[0], c.ncol = (int)h[1], c.W = (int)h[2], c.ni = (int)h[3], c.nligne = (int)h[4], c.pivi = (int)h[5];
+  c.bigparm = (int)h[6];
+  c.smax = __longlong_as_double(h[7]);
+  if (c.nvar < 1 || c.nvar > WP || c.ncol < c.nvar || c.ncol > c.W || c.W > WP || (c.W & 1) || c.ni < 0 || c.ni > slots ||
+      c.nligne < 0 || c.nligne > rows)
+    return false;
+  size_t o = 8;
+  c.ref = h + o, o += c.nligne;
+  c.urow = h + o, o += c.nvar;
+  c.srow = h + o, o += c.ni;
+  c.fl = h + o, o += c.ni;
+  c.size = h + o, o += c.ni;
+  o += (oi + o) & 1;
+  c.vals = h + o, o += EW * (size_t)c.ni * c.W;
+  c.den = h + o, o += EW * (size_t)c.ni;
+  c.nout = 3 + (size_t)c.nligne + c.ni + (size_t)c.ni * (2 + EW + NM) + (lean ? EW * (size_t)c.ni * c.W : 0);
+  if (oi + o > nin || oo + c.nout > nall) return false;
+  // what the functions index tables with
+  for (int k = 0; k < c.nligne; k++) {
+    const i64 rf = c.ref[k];
+    if (rf < 0 || ((rf & UNITBIT) ? (rf & ~(i64)(UNITBIT | UNITZERO)) >= c.nvar : rf >= c.ni)) return false;
+  }
+  for (int k = 0; k < c.nvar; k++)
+    if (c.urow[k] < 0 || c.urow[k] > 0xffff) return false;
+  for (int k = 0; k < c.ni; k++)
+    if (c.srow[k] < 0 || c.srow[k] > 0xffff) return false;
+  if (c.pivi >= 0 && (c.pivi >= c.nligne || (c.ref[c.pivi] & UNITBIT))) return false;
+  return true;
+}
+
+template <class T, class IM>
+__device__ __forceinline__ void select_stage(IM &im, const SelectCase &c, int WP, int tid, int nt) {
+  for (int k = tid; k < IM::NS; k += nt) {
+    const bool in = k < c.ni;
+    im.den[k] = in ? ldv<T>(c.den, k) : (T)0;
+    im.cst[k] = 0;
+    im.size[k] = in ? __uint_as_float((unsigned)c.size[k]) : 0.f;
+    im.sig[k] = 0, im.work[k] = 0, im.nf[k] = 0, im.rcls[k] = 0;
+    im.srow[k] = in ? (u16)c.srow[k] : (u16)NOROW;
+    im.fl[k] = in ? (u8)c.fl[k] : (u8)0;
+  }
+  for (int k = tid; k < IM::NR; k += nt) im.ref[k] = k < c.nligne ? (u16)c.ref[k] : (u16)UNITBIT;
+  for (int k = tid; k < WP; k += nt) {
+    im.prow[k] = 0;
+    im.urow[k] = k < c.nvar ? (u16)c.urow[k] : (u16)NOROW;
+  }
+}
+
+// what every case reports: the tables the function may have written and what the publish functions left per slot
+template <class T, int NM>
+__device__ __forceinline__ void select_report(const Shared<T> &S, const T *cst, const SelectCase &c, int ret, int mc, int tid, int nt) {
+  constexpr int EW = ET<T>::EW;
+  i64 *o = c.out;
+  if (tid == 0) o[0] = 1, o[1] = ret, o[2] = mc;
+  o += 3;
+  for (int k = tid; k < c.nligne; k += nt) o[k] = S.ref[k];
+  o += c.nligne;
+  for (int k = tid; k < c.ni; k += nt) o[k] = S.fl[k];
+  o += c.ni;
+  for (int s = tid; s < c.ni; s += nt) {
+    i64 *p = o + (size_t)s * (2 + EW + NM);
+    p[0] = S.sig[s], p[1] = S.rcls[s];
+    stv<T>(p + 2, 0, cst[s]);
+    for (int e = 0; e < NM; e++) p[2 + EW + e] = (i64)S.nzm[(size_t)s * NM + e];
+  }
+}
+
+template <class T, int NCH, int NW, int MODE, int SLOTS = SEL_SLOTS, int ROWS = SEL_ROWS>
+__global__ __launch_bounds__(64 * NW) void pip_probe_select_kernel(const i64 *in, i64 *out, int ncases) {
+  constexpr int WP = NCH * 64 * ET<T>::CPL, NM = NCH * ET<T>::CPL, NT = 64 * NW;
+  __shared__ SelectImage<T, WP, NM, SLOTS, ROWS> im;
+  const int cs = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (cs >= ncases) return;
+  SelectCase c;
+  if (!select_case<T>(in, out, cs, ncases, WP, NM, SLOTS, ROWS, false, c)) return;
+  select_stage<T>(im, c, WP, tid, NT);
+  __syncthreads();
+  const Shared<T> S = im.shared();
+  const T *vals = reinterpret_cast<const T *>(c.vals);
+  int ret = 0, mc = 0;
+  RowRegs<T, NCH> pr = {};
+  if (wave == 0) {
+    for (int s = 0; s < c.ni; s++) {
+      RowRegs<T, NCH> r;
+      row_load<T, NCH>(r, vals + (size_t)s * c.W, c.W, lane);
+      row_publish<T, NCH>(r, S, s, c.nvar, c.ncol, c.bigparm, -1, 0, c.ncol > c.nvar + 1, lane);
+    }
+    __builtin_amdgcn_wave_barrier();
+    mc = max_row_class(S, c.ni, lane);
+    if (c.pivi >= 0) {  // the pivot row as phase A stages it: zero beyond ncol, a copy in LDS
+      row_load<T, NCH>(pr, vals + (size_t)S.ref[c.pivi] * c.W, c.W, lane);
+#pragma unroll
+      for (int ch = 0; ch < NCH; ch++)
+#pragma unroll
+        for (int h = 0; h < ET<T>::CPL; h++) {
+          const int j = colof<T>(ch, lane, h);
+          if (j >= c.ncol) pr.v[ch][h] = 0;
+          S.prow[j] = pr.v[ch][h];
+        }
+    }
+  }
+  __syncthreads();
+  if constexpr (MODE == SM_EXAM) {
+    ret = exam_rows<T, NW>(S, &im.sc, c.ni);
+  } else if (wave == 0) {
+    if constexpr (MODE == SM_CHOOSE_SMALL || MODE == SM_CHOOSE)
+      ret = choose_column<T, NCH, MODE == SM_CHOOSE_SMALL>(S, pr, vals, c.W, c.nvar, c.nligne, c.pivi, c.W, &im.sc);
+    else if constexpr (MODE == SM_SLOW)
+      ret = choose_column_slow<T>(S, vals, c.W, c.nvar, c.nligne);
+    else
+      sort_rows<T>(S, c.nvar, c.nligne, c.smax);
+  }
+  __syncthreads();
+  if (wave == 0) select_report<T, NM>(S, S.cst, c, ret, mc, lane, 64);
+}
+
+// the lean flavours: the rows are packed into the case's output image (F::store), read back from it (F::load) and
+// summarised by lean_publish, as the lean kernels hold them
+template <class F, bool SMALL>
+__global__ __launch_bounds__(64) void pip_probe_select_lean_kernel(const i64 *in, i64 *out, int ncases) {
+  typedef typename F::T T;
+  typedef typename F::E E;
+  constexpr int WP = F::WP, NM = F::NM, EW = ET<T>::EW;
+  __shared__ SelectImage<T, WP, NM, SEL_SLOTS, SEL_ROWS> im;
+  __shared__ T cstw[SEL_SLOTS];
+  const int cs = blockIdx.x, lane = threadIdx.x;
+  if (cs >= ncases) return;
+  SelectCase c;
+  if (!select_case<T>(in, out, cs, ncases, WP, NM, SEL_SLOTS, SEL_ROWS, true, c) || c.nvar >= WP) return;
+  select_stage<T>(im, c, WP, lane, 64);
+  __syncthreads();
+  const Shared<T> S = im.shared();
+  E *cst = reinterpret_cast<E *>(im.cst);
+  const i64 *rows = c.vals;
+  T *vals = reinterpret_cast<T *>(c.out + (c.nout - (size_t)EW * c.ni * c.W));
+  if (((uintptr_t)vals & 15) != 0) return;
+  for (int s = 0; s < c.ni; s++) {
+    typename F::Row r, z;
+#pragma unroll
+    for (int h = 0; h < F::NV; h++) {
+      const int j = F::col(lane, h);
+      r.v[h] = j < c.W ? (E)ldv<T>(rows, (size_t)s * c.W + j) : (E)0;
+    }
+    F::store(r, vals + (size_t)s * c.W, lane, c.W);
+    __builtin_amdgcn_wave_barrier();
+    F::load(z, vals + (size_t)s * c.W, lane, c.W);
+    lean_publish<F, false>(z, S, cst, s, -1, 0, lane, c.nvar);
+  }
+  __syncthreads();
+  const int mc = max_row_class(S, c.ni, lane);
+  typename F::Row pr = {};
+  if (c.pivi >= 0) F::load(pr, vals + (size_t)S.ref[c.pivi] * c.W, lane, c.W);
+  const int ret = lean_choose_column<F, SMALL>(S, pr, vals, c.W, c.nvar, c.nligne, c.pivi, &im.sc);
+  __syncthreads();
+  for (int s = lane; s < c.ni; s += 64) cstw[s] = (T)cst[s];
+  __syncthreads();
+  select_report<T, NM>(S, cstw, c, ret, mc, lane, 64);
+}
+
 bool probe_ptrs_ok(const void *in, const void *out) {
   return in && out && ((uintptr_t)in & 15) == 0 && ((uintptr_t)out & 15) == 0;
 }
@@ -297,5 +515,34 @@ extern "C" int pipamd_debug_row_update(pipamd_engine *e, int path, const long lo
     case R_LL_M_GS: PIP_PROBE_ROW(pip_probe_lean_kernel<LeanLongRows, false, true>); break;
   }
 #undef PIP_PROBE_ROW
+  return probe_finish(hipGetLastError());
+}
+
+extern "C" int pipamd_debug_select(pipamd_engine *e, int fn, const long long *in, long long *out, int ncases) {
+  if (!e || ncases < 0 || !probe_ptrs_ok(in, out) || fn < 0 || fn >= S_NFN) return PIPAMD_E_INVALID;
+  if (hipSetDevice(e->device) != hipSuccess) return PIPAMD_E_HIP;
+  if (ncases == 0) return PIPAMD_OK;
+#define PIP_PROBE_SEL(NW, ...) hipLaunchKernelGGL((__VA_ARGS__), dim3(ncases), dim3(64 * NW), 0, 0, in, out, ncases)
+  switch (fn) {
+    case S_C64S_1: PIP_PROBE_SEL(1, pip_probe_select_kernel<i64, 1, 1, SM_CHOOSE_SMALL>); break;
+    case S_C64S_2: PIP_PROBE_SEL(1, pip_probe_select_kernel<i64, 2, 1, SM_CHOOSE_SMALL>); break;
+    case S_C64S_4: PIP_PROBE_SEL(1, pip_probe_select_kernel<i64, 4, 1, SM_CHOOSE_SMALL>); break;
+    case S_C64_1: PIP_PROBE_SEL(1, pip_probe_select_kernel<i64, 1, 1, SM_CHOOSE>); break;
+    case S_C64_2: PIP_PROBE_SEL(1, pip_probe_select_kernel<i64, 2, 1, SM_CHOOSE>); break;
+    case S_C64_4: PIP_PROBE_SEL(1, pip_probe_select_kernel<i64, 4, 1, SM_CHOOSE>); break;
+    case S_C128_1: PIP_PROBE_SEL(1, pip_probe_select_kernel<i128, 1, 1, SM_CHOOSE>); break;
+    case S_C128_4: PIP_PROBE_SEL(1, pip_probe_select_kernel<i128, 4, 1, SM_CHOOSE>); break;
+    case S_C128_8: PIP_PROBE_SEL(1, pip_probe_select_kernel<i128, 8, 1, SM_CHOOSE>); break;
+    case S_SLOW64: PIP_PROBE_SEL(1, pip_probe_select_kernel<i64, 4, 1, SM_SLOW>); break;
+    case S_SLOW128: PIP_PROBE_SEL(1, pip_probe_select_kernel<i128, 8, 1, SM_SLOW>); break;
+    case S_LI_S: PIP_PROBE_SEL(1, pip_probe_select_lean_kernel<LeanIntRows, true>); break;
+    case S_LI_M: PIP_PROBE_SEL(1, pip_probe_select_lean_kernel<LeanIntRows, false>); break;
+    case S_LL_S: PIP_PROBE_SEL(1, pip_probe_select_lean_kernel<LeanLongRows, true>); break;
+    case S_LL_M: PIP_PROBE_SEL(1, pip_probe_select_lean_kernel<LeanLongRows, false>); break;
+    case S_SORT64: PIP_PROBE_SEL(1, pip_probe_select_kernel<i64, 1, 1, SM_SORT>); break;
+    case S_EXAM64_1: PIP_PROBE_SEL(1, pip_probe_select_kernel<i64, 1, 1, SM_EXAM>); break;
+    case S_EXAM64_4: PIP_PROBE_SEL(4, pip_probe_select_kernel<i64, 1, 4, SM_EXAM, SEL_SLOTS_NW4, SEL_ROWS_NW4>); break;
+  }
+#undef PIP_PROBE_SEL
   return probe_finish(hipGetLastError());
 }

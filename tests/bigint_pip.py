@@ -117,19 +117,28 @@ def sort_rows(rows, nvar, nligne):
         r.size = np.float32(s)
         if s > smax:
             smax = s
-    for i in range(nvar, nligne):
-        if rows[i].flag & UNIT:
+    def swap(a, b):
+        rows[a], rows[b] = rows[b], rows[a]
+    selection_sort(nvar, nligne, smax, lambda i: rows[i].flag & UNIT, lambda i: float(rows[i].size), swap)
+
+
+def selection_sort(lo, hi, smax, is_unit, size_of, swap):
+    """The selection loop of traiter.c:591-614 over the logical rows lo .. hi-1, on given sizes (floats, widened to
+    doubles in the comparison as C does) and a given bound smax: for each row that is not Unit, the first row at or after
+    it whose size is strictly below the running bound -- smax to begin with -- is swapped into its place."""
+    for i in range(lo, hi):
+        if is_unit(i):
             continue
         s = smax
         pivi = i
-        for j in range(i, nligne):
-            if rows[j].flag & UNIT:
+        for j in range(i, hi):
+            if is_unit(j):
                 continue
-            if float(rows[j].size) < s:
-                s = float(rows[j].size)
+            if size_of(j) < s:
+                s = size_of(j)
                 pivi = j
         if pivi != i:
-            rows[pivi], rows[i] = rows[i], rows[pivi]
+            swap(pivi, i)
 
 
 def _cell(rows, k, j):
