@@ -53,7 +53,9 @@ extern "C" {
  * pipamd_batch_load_sparse / pipamd_batch_dual_sparse and their _part forms -- the plain system as sparse rows (CSR on
  * the device), the tableaux built from them as from the dense expansion; pipamd_batch_load_instances /
  * pipamd_batch_dual_instances and their _part forms -- one parametric system at many parameter points, substituted
- * exactly on the device (a constant that does not fit the entry type: PIPAMD_ST_BADINPUT). */
+ * exactly on the device (a constant that does not fit the entry type: PIPAMD_ST_BADINPUT); pipamd_tape_check /
+ * pipamd_tape_compile / pipamd_tape_eval / pipamd_tape_free and the 128-bit forms of the first two -- a tape evaluated at
+ * many parameter points, a lane per point. */
 #define PIPAMD_VERSION 500
 
 /* ---- error codes (return values) ---- */
@@ -702,6 +704,90 @@ int pipamd_last_device_tree(const pipamd_engine *e, int *served, int *handed_bac
  * PIPAMD_E_INVALID for bad arguments.  Host only: needs neither an engine nor a GPU.  The same decision the solve entries
  * make (interface version 500). */
 int pipamd_device_tree_fits(const pipamd_problem *p, int entier_bits);
+
+/* ------------------------------------------------------------------ tapes at parameter points */
+/* A parametric problem is solved ONCE; its tape -- the cells pipamd_traiter, pipamd_solve_tableau*, pipamd_traiter_many
+ * or pipamd_pip_solve_many handed out -- is then EVALUATED at as many parameter points as the caller likes, a lane per
+ * point (csrc/pip_tape.hip), instead of solving an instance per point (pipamd_batch_load_instances).  Added since
+ * interface version 500.  The grammar, with P the parameters in scope, nparm at the root:
+ *     item := NEW(n) DIV FORM(P+1) VAL x (P+1) VAL(D)   item
+ *           | IF FORM(P+1) VAL x (P+1)   item   item
+ *           | LIST(nvar) { FORM(P+1) VAL x (P+1) } x nvar  [ LIST(ndual) { FORM(1) VAL } x ndual ]
+ *           | NIL
+ * New parameter (integrer.c:171-180): n == P, every denominator 1, D > 0; its value is floor((sum c_j theta_j + c) / D),
+ * a true floor, in scope for the one item behind it (the second item of an enclosing IF starts from the IF's own P
+ * again).  Condition (traiter.c:719-737): one positive denominator; the first item is taken when
+ * sum n_j theta_j + n_c >= 0 (0 included), the second otherwise.  Leaf (traiter.c:262-268, 282-290): per unknown the
+ * parameters' coefficients, then the constant, over one positive denominator D_i; unknown i is N / D_i with
+ * N = sum n_j theta_j + n_c, handed out in lowest terms -- g = gcd(|N|, D_i): (N / g, D_i / g), (0, 1) for N == 0.  With
+ * ndual > 0 a second list of ndual constants follows (PIPAMD_T_DUAL), handed out in lowest terms too.  An empty tape is
+ * the front ends' "void".
+ * Arithmetic.  int64 cells: every sum n_j theta_j + n_c is formed exactly, whatever single products or partial sums do;
+ * a point at which a new parameter's value or a numerator in lowest terms does not fit int64 ends PIPAMD_ST_RANGE.
+ * 128-bit cells: points are int64, new parameters and results __int128; the products and the running sums of a form
+ * are checked against 128 bits in cell order -- coefficients 0 .. P-1, then the constant -- and the first that leaves
+ * them ends the point PIPAMD_ST_RANGE.  Such a point does not disturb the others of the call.
+ * NOT done here, the caller's business: the evaluator knows no context -- points outside the context the problem was
+ * solved under, or negative ones, are evaluated like any other, as pipamd_batch_load_instances solves them; a big
+ * parameter is just another column of the points; and the edits pip_solve makes to its result (sol_quast_edit with
+ * sol_bg, urs_parms and the SOL_MAX / SOL_SHIFT bits of pipamd_pip_info) are not applied: a tape of
+ * pipamd_pip_solve_many qualifies only when its problem has no big parameter and no Urs_parms.
+ * Limits.  PIPAMD_TAPE_MAX_SLOTS: the largest P + 1 of a tape, the root's nparm + 1 included (the kernel keeps a
+ * workgroup's parameters in scope in LDS: 128 points x (slots - 1) values).  The compiled program must stay below 2^31
+ * words.  The program is staged in LDS when 8 * info.words + 128 * (info.slots - 1) * (8 or 16 bytes per value) is at
+ * most PIPAMD_TAPE_LDS_BYTES, and read from global memory otherwise (info.staged says which). */
+#define PIPAMD_TAPE_MAX_SLOTS 32
+#define PIPAMD_TAPE_LDS_BYTES 65536
+typedef struct pipamd_tape_shape {
+  int32_t nvar;     /* forms of a solution list */
+  int32_t nparm;    /* parameters of the problem = values of a point */
+  int32_t ndual;    /* forms of the dual list behind every solution list (the tableau's inequalities); 0: none */
+  int32_t reserved; /* 0 */
+} pipamd_tape_shape;
+typedef struct pipamd_tape_info {
+  int64_t leaves; /* LIST (solution lists) and NIL items; pipamd_tape_eval's d_leaf counts them in tape order from 0 */
+  int64_t ifs;    /* IF cells */
+  int64_t news;   /* NEW cells */
+  int64_t words;  /* 8-byte words of the compiled program (csrc/pip_tape.h) */
+  int32_t slots;  /* the largest P + 1 of any item, at least nparm + 1 */
+  int32_t depth;  /* items nested: 1 for the root, one more for the items of an IF and the item behind a NEW; 0: empty */
+  int32_t staged; /* 1: the kernel copies the program to LDS; 0: it reads it from global memory (or there is none) */
+  int32_t reserved;
+} pipamd_tape_info; /* 48 bytes, offsets 0 8 16 24 32 36 40 44 */
+/* Validates a tape against the grammar and fills *info (which may be NULL).  Host only: needs neither an engine nor a
+ * GPU.  PIPAMD_E_INVALID: a null shape, or null cells with n_cells > 0; a negative count or reserved != 0 in the shape; a
+ * cell of unknown kind, or of another kind than the grammar has in its place; a truncated tape; cells behind the end of
+ * the root item; a FORM whose length is not P + 1 (1 in a dual list); a LIST whose length is not nvar (ndual for the
+ * second); no second LIST with ndual > 0 (one with ndual == 0 is read as the next item); NEW(n) with n != P; a
+ * denominator <= 0; unequal denominators within a form; a DIV form or divisor with a denominator other than 1;
+ * D <= 0.  PIPAMD_E_TOOLARGE: more than PIPAMD_TAPE_MAX_SLOTS slots, or a program of 2^31 words or more.  The empty
+ * tape (n_cells == 0) is valid. */
+int pipamd_tape_check(const pipamd_sol_cell *cells, size_t n_cells, const pipamd_tape_shape *shape, pipamd_tape_info *info);
+int pipamd_tape_check128(const pipamd_sol_cell128 *cells, size_t n_cells, const pipamd_tape_shape *shape,
+                         pipamd_tape_info *info);
+/* The same check, then the tape as a flat program in the memory of the engine's device: nodes in tape order, their
+ * coefficients beside them, every jump strictly forward and inside the program -- the kernel cannot loop or read outside
+ * it, whatever the points are.  The cells are not needed afterwards.  PIPAMD_E_INVALID before any HIP call: a null
+ * engine or `out`, and whatever pipamd_tape_check refuses.  Free with pipamd_tape_free (NULL is allowed); a tape must
+ * not outlive evaluations still running on a stream. */
+typedef struct pipamd_tape pipamd_tape;
+int pipamd_tape_compile(pipamd_engine *e, const pipamd_sol_cell *cells, size_t n_cells, const pipamd_tape_shape *shape,
+                        pipamd_tape **out);
+int pipamd_tape_compile128(pipamd_engine *e, const pipamd_sol_cell128 *cells, size_t n_cells, const pipamd_tape_shape *shape,
+                           pipamd_tape **out);
+void pipamd_tape_free(pipamd_tape *t);
+/* The tape at n_points points: d_points is n_points x nparm int64 (may be NULL when nparm == 0).  Each of the six
+ * outputs may be NULL.  d_status[k]: PIPAMD_ST_SOLUTION, PIPAMD_ST_NIL (a NIL item; every point of an empty tape) or
+ * PIPAMD_ST_RANGE.  d_leaf[k]: the ordinal, in tape order, of the LIST or NIL item reached; -1 for an empty tape and a
+ * RANGE point.  d_x_num / d_x_den: n_points x nvar, d_dual_num / d_dual_den: n_points x ndual -- int64 values, or
+ * little-endian (low, high) int64 pairs for a tape of 128-bit cells; a point that is not PIPAMD_ST_SOLUTION gets (0, 0)
+ * throughout.  One launch on `stream`, no synchronisation, like pipamd_batch_results; n_points == 0 is PIPAMD_OK without
+ * a launch.  The tape is not changed: it may be evaluated any number of times, on any stream of its device, also
+ * concurrently.  PIPAMD_E_INVALID before any HIP call: a null engine or tape, a tape of another device than the
+ * engine's, n_points < 0, null d_points with nparm > 0 and n_points > 0.  PIPAMD_E_TOOLARGE: n_points of 2^38 and more. */
+int pipamd_tape_eval(pipamd_engine *e, const pipamd_tape *t, int64_t n_points, const int64_t *d_points, int32_t *d_status,
+                     int32_t *d_leaf, int64_t *d_x_num, int64_t *d_x_den, int64_t *d_dual_num, int64_t *d_dual_den,
+                     void *stream);
 
 #ifdef __cplusplus
 }

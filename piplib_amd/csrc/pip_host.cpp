@@ -9,6 +9,8 @@
 #include <string.h>
 #include <time.h>
 
+#include <vector>
+
 #include "pip_host.h"
 
 static thread_local char g_err[512];
@@ -1155,6 +1157,353 @@ extern "C" int pipamd_batch_dual_matrices_part(pipamd_engine *e, const void *d_w
 extern "C" int pipamd_batch_dual_matrices(pipamd_engine *e, const void *d_ws, const pipamd_batch_desc *d, const pipamd_matrices *m,
                                           const int64_t *d_rows, int64_t *d_dual_num, int64_t *d_dual_den, void *stream) {
   return pipamd_batch_dual_matrices_part(e, d_ws, d, m, d_rows, 0, d ? d->batch : 0, d_dual_num, d_dual_den, stream);
+}
+
+// ------------------------------------------------------------------ tapes at parameter points
+// (header comment: include/piplib_amd.h; the program: pip_tape.h.)  One walk over the cells serves the check and the
+// compile: it validates the grammar, counts, and -- given a vector -- emits the program.  The walk keeps its own stack of
+// items still to come (an IF pushes its two, a NEW the one behind it), so a deep tape costs heap, not the thread's stack.
+typedef __int128 tape_int;
+static inline tape_int tape_p1(const pipamd_sol_cell &c) { return c.param1; }
+static inline tape_int tape_p2(const pipamd_sol_cell &c) { return c.param2; }
+static inline tape_int tape_wide(int64_t lo, int64_t hi) { return (tape_int)(((unsigned __int128)(uint64_t)hi << 64) | (uint64_t)lo); }
+static inline tape_int tape_p1(const pipamd_sol_cell128 &c) { return tape_wide(c.param1_lo, c.param1_hi); }
+static inline tape_int tape_p2(const pipamd_sol_cell128 &c) { return tape_wide(c.param2_lo, c.param2_hi); }
+
+template <class Cell>
+struct TapeWalk {
+  enum { EW = sizeof(Cell) == sizeof(pipamd_sol_cell) ? 1 : 2 };
+  const Cell *cells;
+  size_t n, pos = 0;
+  std::vector<long long> *prog;  // null: check only
+  long long words = 0;
+  const char *why = nullptr;
+
+  bool fail(const char *w) {
+    if (!why) why = w;
+    return false;
+  }
+  void emit_word(long long w) {
+    if (prog) prog->push_back(w);
+    words++;
+  }
+  void emit(tape_int v) {
+    emit_word((long long)(uint64_t)(unsigned __int128)v);
+    if (EW == 2) emit_word((long long)(uint64_t)((unsigned __int128)v >> 64));
+  }
+  const Cell *take(int kind, const char *w) {
+    if (pos >= n || cells[pos].kind != kind) {
+      fail(w);
+      return nullptr;
+    }
+    return &cells[pos++];
+  }
+  // FORM(len) and its VALs: one positive denominator (1 if `one`); the numerators are emitted, *den gets the denominator
+  bool form(int64_t len, bool one, tape_int *den, const char *w) {
+    const Cell *f = take(PIPAMD_SOL_FORM, w);
+    if (!f) return false;
+    if (tape_p1(*f) != (tape_int)len) return fail(w);
+    tape_int d = 1;
+    for (int64_t j = 0; j < len; j++) {
+      const Cell *v = take(PIPAMD_SOL_VAL, w);
+      if (!v) return false;
+      if (j == 0) d = tape_p2(*v);
+      if (tape_p2(*v) != d || d <= 0 || (one && d != 1)) return fail(w);
+      emit(tape_p1(*v));
+    }
+    *den = d;
+    return true;
+  }
+};
+
+static unsigned __int128 tape_gcd(unsigned __int128 x, unsigned __int128 y) {
+  while (y) {
+    const unsigned __int128 r = x % y;
+    x = y;
+    y = r;
+  }
+  return x;
+}
+
+template <class Cell>
+static int tape_walk(const char *who, const Cell *cells, size_t n_cells, const pipamd_tape_shape *sh, pipamd_tape_info *info,
+                     std::vector<long long> *prog) {
+  if (!sh || (!cells && n_cells > 0)) {
+    pipamd_set_error("%s: null shape, or null cells with n_cells > 0", who);
+    return PIPAMD_E_INVALID;
+  }
+  if (sh->nvar < 0 || sh->nparm < 0 || sh->ndual < 0 || sh->reserved != 0) {
+    pipamd_set_error("%s: negative count (nvar %d, nparm %d, ndual %d) or reserved (%d) not 0", who, sh->nvar, sh->nparm,
+                     sh->ndual, sh->reserved);
+    return PIPAMD_E_INVALID;
+  }
+  enum { EW = TapeWalk<Cell>::EW };
+  TapeWalk<Cell> w{cells, n_cells};
+  w.prog = prog;
+  struct Todo {
+    int64_t P;
+    int64_t depth;
+    long long patch;  // word of the IF header whose else item this is, or -1
+  };
+  std::vector<Todo> todo;
+  pipamd_tape_info I;
+  memset(&I, 0, sizeof I);
+  int64_t slots = (int64_t)sh->nparm + 1, depth = 0;
+  if (n_cells) todo.push_back({sh->nparm, 1, -1});
+  bool ok = true;
+  while (ok && !todo.empty()) {
+    const Todo t = todo.back();
+    todo.pop_back();
+    const int64_t P = t.P;
+    if (t.patch >= 0 && prog) (*prog)[t.patch] |= w.words << 32;
+    if (P + 1 > slots) slots = P + 1;
+    if (t.depth > depth) depth = t.depth;
+    if (w.pos >= w.n) {
+      ok = w.fail("truncated: an item is missing");
+      break;
+    }
+    // (P beyond the limit: the walk goes on to tell an invalid tape from a large one, but emits headers of a fixed P)
+    const int hp = P < TAPE_MAX_SLOTS ? (int)P : TAPE_MAX_SLOTS;
+    const Cell &c = cells[w.pos++];
+    tape_int den;
+    switch (c.kind) {
+      case PIPAMD_SOL_NEW: {
+        if (tape_p1(c) != (tape_int)P) {
+          ok = w.fail("newparm whose number is not the count of parameters in scope");
+          break;
+        }
+        w.emit_word(tape_header(TAPE_NEW, hp, 0));
+        const Cell *d = w.take(PIPAMD_SOL_DIV, "no div behind a newparm");
+        if (!d) {
+          ok = false;
+          break;
+        }
+        // the program has the divisor in front of the form: it is looked up behind the form's cells first
+        const size_t at = w.pos + (size_t)P + 2;
+        if (at >= w.n || cells[at].kind != PIPAMD_SOL_VAL || tape_p2(cells[at]) != 1 || tape_p1(cells[at]) <= 0) {
+          ok = w.fail("div: truncated, or a divisor that is not a positive integer");
+          break;
+        }
+        w.emit(tape_p1(cells[at]));
+        ok = w.form(P + 1, true, &den, "div: a form of P + 1 integers is expected");
+        if (!ok) break;
+        w.pos++;  // the divisor
+        I.news++;
+        todo.push_back({P + 1, t.depth + 1, -1});
+        break;
+      }
+      case PIPAMD_SOL_IF: {
+        const long long at = w.words;
+        w.emit_word(tape_header(TAPE_IF, hp, 0));
+        ok = w.form(P + 1, false, &den, "if: a form of P + 1 values over one positive denominator is expected");
+        if (!ok) break;
+        I.ifs++;
+        todo.push_back({P, t.depth + 1, at});
+        todo.push_back({P, t.depth + 1, -1});
+        break;
+      }
+      case PIPAMD_SOL_LIST: {
+        if (tape_p1(c) != (tape_int)sh->nvar) {
+          ok = w.fail("a solution list whose length is not nvar");
+          break;
+        }
+        w.emit_word(tape_header(TAPE_LEAF, hp, I.leaves));
+        for (int i = 0; ok && i < sh->nvar; i++) {
+          // the denominator goes in front of its numerators: a place is kept, the form emitted, the place filled
+          const size_t at = prog ? prog->size() : 0;
+          w.emit(0);
+          ok = w.form(P + 1, false, &den, "list: forms of P + 1 values over one positive denominator are expected");
+          if (ok && prog) {
+            (*prog)[at] = (long long)(uint64_t)(unsigned __int128)den;
+            if (EW == 2) (*prog)[at + 1] = (long long)(uint64_t)((unsigned __int128)den >> 64);
+          }
+        }
+        if (!ok) break;
+        if (sh->ndual > 0) {
+          const Cell *l = w.take(PIPAMD_SOL_LIST, "no dual list behind a solution list");
+          if (!l || tape_p1(*l) != (tape_int)sh->ndual) {
+            ok = w.fail("a dual list whose length is not ndual");
+            break;
+          }
+          for (int i = 0; ok && i < sh->ndual; i++) {
+            const Cell *f = w.take(PIPAMD_SOL_FORM, "dual list: forms of one value are expected");
+            const Cell *v = f && tape_p1(*f) == 1 ? w.take(PIPAMD_SOL_VAL, "dual list: forms of one value are expected") : nullptr;
+            if (!v || tape_p2(*v) <= 0) {
+              ok = w.fail("dual list: forms of one value over a positive denominator are expected");
+              break;
+            }
+            const tape_int num = tape_p1(*v), dd = tape_p2(*v);
+            const unsigned __int128 mag = num < 0 ? (unsigned __int128)0 - (unsigned __int128)num : (unsigned __int128)num;
+            const unsigned __int128 g = tape_gcd(mag, (unsigned __int128)dd);
+            const unsigned __int128 q = mag / g;
+            w.emit(num < 0 ? (tape_int)((unsigned __int128)0 - q) : (tape_int)q);
+            w.emit((tape_int)((unsigned __int128)dd / g));
+          }
+          if (!ok) break;
+        }
+        I.leaves++;
+        break;
+      }
+      case PIPAMD_SOL_NIL:
+        w.emit_word(tape_header(TAPE_NIL, hp, I.leaves));
+        I.leaves++;
+        break;
+      default:
+        ok = w.fail("a cell of a kind that cannot start an item");
+    }
+    if (w.words >= (1ll << 31)) break;
+  }
+  if (ok && w.words < (1ll << 31) && w.pos != w.n) ok = w.fail("cells behind the end of the root item");
+  if (!ok) {
+    pipamd_set_error("%s: cell %zu of %zu: %s", who, w.pos, n_cells, w.why ? w.why : "invalid tape");
+    return PIPAMD_E_INVALID;
+  }
+  if (slots > TAPE_MAX_SLOTS || w.words >= (1ll << 31)) {
+    pipamd_set_error("%s: %lld slots (at most %d), or a program of 2^31 words or more", who, (long long)slots, TAPE_MAX_SLOTS);
+    return PIPAMD_E_TOOLARGE;
+  }
+  I.words = w.words;
+  I.slots = (int32_t)slots;
+  I.depth = (int32_t)depth;
+  const int bits = 64 * EW;
+  I.staged = n_cells > 0 && 8 * (size_t)w.words + tape_slot_bytes(I.slots, bits) <= (size_t)TAPE_LDS_BYTES;
+  if (info) *info = I;
+  return PIPAMD_OK;
+}
+
+struct pipamd_tape {
+  int device, bits;
+  pipamd_tape_shape shape;
+  pipamd_tape_info info;
+  long long *d_prog;
+};
+
+extern "C" int pipamd_tape_check(const pipamd_sol_cell *cells, size_t n_cells, const pipamd_tape_shape *shape,
+                                 pipamd_tape_info *info) {
+  return tape_walk("tape_check", cells, n_cells, shape, info, nullptr);
+}
+extern "C" int pipamd_tape_check128(const pipamd_sol_cell128 *cells, size_t n_cells, const pipamd_tape_shape *shape,
+                                    pipamd_tape_info *info) {
+  return tape_walk("tape_check128", cells, n_cells, shape, info, nullptr);
+}
+
+template <class Cell>
+static int tape_compile(const char *who, pipamd_engine *e, const Cell *cells, size_t n_cells, const pipamd_tape_shape *shape,
+                        pipamd_tape **out) {
+  if (!e || !out) {
+    pipamd_set_error("%s: null engine or result pointer", who);
+    return PIPAMD_E_INVALID;
+  }
+  *out = nullptr;
+  pipamd_tape_info info;
+  int rc = tape_walk(who, cells, n_cells, shape, &info, nullptr);
+  if (rc) return rc;
+  std::vector<long long> prog;
+  prog.reserve((size_t)info.words);
+  rc = tape_walk(who, cells, n_cells, shape, &info, &prog);
+  if (rc) return rc;
+  if ((long long)prog.size() != info.words) {
+    pipamd_set_error("%s: internal: %zu words emitted, %lld counted", who, prog.size(), (long long)info.words);
+    return PIPAMD_E_INVALID;
+  }
+  // the promise to the kernel, held against the words themselves: every else target behind its IF and inside the program
+  for (long long pc = 0; pc < info.words;) {
+    const long long hdr = prog[pc];
+    const int op = (int)(hdr & 0xff), P = (int)((hdr >> 8) & 0xffff);
+    const long long aux = hdr >> 32;
+    const int ew = sizeof(Cell) == sizeof(pipamd_sol_cell) ? 1 : 2;
+    long long len = 1;
+    if (op == TAPE_NEW) len += ew * (P + 2);
+    else if (op == TAPE_IF) len += ew * (P + 1);
+    else if (op == TAPE_LEAF) len += ew * ((long long)shape->nvar * (P + 2) + 2ll * shape->ndual);
+    if ((op != TAPE_NEW && op != TAPE_IF && op != TAPE_LEAF && op != TAPE_NIL) || P + 1 > info.slots || pc + len > info.words ||
+        (op == TAPE_IF && (aux < pc + len || aux >= info.words)) || ((op == TAPE_NEW || op == TAPE_IF) && pc + len >= info.words)) {
+      pipamd_set_error("%s: internal: word %lld of the program breaks the kernel's contract", who, pc);
+      return PIPAMD_E_INVALID;
+    }
+    pc += len;
+  }
+  if (hipSetDevice(e->device) != hipSuccess) return PIPAMD_E_HIP;
+  pipamd_tape *t = (pipamd_tape *)calloc(1, sizeof *t);
+  if (!t) return PIPAMD_E_NOMEM;
+  t->device = e->device;
+  t->bits = sizeof(Cell) == sizeof(pipamd_sol_cell) ? 64 : 128;
+  t->shape = *shape;
+  t->info = info;
+  if (info.words) {
+    hipError_t he = hipMalloc((void **)&t->d_prog, (size_t)info.words * 8);
+    if (he == hipSuccess) he = hipMemcpy(t->d_prog, prog.data(), (size_t)info.words * 8, hipMemcpyHostToDevice);
+    if (he != hipSuccess) {
+      pipamd_set_error("%s: the program's %lld words on the device: %s", who, (long long)info.words, hipGetErrorString(he));
+      if (t->d_prog) hipFree(t->d_prog);
+      free(t);
+      return PIPAMD_E_HIP;
+    }
+  }
+  *out = t;
+  return PIPAMD_OK;
+}
+
+extern "C" int pipamd_tape_compile(pipamd_engine *e, const pipamd_sol_cell *cells, size_t n_cells, const pipamd_tape_shape *shape,
+                                   pipamd_tape **out) {
+  return tape_compile("tape_compile", e, cells, n_cells, shape, out);
+}
+extern "C" int pipamd_tape_compile128(pipamd_engine *e, const pipamd_sol_cell128 *cells, size_t n_cells,
+                                      const pipamd_tape_shape *shape, pipamd_tape **out) {
+  return tape_compile("tape_compile128", e, cells, n_cells, shape, out);
+}
+
+extern "C" void pipamd_tape_free(pipamd_tape *t) {
+  if (!t) return;
+  if (t->d_prog && hipSetDevice(t->device) == hipSuccess) hipFree(t->d_prog);
+  free(t);
+}
+
+// Testing aid: the words of a compiled tape's program, copied back from its device (tests hold them unchanged by
+// evaluations).  host_out may be NULL to ask for the count alone; the copy waits for the device.
+extern "C" int pipamd_debug_tape_program(const pipamd_tape *t, int64_t *host_out, int64_t cap, int64_t *words) {
+  if (!t || !words || (host_out && cap < t->info.words)) return PIPAMD_E_INVALID;
+  *words = t->info.words;
+  if (host_out && t->info.words) {
+    if (hipSetDevice(t->device) != hipSuccess) return PIPAMD_E_HIP;
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(host_out, t->d_prog, (size_t)t->info.words * 8, hipMemcpyDeviceToHost));
+  }
+  return PIPAMD_OK;
+}
+
+extern "C" int pipamd_tape_eval(pipamd_engine *e, const pipamd_tape *t, int64_t n_points, const int64_t *d_points,
+                                int32_t *d_status, int32_t *d_leaf, int64_t *d_x_num, int64_t *d_x_den, int64_t *d_dual_num,
+                                int64_t *d_dual_den, void *stream) {
+  if (!e || !t || n_points < 0 || t->device != e->device || (n_points > 0 && t->shape.nparm > 0 && !d_points)) {
+    pipamd_set_error("tape_eval: null engine or tape, a tape of another device, n_points < 0, or parameters without points");
+    return PIPAMD_E_INVALID;
+  }
+  if (n_points >= (1ll << 38)) {
+    pipamd_set_error("tape_eval: %lld points, at most 2^38 - 1 a call", (long long)n_points);
+    return PIPAMD_E_TOOLARGE;
+  }
+  if (n_points == 0) return PIPAMD_OK;
+  if (hipSetDevice(e->device) != hipSuccess) return PIPAMD_E_HIP;
+  TapeLaunch L;
+  L.prog = t->d_prog;
+  L.words = t->info.words;
+  L.bits = t->bits;
+  L.staged = t->info.staged;
+  L.nvar = t->shape.nvar;
+  L.nparm = t->shape.nparm;
+  L.ndual = t->shape.ndual;
+  L.slots = t->info.slots;
+  L.n_points = n_points;
+  L.points = (const long long *)d_points;
+  L.status = d_status;
+  L.leaf = d_leaf;
+  L.x_num = d_x_num;
+  L.x_den = d_x_den;
+  L.dual_num = d_dual_num;
+  L.dual_den = d_dual_den;
+  HIPCHK(pipk_launch_tape_eval(&L, (hipStream_t)stream));
+  return PIPAMD_OK;
 }
 
 extern "C" int pipamd_batch_counters(pipamd_engine *e, const void *d_ws, const pipamd_batch_desc *d, uint64_t *d_out4,

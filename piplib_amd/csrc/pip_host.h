@@ -5,6 +5,7 @@
 #include <pthread.h>
 
 #include "pip_job.h"
+#include "pip_tape.h"
 
 #define PIPAMD_MAX_ROUNDS 512
 #define PIPAMD_MAX_GROW 24 /* growth rounds of one solve: the row capacity at least doubles per round, up to PIPAMD_SMAX */

@@ -1,0 +1,46 @@
+// piplib_amd/csrc/pip_tape.h -- a solution tape evaluated at many parameter points (pip_tape.hip): the compiled program
+// and the launch interface.
+//
+// pipamd_tape_compile (pip_host.cpp) turns a checked tape into a flat program of 8-byte words, nodes in tape order.  A
+// value takes EW words, 1 for int64 cells and 2 (low, high) for 128-bit cells.  A node is a header word
+//     bits 0-7 the TAPE_* operation | bits 8-23 P, the parameters in scope | bits 32-62 aux
+// followed by its values:
+//     TAPE_NEW   aux 0              D, c_0 .. c_P            slot P = floor((sum c_j slot_j + c_P) / D); the next node follows
+//     TAPE_IF    aux the else node  n_0 .. n_P               sum n_j slot_j + n_P >= 0: the next node, otherwise word aux
+//     TAPE_LEAF  aux its ordinal    nvar x (D_i, n_0 .. n_P), then ndual x (numerator, denominator) in lowest terms
+//     TAPE_NIL   aux its ordinal
+// The host writes aux of an IF only behind the node's own words and within the program, and every other node either
+// ends the walk or is followed by the next one: a point's position only grows, so the kernel ends after at most as many
+// steps as the program has nodes and reads nothing outside it, whatever the points are.
+#ifndef PIP_TAPE_H
+#define PIP_TAPE_H
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+
+enum { TAPE_NIL = 1, TAPE_IF = 2, TAPE_LEAF = 3, TAPE_NEW = 5 };
+enum {
+  TAPE_BLOCK = 128,       // points per workgroup, a lane each
+  TAPE_MAX_SLOTS = 32,    // PIPAMD_TAPE_MAX_SLOTS: the largest P + 1 served
+  TAPE_LDS_BYTES = 65536  // PIPAMD_TAPE_LDS_BYTES: parameters in scope, and the program when it fits beside them
+};
+// bytes of LDS the parameters in scope take: a row of TAPE_BLOCK values per parameter, slots - 1 of them
+static inline size_t tape_slot_bytes(int slots, int bits) { return (size_t)(slots - 1) * TAPE_BLOCK * (bits / 8); }
+static inline long long tape_header(int op, int P, long long aux) { return (long long)op | ((long long)P << 8) | (aux << 32); }
+
+struct TapeLaunch {
+  const long long *prog;  // device; `words` words
+  long long words;        // 0: the empty tape
+  int bits;               // 64 or 128
+  int staged;             // 1: the program is copied to LDS first; 0: read from global memory
+  int nvar, nparm, ndual;
+  int slots;              // pipamd_tape_info.slots
+  long long n_points;
+  const long long *points;
+  int *status, *leaf;
+  void *x_num, *x_den, *dual_num, *dual_den;
+};
+
+extern "C" {
+hipError_t pipk_launch_tape_eval(const TapeLaunch *t, hipStream_t stream);
+}
+#endif

@@ -1,0 +1,308 @@
+// piplib_amd/csrc/pip_tape.hip -- pipamd_tape_eval: a compiled solution tape (pip_tape.h) walked at many parameter
+// points, one lane per point.
+//
+// A workgroup is TAPE_BLOCK lanes.  The parameters in scope of a lane -- its point's, then the new ones it computes
+// (integrer.c:171-180) -- live in LDS, the slot the slow index and the lane the fast one: slot j of lane t is word
+// j * TAPE_BLOCK + t (128-bit values: the low words of a slot in one row, the high words in the next), so the 8-byte
+// accesses of neighbouring lanes fall on neighbouring banks and no lane holds an array it indexes at run time.  The
+// program is staged behind the slots when both fit TAPE_LDS_BYTES (STAGED) and read from global memory otherwise.
+//
+// Lanes of a wave end up at different nodes.  A position only grows (pip_tape.h), so a wave serves, in every step, the
+// LOWEST position any of its lanes is at: the lanes there execute the node, the others wait.  The node's words are then
+// the same address for every lane -- a broadcast LDS read, or a scalar load --, a wave executes each node at most once,
+// and lanes that took different branches meet again at the first node they share.
+//
+// Arithmetic.  int64 cells: sum c_j theta_j + c is formed exactly -- a product of two int64 values is below 2^126; its
+// signed high and unsigned low halves are summed apart (at most TAPE_MAX_SLOTS terms, nothing wraps) and joined at the
+// end, as inst_constant does in pip_kernels.hip.  A condition needs the sign alone; a new parameter, and a numerator in
+// lowest terms, must fit int64 (PIPAMD_ST_RANGE otherwise).  128-bit cells: every product and every running sum is
+// checked against 128 bits in cell order, exactly, and the first that leaves them ends the point.
+#include <hip/hip_runtime.h>
+
+#include "../../include/piplib_amd.h"
+#include "pip_tape.h"
+
+namespace {
+typedef long long i64;
+typedef unsigned long long u64;
+typedef __int128 i128;
+typedef unsigned __int128 u128;
+
+enum { END = 0x7fffffff };
+
+__device__ __forceinline__ bool fits64(i128 v) { return (i128)(i64)v == v; }
+__device__ __forceinline__ u128 uabs(i128 v) { return v < 0 ? (u128)0 - (u128)v : (u128)v; }
+__device__ __forceinline__ int ubits(u128 u) {
+  const u64 h = (u64)(u >> 64), l = (u64)u;
+  return h ? 128 - __clzll((i64)h) : (l ? 64 - __clzll((i64)l) : 0);
+}
+// a / b and a % b, b > 0: operands of 64 bits divide natively, wider ones by shift and subtract over the difference of
+// the bit lengths.  64-bit division is a long sequence: one copy, out of line, values in registers both ways.
+struct DivMod {
+  u128 q, r;
+};
+__device__ __noinline__ DivMod udivmod(u128 a, u128 b) {
+  DivMod o;
+  if (((a | b) >> 64) == 0) {
+    const u64 q = (u64)a / (u64)b;
+    o.q = q;
+    o.r = (u64)a - q * (u64)b;
+    return o;
+  }
+  u128 q = 0;
+  if (a >= b) {
+    int sh = ubits(a) - ubits(b);
+    u128 d = b << sh;
+    for (; sh >= 0; sh--) {
+      q <<= 1;
+      if (a >= d) {
+        a -= d;
+        q |= 1;
+      }
+      d >>= 1;
+    }
+  }
+  o.q = q;
+  o.r = a;
+  return o;
+}
+__device__ __forceinline__ u128 ugcd(u128 x, u128 y) {  // gcd(0, y) = y
+  while (y) {
+    const u128 r = udivmod(x, y).r;
+    x = y;
+    y = r;
+  }
+  return x;
+}
+// a * b in 128 bits; true where the product leaves them (exact: the magnitudes' halves)
+__device__ __forceinline__ bool mul_leaves128(i128 a, i128 b, i128 *r) {
+  if (fits64(a) && fits64(b)) {
+    *r = a * b;
+    return false;
+  }
+  const u128 ua = uabs(a), ub = uabs(b);
+  const u64 ah = (u64)(ua >> 64), al = (u64)ua, bh = (u64)(ub >> 64), bl = (u64)ub;
+  *r = 0;
+  if (ah && bh) return true;
+  const u128 cross = ah ? (u128)ah * bl : (u128)bh * al;
+  if (cross >> 64) return true;
+  const u128 low = (u128)al * bl, m = low + (cross << 64);
+  if (m < low) return true;
+  if ((a < 0) != (b < 0)) {
+    if (m > ((u128)1 << 127)) return true;
+    *r = (i128)((u128)0 - m);
+  } else {
+    if (m >> 127) return true;
+    *r = (i128)m;
+  }
+  return false;
+}
+
+template <class T>
+struct Width;
+template <>
+struct Width<i64> {
+  enum { EW = 1 };
+  static __device__ __forceinline__ i64 slot(const i64 *S, int j, int tid) { return S[j * TAPE_BLOCK + tid]; }
+  static __device__ __forceinline__ void set_slot(i64 *S, int j, int tid, i64 v) { S[j * TAPE_BLOCK + tid] = v; }
+  static __device__ __forceinline__ i64 word(const i64 *p, int k) { return p[k]; }
+  static __device__ __forceinline__ void out(void *a, i64 at, i64 v) { ((i64 *)a)[at] = v; }
+  static __device__ __forceinline__ bool fits(u128 mag, bool neg) { return neg ? mag <= ((u128)1 << 63) : (mag >> 63) == 0; }
+};
+template <>
+struct Width<i128> {
+  enum { EW = 2 };
+  static __device__ __forceinline__ i128 slot(const i64 *S, int j, int tid) {
+    return (i128)(((u128)(u64)S[(2 * j + 1) * TAPE_BLOCK + tid] << 64) | (u64)S[2 * j * TAPE_BLOCK + tid]);
+  }
+  static __device__ __forceinline__ void set_slot(i64 *S, int j, int tid, i128 v) {
+    S[2 * j * TAPE_BLOCK + tid] = (i64)(u64)(u128)v;
+    S[(2 * j + 1) * TAPE_BLOCK + tid] = (i64)(u64)((u128)v >> 64);
+  }
+  static __device__ __forceinline__ i128 word(const i64 *p, int k) { return (i128)(((u128)(u64)p[2 * k + 1] << 64) | (u64)p[2 * k]); }
+  static __device__ __forceinline__ void out(void *a, i64 at, i128 v) {
+    ((i64 *)a)[2 * at] = (i64)(u64)(u128)v;
+    ((i64 *)a)[2 * at + 1] = (i64)(u64)((u128)v >> 64);
+  }
+  static __device__ __forceinline__ bool fits(u128 mag, bool neg) { return neg ? mag <= ((u128)1 << 127) : (mag >> 127) == 0; }
+};
+
+// sum n_j slot_j + n_P of the P + 1 values at `f`.  ok: the value is `v` (int64 cells: it fits 128 bits; 128-bit cells:
+// no product and no running sum left them); neg: its sign (int64 cells: exact even where !ok)
+struct FormValue {
+  i128 v;
+  bool ok, neg;
+};
+__device__ __forceinline__ FormValue form_value(const i64 *f, int P, const i64 *S, int tid, i64 *) {
+  i128 hi = 0;
+  u128 lo = 0;
+  for (int j = 0; j < P; j++) {
+    const i128 p = (i128)f[j] * (i128)S[j * TAPE_BLOCK + tid];
+    hi += (i128)(i64)(p >> 64);
+    lo += (u128)(u64)(u128)p;
+  }
+  const i64 c = f[P];
+  hi += (i128)(c >> 63);
+  lo += (u128)(u64)c;
+  hi += (i128)(u64)(lo >> 64);
+  FormValue r;
+  r.ok = fits64(hi);
+  r.neg = hi < 0;
+  r.v = (i128)(((u128)hi << 64) | (u64)lo);
+  return r;
+}
+__device__ __forceinline__ FormValue form_value(const i64 *f, int P, const i64 *S, int tid, i128 *) {
+  i128 acc = 0;
+  bool bad = false;
+  for (int j = 0; j < P; j++) {
+    i128 p;
+    bad = bad || mul_leaves128(Width<i128>::word(f, j), Width<i128>::slot(S, j, tid), &p);
+    bad = bad || __builtin_add_overflow(acc, p, &acc);
+  }
+  bad = bad || __builtin_add_overflow(acc, Width<i128>::word(f, P), &acc);
+  FormValue r;
+  r.ok = !bad;
+  r.neg = acc < 0;
+  r.v = acc;
+  return r;
+}
+
+// floor(v / D), D > 0; false where it does not fit T
+template <class T>
+__device__ __forceinline__ bool floor_div(i128 v, T D, T *q) {
+  const DivMod d = udivmod(uabs(v), (u128)D);
+  const bool neg = v < 0;
+  const u128 uq = d.q + (neg && d.r ? 1 : 0);
+  if (!Width<T>::fits(uq, neg)) return false;
+  *q = neg ? (T)((u128)0 - uq) : (T)uq;
+  return true;
+}
+// N / D in lowest terms, D > 0 ((0, 1) for N == 0); false where the numerator does not fit T
+template <class T>
+__device__ __forceinline__ bool lowest_terms(i128 N, T D, T *num, T *den) {
+  const u128 mag = uabs(N), g = ugcd(mag, (u128)D);
+  const u128 qn = udivmod(mag, g).q, qd = udivmod((u128)D, g).q;
+  if (!Width<T>::fits(qn, N < 0)) return false;
+  *num = N < 0 ? (T)((u128)0 - qn) : (T)qn;
+  *den = (T)qd;
+  return true;
+}
+
+__device__ __forceinline__ int wave_min(int x) {
+  for (int o = 32; o; o >>= 1) {
+    const int y = __shfl_xor(x, o);
+    x = y < x ? y : x;
+  }
+  return __builtin_amdgcn_readfirstlane(x);
+}
+
+template <class T, bool STAGED>
+__global__ __launch_bounds__(TAPE_BLOCK) void pip_tape_eval_kernel(TapeLaunch a) {
+  typedef Width<T> W;
+  constexpr int EW = W::EW;
+  extern __shared__ __attribute__((aligned(16))) i64 tape_lds[];
+  i64 *S = tape_lds;  // (slots - 1) * EW rows of TAPE_BLOCK words
+  const int tid = threadIdx.x, nvar = a.nvar, ndual = a.ndual;
+  const i64 pt = (i64)blockIdx.x * TAPE_BLOCK + tid;
+  const bool live = pt < a.n_points;
+  const int words = (int)a.words;
+  const i64 *prog = a.prog;
+  if (STAGED) {
+    i64 *L = tape_lds + (size_t)(a.slots - 1) * EW * TAPE_BLOCK;
+    for (int i = tid; i < words; i += TAPE_BLOCK) L[i] = a.prog[i];
+    prog = L;
+  }
+  if (live)
+    for (int j = 0; j < a.nparm; j++) W::set_slot(S, j, tid, (T)a.points[pt * a.nparm + j]);
+  if (STAGED) __syncthreads();
+
+  int pc = live && words ? 0 : END;
+  int st = PIPAMD_ST_NIL, leaf = -1;
+  for (;;) {
+    const int cur = wave_min(pc);
+    if (cur == END) break;
+    const i64 hdr = prog[cur];
+    const int op = (int)(hdr & 0xff), P = (int)((hdr >> 8) & 0xffff), aux = (int)(hdr >> 32);
+    const i64 *body = prog + cur + 1;
+    if (pc != cur) {
+      // (this lane is further on: it waits for the wave to get there)
+    } else if (op == TAPE_NEW) {
+      const FormValue f = form_value(body + EW, P, S, tid, (T *)nullptr);
+      T q = 0;
+      if (f.ok && floor_div<T>(f.v, W::word(body, 0), &q)) {
+        W::set_slot(S, P, tid, q);
+        pc = cur + 1 + EW * (P + 2);
+      } else {
+        st = PIPAMD_ST_RANGE;
+        pc = END;
+      }
+    } else if (op == TAPE_IF) {
+      const FormValue f = form_value(body, P, S, tid, (T *)nullptr);
+      if (EW == 2 && !f.ok) {
+        st = PIPAMD_ST_RANGE;
+        pc = END;
+      } else {
+        pc = f.neg ? aux : cur + 1 + EW * (P + 1);
+      }
+    } else if (op == TAPE_LEAF) {
+      bool good = true;
+      for (int i = 0; i < nvar; i++) {
+        const i64 *u = body + (size_t)i * EW * (P + 2);
+        const FormValue f = form_value(u + EW, P, S, tid, (T *)nullptr);
+        T num = 0, den = 0;
+        good = good && f.ok && lowest_terms<T>(f.v, W::word(u, 0), &num, &den);
+        if (!good) break;
+        if (a.x_num) W::out(a.x_num, pt * nvar + i, num);
+        if (a.x_den) W::out(a.x_den, pt * nvar + i, den);
+      }
+      if (good) {
+        const i64 *d = body + (size_t)nvar * EW * (P + 2);
+        for (int i = 0; i < ndual; i++) {
+          if (a.dual_num) W::out(a.dual_num, pt * ndual + i, W::word(d, 2 * i));
+          if (a.dual_den) W::out(a.dual_den, pt * ndual + i, W::word(d, 2 * i + 1));
+        }
+        st = PIPAMD_ST_SOLUTION;
+        leaf = aux;
+      } else {
+        st = PIPAMD_ST_RANGE;
+      }
+      pc = END;
+    } else {  // TAPE_NIL
+      st = PIPAMD_ST_NIL;
+      leaf = aux;
+      pc = END;
+    }
+  }
+  if (!live) return;
+  if (a.status) a.status[pt] = st;
+  if (a.leaf) a.leaf[pt] = leaf;
+  if (st != PIPAMD_ST_SOLUTION) {  // (0, 0) throughout, also where a leaf's later unknown left the range
+    for (int i = 0; i < nvar; i++) {
+      if (a.x_num) W::out(a.x_num, pt * nvar + i, (T)0);
+      if (a.x_den) W::out(a.x_den, pt * nvar + i, (T)0);
+    }
+    for (int i = 0; i < ndual; i++) {
+      if (a.dual_num) W::out(a.dual_num, pt * ndual + i, (T)0);
+      if (a.dual_den) W::out(a.dual_den, pt * ndual + i, (T)0);
+    }
+  }
+}
+
+template <class T>
+hipError_t launch(const TapeLaunch &t, hipStream_t stream) {
+  const long long blocks = (t.n_points + TAPE_BLOCK - 1) / TAPE_BLOCK;
+  const size_t slot_bytes = tape_slot_bytes(t.slots, t.bits);
+  if (t.staged)
+    hipLaunchKernelGGL((pip_tape_eval_kernel<T, true>), dim3((unsigned)blocks), dim3(TAPE_BLOCK),
+                       slot_bytes + (size_t)t.words * 8, stream, t);
+  else
+    hipLaunchKernelGGL((pip_tape_eval_kernel<T, false>), dim3((unsigned)blocks), dim3(TAPE_BLOCK), slot_bytes, stream, t);
+  return hipGetLastError();
+}
+}  // namespace
+
+extern "C" hipError_t pipk_launch_tape_eval(const TapeLaunch *t, hipStream_t stream) {
+  if (t->n_points <= 0) return hipSuccess;
+  // (the caller checked: slots <= TAPE_MAX_SLOTS, and a staged program fits TAPE_LDS_BYTES beside the slots)
+  return t->bits == 128 ? launch<i128>(*t, stream) : launch<i64>(*t, stream);
+}

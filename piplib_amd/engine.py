@@ -1026,3 +1026,147 @@ def pip_solve_many(engine, problems, deepest_cut=False, nthreads=8, bits=64):
         got = take(cells[i], ncell[i])
         out.append((got if rcs[i] == 0 else None, rcs[i], sts[i], piv[i], prep.info[i].as_dict()))
     return out
+
+
+# ---------------------------------------------------------------- a tape at many parameter points
+class TapeShape(C.Structure):
+    """pipamd_tape_shape"""
+    _fields_ = [(n, C.c_int32) for n in ("nvar", "nparm", "ndual", "reserved")]
+
+
+class TapeInfo(C.Structure):
+    """pipamd_tape_info: what pipamd_tape_check counts"""
+    _fields_ = [(n, C.c_int64) for n in ("leaves", "ifs", "news", "words")] + \
+               [(n, C.c_int32) for n in ("slots", "depth", "staged", "reserved")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_ if n != "reserved"}
+
+
+class TapeError(RuntimeError):
+    """a tape pipamd_tape_check refuses: code is PIPAMD_E_INVALID (-1) or PIPAMD_E_TOOLARGE (-3)"""
+
+    def __init__(self, code, why):
+        super().__init__(f"piplib_amd error {code}: {why}")
+        self.code = code
+
+
+def _s64(v):
+    v &= (1 << 64) - 1
+    return v - (1 << 64) if v >> 63 else v
+
+
+def _cell_array(cells, bits):
+    """(kind, param1, param2) tuples as an array of pipamd_sol_cell / pipamd_sol_cell128 (None for no cells)"""
+    if bits not in (64, 128):
+        raise ValueError("bits is 64 or 128")
+    n = len(cells)
+    if n == 0:
+        return None
+    if bits == 128:
+        arr = (SolCell128 * n)()
+        for c, (k, a, b) in zip(arr, cells):
+            a, b = int(a), int(b)
+            if not (-(1 << 127) <= a < (1 << 127) and -(1 << 127) <= b < (1 << 127)):
+                raise OverflowError("a tape cell beyond 128 bits")
+            c.kind, c.p1lo, c.p1hi, c.p2lo, c.p2hi = int(k), _s64(a), a >> 64, _s64(b), b >> 64
+    else:
+        arr = (SolCell * n)()
+        for c, (k, a, b) in zip(arr, cells):
+            c.kind, c.param1, c.param2 = int(k), int(a), int(b)
+            if c.param1 != int(a) or c.param2 != int(b):
+                raise OverflowError("a tape cell beyond int64")
+    return arr
+
+
+def _tape_fn(name, bits):
+    L = lib()
+    name += "128" if bits == 128 else ""
+    if not hasattr(L, name):
+        raise RuntimeError(f"libpipamd has no {name}: rebuild the library")
+    return getattr(L, name)
+
+
+def tape_check(cells, nvar, nparm, ndual=0, bits=64, reserved=0):
+    """pipamd_tape_check / pipamd_tape_check128 on cells [(kind, param1, param2), ...]: the dict of pipamd_tape_info, or
+    TapeError where the tape is refused.  Host only: needs neither an engine nor a GPU."""
+    fn = _tape_fn("pipamd_tape_check", bits)
+    fn.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(TapeShape), C.POINTER(TapeInfo)]
+    arr = _cell_array(cells, bits)
+    info = TapeInfo()
+    rc = fn(arr, len(cells), C.byref(TapeShape(int(nvar), int(nparm), int(ndual), int(reserved))), C.byref(info))
+    if rc != 0:
+        raise TapeError(rc, lib().pipamd_last_error().decode())
+    return info.as_dict()
+
+
+class Tape:
+    """A solution tape compiled for one engine's device (pipamd_tape_compile), to be evaluated at parameter points
+    (pipamd_tape_eval): solve a parametric problem once -- solve_tableau_cells, traiter, traiter_many -- and ask for the
+    unknowns at as many points as needed.  The evaluator knows no context and applies none of pip_solve's result edits
+    (include/piplib_amd.h)."""
+    OUTPUTS = ("status", "leaf", "x_num", "x_den", "dual_num", "dual_den")
+
+    def __init__(self, engine, cells, nvar, nparm, ndual=0, bits=64):
+        import torch
+        self.torch = torch
+        self.e = engine
+        self.nvar, self.nparm, self.ndual, self.bits = int(nvar), int(nparm), int(ndual), int(bits)
+        self.info = tape_check(cells, nvar, nparm, ndual, bits)
+        fn = _tape_fn("pipamd_tape_compile", bits)
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(TapeShape), C.POINTER(C.c_void_p)]
+        self._h = C.c_void_p()
+        arr = _cell_array(cells, bits)
+        _check(fn(engine._h, arr, len(cells), C.byref(TapeShape(self.nvar, self.nparm, self.ndual, 0)), C.byref(self._h)))
+        self.dev = torch.device("cuda", engine.device)
+
+    def close(self):
+        if self._h:
+            lib().pipamd_tape_free.argtypes = [C.c_void_p]
+            lib().pipamd_tape_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _points(self, points):
+        """-> (count, device tensor or None)"""
+        t = self.torch
+        if isinstance(points, int):
+            assert self.nparm == 0, "a count stands for points only when the tape has no parameters"
+            return points, None
+        points = (points if t.is_tensor(points) else t.as_tensor(points, dtype=t.int64)).to(device=self.dev, dtype=t.int64)
+        points = points.reshape(points.shape[0], self.nparm).contiguous()
+        return int(points.shape[0]), (points if self.nparm else None)
+
+    def outputs(self, n, names=OUTPUTS):
+        """fresh device tensors for `n` points: int32 status and leaf, int64 (n, nvar) / (n, ndual) values with a trailing
+        2 -- (low, high) -- for 128-bit tapes"""
+        t = self.torch
+        ew = (2,) if self.bits == 128 else ()
+        shapes = {"status": ((n,), t.int32), "leaf": ((n,), t.int32), "x_num": ((n, self.nvar) + ew, t.int64),
+                  "x_den": ((n, self.nvar) + ew, t.int64), "dual_num": ((n, self.ndual) + ew, t.int64),
+                  "dual_den": ((n, self.ndual) + ew, t.int64)}
+        return {k: t.empty(shapes[k][0], dtype=shapes[k][1], device=self.dev) for k in names}
+
+    def eval_into(self, points, out, stream=None):
+        """pipamd_tape_eval into the tensors of `out`, a dict by the names of OUTPUTS; a name that is missing is passed
+        as NULL.  One launch on `stream` (a raw hipStream_t handle; default: torch's current stream), no synchronisation."""
+        n, pts = self._points(points)
+        fn = lib().pipamd_tape_eval
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 8
+        st = C.c_void_p(stream) if stream is not None else C.c_void_p(self.torch.cuda.current_stream(self.dev).cuda_stream)
+        ptrs = [C.c_void_p(out[k].data_ptr()) if out.get(k) is not None else None for k in self.OUTPUTS]
+        _check(fn(self.e._h, self._h, n, C.c_void_p(pts.data_ptr()) if pts is not None else None, *ptrs, st))
+        return out
+
+    def eval(self, points, stream=None):
+        """the tape at `points`, (n, nparm) int64 on the host or the device (an int n when the tape has no parameters):
+        device tensors (status, leaf, x_num, x_den) and, with ndual > 0, (dual_num, dual_den).  Does not synchronise."""
+        n, pts = self._points(points)
+        names = self.OUTPUTS if self.ndual else self.OUTPUTS[:4]
+        out = self.eval_into(pts if pts is not None else n, self.outputs(n, names), stream)
+        return tuple(out[k] for k in names)
