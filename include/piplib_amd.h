@@ -54,7 +54,9 @@ extern "C" {
  * the device), the tableaux built from them as from the dense expansion; pipamd_batch_load_instances /
  * pipamd_batch_dual_instances and their _part forms -- one parametric system at many parameter points, substituted
  * exactly on the device (a constant that does not fit the entry type: PIPAMD_ST_BADINPUT); pipamd_tape_check /
- * pipamd_tape_compile / pipamd_tape_eval / pipamd_tape_free and the 128-bit forms of the first two -- a tape evaluated at
+ * pipamd_tape_compile / pipamd_tape_eval / pipamd_tape_free and the 128-bit forms of the first two (and
+ * pipamd_tape_check_pip / pipamd_tape_compile_pip with pip_solve's result edits, pipamd_tape_point_cols,
+ * pipamd_tape_set_create / _eval / _free for many tapes in one launch) -- a tape evaluated at
  * many parameter points, a lane per point. */
 #define PIPAMD_VERSION 500
 
@@ -728,10 +730,11 @@ int pipamd_device_tree_fits(const pipamd_problem *p, int entier_bits);
  * are checked against 128 bits in cell order -- coefficients 0 .. P-1, then the constant -- and the first that leaves
  * them ends the point PIPAMD_ST_RANGE.  Such a point does not disturb the others of the call.
  * NOT done here, the caller's business: the evaluator knows no context -- points outside the context the problem was
- * solved under, or negative ones, are evaluated like any other, as pipamd_batch_load_instances solves them; a big
- * parameter is just another column of the points; and the edits pip_solve makes to its result (sol_quast_edit with
- * sol_bg, urs_parms and the SOL_MAX / SOL_SHIFT bits of pipamd_pip_info) are not applied: a tape of
- * pipamd_pip_solve_many qualifies only when its problem has no big parameter and no Urs_parms.
+ * solved under, or negative ones, are evaluated like any other, as pipamd_batch_load_instances solves them; and a big
+ * parameter the CALLER gave is just another column of the points.  The edits pip_solve makes to its result
+ * (sol_quast_edit, piplib.c:866) are applied by pipamd_tape_compile_pip below, with one limit: dual lists are handed out
+ * one pair per tableau row as they stand (sol_quast_edit edits them with flags 0, sol.c:706-708); the merge of an
+ * equality's two values (pip_quast_equalities_dual) needs the input's markers and is not done.
  * Limits.  PIPAMD_TAPE_MAX_SLOTS: the largest P + 1 of a tape, the root's nparm + 1 included (the kernel keeps a
  * workgroup's parameters in scope in LDS: 128 points x (slots - 1) values).  The compiled program must stay below 2^31
  * words.  The program is staged in LDS when 8 * info.words + 128 * (info.slots - 1) * (8 or 16 bytes per value) is at
@@ -776,7 +779,8 @@ int pipamd_tape_compile(pipamd_engine *e, const pipamd_sol_cell *cells, size_t n
 int pipamd_tape_compile128(pipamd_engine *e, const pipamd_sol_cell128 *cells, size_t n_cells, const pipamd_tape_shape *shape,
                            pipamd_tape **out);
 void pipamd_tape_free(pipamd_tape *t);
-/* The tape at n_points points: d_points is n_points x nparm int64 (may be NULL when nparm == 0).  Each of the six
+/* The tape at n_points points: d_points is n_points x nparm int64 (may be NULL when nparm == 0; a tape compiled with
+ * an edit: pipamd_tape_point_cols columns in place of nparm).  Each of the six
  * outputs may be NULL.  d_status[k]: PIPAMD_ST_SOLUTION, PIPAMD_ST_NIL (a NIL item; every point of an empty tape) or
  * PIPAMD_ST_RANGE.  d_leaf[k]: the ordinal, in tape order, of the LIST or NIL item reached; -1 for an empty tape and a
  * RANGE point.  d_x_num / d_x_den: n_points x nvar, d_dual_num / d_dual_den: n_points x ndual -- int64 values, or
@@ -788,6 +792,76 @@ void pipamd_tape_free(pipamd_tape *t);
 int pipamd_tape_eval(pipamd_engine *e, const pipamd_tape *t, int64_t n_points, const int64_t *d_points, int32_t *d_status,
                      int32_t *d_leaf, int64_t *d_x_num, int64_t *d_x_den, int64_t *d_dual_num, int64_t *d_dual_den,
                      void *stream);
+
+
+/* pip_solve's result edits (added since interface version 500).  pipamd_pip_solve_many hands out the tape traiter() wrote
+ * and, in pipamd_pip_info, what pip_solve then passes to sol_quast_edit (piplib.c:866): sol_bg, urs_parms, sol_flags.
+ * pipamd_tape_compile_pip applies sol_vector_edit (sol.c:435-512) to every form, so the compiled tape evaluates to what
+ * pip_solve's own answer gives at a point.  edit == NULL, or an edit of all zeros, is exactly pipamd_tape_check /
+ * pipamd_tape_compile; the result is an ordinary pipamd_tape for pipamd_tape_eval.  shape.nparm stays the parameter
+ * count of the tape as solved (info.nparm), and the grammar is checked on the cells as they are (NEW(n) with n the raw
+ * count in scope, forms of the raw P + 1).  With P the raw parameters in scope, bg = sol_bg, U = urs_parms and
+ * first_urs = U + (bg >= 0):
+ *  - column j < nparm of a form is DROPPED when j == bg with SOL_REMOVE, or when first_urs <= j < first_urs + U (the
+ *    negated copies of Urs_parms), whatever it holds; the kept columns are the slots, renumbered in order.  A point is
+ *    pipamd_tape_point_cols = nparm - (REMOVE ? 1 : 0) - U values: the parameters as pip_solve's caller numbers them.
+ *    NEW writes the slot behind the kept parameters in scope; info.slots and PIPAMD_TAPE_MAX_SLOTS count kept columns.
+ *  - conditions and new-parameter forms: the dropping alone (sol.c:694, 714).
+ *  - solution-list forms, unknown i over D_i: with SOL_SHIFT the coefficient at bg becomes n_bg - D_i before any drop;
+ *    where that is not 0 the unknown is UNBOUNDED: its denominator is handed out as 0, the numerator kept -- the
+ *    convention of pipamd_batch_results_shifted.  A shifted coefficient that does not fit the cell type:
+ *    PIPAMD_E_TOOLARGE.  With SOL_NEGATE the unknown's exact value N is negated at the point, before the range check and
+ *    the reduction (a value whose negation leaves the type: PIPAMD_ST_RANGE).  Handed out: (+-N / g, D_i / g or 0) with
+ *    g = gcd(|N|, D_i); (0, 1) or (0, 0) for N == 0.
+ *  - dual lists: as they stand (see "NOT done" above).
+ * Any negative sol_bg means "no big parameter", as sol_vector_edit reads it (pipamd_pip_info has Bg - Nn - 1 there, which
+ * is below -1 for Bg == -1).
+ * PIPAMD_E_INVALID before any HIP call: reserved != 0; sol_flags outside bits 0-3; urs_parms < 0; sol_bg >= nparm;
+ * SOL_SHIFT or SOL_REMOVE without sol_bg >= 0; first_urs + U > nparm; SOL_REMOVE of a column among the Urs
+ * copies; and everything pipamd_tape_check refuses. */
+#define PIPAMD_SOL_SHIFT 1  /* sol.h:36-50, the numbering pipamd_pip_info.sol_flags uses */
+#define PIPAMD_SOL_NEGATE 2
+#define PIPAMD_SOL_REMOVE 4
+#define PIPAMD_SOL_DUAL 8   /* accepted and ignored: shape.ndual says whether dual lists follow */
+typedef struct pipamd_tape_edit {
+  int32_t sol_bg, urs_parms, sol_flags, reserved; /* the three fields of pipamd_pip_info; reserved 0 */
+} pipamd_tape_edit;
+int pipamd_tape_check_pip(const pipamd_sol_cell *cells, size_t n_cells, const pipamd_tape_shape *shape,
+                          const pipamd_tape_edit *edit, pipamd_tape_info *info);
+int pipamd_tape_check_pip128(const pipamd_sol_cell128 *cells, size_t n_cells, const pipamd_tape_shape *shape,
+                             const pipamd_tape_edit *edit, pipamd_tape_info *info);
+int pipamd_tape_compile_pip(pipamd_engine *e, const pipamd_sol_cell *cells, size_t n_cells, const pipamd_tape_shape *shape,
+                            const pipamd_tape_edit *edit, pipamd_tape **out);
+int pipamd_tape_compile_pip128(pipamd_engine *e, const pipamd_sol_cell128 *cells, size_t n_cells,
+                               const pipamd_tape_shape *shape, const pipamd_tape_edit *edit, pipamd_tape **out);
+/* int64 values per point that pipamd_tape_eval reads from d_points (PIPAMD_E_INVALID for NULL) */
+int pipamd_tape_point_cols(const pipamd_tape *t);
+
+/* A set of tapes evaluated in one launch (added since interface version 500): the many small quasts of
+ * pipamd_pip_solve_many, each at a handful of points.  pipamd_tape_set_create takes n >= 1 compiled tapes (edited or
+ * not) of the engine's device and of one cell width -- PIPAMD_E_INVALID otherwise, before any HIP call, as for a null
+ * engine, array, entry or `out`; programs of 2^31 words or more together: PIPAMD_E_TOOLARGE -- and copies their programs
+ * into one device buffer beside a device table per tape.  The tapes may be freed afterwards.  The set is immutable:
+ * pipamd_tape_set_eval is one launch without synchronisation and needs no per-call host table, so it may be called
+ * concurrently on several streams.  *info (may be NULL) gets the strides below. */
+typedef struct pipamd_tape_set pipamd_tape_set;
+typedef struct pipamd_tape_set_info {
+  int64_t words;                                   /* all programs together, < 2^31 */
+  int32_t n, bits, point_cols, nvar, ndual, slots; /* tapes, 64 or 128, and the four maxima over the tapes */
+} pipamd_tape_set_info;                            /* 32 bytes */
+int pipamd_tape_set_create(pipamd_engine *e, int n, const pipamd_tape *const *tapes, pipamd_tape_set **out,
+                           pipamd_tape_set_info *info);
+void pipamd_tape_set_free(pipamd_tape_set *s);
+/* Point k belongs to tape d_tape[k]; points need not be sorted by tape.  The arrays are padded to the set's maxima:
+ * d_points is n_points x info.point_cols (a tape reads its first pipamd_tape_point_cols columns), d_x_* is
+ * n_points x info.nvar, d_dual_* is n_points x info.ndual; entries beyond the tape's own counts get (0, 0).  Statuses,
+ * leaf ordinals (per tape) and values are what pipamd_tape_eval gives for that tape.  d_tape[k] outside 0 .. n-1:
+ * PIPAMD_ST_BADINPUT, leaf -1 and (0, 0) throughout; nothing is read through it and the other points are not disturbed.
+ * PIPAMD_E_INVALID before any HIP call: as pipamd_tape_eval (d_points may be NULL when info.point_cols == 0), and a
+ * null d_tape with n_points > 0.  PIPAMD_E_TOOLARGE: n_points of 2^38 and more. */
+int pipamd_tape_set_eval(pipamd_engine *e, const pipamd_tape_set *s, int64_t n_points, const int32_t *d_tape,
+                         const int64_t *d_points, int32_t *d_status, int32_t *d_leaf, int64_t *d_x_num, int64_t *d_x_den,
+                         int64_t *d_dual_num, int64_t *d_dual_den, void *stream);
 
 #ifdef __cplusplus
 }

@@ -1161,7 +1161,8 @@ extern "C" int pipamd_batch_dual_matrices(pipamd_engine *e, const void *d_ws, co
 
 // ------------------------------------------------------------------ tapes at parameter points
 // (header comment: include/piplib_amd.h; the program: pip_tape.h.)  One walk over the cells serves the check and the
-// compile: it validates the grammar, counts, and -- given a vector -- emits the program.  The walk keeps its own stack of
+// compile: it validates the grammar, counts, applies pip_solve's result edit if there is one (TapeEdit), and -- given a
+// vector -- emits the program.  The walk keeps its own stack of
 // items still to come (an IF pushes its two, a NEW the one behind it), so a deep tape costs heap, not the thread's stack.
 typedef __int128 tape_int;
 static inline tape_int tape_p1(const pipamd_sol_cell &c) { return c.param1; }
@@ -1169,6 +1170,16 @@ static inline tape_int tape_p2(const pipamd_sol_cell &c) { return c.param2; }
 static inline tape_int tape_wide(int64_t lo, int64_t hi) { return (tape_int)(((unsigned __int128)(uint64_t)hi << 64) | (uint64_t)lo); }
 static inline tape_int tape_p1(const pipamd_sol_cell128 &c) { return tape_wide(c.param1_lo, c.param1_hi); }
 static inline tape_int tape_p2(const pipamd_sol_cell128 &c) { return tape_wide(c.param2_lo, c.param2_hi); }
+
+// pip_solve's result edit (sol_vector_edit, sol.c:435-512) as the walk applies it.  Without one: no column is dropped.
+struct TapeEdit {
+  int bg = -1, urs = 0, first_urs = 0, nparm = 0;
+  bool shift = false, negate = false, remove = false;
+  int ndrop() const { return (remove ? 1 : 0) + urs; }
+  // column j of a form is not kept: the big parameter's under SOL_REMOVE, the Urs_parms copies (j >= nparm: a new
+  // parameter or the constant, always kept)
+  bool dropped(int64_t j) const { return (remove && j == bg) || (first_urs <= j && j < first_urs + urs); }
+};
 
 template <class Cell>
 struct TapeWalk {
@@ -1178,6 +1189,8 @@ struct TapeWalk {
   std::vector<long long> *prog;  // null: check only
   long long words = 0;
   const char *why = nullptr;
+  TapeEdit ed;
+  bool toolarge = false;  // a shifted coefficient left the cell type
 
   bool fail(const char *w) {
     if (!why) why = w;
@@ -1198,18 +1211,27 @@ struct TapeWalk {
     }
     return &cells[pos++];
   }
-  // FORM(len) and its VALs: one positive denominator (1 if `one`); the numerators are emitted, *den gets the denominator
-  bool form(int64_t len, bool one, tape_int *den, const char *w) {
+  // FORM(len) and its VALs: one positive denominator (1 if `one`); the numerators of the kept columns are emitted, *den
+  // gets the denominator.  `unbounded` (a solution list's form): under SOL_SHIFT the big parameter's coefficient becomes
+  // n - D before any drop, and *unbounded says whether that is not 0 (sol.c:479-483).
+  bool form(int64_t len, bool one, tape_int *den, const char *w, bool *unbounded = nullptr) {
     const Cell *f = take(PIPAMD_SOL_FORM, w);
     if (!f) return false;
     if (tape_p1(*f) != (tape_int)len) return fail(w);
     tape_int d = 1;
+    if (unbounded) *unbounded = false;
     for (int64_t j = 0; j < len; j++) {
       const Cell *v = take(PIPAMD_SOL_VAL, w);
       if (!v) return false;
       if (j == 0) d = tape_p2(*v);
       if (tape_p2(*v) != d || d <= 0 || (one && d != 1)) return fail(w);
-      emit(tape_p1(*v));
+      tape_int n = tape_p1(*v);
+      if (unbounded && ed.shift && j == ed.bg) {
+        if (__builtin_sub_overflow(n, d, &n) || (EW == 1 && n != (tape_int)(int64_t)n)) toolarge = true;
+        if (n != 0) *unbounded = true;
+      }
+      if (j < ed.nparm && ed.dropped(j)) continue;
+      emit(n);
     }
     *den = d;
     return true;
@@ -1226,8 +1248,8 @@ static unsigned __int128 tape_gcd(unsigned __int128 x, unsigned __int128 y) {
 }
 
 template <class Cell>
-static int tape_walk(const char *who, const Cell *cells, size_t n_cells, const pipamd_tape_shape *sh, pipamd_tape_info *info,
-                     std::vector<long long> *prog) {
+static int tape_walk(const char *who, const Cell *cells, size_t n_cells, const pipamd_tape_shape *sh,
+                     const pipamd_tape_edit *edit, pipamd_tape_info *info, std::vector<long long> *prog) {
   if (!sh || (!cells && n_cells > 0)) {
     pipamd_set_error("%s: null shape, or null cells with n_cells > 0", who);
     return PIPAMD_E_INVALID;
@@ -1240,6 +1262,28 @@ static int tape_walk(const char *who, const Cell *cells, size_t n_cells, const p
   enum { EW = TapeWalk<Cell>::EW };
   TapeWalk<Cell> w{cells, n_cells};
   w.prog = prog;
+  // (an edit of all zeros is no edit: bg 0 without a flag and without Urs_parms changes nothing)
+  if (edit && (edit->sol_bg || edit->urs_parms || edit->sol_flags || edit->reserved)) {
+    const int bg = edit->sol_bg, U = edit->urs_parms, fl = edit->sol_flags;
+    const int64_t first_urs = (int64_t)U + (bg >= 0);
+    const bool rm = (fl & PIPAMD_SOL_REMOVE) != 0;
+    // (any negative sol_bg is "no big parameter", as sol_vector_edit reads it: pipamd_pip_info has Bg - Nn - 1 there)
+    if (edit->reserved != 0 || (fl & ~15) || U < 0 || bg >= sh->nparm ||
+        ((fl & (PIPAMD_SOL_SHIFT | PIPAMD_SOL_REMOVE)) && bg < 0) || first_urs + U > sh->nparm ||
+        (rm && U > 0 && bg >= first_urs && bg < first_urs + U)) {
+      pipamd_set_error("%s: edit (sol_bg %d, urs_parms %d, sol_flags %d, reserved %d) does not fit nparm %d", who, bg, U, fl,
+                       edit->reserved, sh->nparm);
+      return PIPAMD_E_INVALID;
+    }
+    w.ed.bg = bg;
+    w.ed.urs = U;
+    w.ed.first_urs = (int)first_urs;
+    w.ed.nparm = sh->nparm;
+    w.ed.shift = (fl & PIPAMD_SOL_SHIFT) != 0;
+    w.ed.negate = (fl & PIPAMD_SOL_NEGATE) != 0;
+    w.ed.remove = rm;
+  }
+  const int ndrop = w.ed.ndrop();  // P of the cells counts every column; slots and headers count the kept ones
   struct Todo {
     int64_t P;
     int64_t depth;
@@ -1248,7 +1292,7 @@ static int tape_walk(const char *who, const Cell *cells, size_t n_cells, const p
   std::vector<Todo> todo;
   pipamd_tape_info I;
   memset(&I, 0, sizeof I);
-  int64_t slots = (int64_t)sh->nparm + 1, depth = 0;
+  int64_t slots = (int64_t)sh->nparm - ndrop + 1, depth = 0;
   if (n_cells) todo.push_back({sh->nparm, 1, -1});
   bool ok = true;
   while (ok && !todo.empty()) {
@@ -1256,14 +1300,14 @@ static int tape_walk(const char *who, const Cell *cells, size_t n_cells, const p
     todo.pop_back();
     const int64_t P = t.P;
     if (t.patch >= 0 && prog) (*prog)[t.patch] |= w.words << 32;
-    if (P + 1 > slots) slots = P + 1;
+    if (P - ndrop + 1 > slots) slots = P - ndrop + 1;
     if (t.depth > depth) depth = t.depth;
     if (w.pos >= w.n) {
       ok = w.fail("truncated: an item is missing");
       break;
     }
     // (P beyond the limit: the walk goes on to tell an invalid tape from a large one, but emits headers of a fixed P)
-    const int hp = P < TAPE_MAX_SLOTS ? (int)P : TAPE_MAX_SLOTS;
+    const int hp = P - ndrop < TAPE_MAX_SLOTS ? (int)(P - ndrop) : TAPE_MAX_SLOTS;
     const Cell &c = cells[w.pos++];
     tape_int den;
     switch (c.kind) {
@@ -1307,12 +1351,15 @@ static int tape_walk(const char *who, const Cell *cells, size_t n_cells, const p
           ok = w.fail("a solution list whose length is not nvar");
           break;
         }
-        w.emit_word(tape_header(TAPE_LEAF, hp, I.leaves));
+        w.emit_word(tape_header(TAPE_LEAF, hp, I.leaves) | (w.ed.negate ? TAPE_LEAF_NEGATE : 0));
         for (int i = 0; ok && i < sh->nvar; i++) {
-          // the denominator goes in front of its numerators: a place is kept, the form emitted, the place filled
+          // the denominator goes in front of its numerators: a place is kept, the form emitted, the place filled --
+          // negated for an unbounded unknown (pip_tape.h)
           const size_t at = prog ? prog->size() : 0;
+          bool unbounded = false;
           w.emit(0);
-          ok = w.form(P + 1, false, &den, "list: forms of P + 1 values over one positive denominator are expected");
+          ok = w.form(P + 1, false, &den, "list: forms of P + 1 values over one positive denominator are expected", &unbounded);
+          if (unbounded) den = -den;
           if (ok && prog) {
             (*prog)[at] = (long long)(uint64_t)(unsigned __int128)den;
             if (EW == 2) (*prog)[at + 1] = (long long)(uint64_t)((unsigned __int128)den >> 64);
@@ -1362,6 +1409,10 @@ static int tape_walk(const char *who, const Cell *cells, size_t n_cells, const p
     pipamd_set_error("%s: %lld slots (at most %d), or a program of 2^31 words or more", who, (long long)slots, TAPE_MAX_SLOTS);
     return PIPAMD_E_TOOLARGE;
   }
+  if (w.toolarge) {
+    pipamd_set_error("%s: a big parameter's coefficient minus its denominator (SOL_SHIFT) does not fit the cell type", who);
+    return PIPAMD_E_TOOLARGE;
+  }
   I.words = w.words;
   I.slots = (int32_t)slots;
   I.depth = (int32_t)depth;
@@ -1375,54 +1426,86 @@ struct pipamd_tape {
   int device, bits;
   pipamd_tape_shape shape;
   pipamd_tape_info info;
+  int point_cols;     // values of a point: shape.nparm less the columns an edit drops
+  int marks;          // the program holds a mark of an edit (pip_tape.h)
   long long *d_prog;
+  long long *h_prog;  // the same words on the host, for pipamd_tape_set_create
 };
 
 extern "C" int pipamd_tape_check(const pipamd_sol_cell *cells, size_t n_cells, const pipamd_tape_shape *shape,
                                  pipamd_tape_info *info) {
-  return tape_walk("tape_check", cells, n_cells, shape, info, nullptr);
+  return tape_walk("tape_check", cells, n_cells, shape, nullptr, info, nullptr);
 }
 extern "C" int pipamd_tape_check128(const pipamd_sol_cell128 *cells, size_t n_cells, const pipamd_tape_shape *shape,
                                     pipamd_tape_info *info) {
-  return tape_walk("tape_check128", cells, n_cells, shape, info, nullptr);
+  return tape_walk("tape_check128", cells, n_cells, shape, nullptr, info, nullptr);
+}
+extern "C" int pipamd_tape_check_pip(const pipamd_sol_cell *cells, size_t n_cells, const pipamd_tape_shape *shape,
+                                     const pipamd_tape_edit *edit, pipamd_tape_info *info) {
+  return tape_walk("tape_check_pip", cells, n_cells, shape, edit, info, nullptr);
+}
+extern "C" int pipamd_tape_check_pip128(const pipamd_sol_cell128 *cells, size_t n_cells, const pipamd_tape_shape *shape,
+                                        const pipamd_tape_edit *edit, pipamd_tape_info *info) {
+  return tape_walk("tape_check_pip128", cells, n_cells, shape, edit, info, nullptr);
+}
+
+// The promise to the kernel, held against `words` words themselves (a program, or a tape's part of a set's buffer that
+// starts at word `base`): known operations, the negate mark on leaves alone, no denominator of 0, every else target
+// behind its IF and inside these words, and a node behind every NEW and IF.  -1, or the first word that breaks it.
+static long long tape_program_breach(const long long *prog, long long base, long long words, int ew, int nvar, int ndual,
+                                     int slots, bool *marks = nullptr) {
+  for (long long pc = 0; pc < words;) {
+    const long long hdr = prog[base + pc];
+    const int op = (int)(hdr & 0xff), P = (int)((hdr >> 8) & 0xffff), mark = (int)((hdr >> 24) & 0xff);
+    const long long aux = (hdr >> 32) - base;
+    long long len = 1;
+    if (op == TAPE_NEW) len += ew * (P + 2);
+    else if (op == TAPE_IF) len += ew * (P + 1);
+    else if (op == TAPE_LEAF) len += ew * ((long long)nvar * (P + 2) + 2ll * ndual);
+    if ((op != TAPE_NEW && op != TAPE_IF && op != TAPE_LEAF && op != TAPE_NIL) || hdr < 0 || P + 1 > slots || pc + len > words ||
+        (op == TAPE_LEAF ? mark > 1 : mark != 0) || (op == TAPE_IF && (aux < pc + len || aux >= words)) ||
+        ((op == TAPE_NEW || op == TAPE_IF) && pc + len >= words))
+      return pc;
+    if (op == TAPE_LEAF)
+      for (int i = 0; i < nvar; i++) {
+        const long long *d = prog + base + pc + 1 + (long long)i * ew * (P + 2);
+        if (d[0] == 0 && (ew == 1 || d[1] == 0)) return pc;
+        if (marks && (mark || d[ew - 1] < 0)) *marks = true;  // (what the kernel looks for: pip_tape.h)
+      }
+    pc += len;
+  }
+  return -1;
 }
 
 template <class Cell>
 static int tape_compile(const char *who, pipamd_engine *e, const Cell *cells, size_t n_cells, const pipamd_tape_shape *shape,
-                        pipamd_tape **out) {
+                        const pipamd_tape_edit *edit, pipamd_tape **out) {
   if (!e || !out) {
     pipamd_set_error("%s: null engine or result pointer", who);
     return PIPAMD_E_INVALID;
   }
   *out = nullptr;
   pipamd_tape_info info;
-  int rc = tape_walk(who, cells, n_cells, shape, &info, nullptr);
+  int rc = tape_walk(who, cells, n_cells, shape, edit, &info, nullptr);
   if (rc) return rc;
   std::vector<long long> prog;
   prog.reserve((size_t)info.words);
-  rc = tape_walk(who, cells, n_cells, shape, &info, &prog);
+  rc = tape_walk(who, cells, n_cells, shape, edit, &info, &prog);
   if (rc) return rc;
   if ((long long)prog.size() != info.words) {
     pipamd_set_error("%s: internal: %zu words emitted, %lld counted", who, prog.size(), (long long)info.words);
     return PIPAMD_E_INVALID;
   }
-  // the promise to the kernel, held against the words themselves: every else target behind its IF and inside the program
-  for (long long pc = 0; pc < info.words;) {
-    const long long hdr = prog[pc];
-    const int op = (int)(hdr & 0xff), P = (int)((hdr >> 8) & 0xffff);
-    const long long aux = hdr >> 32;
-    const int ew = sizeof(Cell) == sizeof(pipamd_sol_cell) ? 1 : 2;
-    long long len = 1;
-    if (op == TAPE_NEW) len += ew * (P + 2);
-    else if (op == TAPE_IF) len += ew * (P + 1);
-    else if (op == TAPE_LEAF) len += ew * ((long long)shape->nvar * (P + 2) + 2ll * shape->ndual);
-    if ((op != TAPE_NEW && op != TAPE_IF && op != TAPE_LEAF && op != TAPE_NIL) || P + 1 > info.slots || pc + len > info.words ||
-        (op == TAPE_IF && (aux < pc + len || aux >= info.words)) || ((op == TAPE_NEW || op == TAPE_IF) && pc + len >= info.words)) {
-      pipamd_set_error("%s: internal: word %lld of the program breaks the kernel's contract", who, pc);
-      return PIPAMD_E_INVALID;
-    }
-    pc += len;
+  const int ew = sizeof(Cell) == sizeof(pipamd_sol_cell) ? 1 : 2;
+  bool marks = false;
+  const long long breach = tape_program_breach(prog.data(), 0, info.words, ew, shape->nvar, shape->ndual, info.slots, &marks);
+  if (breach >= 0) {
+    pipamd_set_error("%s: internal: word %lld of the program breaks the kernel's contract", who, breach);
+    return PIPAMD_E_INVALID;
   }
+  // (the walk accepted the edit: the columns it drops are distinct and inside nparm)
+  int ndrop = 0;
+  if (edit) ndrop = ((edit->sol_flags & PIPAMD_SOL_REMOVE) ? 1 : 0) + edit->urs_parms;
   if (hipSetDevice(e->device) != hipSuccess) return PIPAMD_E_HIP;
   pipamd_tape *t = (pipamd_tape *)calloc(1, sizeof *t);
   if (!t) return PIPAMD_E_NOMEM;
@@ -1430,12 +1513,21 @@ static int tape_compile(const char *who, pipamd_engine *e, const Cell *cells, si
   t->bits = sizeof(Cell) == sizeof(pipamd_sol_cell) ? 64 : 128;
   t->shape = *shape;
   t->info = info;
+  t->point_cols = shape->nparm - ndrop;
+  t->marks = marks ? 1 : 0;
   if (info.words) {
+    t->h_prog = (long long *)malloc((size_t)info.words * 8);
+    if (!t->h_prog) {
+      free(t);
+      return PIPAMD_E_NOMEM;
+    }
+    memcpy(t->h_prog, prog.data(), (size_t)info.words * 8);
     hipError_t he = hipMalloc((void **)&t->d_prog, (size_t)info.words * 8);
     if (he == hipSuccess) he = hipMemcpy(t->d_prog, prog.data(), (size_t)info.words * 8, hipMemcpyHostToDevice);
     if (he != hipSuccess) {
       pipamd_set_error("%s: the program's %lld words on the device: %s", who, (long long)info.words, hipGetErrorString(he));
       if (t->d_prog) hipFree(t->d_prog);
+      free(t->h_prog);
       free(t);
       return PIPAMD_E_HIP;
     }
@@ -1446,16 +1538,26 @@ static int tape_compile(const char *who, pipamd_engine *e, const Cell *cells, si
 
 extern "C" int pipamd_tape_compile(pipamd_engine *e, const pipamd_sol_cell *cells, size_t n_cells, const pipamd_tape_shape *shape,
                                    pipamd_tape **out) {
-  return tape_compile("tape_compile", e, cells, n_cells, shape, out);
+  return tape_compile("tape_compile", e, cells, n_cells, shape, nullptr, out);
 }
 extern "C" int pipamd_tape_compile128(pipamd_engine *e, const pipamd_sol_cell128 *cells, size_t n_cells,
                                       const pipamd_tape_shape *shape, pipamd_tape **out) {
-  return tape_compile("tape_compile128", e, cells, n_cells, shape, out);
+  return tape_compile("tape_compile128", e, cells, n_cells, shape, nullptr, out);
 }
+extern "C" int pipamd_tape_compile_pip(pipamd_engine *e, const pipamd_sol_cell *cells, size_t n_cells,
+                                       const pipamd_tape_shape *shape, const pipamd_tape_edit *edit, pipamd_tape **out) {
+  return tape_compile("tape_compile_pip", e, cells, n_cells, shape, edit, out);
+}
+extern "C" int pipamd_tape_compile_pip128(pipamd_engine *e, const pipamd_sol_cell128 *cells, size_t n_cells,
+                                          const pipamd_tape_shape *shape, const pipamd_tape_edit *edit, pipamd_tape **out) {
+  return tape_compile("tape_compile_pip128", e, cells, n_cells, shape, edit, out);
+}
+extern "C" int pipamd_tape_point_cols(const pipamd_tape *t) { return t ? t->point_cols : PIPAMD_E_INVALID; }
 
 extern "C" void pipamd_tape_free(pipamd_tape *t) {
   if (!t) return;
   if (t->d_prog && hipSetDevice(t->device) == hipSuccess) hipFree(t->d_prog);
+  free(t->h_prog);
   free(t);
 }
 
@@ -1475,7 +1577,7 @@ extern "C" int pipamd_debug_tape_program(const pipamd_tape *t, int64_t *host_out
 extern "C" int pipamd_tape_eval(pipamd_engine *e, const pipamd_tape *t, int64_t n_points, const int64_t *d_points,
                                 int32_t *d_status, int32_t *d_leaf, int64_t *d_x_num, int64_t *d_x_den, int64_t *d_dual_num,
                                 int64_t *d_dual_den, void *stream) {
-  if (!e || !t || n_points < 0 || t->device != e->device || (n_points > 0 && t->shape.nparm > 0 && !d_points)) {
+  if (!e || !t || n_points < 0 || t->device != e->device || (n_points > 0 && t->point_cols > 0 && !d_points)) {
     pipamd_set_error("tape_eval: null engine or tape, a tape of another device, n_points < 0, or parameters without points");
     return PIPAMD_E_INVALID;
   }
@@ -1490,8 +1592,9 @@ extern "C" int pipamd_tape_eval(pipamd_engine *e, const pipamd_tape *t, int64_t 
   L.words = t->info.words;
   L.bits = t->bits;
   L.staged = t->info.staged;
+  L.marks = t->marks;
   L.nvar = t->shape.nvar;
-  L.nparm = t->shape.nparm;
+  L.nparm = t->point_cols;
   L.ndual = t->shape.ndual;
   L.slots = t->info.slots;
   L.n_points = n_points;
@@ -1503,6 +1606,145 @@ extern "C" int pipamd_tape_eval(pipamd_engine *e, const pipamd_tape *t, int64_t 
   L.dual_num = d_dual_num;
   L.dual_den = d_dual_den;
   HIPCHK(pipk_launch_tape_eval(&L, (hipStream_t)stream));
+  return PIPAMD_OK;
+}
+
+// ------------------------------------------------------------------ a set of tapes in one launch
+struct pipamd_tape_set {
+  int device, bits;
+  pipamd_tape_set_info info;
+  long long *d_prog;      // info.words words: the programs one behind the other, else targets relocated
+  TapeSetEntry *d_table;  // info.n entries
+};
+
+extern "C" int pipamd_tape_set_create(pipamd_engine *e, int n, const pipamd_tape *const *tapes, pipamd_tape_set **out,
+                                      pipamd_tape_set_info *info) {
+  if (out) *out = nullptr;
+  if (!e || !out || n < 1 || !tapes) {
+    pipamd_set_error("tape_set_create: null engine, tapes or result pointer, or n < 1");
+    return PIPAMD_E_INVALID;
+  }
+  pipamd_tape_set_info I;
+  memset(&I, 0, sizeof I);
+  I.n = n;
+  I.slots = 1;
+  for (int i = 0; i < n; i++) {
+    const pipamd_tape *t = tapes[i];
+    if (!t || t->device != e->device || t->bits != tapes[0]->bits) {
+      pipamd_set_error("tape_set_create: tape %d is null, of another device than the engine's, or of another cell width", i);
+      return PIPAMD_E_INVALID;
+    }
+    I.words += t->info.words;
+    if (t->point_cols > I.point_cols) I.point_cols = t->point_cols;
+    if (t->shape.nvar > I.nvar) I.nvar = t->shape.nvar;
+    if (t->shape.ndual > I.ndual) I.ndual = t->shape.ndual;
+    if (t->info.slots > I.slots) I.slots = t->info.slots;
+    if (I.words >= (1ll << 31)) {
+      pipamd_set_error("tape_set_create: programs of 2^31 words or more together");
+      return PIPAMD_E_TOOLARGE;
+    }
+  }
+  I.bits = tapes[0]->bits;
+  const int ew = I.bits / 64;
+  std::vector<long long> prog((size_t)I.words);
+  std::vector<TapeSetEntry> table((size_t)n);
+  long long at = 0;
+  for (int i = 0; i < n; i++) {
+    const pipamd_tape *t = tapes[i];
+    const long long words = t->info.words;
+    TapeSetEntry &en = table[i];
+    memset(&en, 0, sizeof en);
+    en.start = (int)at;
+    en.words = (int)words;
+    en.point_cols = t->point_cols;
+    en.nvar = t->shape.nvar;
+    en.ndual = t->shape.ndual;
+    // the tape's own words, every else target moved by the tape's start (node lengths as tape_compile checked them)
+    for (long long pc = 0; pc < words;) {
+      const long long hdr = t->h_prog[pc];
+      const int op = (int)(hdr & 0xff), P = (int)((hdr >> 8) & 0xffff);
+      long long len = 1;
+      if (op == TAPE_NEW) len += ew * (P + 2);
+      else if (op == TAPE_IF) len += ew * (P + 1);
+      else if (op == TAPE_LEAF) len += ew * ((long long)en.nvar * (P + 2) + 2ll * en.ndual);
+      if (pc + len > words) len = words - pc;  // (cannot be: the re-check below refuses it)
+      memcpy(&prog[(size_t)(at + pc)], t->h_prog + pc, (size_t)len * 8);
+      if (op == TAPE_IF) prog[(size_t)(at + pc)] = hdr + (at << 32);
+      pc += len;
+    }
+    // the promise to the kernel again, on the concatenation: every jump forward and inside its own tape's words
+    const long long breach = tape_program_breach(prog.data(), at, words, ew, en.nvar, en.ndual, t->info.slots);
+    if (breach >= 0) {
+      pipamd_set_error("tape_set_create: internal: word %lld of tape %d breaks the kernel's contract", breach, i);
+      return PIPAMD_E_INVALID;
+    }
+    at += words;
+  }
+  if (hipSetDevice(e->device) != hipSuccess) return PIPAMD_E_HIP;
+  pipamd_tape_set *s = (pipamd_tape_set *)calloc(1, sizeof *s);
+  if (!s) return PIPAMD_E_NOMEM;
+  s->device = e->device;
+  s->bits = I.bits;
+  s->info = I;
+  hipError_t he = hipMalloc((void **)&s->d_table, (size_t)n * sizeof(TapeSetEntry));
+  if (he == hipSuccess) he = hipMemcpy(s->d_table, table.data(), (size_t)n * sizeof(TapeSetEntry), hipMemcpyHostToDevice);
+  if (he == hipSuccess && I.words) he = hipMalloc((void **)&s->d_prog, (size_t)I.words * 8);
+  if (he == hipSuccess && I.words) he = hipMemcpy(s->d_prog, prog.data(), (size_t)I.words * 8, hipMemcpyHostToDevice);
+  if (he != hipSuccess) {
+    pipamd_set_error("tape_set_create: %d tapes, %lld words on the device: %s", n, (long long)I.words, hipGetErrorString(he));
+    if (s->d_table) hipFree(s->d_table);
+    if (s->d_prog) hipFree(s->d_prog);
+    free(s);
+    return PIPAMD_E_HIP;
+  }
+  if (info) *info = I;
+  *out = s;
+  return PIPAMD_OK;
+}
+
+extern "C" void pipamd_tape_set_free(pipamd_tape_set *s) {
+  if (!s) return;
+  if (hipSetDevice(s->device) == hipSuccess) {
+    if (s->d_prog) hipFree(s->d_prog);
+    if (s->d_table) hipFree(s->d_table);
+  }
+  free(s);
+}
+
+extern "C" int pipamd_tape_set_eval(pipamd_engine *e, const pipamd_tape_set *s, int64_t n_points, const int32_t *d_tape,
+                                    const int64_t *d_points, int32_t *d_status, int32_t *d_leaf, int64_t *d_x_num,
+                                    int64_t *d_x_den, int64_t *d_dual_num, int64_t *d_dual_den, void *stream) {
+  if (!e || !s || n_points < 0 || s->device != e->device ||
+      (n_points > 0 && (!d_tape || (s->info.point_cols > 0 && !d_points)))) {
+    pipamd_set_error("tape_set_eval: null engine or set, a set of another device, n_points < 0, points without tape indices, "
+                     "or parameters without points");
+    return PIPAMD_E_INVALID;
+  }
+  if (n_points >= (1ll << 38)) {
+    pipamd_set_error("tape_set_eval: %lld points, at most 2^38 - 1 a call", (long long)n_points);
+    return PIPAMD_E_TOOLARGE;
+  }
+  if (n_points == 0) return PIPAMD_OK;
+  if (hipSetDevice(e->device) != hipSuccess) return PIPAMD_E_HIP;
+  TapeSetLaunch L;
+  L.prog = s->d_prog;
+  L.table = s->d_table;
+  L.n = s->info.n;
+  L.bits = s->bits;
+  L.point_cols = s->info.point_cols;
+  L.nvar = s->info.nvar;
+  L.ndual = s->info.ndual;
+  L.slots = s->info.slots;
+  L.n_points = n_points;
+  L.tape = d_tape;
+  L.points = (const long long *)d_points;
+  L.status = d_status;
+  L.leaf = d_leaf;
+  L.x_num = d_x_num;
+  L.x_den = d_x_den;
+  L.dual_num = d_dual_num;
+  L.dual_den = d_dual_den;
+  HIPCHK(pipk_launch_tape_set_eval(&L, (hipStream_t)stream));
   return PIPAMD_OK;
 }
 

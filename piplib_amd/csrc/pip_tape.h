@@ -12,6 +12,20 @@
 // The host writes aux of an IF only behind the node's own words and within the program, and every other node either
 // ends the walk or is followed by the next one: a point's position only grows, so the kernel ends after at most as many
 // steps as the program has nodes and reads nothing outside it, whatever the points are.
+//
+// pip_solve's result edits (pipamd_tape_compile_pip, sol.c:435-512) are applied by the compiler where they can be: P
+// counts the KEPT parameters in scope, the values of dropped columns are not emitted, and a shifted coefficient is
+// emitted shifted.  Two marks remain for the kernel, both absent from a program compiled without an edit:
+//     TAPE_LEAF_NEGATE, bit 24 of a LEAF's header (bits 24-31 are 0 in every other header): SOL_NEGATE, every unknown's
+//                       exact value N is negated before the range check and the reduction
+//     D_i < 0 in a LEAF: the unknown is unbounded (its shifted coefficient of the big parameter is not 0); the
+//                       denominator is -D_i for the reduction and 0 in what is handed out.  D_i is never 0.
+// The compile says whether a program holds either mark (TapeLaunch.marks); one that holds none is walked by an
+// instantiation of the kernel that does not look for them, so a tape compiled without an edit costs what it did.
+//
+// A set of tapes (pipamd_tape_set_create) is their programs one behind the other in one buffer, every else target moved
+// by its tape's start word, and a table of TapeSetEntry: a lane starts at its tape's first word, positions still only
+// grow, and no jump leaves its tape's words.
 #ifndef PIP_TAPE_H
 #define PIP_TAPE_H
 #include <hip/hip_runtime.h>
@@ -26,13 +40,15 @@ enum {
 // bytes of LDS the parameters in scope take: a row of TAPE_BLOCK values per parameter, slots - 1 of them
 static inline size_t tape_slot_bytes(int slots, int bits) { return (size_t)(slots - 1) * TAPE_BLOCK * (bits / 8); }
 static inline long long tape_header(int op, int P, long long aux) { return (long long)op | ((long long)P << 8) | (aux << 32); }
+static const long long TAPE_LEAF_NEGATE = 1ll << 24;
 
 struct TapeLaunch {
   const long long *prog;  // device; `words` words
   long long words;        // 0: the empty tape
   int bits;               // 64 or 128
   int staged;             // 1: the program is copied to LDS first; 0: read from global memory
-  int nvar, nparm, ndual;
+  int marks;              // 1: the program holds a TAPE_LEAF_NEGATE bit or a negative D_i; 0: it holds neither
+  int nvar, nparm, ndual;  // nparm: the values of a point (pipamd_tape_point_cols)
   int slots;              // pipamd_tape_info.slots
   long long n_points;
   const long long *points;
@@ -40,7 +56,26 @@ struct TapeLaunch {
   void *x_num, *x_den, *dual_num, *dual_den;
 };
 
+struct TapeSetEntry {
+  int start, words;  // first word in the set's buffer; 0 words: the empty tape
+  int point_cols, nvar, ndual;
+  int pad[3];
+};  // 32 bytes
+
+struct TapeSetLaunch {
+  const long long *prog;      // device; all programs, else targets relocated
+  const TapeSetEntry *table;  // device; n entries
+  int n, bits;
+  int point_cols, nvar, ndual, slots;  // the maxima: the strides of points, x_* and dual_*, and the LDS rows
+  long long n_points;
+  const int *tape;  // device; a tape index per point
+  const long long *points;
+  int *status, *leaf;
+  void *x_num, *x_den, *dual_num, *dual_den;
+};
+
 extern "C" {
 hipError_t pipk_launch_tape_eval(const TapeLaunch *t, hipStream_t stream);
+hipError_t pipk_launch_tape_set_eval(const TapeSetLaunch *t, hipStream_t stream);
 }
 #endif

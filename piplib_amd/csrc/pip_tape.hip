@@ -10,7 +10,8 @@
 // Lanes of a wave end up at different nodes.  A position only grows (pip_tape.h), so a wave serves, in every step, the
 // LOWEST position any of its lanes is at: the lanes there execute the node, the others wait.  The node's words are then
 // the same address for every lane -- a broadcast LDS read, or a scalar load --, a wave executes each node at most once,
-// and lanes that took different branches meet again at the first node they share.
+// and lanes that took different branches meet again at the first node they share.  pip_tape_set_eval_kernel walks the
+// programs of a set of tapes the same way, a tape per point, through the same walk (tape_walk).
 //
 // Arithmetic.  int64 cells: sum c_j theta_j + c is formed exactly -- a product of two int64 values is below 2^126; its
 // signed high and unsigned low halves are summed apart (at most TAPE_MAX_SLOTS terms, nothing wraps) and joined at the
@@ -177,13 +178,16 @@ __device__ __forceinline__ bool floor_div(i128 v, T D, T *q) {
   *q = neg ? (T)((u128)0 - uq) : (T)uq;
   return true;
 }
-// N / D in lowest terms, D > 0 ((0, 1) for N == 0); false where the numerator does not fit T
+// N / D in lowest terms -- N negated first where `flip` --, D > 0 ((0, 1) for N == 0); false where the numerator does
+// not fit T.  (The magnitude of the most negative i128 is itself; flipping it leaves 128 bits, and no T holds it.)
 template <class T>
-__device__ __forceinline__ bool lowest_terms(i128 N, T D, T *num, T *den) {
+__device__ __forceinline__ bool lowest_terms(i128 N, bool flip, T D, T *num, T *den) {
   const u128 mag = uabs(N), g = ugcd(mag, (u128)D);
   const u128 qn = udivmod(mag, g).q, qd = udivmod((u128)D, g).q;
-  if (!Width<T>::fits(qn, N < 0)) return false;
-  *num = N < 0 ? (T)((u128)0 - qn) : (T)qn;
+  const bool neg = flip ? N > 0 : N < 0;
+  if (flip && mag == ((u128)1 << 127)) return false;
+  if (!Width<T>::fits(qn, neg)) return false;
+  *num = neg ? (T)((u128)0 - qn) : (T)qn;
   *den = (T)qd;
   return true;
 }
@@ -196,28 +200,23 @@ __device__ __forceinline__ int wave_min(int x) {
   return __builtin_amdgcn_readfirstlane(x);
 }
 
-template <class T, bool STAGED>
-__global__ __launch_bounds__(TAPE_BLOCK) void pip_tape_eval_kernel(TapeLaunch a) {
+// The results of a launch, and where a point's go: unknown i of point pt is value pt * xs + i, dual value i is
+// pt * ds + i (one tape: its own nvar and ndual; a set: the set's maxima)
+struct TapeOut {
+  int *status, *leaf;
+  void *x_num, *x_den, *dual_num, *dual_den;
+  int xs, ds;
+};
+
+// The walk of a lane that starts at word `pc` of `prog` (END: it has nothing to walk), together with its wave: in
+// every step the lanes at the lowest position execute the node there, the others wait.  At the end st and leaf are set
+// and a solution's values written.  nvar and ndual are the lane's tape's.  MARKS: the program may hold the two marks of
+// pip_solve's result edits (pip_tape.h); a program without them is walked by code that does not look for them.
+template <class T, bool MARKS>
+__device__ __forceinline__ void tape_walk(const i64 *prog, int pc, i64 *S, int tid, int nvar, int ndual, i64 pt,
+                                          const TapeOut &o, int &st, int &leaf) {
   typedef Width<T> W;
   constexpr int EW = W::EW;
-  extern __shared__ __attribute__((aligned(16))) i64 tape_lds[];
-  i64 *S = tape_lds;  // (slots - 1) * EW rows of TAPE_BLOCK words
-  const int tid = threadIdx.x, nvar = a.nvar, ndual = a.ndual;
-  const i64 pt = (i64)blockIdx.x * TAPE_BLOCK + tid;
-  const bool live = pt < a.n_points;
-  const int words = (int)a.words;
-  const i64 *prog = a.prog;
-  if (STAGED) {
-    i64 *L = tape_lds + (size_t)(a.slots - 1) * EW * TAPE_BLOCK;
-    for (int i = tid; i < words; i += TAPE_BLOCK) L[i] = a.prog[i];
-    prog = L;
-  }
-  if (live)
-    for (int j = 0; j < a.nparm; j++) W::set_slot(S, j, tid, (T)a.points[pt * a.nparm + j]);
-  if (STAGED) __syncthreads();
-
-  int pc = live && words ? 0 : END;
-  int st = PIPAMD_ST_NIL, leaf = -1;
   for (;;) {
     const int cur = wave_min(pc);
     if (cur == END) break;
@@ -245,21 +244,26 @@ __global__ __launch_bounds__(TAPE_BLOCK) void pip_tape_eval_kernel(TapeLaunch a)
         pc = f.neg ? aux : cur + 1 + EW * (P + 1);
       }
     } else if (op == TAPE_LEAF) {
+      const bool flip = MARKS && (hdr & TAPE_LEAF_NEGATE) != 0;
       bool good = true;
       for (int i = 0; i < nvar; i++) {
         const i64 *u = body + (size_t)i * EW * (P + 2);
         const FormValue f = form_value(u + EW, P, S, tid, (T *)nullptr);
+        // (a negative D_i marks an unbounded unknown, pip_tape.h: the reduction is by -D_i, the denominator handed out 0)
+        const T D = W::word(u, 0);
         T num = 0, den = 0;
-        good = good && f.ok && lowest_terms<T>(f.v, W::word(u, 0), &num, &den);
+        const bool unbounded = MARKS && D < 0;
+        good = good && f.ok && lowest_terms<T>(f.v, flip, unbounded ? -D : D, &num, &den);
         if (!good) break;
-        if (a.x_num) W::out(a.x_num, pt * nvar + i, num);
-        if (a.x_den) W::out(a.x_den, pt * nvar + i, den);
+        if (unbounded) den = 0;
+        if (o.x_num) W::out(o.x_num, pt * o.xs + i, num);
+        if (o.x_den) W::out(o.x_den, pt * o.xs + i, den);
       }
       if (good) {
         const i64 *d = body + (size_t)nvar * EW * (P + 2);
         for (int i = 0; i < ndual; i++) {
-          if (a.dual_num) W::out(a.dual_num, pt * ndual + i, W::word(d, 2 * i));
-          if (a.dual_den) W::out(a.dual_den, pt * ndual + i, W::word(d, 2 * i + 1));
+          if (o.dual_num) W::out(o.dual_num, pt * o.ds + i, W::word(d, 2 * i));
+          if (o.dual_den) W::out(o.dual_den, pt * o.ds + i, W::word(d, 2 * i + 1));
         }
         st = PIPAMD_ST_SOLUTION;
         leaf = aux;
@@ -273,30 +277,109 @@ __global__ __launch_bounds__(TAPE_BLOCK) void pip_tape_eval_kernel(TapeLaunch a)
       pc = END;
     }
   }
-  if (!live) return;
-  if (a.status) a.status[pt] = st;
-  if (a.leaf) a.leaf[pt] = leaf;
-  if (st != PIPAMD_ST_SOLUTION) {  // (0, 0) throughout, also where a leaf's later unknown left the range
-    for (int i = 0; i < nvar; i++) {
-      if (a.x_num) W::out(a.x_num, pt * nvar + i, (T)0);
-      if (a.x_den) W::out(a.x_den, pt * nvar + i, (T)0);
-    }
-    for (int i = 0; i < ndual; i++) {
-      if (a.dual_num) W::out(a.dual_num, pt * ndual + i, (T)0);
-      if (a.dual_den) W::out(a.dual_den, pt * ndual + i, (T)0);
-    }
+}
+
+// status and leaf of a point, and (0, 0) in the values from `xfrom` / `dfrom` on: everything for a point without a
+// solution (also where a leaf's later unknown left the range), a set's padding behind a tape's own counts otherwise
+template <class T>
+__device__ __forceinline__ void tape_finish(const TapeOut &o, i64 pt, int st, int leaf, int xfrom, int dfrom) {
+  typedef Width<T> W;
+  if (o.status) o.status[pt] = st;
+  if (o.leaf) o.leaf[pt] = leaf;
+  for (int i = xfrom; i < o.xs; i++) {
+    if (o.x_num) W::out(o.x_num, pt * o.xs + i, (T)0);
+    if (o.x_den) W::out(o.x_den, pt * o.xs + i, (T)0);
+  }
+  for (int i = dfrom; i < o.ds; i++) {
+    if (o.dual_num) W::out(o.dual_num, pt * o.ds + i, (T)0);
+    if (o.dual_den) W::out(o.dual_den, pt * o.ds + i, (T)0);
   }
 }
 
+template <class T, bool STAGED, bool MARKS>
+__global__ __launch_bounds__(TAPE_BLOCK) void pip_tape_eval_kernel(TapeLaunch a) {
+  typedef Width<T> W;
+  constexpr int EW = W::EW;
+  extern __shared__ __attribute__((aligned(16))) i64 tape_lds[];
+  i64 *S = tape_lds;  // (slots - 1) * EW rows of TAPE_BLOCK words
+  const int tid = threadIdx.x, nvar = a.nvar, ndual = a.ndual;
+  const i64 pt = (i64)blockIdx.x * TAPE_BLOCK + tid;
+  const bool live = pt < a.n_points;
+  const int words = (int)a.words;
+  const i64 *prog = a.prog;
+  if (STAGED) {
+    i64 *L = tape_lds + (size_t)(a.slots - 1) * EW * TAPE_BLOCK;
+    for (int i = tid; i < words; i += TAPE_BLOCK) L[i] = a.prog[i];
+    prog = L;
+  }
+  if (live)
+    for (int j = 0; j < a.nparm; j++) W::set_slot(S, j, tid, (T)a.points[pt * a.nparm + j]);
+  if (STAGED) __syncthreads();
+  TapeOut o;
+  o.status = a.status, o.leaf = a.leaf;
+  o.x_num = a.x_num, o.x_den = a.x_den, o.dual_num = a.dual_num, o.dual_den = a.dual_den;
+  o.xs = nvar, o.ds = ndual;
+
+  int pc = live && words ? 0 : END;
+  int st = PIPAMD_ST_NIL, leaf = -1;
+  tape_walk<T, MARKS>(prog, pc, S, tid, nvar, ndual, pt, o, st, leaf);
+  if (!live) return;
+  if (st != PIPAMD_ST_SOLUTION) {
+    tape_finish<T>(o, pt, st, leaf, 0, 0);  // (0, 0) throughout
+  } else {
+    if (a.status) a.status[pt] = st;
+    if (a.leaf) a.leaf[pt] = leaf;
+  }
+}
+
+// A set of tapes: point pt is of tape a.tape[pt], and its lane starts at that tape's first word.  Positions only grow
+// within a tape and tapes do not overlap in the buffer, so serving the lowest position of the wave still executes every
+// node at most once a wave: a wave of one tape walks as above, a wave of 64 tapes serves them one after the other.  The
+// programs are read from global memory, at a wave-uniform address.
 template <class T>
+__global__ __launch_bounds__(TAPE_BLOCK) void pip_tape_set_eval_kernel(TapeSetLaunch a) {
+  typedef Width<T> W;
+  extern __shared__ __attribute__((aligned(16))) i64 tape_lds[];
+  i64 *S = tape_lds;  // (a.slots - 1) * W::EW rows of TAPE_BLOCK words
+  const int tid = threadIdx.x;
+  const i64 pt = (i64)blockIdx.x * TAPE_BLOCK + tid;
+  const bool live = pt < a.n_points;  // (the other lanes stay for the wave's shuffles, at END)
+  TapeOut o;
+  o.status = a.status, o.leaf = a.leaf;
+  o.x_num = a.x_num, o.x_den = a.x_den, o.dual_num = a.dual_num, o.dual_den = a.dual_den;
+  o.xs = a.nvar, o.ds = a.ndual;
+
+  const int k = live ? a.tape[pt] : -1;
+  int pc = END, st = PIPAMD_ST_BADINPUT, leaf = -1, nvar = 0, ndual = 0;
+  if (k >= 0 && k < a.n) {  // (nothing is read through an index outside the table)
+    const TapeSetEntry e = a.table[k];
+    nvar = e.nvar, ndual = e.ndual;
+    for (int j = 0; j < e.point_cols; j++) W::set_slot(S, j, tid, (T)a.points[pt * a.point_cols + j]);
+    st = PIPAMD_ST_NIL;
+    if (e.words) pc = e.start;
+  }
+  tape_walk<T, true>(a.prog, pc, S, tid, nvar, ndual, pt, o, st, leaf);
+  if (!live) return;
+  const bool sol = st == PIPAMD_ST_SOLUTION;
+  tape_finish<T>(o, pt, st, leaf, sol ? nvar : 0, sol ? ndual : 0);
+}
+
+template <class T, bool MARKS>
 hipError_t launch(const TapeLaunch &t, hipStream_t stream) {
   const long long blocks = (t.n_points + TAPE_BLOCK - 1) / TAPE_BLOCK;
   const size_t slot_bytes = tape_slot_bytes(t.slots, t.bits);
   if (t.staged)
-    hipLaunchKernelGGL((pip_tape_eval_kernel<T, true>), dim3((unsigned)blocks), dim3(TAPE_BLOCK),
+    hipLaunchKernelGGL((pip_tape_eval_kernel<T, true, MARKS>), dim3((unsigned)blocks), dim3(TAPE_BLOCK),
                        slot_bytes + (size_t)t.words * 8, stream, t);
   else
-    hipLaunchKernelGGL((pip_tape_eval_kernel<T, false>), dim3((unsigned)blocks), dim3(TAPE_BLOCK), slot_bytes, stream, t);
+    hipLaunchKernelGGL((pip_tape_eval_kernel<T, false, MARKS>), dim3((unsigned)blocks), dim3(TAPE_BLOCK), slot_bytes, stream, t);
+  return hipGetLastError();
+}
+template <class T>
+hipError_t launch_set(const TapeSetLaunch &t, hipStream_t stream) {
+  const long long blocks = (t.n_points + TAPE_BLOCK - 1) / TAPE_BLOCK;
+  hipLaunchKernelGGL((pip_tape_set_eval_kernel<T>), dim3((unsigned)blocks), dim3(TAPE_BLOCK),
+                     tape_slot_bytes(t.slots, t.bits), stream, t);
   return hipGetLastError();
 }
 }  // namespace
@@ -304,5 +387,12 @@ hipError_t launch(const TapeLaunch &t, hipStream_t stream) {
 extern "C" hipError_t pipk_launch_tape_eval(const TapeLaunch *t, hipStream_t stream) {
   if (t->n_points <= 0) return hipSuccess;
   // (the caller checked: slots <= TAPE_MAX_SLOTS, and a staged program fits TAPE_LDS_BYTES beside the slots)
-  return t->bits == 128 ? launch<i128>(*t, stream) : launch<i64>(*t, stream);
+  if (t->marks) return t->bits == 128 ? launch<i128, true>(*t, stream) : launch<i64, true>(*t, stream);
+  return t->bits == 128 ? launch<i128, false>(*t, stream) : launch<i64, false>(*t, stream);
+}
+
+extern "C" hipError_t pipk_launch_tape_set_eval(const TapeSetLaunch *t, hipStream_t stream) {
+  if (t->n_points <= 0) return hipSuccess;
+  // (pipamd_tape_set_create checked: slots <= TAPE_MAX_SLOTS, every jump inside its own tape's words)
+  return t->bits == 128 ? launch_set<i128>(*t, stream) : launch_set<i64>(*t, stream);
 }

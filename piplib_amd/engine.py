@@ -1087,14 +1087,38 @@ def _tape_fn(name, bits):
     return getattr(L, name)
 
 
-def tape_check(cells, nvar, nparm, ndual=0, bits=64, reserved=0):
+SOL_SHIFT, SOL_NEGATE, SOL_REMOVE, SOL_DUAL = 1, 2, 4, 8
+
+
+class TapeEdit(C.Structure):
+    """pipamd_tape_edit: what pip_solve passes to sol_quast_edit"""
+    _fields_ = [(n, C.c_int32) for n in ("sol_bg", "urs_parms", "sol_flags", "reserved")]
+
+
+def _tape_edit(edit):
+    """None, a dict with sol_bg / urs_parms / sol_flags (the dict of pipamd_pip_info will do; "reserved" is passed on if
+    present) or a PipInfo -> TapeEdit or None"""
+    if edit is None:
+        return None
+    get = edit.get if isinstance(edit, dict) else (lambda k, d=0: getattr(edit, k, d))
+    return TapeEdit(int(get("sol_bg", 0)), int(get("urs_parms", 0)), int(get("sol_flags", 0)), int(get("reserved", 0)))
+
+
+def tape_check(cells, nvar, nparm, ndual=0, bits=64, reserved=0, edit=None):
     """pipamd_tape_check / pipamd_tape_check128 on cells [(kind, param1, param2), ...]: the dict of pipamd_tape_info, or
-    TapeError where the tape is refused.  Host only: needs neither an engine nor a GPU."""
-    fn = _tape_fn("pipamd_tape_check", bits)
-    fn.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(TapeShape), C.POINTER(TapeInfo)]
+    TapeError where the tape is refused.  With `edit` (see Tape): pipamd_tape_check_pip / _pip128.  Host only: needs
+    neither an engine nor a GPU."""
     arr = _cell_array(cells, bits)
     info = TapeInfo()
-    rc = fn(arr, len(cells), C.byref(TapeShape(int(nvar), int(nparm), int(ndual), int(reserved))), C.byref(info))
+    shape = TapeShape(int(nvar), int(nparm), int(ndual), int(reserved))
+    if edit is not None:
+        fn = _tape_fn("pipamd_tape_check_pip", bits)
+        fn.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(TapeShape), C.POINTER(TapeEdit), C.POINTER(TapeInfo)]
+        rc = fn(arr, len(cells), C.byref(shape), C.byref(_tape_edit(edit)), C.byref(info))
+    else:
+        fn = _tape_fn("pipamd_tape_check", bits)
+        fn.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(TapeShape), C.POINTER(TapeInfo)]
+        rc = fn(arr, len(cells), C.byref(shape), C.byref(info))
     if rc != 0:
         raise TapeError(rc, lib().pipamd_last_error().decode())
     return info.as_dict()
@@ -1103,21 +1127,32 @@ def tape_check(cells, nvar, nparm, ndual=0, bits=64, reserved=0):
 class Tape:
     """A solution tape compiled for one engine's device (pipamd_tape_compile), to be evaluated at parameter points
     (pipamd_tape_eval): solve a parametric problem once -- solve_tableau_cells, traiter, traiter_many -- and ask for the
-    unknowns at as many points as needed.  The evaluator knows no context and applies none of pip_solve's result edits
-    (include/piplib_amd.h)."""
+    unknowns at as many points as needed.  The evaluator knows no context.  `edit` -- a dict or PipInfo with sol_bg,
+    urs_parms and sol_flags, as pip_solve_many hands them out -- applies pip_solve's result edits
+    (pipamd_tape_compile_pip, include/piplib_amd.h): a point then has `point_cols` values, the parameters as pip_solve's
+    caller numbers them; nparm stays the parameter count of the tape as solved."""
     OUTPUTS = ("status", "leaf", "x_num", "x_den", "dual_num", "dual_den")
 
-    def __init__(self, engine, cells, nvar, nparm, ndual=0, bits=64):
+    def __init__(self, engine, cells, nvar, nparm, ndual=0, bits=64, edit=None):
         import torch
         self.torch = torch
         self.e = engine
         self.nvar, self.nparm, self.ndual, self.bits = int(nvar), int(nparm), int(ndual), int(bits)
-        self.info = tape_check(cells, nvar, nparm, ndual, bits)
-        fn = _tape_fn("pipamd_tape_compile", bits)
-        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(TapeShape), C.POINTER(C.c_void_p)]
+        self.info = tape_check(cells, nvar, nparm, ndual, bits, edit=edit)
         self._h = C.c_void_p()
         arr = _cell_array(cells, bits)
-        _check(fn(engine._h, arr, len(cells), C.byref(TapeShape(self.nvar, self.nparm, self.ndual, 0)), C.byref(self._h)))
+        shape = TapeShape(self.nvar, self.nparm, self.ndual, 0)
+        if edit is not None:
+            fn = _tape_fn("pipamd_tape_compile_pip", bits)
+            fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(TapeShape), C.POINTER(TapeEdit), C.POINTER(C.c_void_p)]
+            _check(fn(engine._h, arr, len(cells), C.byref(shape), C.byref(_tape_edit(edit)), C.byref(self._h)))
+        else:
+            fn = _tape_fn("pipamd_tape_compile", bits)
+            fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(TapeShape), C.POINTER(C.c_void_p)]
+            _check(fn(engine._h, arr, len(cells), C.byref(shape), C.byref(self._h)))
+        pc = lib().pipamd_tape_point_cols
+        pc.argtypes = [C.c_void_p]
+        self.point_cols = int(pc(self._h))
         self.dev = torch.device("cuda", engine.device)
 
     def close(self):
@@ -1136,11 +1171,11 @@ class Tape:
         """-> (count, device tensor or None)"""
         t = self.torch
         if isinstance(points, int):
-            assert self.nparm == 0, "a count stands for points only when the tape has no parameters"
+            assert self.point_cols == 0, "a count stands for points only when the tape has no parameters"
             return points, None
         points = (points if t.is_tensor(points) else t.as_tensor(points, dtype=t.int64)).to(device=self.dev, dtype=t.int64)
-        points = points.reshape(points.shape[0], self.nparm).contiguous()
-        return int(points.shape[0]), (points if self.nparm else None)
+        points = points.reshape(points.shape[0], self.point_cols).contiguous()
+        return int(points.shape[0]), (points if self.point_cols else None)
 
     def outputs(self, n, names=OUTPUTS):
         """fresh device tensors for `n` points: int32 status and leaf, int64 (n, nvar) / (n, ndual) values with a trailing
@@ -1164,9 +1199,100 @@ class Tape:
         return out
 
     def eval(self, points, stream=None):
-        """the tape at `points`, (n, nparm) int64 on the host or the device (an int n when the tape has no parameters):
+        """the tape at `points`, (n, point_cols) int64 on the host or the device (an int n when the tape has no parameters):
         device tensors (status, leaf, x_num, x_den) and, with ndual > 0, (dual_num, dual_den).  Does not synchronise."""
         n, pts = self._points(points)
         names = self.OUTPUTS if self.ndual else self.OUTPUTS[:4]
         out = self.eval_into(pts if pts is not None else n, self.outputs(n, names), stream)
+        return tuple(out[k] for k in names)
+
+
+class TapeSetInfo(C.Structure):
+    """pipamd_tape_set_info"""
+    _fields_ = [("words", C.c_int64)] + [(n, C.c_int32) for n in ("n", "bits", "point_cols", "nvar", "ndual", "slots")]
+
+    def as_dict(self):
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class TapeSet:
+    """Compiled tapes (Tape objects of one engine and one width, edited or not) evaluated in ONE launch
+    (pipamd_tape_set_create / pipamd_tape_set_eval): point k is of tape tape_index[k].  Points, unknowns and dual values
+    are padded to the set's maxima (info["point_cols"], info["nvar"], info["ndual"]); a tape reads its first columns and
+    values beyond its own counts are (0, 0).  The tapes may be closed once the set exists."""
+    OUTPUTS = Tape.OUTPUTS
+
+    def __init__(self, engine, tapes):
+        import torch
+        self.torch = torch
+        self.e = engine
+        L = lib()
+        if not hasattr(L, "pipamd_tape_set_create"):
+            raise RuntimeError("libpipamd has no pipamd_tape_set_create: rebuild the library")
+        fn = L.pipamd_tape_set_create
+        fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(TapeSetInfo)]
+        n = len(tapes)
+        arr = (C.c_void_p * max(1, n))(*[t._h.value if isinstance(t, Tape) else t for t in tapes])
+        self._h = C.c_void_p()
+        info = TapeSetInfo()
+        rc = fn(engine._h, n, arr, C.byref(self._h), C.byref(info))
+        if rc != 0:
+            raise TapeError(rc, L.pipamd_last_error().decode())
+        self.info = info.as_dict()
+        self.n, self.bits = self.info["n"], self.info["bits"]
+        self.point_cols, self.nvar, self.ndual = self.info["point_cols"], self.info["nvar"], self.info["ndual"]
+        self.dev = torch.device("cuda", engine.device)
+
+    def close(self):
+        if self._h:
+            lib().pipamd_tape_set_free.argtypes = [C.c_void_p]
+            lib().pipamd_tape_set_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _args(self, tape_index, points):
+        t = self.torch
+        idx = (tape_index if t.is_tensor(tape_index) else t.as_tensor(tape_index, dtype=t.int32))
+        idx = idx.to(device=self.dev, dtype=t.int32).reshape(-1).contiguous()
+        n = int(idx.shape[0])
+        if points is None:
+            assert self.point_cols == 0, "points may be left out only when no tape of the set has parameters"
+            return n, idx, None
+        points = (points if t.is_tensor(points) else t.as_tensor(points, dtype=t.int64)).to(device=self.dev, dtype=t.int64)
+        points = points.reshape(n, self.point_cols).contiguous()
+        return n, idx, (points if self.point_cols else None)
+
+    def outputs(self, n, names=OUTPUTS):
+        """fresh device tensors for `n` points, shaped by the set's maxima (a trailing 2 for a 128-bit set)"""
+        t = self.torch
+        ew = (2,) if self.bits == 128 else ()
+        shapes = {"status": ((n,), t.int32), "leaf": ((n,), t.int32), "x_num": ((n, self.nvar) + ew, t.int64),
+                  "x_den": ((n, self.nvar) + ew, t.int64), "dual_num": ((n, self.ndual) + ew, t.int64),
+                  "dual_den": ((n, self.ndual) + ew, t.int64)}
+        return {k: t.empty(shapes[k][0], dtype=shapes[k][1], device=self.dev) for k in names}
+
+    def eval_into(self, tape_index, points, out, stream=None):
+        """pipamd_tape_set_eval into the tensors of `out`, a dict by the names of OUTPUTS; a name that is missing is
+        passed as NULL.  One launch on `stream` (a raw hipStream_t handle; default: torch's current stream), no
+        synchronisation."""
+        n, idx, pts = self._args(tape_index, points)
+        fn = lib().pipamd_tape_set_eval
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 9
+        st = C.c_void_p(stream) if stream is not None else C.c_void_p(self.torch.cuda.current_stream(self.dev).cuda_stream)
+        ptrs = [C.c_void_p(out[k].data_ptr()) if out.get(k) is not None else None for k in self.OUTPUTS]
+        _check(fn(self.e._h, self._h, n, C.c_void_p(idx.data_ptr()) if n else None,
+                  C.c_void_p(pts.data_ptr()) if pts is not None and n else None, *ptrs, st))
+        return out
+
+    def eval(self, tape_index, points, stream=None):
+        """the set at `points`, (n, point_cols) int64, point k of tape tape_index[k]: device tensors (status, leaf, x_num,
+        x_den) and, where a tape of the set has dual lists, (dual_num, dual_den).  Does not synchronise."""
+        n, idx, pts = self._args(tape_index, points)
+        names = self.OUTPUTS if self.ndual else self.OUTPUTS[:4]
+        out = self.eval_into(idx, pts, self.outputs(n, names), stream)
         return tuple(out[k] for k in names)
