@@ -57,7 +57,8 @@ extern "C" {
  * pipamd_tape_compile / pipamd_tape_eval / pipamd_tape_free and the 128-bit forms of the first two (and
  * pipamd_tape_check_pip / pipamd_tape_compile_pip with pip_solve's result edits, pipamd_tape_point_cols,
  * pipamd_tape_set_create / _eval / _free for many tapes in one launch) -- a tape evaluated at
- * many parameter points, a lane per point. */
+ * many parameter points, a lane per point; pipamd_tape_sweep_plan / pipamd_tape_sweep -- a tape swept over a box of
+ * points the kernel makes itself, under a context (PIPAMD_ST_OUTSIDE), with a summary reduced on the device. */
 #define PIPAMD_VERSION 500
 
 /* ---- error codes (return values) ---- */
@@ -96,6 +97,7 @@ extern "C" {
 #define PIPAMD_ST_INTERNAL 8
 #define PIPAMD_ST_MAXCOL 9       /* "Too many variables" (integrer.c:324) */
 #define PIPAMD_ST_BADINPUT 10    /* a system the load could not take (see pipamd_batch_load_matrices, _sparse, _instances) */
+#define PIPAMD_ST_OUTSIDE 11     /* pipamd_tape_sweep alone: the point violates a row of the context */
 
 /* ---- row flags (reference tab.h:55-62) ---- */
 #define PIPAMD_F_UNIT 1
@@ -729,8 +731,9 @@ int pipamd_device_tree_fits(const pipamd_problem *p, int entier_bits);
  * 128-bit cells: points are int64, new parameters and results __int128; the products and the running sums of a form
  * are checked against 128 bits in cell order -- coefficients 0 .. P-1, then the constant -- and the first that leaves
  * them ends the point PIPAMD_ST_RANGE.  Such a point does not disturb the others of the call.
- * NOT done here, the caller's business: the evaluator knows no context -- points outside the context the problem was
- * solved under, or negative ones, are evaluated like any other, as pipamd_batch_load_instances solves them; and a big
+ * NOT done here, the caller's business: pipamd_tape_eval knows no context -- points outside the context the problem was
+ * solved under, or negative ones, are evaluated like any other, as pipamd_batch_load_instances solves them
+ * (pipamd_tape_sweep below tests the points of a box against the context's rows and marks them); and a big
  * parameter the CALLER gave is just another column of the points.  The edits pip_solve makes to its result
  * (sol_quast_edit, piplib.c:866) are applied by pipamd_tape_compile_pip below, with one limit: dual lists are handed out
  * one pair per tableau row as they stand (sol_quast_edit edits them with flags 0, sol.c:706-708); the merge of an
@@ -862,6 +865,63 @@ void pipamd_tape_set_free(pipamd_tape_set *s);
 int pipamd_tape_set_eval(pipamd_engine *e, const pipamd_tape_set *s, int64_t n_points, const int32_t *d_tape,
                          const int64_t *d_points, int32_t *d_status, int32_t *d_leaf, int64_t *d_x_num, int64_t *d_x_den,
                          int64_t *d_dual_num, int64_t *d_dual_den, void *stream);
+
+/* A tape swept over a box of integer points, under a context, with a summary reduced on the device (added since
+ * interface version 500).  The kernel makes the points itself -- nothing is uploaded for the box --, tests each against
+ * the context's rows exactly, walks the tape as pipamd_tape_eval does, and reduces integer figures on chip; the six
+ * per-point arrays are optional, so a box far larger than memory for its answers can still be counted.
+ *
+ * pipamd_tape_sweep_plan is host only: it needs neither an engine nor a GPU; `info` comes from pipamd_tape_check*,
+ * `bits` (64 or 128) is the tape's cell width, `point_cols` what pipamd_tape_point_cols gives (nparm without an edit).
+ * PIPAMD_E_INVALID: null info or plan; bits not 64 or 128; point_cols outside 0 .. PIPAMD_TAPE_MAX_SLOTS - 1; null lo or
+ * hi with point_cols > 0; any lo[c] > hi[c].  PIPAMD_E_TOOLARGE: n_points >= 2^38, pipamd_tape_eval's limit; the product
+ * is formed without wrapping (lo = INT64_MIN, hi = INT64_MAX in one column is a legal question, answered TOOLARGE).
+ * plan.binned: 1 exactly when 16 * (info.leaves + 4) bytes fit within PIPAMD_TAPE_LDS_BYTES beside the slots
+ * (128 * (info.slots - 1) values of bits / 8 bytes) and beside the program (8 * info.words) where info.staged. */
+struct pipamd_tape_sweep_plan { /* (a struct tag only: the function below has the name, so no typedef can) */
+  int64_t n_points;      /* prod (hi[c] - lo[c] + 1); 1 when point_cols == 0 */
+  int64_t summary_words; /* 8 + 2 * info->leaves */
+  int32_t binned;        /* 1: per-leaf figures are gathered in LDS per workgroup; 0: wave-aggregated global atomics */
+  int32_t reserved;
+}; /* 24 bytes */
+int pipamd_tape_sweep_plan(const pipamd_tape_info *info, int bits, int point_cols, const int64_t *lo, const int64_t *hi,
+                           struct pipamd_tape_sweep_plan *plan);
+/* The summary: plan.summary_words int64 on the device, L = info.leaves.  Counts of the points that ended SOLUTION, NIL,
+ * RANGE, OUTSIDE; the smallest k with that status (-1: none); per leaf ordinal (LIST and NIL items, as d_leaf counts
+ * them) the points that reached it, and the smallest such k (-1: none).  All figures are order-independent integers:
+ * the summary is deterministic.  A caller can rely on: words 0..3 sum to n_points; the leaf counts sum to SOLUTION + NIL
+ * (for an empty tape every inside point is NIL with leaf -1, and the leaf counts sum to 0). */
+#define PIPAMD_SWEEP_COUNT 0            /* + PIPAMD_SWEEP_SOLUTION .. PIPAMD_SWEEP_OUTSIDE */
+#define PIPAMD_SWEEP_FIRST 4            /* + the same */
+#define PIPAMD_SWEEP_SOLUTION 0
+#define PIPAMD_SWEEP_NIL 1
+#define PIPAMD_SWEEP_RANGE 2
+#define PIPAMD_SWEEP_OUTSIDE 3
+#define PIPAMD_SWEEP_LEAF_COUNT(L) 8    /* + leaf ordinal */
+#define PIPAMD_SWEEP_LEAF_FIRST(L) (8 + (L)) /* + leaf ordinal */
+#define PIPAMD_SWEEP_WORDS(L) (8 + 2 * (L))
+/* Box: lo and hi are HOST arrays of pipamd_tape_point_cols(t) values, bounds inclusive.  Point k of 0 .. n_points-1 is
+ * the box in row-major order, the last column fastest: column c holds lo[c] + digit_c(k) -- the order and the values of
+ * numpy.indices / itertools.product.
+ * Context: d_ctx is a DEVICE array of n_ctx x ctx_cols int64 laid out as PolyLib lays out ineqpar: marker, point_cols
+ * coefficients, constant; ctx_cols must be point_cols + 2 when n_ctx > 0.  Marker 0: the row is an equality; any other
+ * marker: >= 0 (the reference's piplib_int_zero(p[i][0]), piplib.c:671).  Coefficients are int64 for tapes of either
+ * cell width, and a row's value sum a_j theta_j + b is decided exactly whatever single products or partial sums do.  A
+ * point that fails any row ends PIPAMD_ST_OUTSIDE, leaf -1, (0, 0) throughout; the tape is not walked for it.
+ * n_ctx == 0: every point is inside.  The columns are the point columns: pip_solve's ineqpar can be passed as it stands
+ * when the tape was compiled with pip_solve's edit (pipamd_tape_compile_pip) or when that edit drops no column (no big
+ * parameter removed, no Urs_parms); for a tape compiled without an edit the rows must be given over the tape's own
+ * nparm columns.
+ * Outputs: the six arrays of pipamd_tape_eval, indexed by k; each may be NULL, and all may be.  For every point that is
+ * not OUTSIDE they hold what pipamd_tape_eval writes for that point, bit for bit.  d_summary (may be NULL) is
+ * initialised by the call on `stream` before the kernel: callers need not, and two calls do not accumulate.
+ * A fill of the summary and one kernel on `stream`, no synchronisation; the call may run concurrently on several
+ * streams with different output buffers.  PIPAMD_E_INVALID before any HIP call: whatever the planner refuses; a null
+ * engine or tape; a tape of another device; n_ctx < 0; n_ctx > 0 with a null d_ctx or ctx_cols != point_cols + 2.
+ * PIPAMD_E_TOOLARGE as the planner. */
+int pipamd_tape_sweep(pipamd_engine *e, const pipamd_tape *t, const int64_t *lo, const int64_t *hi, int n_ctx, int ctx_cols,
+                      const int64_t *d_ctx, int64_t *d_summary, int32_t *d_status, int32_t *d_leaf, int64_t *d_x_num,
+                      int64_t *d_x_den, int64_t *d_dual_num, int64_t *d_dual_den, void *stream);
 
 #ifdef __cplusplus
 }

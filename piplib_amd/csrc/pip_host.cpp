@@ -45,6 +45,7 @@ extern "C" int pipamd_engine_create(pipamd_engine **out, int device) {
   if (!e) return PIPAMD_E_NOMEM;
   e->device = device;
   e->iter_limit = PIPAMD_DETLOG;
+  if (hipDeviceGetAttribute(&e->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || e->cus < 1) e->cus = 1;
   {
     const char *nl = getenv("PIPAMD_NO_LEAN");  // measurement aid, like pipamd_debug_lean(e, 0)
     e->no_lean = nl && nl[0] == '1';
@@ -1606,6 +1607,106 @@ extern "C" int pipamd_tape_eval(pipamd_engine *e, const pipamd_tape *t, int64_t 
   L.dual_num = d_dual_num;
   L.dual_den = d_dual_den;
   HIPCHK(pipk_launch_tape_eval(&L, (hipStream_t)stream));
+  return PIPAMD_OK;
+}
+
+// ------------------------------------------------------------------ a tape swept over a box of points
+// The box's arithmetic, shared by the planner and the sweep: extents and their product, formed without wrapping.
+static int tape_sweep_box(const char *who, int point_cols, const int64_t *lo, const int64_t *hi, unsigned long long *ext,
+                          int64_t *n_points) {
+  if (point_cols < 0 || point_cols > TAPE_MAX_SLOTS - 1 || (point_cols > 0 && (!lo || !hi))) {
+    pipamd_set_error("%s: %d point columns (0 .. %d), or a box without bounds", who, point_cols, TAPE_MAX_SLOTS - 1);
+    return PIPAMD_E_INVALID;
+  }
+  for (int c = 0; c < point_cols; c++)
+    if (lo[c] > hi[c]) {
+      pipamd_set_error("%s: column %d: lo %lld above hi %lld", who, c, (long long)lo[c], (long long)hi[c]);
+      return PIPAMD_E_INVALID;
+    }
+  unsigned __int128 n = 1;  // (stays below 2^38 * 2^64)
+  for (int c = 0; c < point_cols; c++) {
+    // hi - lo in unsigned arithmetic is exact; + 1 wraps to 0 for the full range alone
+    const unsigned long long span = (unsigned long long)hi[c] - (unsigned long long)lo[c];
+    n *= (unsigned __int128)span + 1;
+    if (n >= ((unsigned __int128)1 << 38)) {
+      pipamd_set_error("%s: the box has 2^38 points or more (at most 2^38 - 1 a call)", who);
+      return PIPAMD_E_TOOLARGE;
+    }
+    if (ext) ext[c] = span + 1;
+  }
+  *n_points = (int64_t)n;
+  return PIPAMD_OK;
+}
+
+extern "C" int pipamd_tape_sweep_plan(const pipamd_tape_info *info, int bits, int point_cols, const int64_t *lo,
+                                      const int64_t *hi, struct pipamd_tape_sweep_plan *plan) {
+  if (!info || !plan || (bits != 64 && bits != 128)) {
+    pipamd_set_error("tape_sweep_plan: null info or plan, or bits other than 64 and 128");
+    return PIPAMD_E_INVALID;
+  }
+  int64_t n = 0;
+  const int rc = tape_sweep_box("tape_sweep_plan", point_cols, lo, hi, nullptr, &n);
+  if (rc) return rc;
+  plan->n_points = n;
+  plan->summary_words = PIPAMD_SWEEP_WORDS(info->leaves);
+  const unsigned __int128 lds = (unsigned __int128)tape_slot_bytes(info->slots > 0 ? info->slots : 1, bits) +
+                                (info->staged ? (unsigned __int128)8 * (unsigned long long)info->words : 0) +
+                                (unsigned __int128)16 * ((unsigned long long)info->leaves + 4);
+  plan->binned = info->leaves >= 0 && lds <= (unsigned __int128)TAPE_LDS_BYTES;
+  plan->reserved = 0;
+  return PIPAMD_OK;
+}
+
+static int g_tape_sweep_blocks;  // pipamd_debug_tape_sweep_blocks
+// Testing aid: at most n workgroups for the sweeps that follow (0: the default bound), so that small boxes drive the
+// kernel's grid-stride loop.
+extern "C" int pipamd_debug_tape_sweep_blocks(int n) {
+  if (n < 0) return PIPAMD_E_INVALID;
+  g_tape_sweep_blocks = n;
+  return PIPAMD_OK;
+}
+
+extern "C" int pipamd_tape_sweep(pipamd_engine *e, const pipamd_tape *t, const int64_t *lo, const int64_t *hi, int n_ctx,
+                                 int ctx_cols, const int64_t *d_ctx, int64_t *d_summary, int32_t *d_status, int32_t *d_leaf,
+                                 int64_t *d_x_num, int64_t *d_x_den, int64_t *d_dual_num, int64_t *d_dual_den, void *stream) {
+  if (!e || !t || t->device != e->device || n_ctx < 0 || (n_ctx > 0 && (!d_ctx || ctx_cols != t->point_cols + 2))) {
+    pipamd_set_error("tape_sweep: null engine or tape, a tape of another device, n_ctx < 0, or context rows without an "
+                     "array of point_cols + 2 columns");
+    return PIPAMD_E_INVALID;
+  }
+  TapeSweepLaunch L;
+  memset(&L, 0, sizeof L);
+  struct pipamd_tape_sweep_plan plan;
+  int rc = tape_sweep_box("tape_sweep", t->point_cols, lo, hi, L.ext, &plan.n_points);
+  if (rc) return rc;
+  rc = pipamd_tape_sweep_plan(&t->info, t->bits, t->point_cols, lo, hi, &plan);
+  if (rc) return rc;
+  if (hipSetDevice(e->device) != hipSuccess) return PIPAMD_E_HIP;
+  L.t.prog = t->d_prog;
+  L.t.words = t->info.words;
+  L.t.bits = t->bits;
+  L.t.staged = t->info.staged;
+  L.t.marks = t->marks;
+  L.t.nvar = t->shape.nvar;
+  L.t.nparm = t->point_cols;
+  L.t.ndual = t->shape.ndual;
+  L.t.slots = t->info.slots;
+  L.t.n_points = plan.n_points;
+  L.t.status = d_status;
+  L.t.leaf = d_leaf;
+  L.t.x_num = d_x_num;
+  L.t.x_den = d_x_den;
+  L.t.dual_num = d_dual_num;
+  L.t.dual_den = d_dual_den;
+  L.n_ctx = n_ctx;
+  L.ctx = (const long long *)d_ctx;
+  L.summary = (long long *)d_summary;
+  L.leaves = t->info.leaves;
+  L.binned = plan.binned;
+  for (int c = 0; c < t->point_cols; c++) L.lo[c] = lo[c];
+  L.cus = e->cus;
+  L.max_blocks = g_tape_sweep_blocks;
+  HIPCHK(pipk_launch_tape_sweep(&L, (hipStream_t)stream));
   return PIPAMD_OK;
 }
 

@@ -61,6 +61,7 @@ struct pipamd_engine {
   int grow_step;     /* testing aid: rows added per growth round (0 = double) */
   int last_rehoused; /* tableaux the last pipamd_batch_solve re-housed (all rounds) */
   struct BatchRun *run; /* the batch solve in progress (pipamd_batch_solve_async .. pipamd_batch_wait) */
+  int cus;           /* compute units of the device: the bound of pipamd_tape_sweep's persistent grid */
 };
 
 void pipamd_set_error(const char *fmt, ...);

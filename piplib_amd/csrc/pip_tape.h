@@ -74,7 +74,33 @@ struct TapeSetLaunch {
   void *x_num, *x_den, *dual_num, *dual_den;
 };
 
+// pipamd_tape_sweep: the points are those of a box, made by the kernel.  Point k, 0 <= k < n_points, is the box in
+// row-major order, the last column fastest: column c is lo[c] + digit_c(k), the digits of k in the mixed radix ext[].
+// A bounded grid of persistent workgroups takes the chunks of TAPE_BLOCK consecutive k in turn: as many as the device
+// holds at once (the occupancy of the instantiation with the launch's LDS, at most TAPE_SWEEP_WG_PER_CU a compute
+// unit, TAPE_SWEEP_WG_PER_CU_SUM with a summary).  The summary (piplib_amd.h, PIPAMD_SWEEP_*): the status figures are gathered per wave in registers; with `binned` they and a count and a minimum
+// per leaf are gathered per workgroup in LDS behind the slots and the staged program and flushed once; without `binned`
+// a wave's aggregates go to global atomics directly.
+enum {
+  TAPE_SWEEP_WG_PER_CU = 16,    // the grid's bound: workgroups per compute unit (8 waves per SIMD)
+  TAPE_SWEEP_WG_PER_CU_SUM = 8  // the same when a summary is asked for
+};
+static inline size_t tape_sweep_bin_bytes(long long leaves) { return 16 * ((size_t)leaves + 4); }
+struct TapeSweepLaunch {
+  TapeLaunch t;           // the program and the outputs; t.points is not read; t.n_points = prod ext[c]
+  int n_ctx;              // rows of the context
+  int binned;             // pipamd_tape_sweep_plan.binned
+  int cus;                // compute units of the device
+  int max_blocks;         // testing aid: at most this many workgroups (0: the bound above)
+  const long long *ctx;   // device; n_ctx x (t.nparm + 2): marker, coefficients, constant
+  long long *summary;     // device; 8 + 2 * leaves words, initialised by the launch; or NULL
+  long long leaves;
+  long long lo[TAPE_MAX_SLOTS - 1];
+  unsigned long long ext[TAPE_MAX_SLOTS - 1];  // hi[c] - lo[c] + 1, each below 2^38
+};
+
 extern "C" {
+hipError_t pipk_launch_tape_sweep(const TapeSweepLaunch *t, hipStream_t stream);
 hipError_t pipk_launch_tape_eval(const TapeLaunch *t, hipStream_t stream);
 hipError_t pipk_launch_tape_set_eval(const TapeSetLaunch *t, hipStream_t stream);
 }

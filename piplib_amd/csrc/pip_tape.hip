@@ -364,6 +364,191 @@ __global__ __launch_bounds__(TAPE_BLOCK) void pip_tape_set_eval_kernel(TapeSetLa
   tape_finish<T>(o, pt, st, leaf, sol ? nvar : 0, sol ? ndual : 0);
 }
 
+// ------------------------------------------------------------------ pipamd_tape_sweep
+// The points of a box, made here (TapeSweepLaunch, pip_tape.h).  gridDim.x persistent workgroups take the chunks of
+// TAPE_BLOCK consecutive k in turn; a staged program is copied to LDS once per workgroup.  Per chunk: the first k is
+// decoded into its mixed-radix digits from the last column -- wave-uniform divisions, in 32 bits where both operands
+// fit, none once the quotient is 0 --, and in the same pass lane t carries its offset t through them (a carry is at most 127: behind an extent of 2^16
+// and more it is 0 or 1, a compare; behind a smaller one a 32-bit division).  The raw int64 point goes to slot rows
+// 0 .. cols-1 as int64 cells have them; the context's rows are tested on those by the int64 form_value (exact sign,
+// exactly zero iff ok && v == 0), read at a wave-uniform address; then 128-bit cells widen the rows in place, from the
+// last (row j moves to rows 2j, 2j+1 >= j, and a lane touches its own column alone).  A lane outside leaves the walk at
+// END with PIPAMD_ST_OUTSIDE; its wave still takes part in wave_min.
+// Summary: the four status counts and firsts are wave-uniform accumulators over all chunks of a wave (a ballot and a
+// popcount per status and chunk; the lowest set lane holds the smallest k, k growing with the lane).  Per leaf a wave
+// aggregates likewise -- the leaf of its first pending lane, the ballot of the lanes that share it -- and each group's
+// lowest lane adds (count, its k) to the workgroup's LDS bins (binned) or to the summary in global memory, all groups in
+// one atomic instruction pair.  At the end the bins -- with the waves' status figures added -- are flushed, one 64-bit
+// atomicAdd and one unsigned atomicMin per non-empty bin; -1, all ones, is the minimum's identity.  Without
+// bins a wave flushes its status figures itself.
+// OUT / SUM: per-point arrays / a summary are asked for; what is not costs no instruction in the loop.
+__device__ __forceinline__ int sweep_class(int st) {
+  return st == PIPAMD_ST_SOLUTION ? PIPAMD_SWEEP_SOLUTION
+                                  : (st == PIPAMD_ST_NIL ? PIPAMD_SWEEP_NIL : (st == PIPAMD_ST_OUTSIDE ? PIPAMD_SWEEP_OUTSIDE : PIPAMD_SWEEP_RANGE));
+}
+__device__ __forceinline__ bool sweep_zero_word(i64 i, i64 L) { return i < PIPAMD_SWEEP_FIRST || (i >= 8 && i < 8 + L); }
+
+__global__ void pip_tape_sweep_fill_kernel(i64 *sum, i64 L) {
+  const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < PIPAMD_SWEEP_WORDS(L)) sum[i] = sweep_zero_word(i, L) ? 0 : -1;
+}
+
+template <class T, bool STAGED, bool MARKS, bool OUT, bool SUM>
+__global__ __launch_bounds__(TAPE_BLOCK) void pip_tape_sweep_kernel(TapeSweepLaunch a) {
+  typedef Width<T> W;
+  constexpr int EW = W::EW;
+  extern __shared__ __attribute__((aligned(16))) i64 tape_lds[];
+  i64 *S = tape_lds;  // (slots - 1) * EW rows of TAPE_BLOCK words
+  const int tid = threadIdx.x, lane = tid & 63, nvar = a.t.nvar, ndual = a.t.ndual, cols = a.t.nparm;
+  const int words = (int)a.t.words;
+  const i64 n = a.t.n_points, L = a.leaves;
+  const i64 *prog = a.t.prog;
+  i64 *behind = tape_lds + (size_t)(a.t.slots - 1) * EW * TAPE_BLOCK;
+  if (STAGED) {
+    for (int i = tid; i < words; i += TAPE_BLOCK) behind[i] = a.t.prog[i];
+    prog = behind;
+    behind += words;
+  }
+  u64 *bins = (u64 *)behind;  // binned: the summary's PIPAMD_SWEEP_WORDS(L) words, for this workgroup
+  u64 *sum = (u64 *)a.summary;
+  const bool binned = SUM && a.binned;
+  if (binned)
+    for (i64 i = tid; i < PIPAMD_SWEEP_WORDS(L); i += TAPE_BLOCK) bins[i] = sweep_zero_word(i, L) ? 0 : ~(u64)0;
+  if (STAGED || SUM) __syncthreads();
+  TapeOut o;
+  o.status = OUT ? a.t.status : nullptr, o.leaf = OUT ? a.t.leaf : nullptr;
+  o.x_num = OUT ? a.t.x_num : nullptr, o.x_den = OUT ? a.t.x_den : nullptr;
+  o.dual_num = OUT ? a.t.dual_num : nullptr, o.dual_den = OUT ? a.t.dual_den : nullptr;
+  o.xs = nvar, o.ds = ndual;
+  u64 cnt[4] = {0, 0, 0, 0}, first[4] = {~(u64)0, ~(u64)0, ~(u64)0, ~(u64)0};
+
+  for (i64 k0 = (i64)blockIdx.x * TAPE_BLOCK; k0 < n; k0 += (i64)gridDim.x * TAPE_BLOCK) {
+    const i64 pt = k0 + tid;
+    const bool live = pt < n;
+    u64 rem = (u64)k0;
+    unsigned carry = (unsigned)tid;
+    for (int c = cols - 1; c >= 0; c--) {
+      const u64 ext = a.ext[c];
+      u64 s = carry;
+      if (rem) {  // (wave-uniform; operands of 32 bits, every box below 2^32 points, divide in 32)
+        const u64 q = ((rem | ext) >> 32) ? rem / ext : (u64)((unsigned)rem / (unsigned)ext);
+        s += rem - q * ext;
+        rem = q;
+      }
+      if (ext >> 16) {
+        carry = s >= ext;
+        s -= carry ? ext : 0;
+      } else {
+        const unsigned q = (unsigned)s / (unsigned)ext;
+        s = (unsigned)s - q * (unsigned)ext;
+        carry = q;
+      }
+      S[c * TAPE_BLOCK + tid] = (i64)((u64)a.lo[c] + s);
+    }
+    bool inside = live;
+    for (int r = 0; r < a.n_ctx; r++) {
+      const i64 *row = a.ctx + (size_t)r * (cols + 2);
+      const FormValue f = form_value(row + 1, cols, S, tid, (i64 *)nullptr);
+      inside = inside && (row[0] == 0 ? f.ok && f.v == 0 : !f.neg);
+    }
+    if (EW == 2)
+      for (int j = cols - 1; j >= 0; j--) W::set_slot(S, j, tid, (T)S[j * TAPE_BLOCK + tid]);
+
+    int st = live && !inside ? PIPAMD_ST_OUTSIDE : PIPAMD_ST_NIL, leaf = -1;
+    tape_walk<T, MARKS>(prog, inside && words ? 0 : END, S, tid, nvar, ndual, pt, o, st, leaf);
+    if (OUT && live) {
+      if (st != PIPAMD_ST_SOLUTION) {
+        tape_finish<T>(o, pt, st, leaf, 0, 0);  // (0, 0) throughout
+      } else {
+        if (o.status) o.status[pt] = st;
+        if (o.leaf) o.leaf[pt] = leaf;
+      }
+    }
+    if (SUM) {
+      const int cls = sweep_class(st);
+      const u64 wave_k = (u64)(k0 + (tid & ~63));
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        const u64 m = __ballot(live && cls == i);
+        if (m) {
+          const u64 k = wave_k + (u64)(__ffsll((unsigned long long)m) - 1);
+          cnt[i] += (u64)__popcll(m);
+          first[i] = k < first[i] ? k : first[i];
+        }
+      }
+      // per leaf: every lane learns its group's size and whether it is the group's lowest lane; the leaders then add
+      // (size, their k) in one atomic instruction pair for the whole wave -- no memory operation inside the loop
+      u64 pend = __ballot(live && leaf >= 0);
+      int group = 0;
+      bool leader = false;
+      while (pend) {
+        const int src = __ffsll((unsigned long long)pend) - 1;
+        const int l = __builtin_amdgcn_readlane(leaf, src);
+        const u64 m = __ballot(live && leaf == l);
+        if (live && leaf == l) {
+          group = __popcll(m);
+          leader = lane == src;
+        }
+        pend &= ~m;
+      }
+      if (leader && (u64)leaf < (u64)L) {  // (a compiled program's ordinals are below L; nothing is written beyond)
+        u64 *to = binned ? bins : sum;
+        atomicAdd(&to[PIPAMD_SWEEP_LEAF_COUNT(L) + leaf], (u64)group);
+        atomicMin(&to[PIPAMD_SWEEP_LEAF_FIRST(L) + leaf], (u64)pt);
+      }
+    }
+  }
+
+  if (SUM) {
+    if (lane == 0)
+      for (int i = 0; i < 4; i++)
+        if (cnt[i]) {
+          u64 *to = binned ? bins : sum;
+          atomicAdd(&to[PIPAMD_SWEEP_COUNT + i], cnt[i]);
+          atomicMin(&to[PIPAMD_SWEEP_FIRST + i], first[i]);
+        }
+    if (binned) {
+      __syncthreads();
+      for (i64 i = tid; i < 4 + L; i += TAPE_BLOCK) {
+        const i64 ci = i < 4 ? PIPAMD_SWEEP_COUNT + i : PIPAMD_SWEEP_LEAF_COUNT(L) + (i - 4);
+        const i64 fi = i < 4 ? PIPAMD_SWEEP_FIRST + i : PIPAMD_SWEEP_LEAF_FIRST(L) + (i - 4);
+        const u64 c = bins[ci];
+        if (c) {
+          atomicAdd(&sum[ci], c);
+          atomicMin(&sum[fi], bins[fi]);
+        }
+      }
+    }
+  }
+}
+
+template <class T, bool MARKS, bool OUT, bool SUM>
+hipError_t launch_sweep_as(const TapeSweepLaunch &s, hipStream_t stream) {
+  size_t lds = tape_slot_bytes(s.t.slots, s.t.bits) + (s.t.staged ? (size_t)s.t.words * 8 : 0);
+  if (SUM && s.binned) lds += tape_sweep_bin_bytes(s.leaves);
+  void (*kernel)(TapeSweepLaunch) = s.t.staged ? pip_tape_sweep_kernel<T, true, MARKS, OUT, SUM> : pip_tape_sweep_kernel<T, false, MARKS, OUT, SUM>;
+  // the grid: as many workgroups as the device holds at once with this kernel's registers and this launch's LDS (a
+  // workgroup that waited for room would start its share of the chunks late), no more than there are chunks
+  int per_cu = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, TAPE_BLOCK, lds) != hipSuccess || per_cu < 1) per_cu = 1;
+  // (with a summary every workgroup ends with an atomic add on the few words all share, and they end together: fewer,
+  // longer-lived workgroups keep that queue short -- measured)
+  const int bound = SUM ? TAPE_SWEEP_WG_PER_CU_SUM : TAPE_SWEEP_WG_PER_CU;
+  if (per_cu > bound) per_cu = bound;
+  const long long chunks = (s.t.n_points + TAPE_BLOCK - 1) / TAPE_BLOCK;
+  long long blocks = (long long)(s.cus > 0 ? s.cus : 1) * per_cu;
+  if (s.max_blocks > 0 && s.max_blocks < blocks) blocks = s.max_blocks;
+  if (chunks < blocks) blocks = chunks;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(TAPE_BLOCK), lds, stream, s);
+  return hipGetLastError();
+}
+template <class T, bool MARKS>
+hipError_t launch_sweep(const TapeSweepLaunch &s, hipStream_t stream) {
+  const bool out = s.t.status || s.t.leaf || s.t.x_num || s.t.x_den || s.t.dual_num || s.t.dual_den;
+  if (s.summary) return out ? launch_sweep_as<T, MARKS, true, true>(s, stream) : launch_sweep_as<T, MARKS, false, true>(s, stream);
+  return launch_sweep_as<T, MARKS, true, false>(s, stream);  // (nothing asked for: the walk with nothing to write)
+}
+
 template <class T, bool MARKS>
 hipError_t launch(const TapeLaunch &t, hipStream_t stream) {
   const long long blocks = (t.n_points + TAPE_BLOCK - 1) / TAPE_BLOCK;
@@ -389,6 +574,19 @@ extern "C" hipError_t pipk_launch_tape_eval(const TapeLaunch *t, hipStream_t str
   // (the caller checked: slots <= TAPE_MAX_SLOTS, and a staged program fits TAPE_LDS_BYTES beside the slots)
   if (t->marks) return t->bits == 128 ? launch<i128, true>(*t, stream) : launch<i64, true>(*t, stream);
   return t->bits == 128 ? launch<i128, false>(*t, stream) : launch<i64, false>(*t, stream);
+}
+
+extern "C" hipError_t pipk_launch_tape_sweep(const TapeSweepLaunch *s, hipStream_t stream) {
+  // (the caller checked: 1 <= n_points < 2^38, every extent's product within it, slots <= TAPE_MAX_SLOTS, the LDS the
+  // plan counted within TAPE_LDS_BYTES)
+  if (s->summary) {
+    const long long w = PIPAMD_SWEEP_WORDS(s->leaves);
+    hipLaunchKernelGGL(pip_tape_sweep_fill_kernel, dim3((unsigned)((w + 255) / 256)), dim3(256), 0, stream, s->summary, s->leaves);
+    const hipError_t he = hipGetLastError();
+    if (he != hipSuccess) return he;
+  }
+  if (s->t.marks) return s->t.bits == 128 ? launch_sweep<i128, true>(*s, stream) : launch_sweep<i64, true>(*s, stream);
+  return s->t.bits == 128 ? launch_sweep<i128, false>(*s, stream) : launch_sweep<i64, false>(*s, stream);
 }
 
 extern "C" hipError_t pipk_launch_tape_set_eval(const TapeSetLaunch *t, hipStream_t stream) {

@@ -1127,7 +1127,7 @@ def tape_check(cells, nvar, nparm, ndual=0, bits=64, reserved=0, edit=None):
 class Tape:
     """A solution tape compiled for one engine's device (pipamd_tape_compile), to be evaluated at parameter points
     (pipamd_tape_eval): solve a parametric problem once -- solve_tableau_cells, traiter, traiter_many -- and ask for the
-    unknowns at as many points as needed.  The evaluator knows no context.  `edit` -- a dict or PipInfo with sol_bg,
+    unknowns at as many points as needed.  eval() knows no context; sweep() tests the points of a box against one.  `edit` -- a dict or PipInfo with sol_bg,
     urs_parms and sol_flags, as pip_solve_many hands them out -- applies pip_solve's result edits
     (pipamd_tape_compile_pip, include/piplib_amd.h): a point then has `point_cols` values, the parameters as pip_solve's
     caller numbers them; nparm stays the parameter count of the tape as solved."""
@@ -1205,6 +1205,92 @@ class Tape:
         names = self.OUTPUTS if self.ndual else self.OUTPUTS[:4]
         out = self.eval_into(pts if pts is not None else n, self.outputs(n, names), stream)
         return tuple(out[k] for k in names)
+
+    def _box(self, lo, hi):
+        lo, hi = [int(v) for v in lo], [int(v) for v in hi]
+        assert len(lo) == len(hi) == self.point_cols, "a box has point_cols bounds on either side"
+        n = max(1, self.point_cols)
+        return (C.c_int64 * n)(*lo), (C.c_int64 * n)(*hi)
+
+    def sweep_plan(self, lo, hi):
+        """sweep_plan() for this tape: n_points, summary_words, binned"""
+        return sweep_plan(self.info, self.bits, self.point_cols, lo, hi)
+
+    def sweep_into(self, lo, hi, out, ctx=None, summary=None, stream=None):
+        """pipamd_tape_sweep: the tape at every integer point of the box lo .. hi (inclusive; point k is the box in
+        row-major order, the last column fastest, as numpy.indices has it) into the tensors of `out`, a dict by the names
+        of OUTPUTS; a name that is missing is passed as NULL, and `out` may be empty.  ctx: None, or a host or device
+        (n_ctx, point_cols + 2) int64 array of PolyLib rows (marker, coefficients, constant); a point that violates one
+        ends ST_OUTSIDE.  summary: None, a device int64 tensor of sweep_plan()["summary_words"], or True to allocate one.
+        Returns (summary or None, out).  A fill and one launch on `stream` (default: torch's current), no synchronisation."""
+        t = self.torch
+        fn = _tape_fn("pipamd_tape_sweep", 64)
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 9
+        clo, chi = self._box(lo, hi)
+        n_ctx, cptr = 0, None
+        if ctx is not None:
+            import numpy as np
+            ctx = (ctx if t.is_tensor(ctx) else t.as_tensor(np.asarray(ctx, dtype=np.int64).reshape(-1, self.point_cols + 2))).to(device=self.dev, dtype=t.int64)
+            ctx = ctx.reshape(-1, self.point_cols + 2).contiguous()
+            n_ctx = int(ctx.shape[0])
+            cptr = C.c_void_p(ctx.data_ptr()) if n_ctx else None
+        if summary is True:
+            summary = t.empty(8 + 2 * self.info["leaves"], dtype=t.int64, device=self.dev)
+        if summary is not None:
+            assert summary.dtype == t.int64 and summary.is_contiguous() and summary.numel() >= 8 + 2 * self.info["leaves"]
+        st = C.c_void_p(stream) if stream is not None else C.c_void_p(t.cuda.current_stream(self.dev).cuda_stream)
+        ptrs = [C.c_void_p(out[k].data_ptr()) if out.get(k) is not None else None for k in self.OUTPUTS]
+        rc = fn(self.e._h, self._h, clo, chi, n_ctx, self.point_cols + 2, cptr,
+                C.c_void_p(summary.data_ptr()) if summary is not None else None, *ptrs, st)
+        if rc in (-1, -3):
+            raise TapeError(rc, lib().pipamd_last_error().decode())
+        _check(rc)
+        self._ctx_alive = ctx  # (the rows stay allocated until the next sweep: the launch is asynchronous)
+        return summary, out
+
+    def sweep(self, lo, hi, ctx=None, outputs=OUTPUTS, stream=None):
+        """the tape over the box lo .. hi with a summary: (summary tensor, dict of the per-point tensors named in
+        `outputs`); outputs=() sweeps for the summary alone.  dual_num / dual_den are left out when the tape has no
+        dual lists.  See sweep_into and sweep_summary."""
+        names = tuple(k for k in outputs if self.ndual or not k.startswith("dual"))
+        n = self.sweep_plan(lo, hi)["n_points"]
+        return self.sweep_into(lo, hi, self.outputs(n, names), ctx, True, stream)
+
+
+ST_OUTSIDE = 11  # pipamd_tape_sweep: the point violates a row of the context (PIPAMD_ST_OUTSIDE)
+SWEEP_STATUS = (("solution", ST_SOLUTION), ("nil", ST_NIL), ("range", ST_RANGE), ("outside", ST_OUTSIDE))
+
+
+class TapeSweepPlan(C.Structure):
+    """struct pipamd_tape_sweep_plan"""
+    _fields_ = [("n_points", C.c_int64), ("summary_words", C.c_int64), ("binned", C.c_int32), ("reserved", C.c_int32)]
+
+
+def sweep_plan(info, bits, point_cols, lo, hi):
+    """pipamd_tape_sweep_plan: {"n_points", "summary_words", "binned"} for a tape with `info` (the dict of tape_check, or a
+    TapeInfo) swept over the box lo .. hi, or TapeError where the box is refused.  Host only."""
+    fn = _tape_fn("pipamd_tape_sweep_plan", 64)
+    fn.argtypes = [C.POINTER(TapeInfo), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(TapeSweepPlan)]
+    if isinstance(info, dict):
+        info = TapeInfo(**{k: int(v) for k, v in info.items()})
+    n = max(1, len(lo))
+    clo, chi = (C.c_int64 * n)(*[int(v) for v in lo]), (C.c_int64 * n)(*[int(v) for v in hi])
+    plan = TapeSweepPlan()
+    rc = fn(C.byref(info), int(bits), int(point_cols), clo, chi, C.byref(plan))
+    if rc != 0:
+        raise TapeError(rc, lib().pipamd_last_error().decode())
+    return {"n_points": int(plan.n_points), "summary_words": int(plan.summary_words), "binned": int(plan.binned)}
+
+
+def sweep_summary(tensor, leaves):
+    """a sweep's summary (device or host int64 tensor, or a sequence) as a dict: counts and first by status name
+    ("solution", "nil", "range", "outside"; first: the smallest k, -1 if none), leaf_count and leaf_first by leaf ordinal"""
+    w = [int(v) for v in (tensor.cpu().tolist() if hasattr(tensor, "cpu") else tensor)]
+    L = int(leaves)
+    assert len(w) >= 8 + 2 * L
+    return {"counts": {n: w[i] for i, (n, _) in enumerate(SWEEP_STATUS)},
+            "first": {n: w[4 + i] for i, (n, _) in enumerate(SWEEP_STATUS)},
+            "leaf_count": w[8:8 + L], "leaf_first": w[8 + L:8 + 2 * L]}
 
 
 class TapeSetInfo(C.Structure):
