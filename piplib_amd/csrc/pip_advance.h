@@ -1270,6 +1270,13 @@ __device__ __forceinline__ void det_limb_store(PipJob *J, int i, T x) {
   } else
     J->det[i] = (i64)x;
 }
+// The pivots a job has counted behind its last log entry: npiv counts every call of pivoter, the log holds those that
+// found a column, and the one call that finds none ends the job (PIPAMD_AUX_NOCOLUMN).  An overflow at entry k of a log of
+// nlog entries is the pivot npiv - det_unlogged - nlog + k + 1: the job may have pivoted on to that end before a
+// deferred replay looks at its log.
+__device__ __forceinline__ int det_unlogged(const PipJob *J) {
+  return J->status == PIPAMD_ST_NIL && J->aux == PIPAMD_AUX_NOCOLUMN ? 1 : 0;
+}
 // The determinant replay of ONE job by ONE lane (traiter.c:394-446 for the pivots the job's launches logged; the text on
 // the replay kernels, pip_kernels.hip): the lane walks the job's log alone, CH entries loaded at a time.  The body of
 // pip_det_replay_lanes_kernel, and of the lean kernel's spare blocks (pip_lean.h), which run it beside the launch's
@@ -1303,8 +1310,8 @@ __device__ __forceinline__ void det_replay_lane(PipJob *J, i64 *arena) {
         }
       }
       if (!det_step<T>(det0, det1, det2, det3, ldet, ppivot, dppiv)) {
+        J->npiv = J->npiv - det_unlogged(J) - nlog + k + 1;
         J->status = PIPAMD_ST_OVERFLOW;
-        J->npiv = J->npiv - nlog + k + 1;
         stop = true;
       }
     }
@@ -2650,6 +2657,9 @@ __global__ __launch_bounds__(64 * NW, (NW == 1 && NCH == 1 && sizeof(T) == 8) ? 
   int mc = 0;
   if (wave == 0) mc = max_row_class(S, ni, lane);
   if (tid == 0) {
+    // (the header still holds the counts the launch began with: a pivot it counted and did not log is the call of pivoter
+    // that found no column and ended the job -- det_unlogged)
+    const bool nocolumn = status == PIPAMD_ST_NIL && npiv - nlog != J->npiv - J->nlog;
     J->ni = ni;
     J->npiv = npiv;
     J->ncut = ncut;
@@ -2658,7 +2668,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 1 && NCH == 1 && sizeof(T) == 8) ? 
     J->tflags = tflags;
     J->state_nch = NCH;
     J->maxabs = (u64)mc;  // magnitude class of the largest entry
-    J->aux = sc.aux;
+    J->aux = nocolumn ? PIPAMD_AUX_NOCOLUMN : sc.aux;
     J->status = status;
     if (status == PIPAMD_ST_RUN && q.out_count) {  // paused: the next launch resumes it
       q.out_list[atomicAdd(q.out_count, 1)] = jb;

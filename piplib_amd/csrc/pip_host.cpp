@@ -358,7 +358,8 @@ struct BatchRun {
     // The determinant logs of the bulk launches are replayed once, behind the first tail launch, for all tableaux
     // (pipk_launch_replay_all): a replay kernel between two launches is a tiny launch that waits milliseconds for a
     // turn on a device busy with other batches' bulk launches, and nothing in the pivot launches depends on it -- a
-    // tableau that overflowed goes on pivoting until the replay says so, its status and pivot count are the same.
+    // tableau that overflowed goes on pivoting until the replay says so, its status and pivot count are the same (also
+    // where it meanwhile ended in a pivot without a column, counted and not logged: det_unlogged, pip_advance.h).
     // The bulk launches together log fewer pivots per tableau than the log holds (`defer` in begin()).
     // Where the second lean launch's spare blocks have replayed the logs of the jobs the first one finished
     // (spare_went), this replay is the catch-all for what is left -- the few hundred tableaux of the second launch and the

@@ -21,6 +21,10 @@
  * the log right after the launch, one wave per job: the gcds of 64 pivots at a time on the lanes,
  * only the walk over the limbs sequentially. */
 #define PIPAMD_DETLOG 512
+/* PipJob.aux of a job that ended PIPAMD_ST_NIL in a call of pivoter that found no pivot column (traiter.c:782-785): that
+ * call is counted in npiv and has no log entry, which the replay's pivot count of an overflow has to know (a cut's row
+ * index, the other use of aux, is never negative) */
+#define PIPAMD_AUX_NOCOLUMN (-1)
 
 /* One problem ("job") in the device arena: a PipJob header and a block of int64 words.  Every offset is in int64
  * units and even (rows are 16-byte aligned); an entry is `ew` words (1: 64-bit entries, 2: 128-bit entries).  A block

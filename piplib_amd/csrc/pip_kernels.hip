@@ -70,8 +70,8 @@ __global__ __launch_bounds__(64) void pip_det_replay_kernel(PipJob *jobs, i64 *a
   }
   if (lane == 0) {
     if (bad >= 0) {
+      J->npiv = J->npiv - det_unlogged(J) - nlog + bad + 1;
       J->status = PIPAMD_ST_OVERFLOW;
-      J->npiv = J->npiv - nlog + bad + 1;
     }
     det_limb_store<T>(J, 0, det0);
     det_limb_store<T>(J, 1, det1);
@@ -1395,6 +1395,26 @@ extern "C" hipError_t pipk_launch_replay_all(PipJob *jobs, i64 *arena, int njobs
     hipLaunchKernelGGL(pip_det_replay_lanes_kernel<i128>, dim3((njobs + 63) / 64), dim3(64), 0, stream, jobs, arena, njobs, q);
   else
     hipLaunchKernelGGL(pip_det_replay_lanes_kernel<i64>, dim3((njobs + 63) / 64), dim3(64), 0, stream, jobs, arena, njobs, q);
+  return hipGetLastError();
+}
+
+// One of the two replay kernels over a caller's jobs, a block (wave_per_job) or a lane per job of `njobs`, with or
+// without an input list and its device-side count: for the replay probe (pip_probe.hip, pipamd_debug_det_replay), which
+// cannot name the kernels of this file.  Nothing else calls it.
+extern "C" hipError_t pipk_launch_det_replay(PipJob *jobs, i64 *arena, int njobs, int ebits, int wave_per_job, const int *in_list,
+                                             const int *in_count, hipStream_t stream) {
+  if (njobs <= 0) return hipSuccess;
+  const PipQueue q{in_list, in_count, nullptr, nullptr, nullptr};
+  const dim3 grid(wave_per_job ? njobs : (njobs + 63) / 64);
+  if (wave_per_job) {
+    if (ebits == 128)
+      hipLaunchKernelGGL(pip_det_replay_kernel<i128>, grid, dim3(64), 0, stream, jobs, arena, njobs, q);
+    else
+      hipLaunchKernelGGL(pip_det_replay_kernel<i64>, grid, dim3(64), 0, stream, jobs, arena, njobs, q);
+  } else if (ebits == 128)
+    hipLaunchKernelGGL(pip_det_replay_lanes_kernel<i128>, grid, dim3(64), 0, stream, jobs, arena, njobs, q);
+  else
+    hipLaunchKernelGGL(pip_det_replay_lanes_kernel<i64>, grid, dim3(64), 0, stream, jobs, arena, njobs, q);
   return hipGetLastError();
 }
 

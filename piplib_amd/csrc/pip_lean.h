@@ -1166,6 +1166,9 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
   }
   const int mc = max_row_class(S, ni, lane);
   if (lane == 0) {
+    // (the header still holds the counts the launch began with: a pivot it counted and did not log is the call of pivoter
+    // that found no column and ended the job -- det_unlogged, pip_advance.h)
+    const bool nocolumn = status == PIPAMD_ST_NIL && npiv - nlog != J->npiv - J->nlog;
     J->ni = ni;
     J->npiv = npiv;
     J->ncut = ncut0 + ni;
@@ -1175,7 +1178,7 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
     J->tflags = tflags;
     J->state_nch = F::NCH;
     J->maxabs = (u64)mc;
-    J->aux = sc.aux;
+    J->aux = nocolumn ? PIPAMD_AUX_NOCOLUMN : sc.aux;
     J->status = status;
     if (status == PIPAMD_ST_RUN && q.out_count) {
       q.out_list[atomicAdd(q.out_count, 1)] = jb;

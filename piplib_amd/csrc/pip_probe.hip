@@ -11,15 +11,24 @@
 //     taken -- choose_column / choose_column_slow / lean_choose_column (choisir_piv), sort_rows (tab_sort_rows), exam_rows
 //     (exam_coef) -- on a small tableau, after row_publish / lean_publish have summarised its rows; the summaries are
 //     reported too (tests/test_gpu_select_probe.py; the case layout stands above the kernels).
+//   pipamd_debug_det_replay(engine, which, ebits, in, out, njobs, list, nlist)   the determinant replay's kernels and the
+//     spare blocks' one-lane walk on job headers and logs the caller gives (tests/test_gpu_det_replay_probe.py).
 //
 // `in` / `out`: device pointers to int64 words, 16-byte aligned; a 128-bit value is two words, low then high (as
 // det_limb).  Exported, not declared in include/piplib_amd.h (like pipamd_debug_lean): no part of the interface.
+#include <string.h>
+
+#include <vector>
+
 #include "pip_lean.h"
 #include "pip_host.h"
 #include "../../include/piplib_amd.h"
 
 // the device tree's helpers live in pip_quast.hip's anonymous namespace: its own probe kernel, launched from here
 extern "C" hipError_t pipk_launch_quast_probe(int op, const long long *in, long long *out, int n, hipStream_t stream);
+// the two replay kernels live in pip_kernels.hip: its launcher for a caller's jobs, list and count
+extern "C" hipError_t pipk_launch_det_replay(PipJob *jobs, long long *arena, int njobs, int ebits, int wave_per_job,
+                                             const int *in_list, const int *in_count, hipStream_t stream);
 
 namespace {
 
@@ -458,6 +467,24 @@ __global__ __launch_bounds__(64) void pip_probe_select_lean_kernel(const i64 *in
   select_report<T, NM>(S, cstw, c, ret, mc, lane, 64);
 }
 
+// ---- pipamd_debug_det_replay: the determinant replay (pip_kernels.hip, det_replay_lane of pip_advance.h) on job headers
+// and logs the caller gives.  Per job RP_IN words in: the header's det[] (8 words), ldet, npiv, status, nlog, ebits, aux, two
+// words of padding, then the log area as the pivot kernels fill it -- pair k at entries 2k, 2k + 1 of the job's entry
+// type, room for PIPAMD_DETLOG pairs of 128-bit entries; what stands behind the job's nlog pairs is the caller's too (no
+// replay may read it into a result).  RP_OUT words out: det[], ldet, npiv, status, nlog as the launch left them.
+enum { RP_HDR = 16, RP_LOG = 2 * PIPAMD_DETLOG * 2, RP_IN = RP_HDR + RP_LOG, RP_OUT = 12 };
+
+// which = 2: the lean kernel's spare blocks' instantiation of the one-lane walk (lean_spare_replay, pip_lean.h), a lane
+// per job as pip_det_replay_lanes_kernel indexes them
+template <class T>
+__global__ __launch_bounds__(64) void pip_probe_replay_spare_kernel(PipJob *jobs, i64 *arena, int njobs, const int *in_list,
+                                                                    const int *in_count) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int nq = in_count ? *in_count : njobs;
+  if (t >= nq) return;
+  det_replay_lane<T, PIP_LEAN_REPLAY_CH>(&jobs[in_list ? in_list[t] : t], arena);
+}
+
 bool probe_ptrs_ok(const void *in, const void *out) {
   return in && out && ((uintptr_t)in & 15) == 0 && ((uintptr_t)out & 15) == 0;
 }
@@ -545,4 +572,81 @@ extern "C" int pipamd_debug_select(pipamd_engine *e, int fn, const long long *in
   }
 #undef PIP_PROBE_SEL
   return probe_finish(hipGetLastError());
+}
+
+// pipamd_debug_det_replay(engine, which, ebits, in, out, njobs, list, nlist): `in` / `out` device pointers (layout above
+// the probe kernel), `list` a HOST array of nlist job indices or NULL.  The job headers and their log areas are built in a
+// scratch arena of the call's own; then ONE launch of the shipped code for entries of `ebits` bits -- which = 0:
+// pip_det_replay_kernel (a wave per job), 1: pip_det_replay_lanes_kernel (a lane per job), 2: the spare blocks'
+// det_replay_lane<T, PIP_LEAN_REPLAY_CH> -- over all njobs jobs, or, with a list, over the listed ones with the count in a
+// device word and the grid still sized by njobs (the blocks and lanes beyond the count must leave every job alone).
+extern "C" int pipamd_debug_det_replay(pipamd_engine *e, int which, int ebits, const long long *in, long long *out, int njobs,
+                                       const int *list, int nlist) {
+  if (!e || njobs < 0 || njobs > 65536 || !probe_ptrs_ok(in, out) || which < 0 || which > 2 || (ebits != 64 && ebits != 128) ||
+      (list ? (nlist < 0 || nlist > njobs) : nlist != 0))
+    return PIPAMD_E_INVALID;
+  for (int i = 0; list && i < nlist; i++)
+    if (list[i] < 0 || list[i] >= njobs) return PIPAMD_E_INVALID;
+  if (hipSetDevice(e->device) != hipSuccess) return PIPAMD_E_HIP;
+  if (njobs == 0) return PIPAMD_OK;
+  std::vector<long long> h((size_t)njobs * RP_IN), arena_h((size_t)njobs * RP_LOG), o((size_t)njobs * RP_OUT);
+  std::vector<PipJob> jobs_h(njobs);
+  if (hipMemcpy(h.data(), in, h.size() * sizeof(long long), hipMemcpyDeviceToHost) != hipSuccess) return PIPAMD_E_HIP;
+  for (int j = 0; j < njobs; j++) {
+    const long long *c = &h[(size_t)j * RP_IN];
+    PipJob &J = jobs_h[j];
+    memset(&J, 0, sizeof J);
+    if (c[11] < 0 || c[11] > PIPAMD_DETLOG || (c[12] != 64 && c[12] != 128)) return PIPAMD_E_INVALID;  // the log holds no more
+    for (int i = 0; i < 2 * PIPAMD_MAXDET; i++) J.det[i] = c[i];
+    J.ldet = (int)c[8];
+    J.npiv = (int)c[9];
+    J.status = (int)c[10];
+    J.nlog = (int)c[11];
+    J.ebits = (int)c[12];
+    J.aux = (int)c[13];
+    J.log_off = (int64_t)j * RP_LOG;
+    memcpy(&arena_h[(size_t)j * RP_LOG], c + RP_HDR, RP_LOG * sizeof(long long));
+  }
+  PipJob *d_jobs = nullptr;
+  long long *d_arena = nullptr;
+  int *d_list = nullptr;  // the list, then the count
+  hipError_t he = hipMalloc((void **)&d_jobs, jobs_h.size() * sizeof(PipJob));
+  if (he == hipSuccess) he = hipMalloc((void **)&d_arena, arena_h.size() * sizeof(long long));
+  if (he == hipSuccess && list) he = hipMalloc((void **)&d_list, ((size_t)nlist + 1) * sizeof(int));
+  if (he == hipSuccess) he = hipMemcpy(d_jobs, jobs_h.data(), jobs_h.size() * sizeof(PipJob), hipMemcpyHostToDevice);
+  if (he == hipSuccess) he = hipMemcpy(d_arena, arena_h.data(), arena_h.size() * sizeof(long long), hipMemcpyHostToDevice);
+  if (he == hipSuccess && list) {
+    std::vector<int> l(list, list + nlist);
+    l.push_back(nlist);
+    he = hipMemcpy(d_list, l.data(), l.size() * sizeof(int), hipMemcpyHostToDevice);
+  }
+  if (he == hipSuccess) {
+    const int *cnt = list ? d_list + nlist : nullptr;
+    if (which == 2) {
+      if (ebits == 128)
+        hipLaunchKernelGGL(pip_probe_replay_spare_kernel<i128>, dim3((njobs + 63) / 64), dim3(64), 0, 0, d_jobs, d_arena, njobs, d_list, cnt);
+      else
+        hipLaunchKernelGGL(pip_probe_replay_spare_kernel<i64>, dim3((njobs + 63) / 64), dim3(64), 0, 0, d_jobs, d_arena, njobs, d_list, cnt);
+      he = hipGetLastError();
+    } else {
+      he = pipk_launch_det_replay(d_jobs, d_arena, njobs, ebits, which == 0, d_list, cnt, 0);
+    }
+  }
+  if (he == hipSuccess) he = hipDeviceSynchronize();
+  if (he == hipSuccess) he = hipMemcpy(jobs_h.data(), d_jobs, jobs_h.size() * sizeof(PipJob), hipMemcpyDeviceToHost);
+  for (int j = 0; he == hipSuccess && j < njobs; j++) {
+    const PipJob &J = jobs_h[j];
+    long long *c = &o[(size_t)j * RP_OUT];
+    for (int i = 0; i < 2 * PIPAMD_MAXDET; i++) c[i] = J.det[i];
+    c[8] = J.ldet, c[9] = J.npiv, c[10] = J.status, c[11] = J.nlog;
+  }
+  if (he == hipSuccess) he = hipMemcpy(out, o.data(), o.size() * sizeof(long long), hipMemcpyHostToDevice);
+  hipFree(d_jobs);
+  hipFree(d_arena);
+  hipFree(d_list);
+  if (he != hipSuccess) {
+    pipamd_set_error("replay probe: %s", hipGetErrorString(he));
+    return PIPAMD_E_HIP;
+  }
+  return PIPAMD_OK;
 }

@@ -47,6 +47,8 @@ class Stats:
     rows_changed: List[int] = field(default_factory=list)   # per pivot: rows whose bits change
     entry_bits: List[int] = field(default_factory=list)     # per pivot: max entry bits after it
     nrows: List[int] = field(default_factory=list)          # per pivot: real rows
+    det_log: List[tuple] = field(default_factory=list)      # per pivot with a column: (pivot, denominator of the pivot row),
+                                                            # what the pivot kernels log for the determinant replay
 
     @property
     def exact(self):
@@ -240,6 +242,7 @@ def pivot_step(rows, det, pivi, nvar, ni, st):
         return -1
     prow = rows[pivi].v
     pivot, dpiv = int(prow[pivj]), rows[pivi].den
+    st.det_log.append((pivot, dpiv))
     det_update(det, pivot, dpiv, st.bits)
     fresh = -prow
     fresh[pivj] = dpiv
@@ -302,9 +305,12 @@ def gomory(rows, nvar, ni, st):
     return 0
 
 
-def solve(ineq, integer=True, bits=64) -> Result:
+def solve(ineq, integer=True, bits=64, det_out=None, stop_inexact=False) -> Result:
     """ineq: (ni, nvar+1) integers (unknowns | constant).  Returns what traiter() leaves on the
-    solution tape for a problem without parameters."""
+    solution tape for a problem without parameters.  `det_out`: a list that receives the determinant's limbs as the last
+    det_update left them (at an Overflow: as it left them when it raised).  `stop_inexact`: give up, with status None,
+    before the first pivot that follows an intermediate of `bits` bits or more -- from there on a fixed-width run is
+    not comparable, and a caller that only asks about the comparable part need not pay for the rest."""
     ineq = np.asarray(ineq, dtype=object)
     ni, ncol = ineq.shape
     nvar = ncol - 1
@@ -343,11 +349,17 @@ def solve(ineq, integer=True, bits=64) -> Result:
                     status = ST_NIL
                     break
                 ni += 1
+            if stop_inexact and not st.exact:
+                break
             if pivot_step(rows, det, pivi, nvar, ni, st) < 0:
                 status = ST_NIL
                 break
     except Overflow:
+        if det_out is not None:
+            det_out[:] = det
         return Result(ST_OVERFLOW, st.pivots, st.cuts, None, None, st)
+    if det_out is not None:
+        det_out[:] = det
     if status == ST_SOLUTION:
         num = [0 if (rows[i].flag & UNIT) else int(rows[i].v[nvar]) for i in range(nvar)]
         den = [1 if (rows[i].flag & UNIT) else int(rows[i].den) for i in range(nvar)]

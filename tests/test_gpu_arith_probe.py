@@ -33,6 +33,7 @@ import numpy as np
 import pytest
 
 import bigint_pip as bp
+from replay_model import det_model  # det_step in Python ints; shared with the replay probe's model
 
 pytestmark = pytest.mark.gpu
 
@@ -647,26 +648,6 @@ def test_bezout(probe):
         assert clear > len(cs) // 2
         check("bezout%d" % W, probe, cs, [(z,) for z in dev])
         check("q_bezout%d" % W, probe, cs, qk)
-
-
-def det_model(limbs, ldet, ppivot, dppiv, W):
-    """det_step's outputs by bigint_pip.det_update: the limbs in use walk, the others stay as they are"""
-    det = list(limbs[:ldet])
-    ok = 1
-    try:
-        bp.det_update(det, ppivot, dppiv, W)
-    except bp.Overflow:
-        ok = 0
-        if len(det) == ldet:
-            # det_update raises before it appends; det_step has counted the fourth limb by then (ldet++ before its test)
-            d = dppiv
-            for x in limbs[:ldet]:
-                d //= math.gcd(x, d)
-            if d == 1:
-                det = det + [None]
-    n = len(det)
-    out = [det[i] if i < n and det[i] is not None else limbs[i] for i in range(4)]
-    return tuple(out) + (n, ok)
 
 
 def det_cases(W, seed):

@@ -68,9 +68,16 @@ def test_lean_prepared_rows(name, gen, seed, batch, nvar, ni, stay):
     st, pv, _, num, den = outs[1]
     o = oracle_batch(rows, nvar, 0, 1).results
     assert len(o) == batch
+    # an "Integer overflow" the model follows in exact arithmetic is the determinant's, and its pivot count the oracle's
+    # (tests/replay_fixture.py; the dense family has none: every abort of it follows wrapped arithmetic)
+    import replay_fixture as rf
+    fam = rf.family_of(gen + "_batch", seed, batch, nvar, ni, **(dict(cmax=3) if gen == "dense" else {}))
+    exact = rf.exact_aborts(fam) if fam else {}
     for k, r in enumerate(o):
         if r.status == pb.ST_ABORT:
             assert st[k] == {2: eng.ST_OVERFLOW, 4: eng.ST_MAXCOL}.get(r.abort_code, eng.ST_OVERFLOW), (k, st[k], r.abort_code)
+            if r.abort_code == 2 and k in exact:
+                assert pv[k] == r.pivots == exact[k], (k, pv[k], r.pivots)
             continue
         assert st[k] in (eng.ST_SOLUTION, eng.ST_NIL), (k, st[k])
         assert pv[k] == r.pivots, (k, pv[k], r.pivots)

@@ -338,6 +338,11 @@ def _check_against_gmp(g, name, lo=0, hi=None):
             # unbounded determinant: the only verdict that may differ, and the CPU restatement must share it
             o = pb.run_batch(pb.ORACLEPIP128, [probs[i]], flags, timeout=120).results[0]
             assert o.status == pb.ST_ABORT and o.abort_code == 2, (name, i)
+            # ... and where the model follows the run to that abort with nothing beyond 128 bits, the pivot count too
+            import bigint_pip as bp
+            m = bp.solve(probs[i].ineq, integer=bool(probs[i].nq), bits=128, stop_inexact=True)
+            if m.stats.exact and probs[i].nparm == 0:
+                assert m.status == bp.ST_OVERFLOW and pv[b] == o.pivots == m.pivots, (name, i, pv[b], o.pivots, m.pivots)
             limb += 1
             continue
         assert st[b] in (eng.ST_SOLUTION, eng.ST_NIL), (name, i, st[b])
@@ -754,14 +759,26 @@ def test_lean_kernel_paths(name, ni, nq, kw, cap, stay):
         assert (x == y).all()
     st, pv, _, num, den = outs[1]
     o = oracle_batch(rows, nvar, 0, nq).results
+    # an "Integer overflow" the model follows in exact arithmetic is the determinant's, found by the replay, and its pivot
+    # count is the oracle's (tests/replay_fixture.py: 143 of the 160 tableaux of "overflow"; the three aborts of the
+    # "beyond-32-bits" families come after entries of 67 .. 69 bits, which the model does not follow)
+    import replay_fixture as rf
+    exact = rf.exact_aborts("lean-paths-overflow") if name == "overflow" else {}
+    held = 0
     for k, r in enumerate(o):
         if r.status == pb.ST_ABORT:
             assert st[k] == {2: eng.ST_OVERFLOW, 4: eng.ST_MAXCOL}.get(r.abort_code, eng.ST_OVERFLOW), (k, st[k], r.abort_code)
+            if r.abort_code == 2 and k in exact:
+                assert pv[k] == r.pivots == exact[k], (k, pv[k], r.pivots)
+                held += 1
             continue
         assert st[k] in (eng.ST_SOLUTION, eng.ST_NIL), (k, st[k])
         assert pv[k] == r.pivots, (k, pv[k], r.pivots)
         got = "()" if st[k] == eng.ST_NIL else pb.squash(solution_text(num[k], den[k]))
         assert got == pb.squash(r.text), k
+    if name == "overflow":
+        assert rf.SCREEN["lean-paths-overflow"] == ("lexmin_batch", 4000 + ni + len(name), batch, nvar, ni, kw)
+        assert held == len(exact) >= 120, (held, len(exact))
 
 
 @pytest.mark.parametrize("nvar,ni,nq,stay", [
