@@ -13,6 +13,9 @@
 //     reported too (tests/test_gpu_select_probe.py; the case layout stands above the kernels).
 //   pipamd_debug_det_replay(engine, which, ebits, in, out, njobs, list, nlist)   the determinant replay's kernels and the
 //     spare blocks' one-lane walk on job headers and logs the caller gives (tests/test_gpu_det_replay_probe.py).
+//   pipamd_debug_quast_step(engine, inst, in, nin, out, nout, ncases)   one wave per case: the wave-level steps of the device
+//     tree (pip_quast.hip: classify_rows, sort_rows, pivot_step, make_cut, deepen, find_quotient, build_sub, solve_plain)
+//     on a tableau the caller gives (tests/test_gpu_quast_step_probe.py; the case layout stands in pip_quast.h).
 //
 // `in` / `out`: device pointers to int64 words, 16-byte aligned; a 128-bit value is two words, low then high (as
 // det_limb).  Exported, not declared in include/piplib_amd.h (like pipamd_debug_lean): no part of the interface.
@@ -22,6 +25,7 @@
 
 #include "pip_lean.h"
 #include "pip_host.h"
+#include "pip_quast.h"
 #include "../../include/piplib_amd.h"
 
 // the device tree's helpers live in pip_quast.hip's anonymous namespace: its own probe kernel, launched from here
@@ -572,6 +576,66 @@ extern "C" int pipamd_debug_select(pipamd_engine *e, int fn, const long long *in
   }
 #undef PIP_PROBE_SEL
   return probe_finish(hipGetLastError());
+}
+
+// ---- pipamd_debug_quast_step: the cases of a call, checked on the host before anything is launched (layout: pip_quast.h).
+// Every index a step forms from the case's own words is held within the image here -- the kernel stages and calls, it
+// checks nothing -- and every case's image within the dynamic LDS a kernel gets without opting in to more.  `h`: the nin
+// words of `in`.  Returns the largest image in bytes, 0 for a call that must not run.
+static size_t quast_step_check(const long long *h, size_t nin, size_t nout, int inst, int ncases) {
+  const int NB = 1 + (inst & 1), CMAX = 64 * NB;
+  const size_t EW = inst >= 2 ? 2 : 1;
+  if (nin < 2 + 2 * (size_t)ncases || (size_t)h[0] != nin || (size_t)h[1] != nout) return 0;
+  size_t shm = 0, out_end = 0;
+  for (int cs = 0; cs < ncases; cs++) {
+    const unsigned long long oi = (unsigned long long)h[2 + cs], oo = (unsigned long long)h[2 + ncases + cs];
+    if (oi < 2 + 2 * (size_t)ncases || oi > nin || nin - oi < QS_HDR || oo < out_end || oo > nout) return 0;
+    const long long *c = h + oi;
+    for (int k = 0; k < QS_HDR; k++)
+      if (c[k] < -1 || c[k] > 4096 || (k >= 18 && c[k] != 0)) return 0;
+    QStepCase g;
+    qstep_read(c, &g);
+    if (g.fn < 0 || g.fn >= QS_NFN || g.W < 1 || g.W > CMAX || g.S < 1 || g.S > 256 || g.R < 1 || g.R > 256 || g.CR < 0 || g.CR > 128 ||
+        g.CW < 1 || g.CW > 64 || g.nvar < 1 || g.nvar >= g.ncol || g.ncol > g.W || g.nligne < 0 || g.nligne > g.R || g.ni < 0 ||
+        g.ni > g.S || g.bigparm >= g.ncol || g.pivi < 0 || g.nc < 0 || g.nc > g.CR || g.nparm < 0 || g.nparm >= g.CW ||
+        g.deepest < 0 || g.deepest > 1 || g.budget < 0 || g.opts < 0 || g.opts > 7 || g.ldet < 0 || g.ldet > PIPAMD_MAXDET)
+      return 0;
+    const size_t lds = qstep_lds_bytes(g, 8 * EW), nw = qstep_in_words(g, EW), ow = qstep_out_words(g, EW, NB);
+    if (lds > QS_LDS_MAX || nin - oi < nw || nout - oo < ow) return 0;
+    out_end = oo + ow;
+    shm = lds > shm ? lds : shm;
+    const long long *flag = c + QS_HDR, *ref = flag + g.R, *pos = ref + g.R, *den = pos + QS_POS + EW * PIPAMD_MAXDET;
+    for (int k = 0; k < g.R; k++) {
+      if (flag[k] < 0 || flag[k] > 63 || ref[k] < 0 || ref[k] >= ((flag[k] & 1) ? g.nvar : g.S)) return 0;
+      const long long hi = den[EW * k + EW - 1];  // a denominator is at least 1: every step divides by it
+      if (hi < 0 || (hi == 0 && (EW == 1 || den[EW * k] == 0))) return 0;
+    }
+    for (int k = 0; k < QS_POS; k++)
+      if (pos[k] < 0 || pos[k] > 255) return 0;
+    const bool row_step = g.fn == QS_PIVOT || g.fn == QS_MAKE_CUT || g.fn == QS_DEEPEN || g.fn == QS_CUT_CHAIN;
+    if (row_step && (g.pivi >= g.nligne || (flag[g.pivi] & 1))) return 0;  // the pivot row / the row to cut is a real row
+    if (g.fn == QS_SORT && g.nvar > g.nligne) return 0;
+    if (g.fn >= QS_FIND_QUOTIENT && NB != 1) return 0;  // as shipped: one column block
+    if (g.fn == QS_SOLVE_PLAIN && (g.ncol != g.nvar + 1 || g.nvar + g.ni != g.nligne)) return 0;
+  }
+  return shm;
+}
+
+// pipamd_debug_quast_step(engine, inst, in, nin, out, nout, ncases): `in` / `out` device pointers to nin / nout words.
+// inst: 0 <long long, 1>, 1 <long long, 2>, 2 <__int128, 1>, 3 <__int128, 2> of QK<QI, NB> (pip_quast.hip).  A call with a
+// malformed case is refused whole: nothing is launched and `out` is left alone.
+extern "C" int pipamd_debug_quast_step(pipamd_engine *e, int inst, const long long *in, long long nin, long long *out, long long nout,
+                                       int ncases) {
+  if (!e || inst < 0 || inst > 3 || ncases < 0 || ncases > 65536 || nin < 2 || nout < 0 || nin > (1ll << 27) || nout > (1ll << 27) ||
+      !probe_ptrs_ok(in, out))
+    return PIPAMD_E_INVALID;
+  if (hipSetDevice(e->device) != hipSuccess) return PIPAMD_E_HIP;
+  if (ncases == 0) return PIPAMD_OK;
+  std::vector<long long> h((size_t)nin);
+  if (hipMemcpy(h.data(), in, h.size() * sizeof(long long), hipMemcpyDeviceToHost) != hipSuccess) return PIPAMD_E_HIP;
+  const size_t shm = quast_step_check(h.data(), (size_t)nin, (size_t)nout, inst, ncases);
+  if (shm == 0) return PIPAMD_E_INVALID;
+  return probe_finish(pipk_launch_quast_step(inst, in, out, ncases, shm, 0));
 }
 
 // pipamd_debug_det_replay(engine, which, ebits, in, out, njobs, list, nlist): `in` / `out` device pointers (layout above

@@ -34,7 +34,47 @@ enum {
   Q_WHY_OTHER = 16     // too many parameters, iteration guard, assert(ok_var), ...
 };
 
+// ---- testing aid (pip_probe.hip, pipamd_debug_quast_step; tests/test_gpu_quast_step_probe.py): one wave-level step of the
+// device tree -- classify_rows, sort_rows, pivot_step, make_cut, deepen, find_quotient, build_sub, solve_plain -- on a
+// tableau the caller gives.  `in`: words 0, 1 the lengths of `in` and `out` in words, then the cases' offsets into `in`
+// (ncases words) and into `out` (ncases words), then the cases.  A case, in int64 words (a value of the instantiation's
+// entry type is one word, or two, low then high):
+//   the QS_HDR header words in the order of QStepCase (two reserved words behind them)
+//   flag[R], ref[R], pos[128]                                                    a word each
+//   det[4], den[R], val[S * W], ctx[CR * CW], cutv[CW + 2]                       values
+// out: status (1: the step ran), its return value (the lanes' values or-ed), aux (bits 0..2 ok_var, ok_const, ok_parm of
+// make_cut; bits 8.. the `bad` that deepen / find_quotient left), ldet; flag[R], ref[R], pos[128], skey[128] a word each;
+// det[4], den[R], val[S * W], ctx[CR * CW], cutv[CW + 2] and the cut vector (64 values per column block) as values.
+// pivi is the pivot row of QS_PIVOT and the row i of the cut steps; QS_DEEPEN reads the cut vector from row i itself, and
+// QS_BUILD_SUB its extra row (a lane per column, as compa_test hands it over) from cutv.
+enum { QS_CLASSIFY, QS_SORT, QS_PIVOT, QS_MAKE_CUT, QS_DEEPEN, QS_CUT_CHAIN, QS_FIND_QUOTIENT, QS_BUILD_SUB, QS_SOLVE_PLAIN, QS_NFN };
+enum { QS_HDR = 20, QS_POS = 128, QS_SKEY = 128, QS_SKEY_FILL = -2,
+       QS_OPT_POS = 1, QS_OPT_SKEY = 2, QS_OPT_EXTRA = 4,  // `opts`: hand sort_rows pos / skey; build_sub gets the extra row
+       QS_LDS_MAX = 65536 };                               // the dynamic LDS a kernel gets without asking for more
+struct QStepCase {
+  int fn, W, S, R, nvar, ncol, nligne, ni, bigparm, pivi, CR, CW, nc, nparm, deepest, budget, opts, ldet;
+};
+static inline __host__ __device__ void qstep_read(const long long *c, QStepCase *g) {
+  int *f = &g->fn;
+  for (int k = 0; k < 18; k++) f[k] = (int)c[k];
+}
+// values of a case's image in LDS and in `in`, and the bytes of the image; EB bytes a value
+static inline __host__ __device__ size_t qstep_values(const QStepCase &g) {
+  return 4 + (size_t)g.R + (size_t)g.S * g.W + (size_t)g.CR * g.CW + (size_t)g.CW + 2;
+}
+static inline __host__ __device__ size_t qstep_lds_bytes(const QStepCase &g, size_t EB) {
+  return EB * qstep_values(g) + 8 * (size_t)g.R + 16 + 4 * QS_SKEY + QS_POS;
+}
+static inline __host__ __device__ size_t qstep_in_words(const QStepCase &g, size_t EW) {
+  return QS_HDR + 2 * (size_t)g.R + QS_POS + EW * qstep_values(g);
+}
+static inline __host__ __device__ size_t qstep_out_words(const QStepCase &g, size_t EW, int NB) {
+  return 4 + 2 * (size_t)g.R + QS_POS + QS_SKEY + EW * (qstep_values(g) + 64 * (size_t)NB);
+}
+
 extern "C" {
+// inst: 0 <long long, 1>, 1 <long long, 2>, 2 <__int128, 1>, 3 <__int128, 2>; shm: the largest image among the cases
+hipError_t pipk_launch_quast_step(int inst, const long long *in, long long *out, int ncases, size_t shm, hipStream_t stream);
 // ebits: the entry width of the launch, 64 (the reference's long long build) or 128 (the overflow-safe flavour)
 size_t pipk_quast_lds_bytes(const QCaps *c, int ebits);
 size_t pipk_quast_frame_words(const QCaps *c, int ebits);  // entries of one stack frame

@@ -58,14 +58,22 @@ __device__ __forceinline__ bool qsubo(w64 a, w64 b, w64 *r) { return __builtin_s
 __device__ __forceinline__ bool qmulo(w64 a, w64 b, w64 *r) { return __builtin_mul_overflow(a, b, r); }
 __device__ __forceinline__ bool qaddo(w128 a, w128 b, w128 *r) { return __builtin_add_overflow(a, b, r); }
 __device__ __forceinline__ bool qsubo(w128 a, w128 b, w128 *r) { return __builtin_sub_overflow(a, b, r); }
-// 128 x 128: exact when both fit long longs; else by the bit lengths -- a sum of at most 126 cannot overflow, 128 and more
-// must, and 127 (either) is reported as overflow: the problem is handed back, never answered wrongly
+// 128 x 128: exact when both fit long longs; else by the bit lengths na + nb of the magnitudes, whose product P lies in
+// [2^(na+nb-2), 2^(na+nb)): a sum of at most 127 cannot overflow and 130 and more must; at 128 P is below 2^128, so the
+// wrapped product holds its magnitude, which is compared with the bound of its sign; at 129 P is at least 2^127, which
+// only -2^127 itself -- two powers of two under a negative sign -- fits
 __device__ __forceinline__ bool qmulo(w128 a, w128 b, w128 *r) {
   *r = (w128)((u128)a * (u128)b);
   if ((w128)(w64)a == a && (w128)(w64)b == b) return false;
   if (a == 0 || b == 0) return false;
   const u128 ua = a < 0 ? (u128)0 - (u128)a : (u128)a, ub = b < 0 ? (u128)0 - (u128)b : (u128)b;
-  return qbits(ua) + qbits(ub) > 126;
+  const int n = qbits(ua) + qbits(ub);
+  if (n <= 127) return false;
+  if (n >= 130) return true;
+  const bool neg = (a < 0) != (b < 0);
+  if (n == 129) return !(neg && (ua & (ua - 1)) == 0 && (ub & (ub - 1)) == 0);
+  const u128 m = neg ? (u128)0 - (u128)*r : (u128)*r;
+  return m > ((u128)1 << 127) - (neg ? 0 : 1);
 }
 // 64-bit division is a ~150-instruction sequence: one copy each, out of line (operands rarely need it)
 __device__ __noinline__ u64 umod_wide(u64 a, u64 b) { return a % b; }
@@ -1591,6 +1599,163 @@ __global__ __launch_bounds__(64) void pip_quast_probe_kernel(int fn, const w64 *
   o[EW] = bad ? 1 : 0;
 }
 
+// Testing aid (pip_probe.hip, pipamd_debug_quast_step): ONE wave-level step of the tree above on a tableau the caller
+// gives, one wave per case.  The case's image is staged in dynamic LDS, the shipped function is called, and every word it
+// can touch goes back: its return value, the whole image, and the cut vector and ok_* bits of the cut steps (the layout
+// stands in pip_quast.h).  The host entry has checked every index a step forms from the case before anything is launched.
+template <class QI, int NB>
+__global__ __launch_bounds__(64) void pip_quast_step_kernel(const w64 *in, w64 *out, int ncases) {
+  typedef QK<QI, NB> K;
+  typedef typename QT<QI>::U U;
+  typedef LDS QI lq;
+  constexpr int EW = sizeof(QI) / 8;
+  constexpr size_t EB = sizeof(QI);
+  extern __shared__ __align__(16) unsigned char smem[];
+  const int cs = blockIdx.x, lane = threadIdx.x;
+  if (cs >= ncases) return;
+  const w64 *c = in + in[2 + cs];
+  w64 *o = out + in[2 + ncases + cs];
+  QStepCase g;
+  qstep_read(c, &g);
+  const auto ldq = [](const w64 *p, size_t k) -> QI {
+    if constexpr (EW == 2)
+      return (QI)(((u128)(u64)p[2 * k + 1] << 64) | (u64)p[2 * k]);
+    else
+      return p[k];
+  };
+  const auto stq = [](w64 *p, size_t k, QI x) {
+    if constexpr (EW == 2) {
+      p[2 * k] = (w64)(u64)(U)x;
+      p[2 * k + 1] = (w64)(u64)((U)x >> 64);
+    } else {
+      p[k] = x;
+    }
+  };
+  // ---- LDS carve-up: den | val | det | ctx | cutv | flag | ref | ldet | skey | pos
+  LDS unsigned char *q = (LDS unsigned char *)smem;
+  typename K::Tab T;
+  T.den = (lq *)q;
+  q += EB * (size_t)g.R;
+  T.val = (lq *)q;
+  q += EB * (size_t)g.S * g.W;
+  T.det = (lq *)q;
+  q += EB * MAXDET;
+  lq *ctx = (lq *)q;
+  q += EB * (size_t)g.CR * g.CW;
+  lq *cutv = (lq *)q;
+  q += EB * ((size_t)g.CW + 2);
+  T.flag = (lint *)q;
+  q += 4 * (size_t)g.R;
+  T.ref = (lint *)q;
+  q += 4 * (size_t)g.R;
+  T.ldet = (lint *)q;
+  q += 16;
+  LDS int *skey = (LDS int *)q;
+  q += 4 * QS_SKEY;
+  LDS unsigned char *pos = q;
+  T.W = g.W;
+  T.rows_cap = g.R;
+  T.slots_cap = g.S;
+  const int nval = g.S * g.W, nctx = g.CR * g.CW;
+  {
+    const w64 *ci = c + QS_HDR;
+    for (int k = lane; k < g.R; k += 64) {
+      T.flag[k] = (int)ci[k];
+      T.ref[k] = (int)ci[g.R + k];
+    }
+    for (int k = lane; k < QS_POS; k += 64) pos[k] = (unsigned char)ci[2 * g.R + k];
+    for (int k = lane; k < QS_SKEY; k += 64) skey[k] = QS_SKEY_FILL;
+    const w64 *cv = ci + 2 * g.R + QS_POS;
+    for (int k = lane; k < MAXDET; k += 64) T.det[k] = ldq(cv, k);
+    cv += EW * MAXDET;
+    for (int k = lane; k < g.R; k += 64) T.den[k] = ldq(cv, k);
+    cv += EW * (size_t)g.R;
+    for (int k = lane; k < nval; k += 64) T.val[k] = ldq(cv, k);
+    cv += EW * (size_t)nval;
+    for (int k = lane; k < nctx; k += 64) ctx[k] = ldq(cv, k);
+    cv += EW * (size_t)nctx;
+    for (int k = lane; k < g.CW + 2; k += 64) cutv[k] = ldq(cv, k);
+    if (lane == 0) *T.ldet = g.ldet;
+  }
+  __syncthreads();
+  int ret = 0, aux = 0;
+  QI cut[NB];
+#pragma unroll
+  for (int h = 0; h < NB; h++) cut[h] = 0;
+  switch (g.fn) {
+    case QS_CLASSIFY: ret = K::classify_rows(T, g.nvar, g.ncol, g.bigparm, g.nligne, lane); break;
+    case QS_SORT:
+      ret = K::sort_rows(T, g.nvar, g.nligne, lane, (g.opts & QS_OPT_POS) ? pos : nullptr, (g.opts & QS_OPT_SKEY) ? skey : nullptr);
+      break;
+    case QS_PIVOT: ret = K::pivot_step(T, g.pivi, g.nvar, g.ncol, g.nligne, lane); break;
+    case QS_MAKE_CUT:
+    case QS_DEEPEN:
+    case QS_CUT_CHAIN: {
+      typename K::Cut qc;
+      if (g.fn == QS_DEEPEN) {
+#pragma unroll
+        for (int h = 0; h < NB; h++) qc.c[h] = lane + 64 * h < g.W ? T.val[T.ref[g.pivi] * g.W + lane + 64 * h] : 0;
+      } else {
+        qc = K::make_cut(T, g.pivi, g.nvar, g.ncol, g.bigparm, lane);
+        aux = (qc.ok_var ? 1 : 0) | (qc.ok_const ? 2 : 0) | (qc.ok_parm ? 4 : 0);
+      }
+      if (g.fn != QS_MAKE_CUT) {
+        int bad = 0;
+        K::deepen(qc.c, T.den[g.pivi], g.nvar, lane, bad);
+        for (int s = 32; s; s >>= 1) bad |= __shfl_xor(bad, s);
+        aux |= bad << 8;
+      }
+#pragma unroll
+      for (int h = 0; h < NB; h++) cut[h] = qc.c[h];
+      break;
+    }
+    default:
+      if constexpr (NB == 1) {  // (as shipped: the context's functions and solve_plain run one column block)
+        if (g.fn == QS_FIND_QUOTIENT) {
+          int bad = 0;
+          ret = K::find_quotient(ctx, g.CW, g.nc, g.nparm, cutv, lane, bad);
+          for (int s = 32; s; s >>= 1) bad |= __shfl_xor(bad, s);
+          aux = bad << 8;
+        } else if (g.fn == QS_BUILD_SUB) {
+          ret = K::build_sub(T, ctx, g.CW, g.nparm, g.nc, (g.opts & QS_OPT_EXTRA) != 0, lane < g.CW + 2 ? cutv[lane] : (QI)0, lane);
+        } else if (g.fn == QS_SOLVE_PLAIN) {
+          ret = K::solve_plain(T, g.nvar, g.ni, lane, g.deepest, g.budget);
+        }
+      }
+      break;
+  }
+  for (int s = 32; s; s >>= 1) ret |= __shfl_xor(ret, s);
+  __syncthreads();
+  if (lane == 0) {
+    o[0] = 1;
+    o[1] = ret;
+    o[2] = aux;
+    o[3] = *T.ldet;
+  }
+  w64 *oi = o + 4;
+  for (int k = lane; k < g.R; k += 64) {
+    oi[k] = T.flag[k];
+    oi[g.R + k] = T.ref[k];
+  }
+  oi += 2 * g.R;
+  for (int k = lane; k < QS_POS; k += 64) oi[k] = pos[k];
+  oi += QS_POS;
+  for (int k = lane; k < QS_SKEY; k += 64) oi[k] = skey[k];
+  oi += QS_SKEY;
+  for (int k = lane; k < MAXDET; k += 64) stq(oi, k, T.det[k]);
+  oi += EW * MAXDET;
+  for (int k = lane; k < g.R; k += 64) stq(oi, k, T.den[k]);
+  oi += EW * (size_t)g.R;
+  for (int k = lane; k < nval; k += 64) stq(oi, k, T.val[k]);
+  oi += EW * (size_t)nval;
+  for (int k = lane; k < nctx; k += 64) stq(oi, k, ctx[k]);
+  oi += EW * (size_t)nctx;
+  for (int k = lane; k < g.CW + 2; k += 64) stq(oi, k, cutv[k]);
+  oi += EW * ((size_t)g.CW + 2);
+#pragma unroll
+  for (int h = 0; h < NB; h++) stq(oi, lane + 64 * h, cut[h]);
+}
+
 }  // namespace
 
 // LDS image and stack frame of a launch, by entry width (ebits 64 or 128): EB bytes an entry
@@ -1645,6 +1810,21 @@ extern "C" hipError_t pipk_launch_quast_pack(const long long *cells, const long 
                                              int cells_cap, int ebits, hipStream_t stream) {
   if (nprob <= 0) return hipSuccess;
   hipLaunchKernelGGL(pip_quast_pack_kernel, dim3(nprob), dim3(128), 0, stream, cells, off, packed, cells_cap, ebits == 128 ? 6 : 3);
+  return hipGetLastError();
+}
+// see pip_quast_step_kernel; shm stays within what a kernel gets without opting in to more
+extern "C" hipError_t pipk_launch_quast_step(int inst, const long long *in, long long *out, int ncases, size_t shm,
+                                             hipStream_t stream) {
+  if (ncases <= 0) return hipSuccess;
+  if (inst < 0 || inst > 3 || shm > QS_LDS_MAX) return hipErrorInvalidValue;
+#define PIP_QUAST_STEP(...) hipLaunchKernelGGL((__VA_ARGS__), dim3(ncases), dim3(64), shm, stream, in, out, ncases)
+  switch (inst) {
+    case 0: PIP_QUAST_STEP(pip_quast_step_kernel<w64, 1>); break;
+    case 1: PIP_QUAST_STEP(pip_quast_step_kernel<w64, 2>); break;
+    case 2: PIP_QUAST_STEP(pip_quast_step_kernel<w128, 1>); break;
+    default: PIP_QUAST_STEP(pip_quast_step_kernel<w128, 2>); break;
+  }
+#undef PIP_QUAST_STEP
   return hipGetLastError();
 }
 // op: 2 * fn + (128-bit entries ? 1 : 0), see pip_quast_probe_kernel

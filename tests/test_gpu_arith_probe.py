@@ -535,13 +535,9 @@ def test_bit_counts(probe):
 
 
 def qmulo_model(a, b, W):
-    """the documented rule of the device tree's checked multiply: w64 exact; w128 exact when both fit long longs, else by
-    the bit lengths -- a sum of at most 126 cannot overflow, 127 and more is reported"""
-    if W == 64:
-        return 0 if fits(a * b, 64) else 1
-    if (fits(a, 64) and fits(b, 64)) or a == 0 or b == 0:
-        return 0
-    return 1 if abs(a).bit_length() + abs(b).bit_length() > 126 else 0
+    """the device tree's checked multiply flags exactly the products that leave W bits, in both widths (w128: by the bit
+    lengths where they decide -- a sum of at most 127 fits, 130 and more cannot -- and by the 256-bit product in between)"""
+    return 0 if fits(a * b, W) else 1
 
 
 def checked_cases(W, seed):
@@ -563,17 +559,15 @@ def checked_cases(W, seed):
 
 
 def test_checked_arithmetic(probe):
-    """cmul (qmulo), cadd, csub of the device tree in both widths: the result and the `bad` flag.  `bad` clear implies the
-    true product; a true overflow implies `bad`; both operands within 64 bits, or bit lengths summing to at most 126, imply
-    `bad` clear (qmulo(w128)'s 126 / 127-bit band is reported as overflow: handed back, never answered wrongly)"""
+    """cmul (qmulo), cadd, csub of the device tree in both widths: the result and the `bad` flag, which is set exactly when
+    the true result leaves W bits.  The w128 list holds products whose operands' bit lengths sum to 128 and 129 -- where the
+    lengths alone do not decide -- on both sides of 2^127, and -2^127 itself."""
     for W in (64, 128):
         ps = checked_cases(W, 120 + W)
         bad = [qmulo_model(a, b, W) for a, b in ps]
-        for (a, b), f in zip(ps, bad):   # the rule itself against the true product
-            assert f or fits(a * b, W)
-            assert not (fits(a, 64) and fits(b, 64) and W == 128) or not f
-            assert abs(a).bit_length() + abs(b).bit_length() > 126 or W == 64 or not f
-        assert sum(bad) > 100 and sum(1 for (a, b), f in zip(ps, bad) if f and fits(a * b, W)) > (10 if W == 128 else -1)
+        band = [f for (a, b), f in zip(ps, bad) if abs(a).bit_length() + abs(b).bit_length() in (W, W + 1) and not (fits(a, 64) and fits(b, 64))]
+        assert sum(bad) > 100 and any(a * b == -(1 << (W - 1)) for a, b in ps)
+        assert W == 64 or (sum(band) > 10 and len(band) - sum(band) > 10)
         tri = [(a, b, 0) for a, b in ps]
         check("q_cmul%d" % W, probe, tri, [(a * b, f) for (a, b), f in zip(ps, bad)])
         check("q_cadd%d" % W, probe, tri, [(a + b, 0 if fits(a + b, W) else 1) for a, b in ps])
@@ -631,7 +625,9 @@ def bezout_cases(W, seed):
 
 def test_bezout(probe):
     """bezout_dev<i64>, bezout_dev<i128> and QK::bezout in both widths (delta >= 1, deepen()'s call): the three agree wherever
-    the device tree's `bad` is clear, there (z y - x) % delta == 0 when gcd(y, delta) == 1 and z == 0 otherwise"""
+    the device tree's `bad` is clear, there (z y - x) % delta == 0 when gcd(y, delta) == 1 and z == 0 otherwise.  QK::bezout's
+    `bad` is set exactly when a product or difference of the walk leaves W bits (qmulo_model: the multiply is exact in
+    both widths)"""
     for W in (64, 128):
         cs = bezout_cases(W, 130 + W)
         dev = [bezout_wrap(x, y, d, W, False)[0] for x, y, d in cs]
