@@ -58,7 +58,9 @@ extern "C" {
  * pipamd_tape_check_pip / pipamd_tape_compile_pip with pip_solve's result edits, pipamd_tape_point_cols,
  * pipamd_tape_set_create / _eval / _free for many tapes in one launch) -- a tape evaluated at
  * many parameter points, a lane per point; pipamd_tape_sweep_plan / pipamd_tape_sweep -- a tape swept over a box of
- * points the kernel makes itself, under a context (PIPAMD_ST_OUTSIDE), with a summary reduced on the device. */
+ * points the kernel makes itself, under a context (PIPAMD_ST_OUTSIDE), with a summary reduced on the device;
+ * pipamd_tape_compare_plan / pipamd_tape_compare / pipamd_tape_compare_sweep -- two tapes, of either cell width each,
+ * compared by value at the points of a list or a box (PIPAMD_CMP_*). */
 #define PIPAMD_VERSION 500
 
 /* ---- error codes (return values) ---- */
@@ -922,6 +924,59 @@ int pipamd_tape_sweep_plan(const pipamd_tape_info *info, int bits, int point_col
 int pipamd_tape_sweep(pipamd_engine *e, const pipamd_tape *t, const int64_t *lo, const int64_t *hi, int n_ctx, int ctx_cols,
                       const int64_t *d_ctx, int64_t *d_summary, int32_t *d_status, int32_t *d_leaf, int64_t *d_x_num,
                       int64_t *d_x_den, int64_t *d_dual_num, int64_t *d_dual_den, void *stream);
+
+/* Two tapes compared point by point on the device (added since interface version 500): do two answers to the same
+ * problem agree, and if not, where?  The tapes may be of different shape (other forks, other new parameters) and of
+ * different cell widths; they are compared by value at points, never by cells or leaf ordinals.  Per point, sa and sb
+ * are the statuses pipamd_tape_eval gives tape a and tape b there, each evaluated in its own width with its own edit
+ * marks and PIPAMD_ST_RANGE rules, and the class is, in this order: RANGE if either status is PIPAMD_ST_RANGE; STATUS if
+ * sa != sb; VALUE if any unknown's handed-out (numerator, denominator) pair differs; SAME otherwise.  Pairs are compared
+ * as integers, int64 widened to 128 bits: both tapes hand out lowest terms over a positive denominator, or over 0 for
+ * an unbounded unknown, so equal pairs are equal values, and (0, 1) differs from (0, 0).  Every unknown of both leaves is
+ * evaluated whatever was found before: a later unknown that leaves the range makes the point RANGE.  With
+ * PIPAMD_CMP_DUAL the ndual dual pairs are compared behind the unknowns. */
+#define PIPAMD_CMP_SAME 0    /* both NIL, or both SOLUTION with every handed-out pair equal */
+#define PIPAMD_CMP_STATUS 1  /* one SOLUTION, the other NIL */
+#define PIPAMD_CMP_VALUE 2   /* both SOLUTION, some pair differs */
+#define PIPAMD_CMP_RANGE 3   /* either tape ends PIPAMD_ST_RANGE at the point: undecided */
+#define PIPAMD_CMP_OUTSIDE 4 /* pipamd_tape_compare_sweep alone: the point fails a row of the context */
+#define PIPAMD_CMP_WORDS 10  /* the summary: 5 counts by class, then 5 firsts (the smallest k of the class, -1: none) */
+#define PIPAMD_CMP_DUAL 1    /* flags: compare the dual lists too */
+/* pipamd_tape_compare_plan is host only (neither an engine nor a GPU): the infos come from pipamd_tape_check*, bits_a and
+ * bits_b are the cell widths, point_cols, lo and hi as for pipamd_tape_sweep_plan.  PIPAMD_E_INVALID: a null info or
+ * plan, a width other than 64 and 128, whatever pipamd_tape_sweep_plan refuses of a box.  PIPAMD_E_TOOLARGE: 2^38 points
+ * or more; a pair whose slot areas together -- 128 * (slots - 1) values of bits / 8 bytes for either tape -- exceed
+ * PIPAMD_TAPE_LDS_BYTES: a lane keeps the parameters in scope of BOTH tapes on chip, so e.g. two 128-bit tapes of 32
+ * slots each (2 x 63,488 bytes) cannot be compared, while each can be evaluated alone.  plan.staged: 1 exactly when both
+ * programs (8 * words each) fit beside the slot areas too; otherwise both are read from global memory. */
+struct pipamd_tape_compare_plan {
+  int64_t n_points; /* prod (hi[c] - lo[c] + 1); 1 when point_cols == 0 */
+  int32_t staged;
+  int32_t reserved;
+}; /* 16 bytes */
+int pipamd_tape_compare_plan(const pipamd_tape_info *a, int bits_a, const pipamd_tape_info *b, int bits_b, int point_cols,
+                             const int64_t *lo, const int64_t *hi, struct pipamd_tape_compare_plan *plan);
+/* The list form: n_points points in d_points as pipamd_tape_eval takes them (no context: never OUTSIDE).  The sweep
+ * form: box, row-major order of k and context rows exactly as pipamd_tape_sweep has them; an OUTSIDE point is walked by
+ * neither tape.  An empty tape is NIL at every (inside) point.  Outputs, each may be NULL and all may be:
+ *   d_class[k]     int32, PIPAMD_CMP_*
+ *   d_where[k]     int32: the smallest unknown index whose pair differs; nvar + i for the first differing dual pair i
+ *                  when all unknowns agree (PIPAMD_CMP_DUAL); -1 whenever the class is not PIPAMD_CMP_VALUE
+ *   d_status_a[k], d_status_b[k]  int32: sa and sb; both PIPAMD_ST_OUTSIDE for a point outside the context
+ *   d_summary      PIPAMD_CMP_WORDS int64, initialised by the call on `stream` (two calls do not accumulate): the
+ *                  counts sum to n_points; order-independent integers throughout, so the summary is deterministic.
+ * A fill of the summary and one kernel on `stream`, no synchronisation; may run concurrently on several streams with
+ * different output buffers; neither tape is changed.  PIPAMD_E_INVALID before any HIP call: a null engine or tape; a tape
+ * of another device than the engine's; nvar or pipamd_tape_point_cols differing between the tapes; PIPAMD_CMP_DUAL with
+ * differing ndual; unknown flag bits; and what pipamd_tape_eval (list form) or pipamd_tape_sweep (sweep form) refuse for
+ * their points, box and context.  PIPAMD_E_TOOLARGE: as the planner.  pipamd_debug_tape_sweep_blocks bounds the sweep
+ * form's grid too. */
+int pipamd_tape_compare(pipamd_engine *e, const pipamd_tape *a, const pipamd_tape *b, int flags, int64_t n_points,
+                        const int64_t *d_points, int64_t *d_summary, int32_t *d_class, int32_t *d_where,
+                        int32_t *d_status_a, int32_t *d_status_b, void *stream);
+int pipamd_tape_compare_sweep(pipamd_engine *e, const pipamd_tape *a, const pipamd_tape *b, int flags, const int64_t *lo,
+                              const int64_t *hi, int n_ctx, int ctx_cols, const int64_t *d_ctx, int64_t *d_summary,
+                              int32_t *d_class, int32_t *d_where, int32_t *d_status_a, int32_t *d_status_b, void *stream);
 
 #ifdef __cplusplus
 }

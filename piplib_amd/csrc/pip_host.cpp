@@ -1667,10 +1667,15 @@ extern "C" int pipamd_debug_tape_sweep_blocks(int n) {
   return PIPAMD_OK;
 }
 
+// The context's rows as the sweeps take them: none, or an array of point_cols + 2 columns
+static inline bool tape_ctx_ok(int n_ctx, int ctx_cols, const int64_t *d_ctx, int point_cols) {
+  return n_ctx >= 0 && (n_ctx == 0 || (d_ctx && ctx_cols == point_cols + 2));
+}
+
 extern "C" int pipamd_tape_sweep(pipamd_engine *e, const pipamd_tape *t, const int64_t *lo, const int64_t *hi, int n_ctx,
                                  int ctx_cols, const int64_t *d_ctx, int64_t *d_summary, int32_t *d_status, int32_t *d_leaf,
                                  int64_t *d_x_num, int64_t *d_x_den, int64_t *d_dual_num, int64_t *d_dual_den, void *stream) {
-  if (!e || !t || t->device != e->device || n_ctx < 0 || (n_ctx > 0 && (!d_ctx || ctx_cols != t->point_cols + 2))) {
+  if (!e || !t || t->device != e->device || !tape_ctx_ok(n_ctx, ctx_cols, d_ctx, t->point_cols)) {
     pipamd_set_error("tape_sweep: null engine or tape, a tape of another device, n_ctx < 0, or context rows without an "
                      "array of point_cols + 2 columns");
     return PIPAMD_E_INVALID;
@@ -1708,6 +1713,130 @@ extern "C" int pipamd_tape_sweep(pipamd_engine *e, const pipamd_tape *t, const i
   L.cus = e->cus;
   L.max_blocks = g_tape_sweep_blocks;
   HIPCHK(pipk_launch_tape_sweep(&L, (hipStream_t)stream));
+  return PIPAMD_OK;
+}
+
+// ------------------------------------------------------------------ two tapes compared point by point
+// The LDS of a pair: both slot areas must fit (TOOLARGE otherwise); staged: both programs fit beside them too.
+static int tape_compare_lds(const char *who, const pipamd_tape_info *a, int bits_a, const pipamd_tape_info *b, int bits_b,
+                            int *staged) {
+  if (!a || !b || (bits_a != 64 && bits_a != 128) || (bits_b != 64 && bits_b != 128)) {
+    pipamd_set_error("%s: null info, or bits other than 64 and 128", who);
+    return PIPAMD_E_INVALID;
+  }
+  const unsigned __int128 slots = (unsigned __int128)tape_slot_bytes(a->slots > 0 ? a->slots : 1, bits_a) +
+                                  (unsigned __int128)tape_slot_bytes(b->slots > 0 ? b->slots : 1, bits_b);
+  if (slots > (unsigned __int128)TAPE_LDS_BYTES) {
+    pipamd_set_error("%s: %d slots of %d bits and %d slots of %d bits: the two slot areas exceed %d bytes of LDS", who,
+                     a->slots, bits_a, b->slots, bits_b, TAPE_LDS_BYTES);
+    return PIPAMD_E_TOOLARGE;
+  }
+  *staged = a->words >= 0 && b->words >= 0 &&
+            slots + (unsigned __int128)8 * ((unsigned __int128)a->words + (unsigned __int128)b->words) <= (unsigned __int128)TAPE_LDS_BYTES;
+  return PIPAMD_OK;
+}
+
+extern "C" int pipamd_tape_compare_plan(const pipamd_tape_info *a, int bits_a, const pipamd_tape_info *b, int bits_b,
+                                        int point_cols, const int64_t *lo, const int64_t *hi,
+                                        struct pipamd_tape_compare_plan *plan) {
+  if (!plan) {
+    pipamd_set_error("tape_compare_plan: null plan");
+    return PIPAMD_E_INVALID;
+  }
+  int staged = 0;
+  int rc = tape_compare_lds("tape_compare_plan", a, bits_a, b, bits_b, &staged);
+  if (rc == PIPAMD_E_INVALID) return rc;
+  int64_t n = 0;
+  const int rb = tape_sweep_box("tape_compare_plan", point_cols, lo, hi, nullptr, &n);
+  if (rb) return rb;
+  if (rc) return tape_compare_lds("tape_compare_plan", a, bits_a, b, bits_b, &staged);  // (its message again)
+  plan->n_points = n;
+  plan->staged = staged;
+  plan->reserved = 0;
+  return PIPAMD_OK;
+}
+
+// What both entries refuse of their handles and flags, then the pair's part of the launch
+static int tape_compare_pair(const char *who, pipamd_engine *e, const pipamd_tape *a, const pipamd_tape *b, int flags,
+                             TapeCompareLaunch *L) {
+  if (flags & ~PIPAMD_CMP_DUAL) {
+    pipamd_set_error("%s: unknown flag bits in %d", who, flags);
+    return PIPAMD_E_INVALID;
+  }
+  if (!e || !a || !b || a->device != e->device || b->device != e->device) {
+    pipamd_set_error("%s: null engine or tape, or a tape of another device than the engine's", who);
+    return PIPAMD_E_INVALID;
+  }
+  if (a->shape.nvar != b->shape.nvar || a->point_cols != b->point_cols ||
+      ((flags & PIPAMD_CMP_DUAL) && a->shape.ndual != b->shape.ndual)) {
+    pipamd_set_error("%s: the tapes differ in nvar (%d, %d), in point columns (%d, %d) or -- PIPAMD_CMP_DUAL -- in ndual (%d, %d)",
+                     who, a->shape.nvar, b->shape.nvar, a->point_cols, b->point_cols, a->shape.ndual, b->shape.ndual);
+    return PIPAMD_E_INVALID;
+  }
+  memset(L, 0, sizeof *L);
+  L->prog_a = a->d_prog, L->prog_b = b->d_prog;
+  L->words_a = a->info.words, L->words_b = b->info.words;
+  L->bits_a = a->bits, L->bits_b = b->bits;
+  L->slots_a = a->info.slots, L->slots_b = b->info.slots;
+  L->nvar = a->shape.nvar;
+  L->nparm = a->point_cols;
+  L->ndual = (flags & PIPAMD_CMP_DUAL) ? a->shape.ndual : 0;
+  L->cus = e->cus;
+  return PIPAMD_OK;
+}
+
+extern "C" int pipamd_tape_compare(pipamd_engine *e, const pipamd_tape *a, const pipamd_tape *b, int flags, int64_t n_points,
+                                   const int64_t *d_points, int64_t *d_summary, int32_t *d_class, int32_t *d_where,
+                                   int32_t *d_status_a, int32_t *d_status_b, void *stream) {
+  TapeCompareLaunch L;
+  int rc = tape_compare_pair("tape_compare", e, a, b, flags, &L);
+  if (rc) return rc;
+  if (n_points < 0 || (n_points > 0 && a->point_cols > 0 && !d_points)) {
+    pipamd_set_error("tape_compare: n_points < 0, or parameters without points");
+    return PIPAMD_E_INVALID;
+  }
+  if (n_points >= (1ll << 38)) {
+    pipamd_set_error("tape_compare: %lld points, at most 2^38 - 1 a call", (long long)n_points);
+    return PIPAMD_E_TOOLARGE;
+  }
+  rc = tape_compare_lds("tape_compare", &a->info, a->bits, &b->info, b->bits, &L.staged);
+  if (rc) return rc;
+  if (n_points == 0 && !d_summary) return PIPAMD_OK;
+  if (hipSetDevice(e->device) != hipSuccess) return PIPAMD_E_HIP;
+  L.n_points = n_points;
+  L.points = (const long long *)d_points;
+  L.summary = (long long *)d_summary;
+  L.cls = d_class, L.where = d_where, L.status_a = d_status_a, L.status_b = d_status_b;
+  HIPCHK(pipk_launch_tape_compare(&L, (hipStream_t)stream));
+  return PIPAMD_OK;
+}
+
+extern "C" int pipamd_tape_compare_sweep(pipamd_engine *e, const pipamd_tape *a, const pipamd_tape *b, int flags,
+                                         const int64_t *lo, const int64_t *hi, int n_ctx, int ctx_cols, const int64_t *d_ctx,
+                                         int64_t *d_summary, int32_t *d_class, int32_t *d_where, int32_t *d_status_a,
+                                         int32_t *d_status_b, void *stream) {
+  TapeCompareLaunch L;
+  int rc = tape_compare_pair("tape_compare_sweep", e, a, b, flags, &L);
+  if (rc) return rc;
+  if (!tape_ctx_ok(n_ctx, ctx_cols, d_ctx, a->point_cols)) {
+    pipamd_set_error("tape_compare_sweep: n_ctx < 0, or context rows without an array of point_cols + 2 columns");
+    return PIPAMD_E_INVALID;
+  }
+  int64_t n = 0;
+  rc = tape_sweep_box("tape_compare_sweep", a->point_cols, lo, hi, L.ext, &n);
+  if (rc) return rc;
+  rc = tape_compare_lds("tape_compare_sweep", &a->info, a->bits, &b->info, b->bits, &L.staged);
+  if (rc) return rc;
+  if (hipSetDevice(e->device) != hipSuccess) return PIPAMD_E_HIP;
+  L.box = 1;
+  L.n_points = n;
+  for (int c = 0; c < a->point_cols; c++) L.lo[c] = lo[c];
+  L.n_ctx = n_ctx;
+  L.ctx = (const long long *)d_ctx;
+  L.max_blocks = g_tape_sweep_blocks;
+  L.summary = (long long *)d_summary;
+  L.cls = d_class, L.where = d_where, L.status_a = d_status_a, L.status_b = d_status_b;
+  HIPCHK(pipk_launch_tape_compare(&L, (hipStream_t)stream));
   return PIPAMD_OK;
 }
 

@@ -99,7 +99,32 @@ struct TapeSweepLaunch {
   unsigned long long ext[TAPE_MAX_SLOTS - 1];  // hi[c] - lo[c] + 1, each below 2^38
 };
 
+// pipamd_tape_compare / pipamd_tape_compare_sweep: two programs, possibly of different cell widths, walked per lane at
+// the same point, their leaves compared without writing them out (piplib_amd.h, PIPAMD_CMP_*).  LDS: the slot rows of
+// `a`, those of `b`, then -- staged -- the words of `a` and of `b`.  box: the points are those of lo / ext as in
+// TapeSweepLaunch, tested against ctx, taken by the sweep's bounded persistent grid; otherwise they are read from
+// `points`, a workgroup per chunk of TAPE_BLOCK.
+struct TapeCompareLaunch {
+  const long long *prog_a, *prog_b;  // device
+  long long words_a, words_b;        // 0: the empty tape
+  int bits_a, bits_b;                // 64 or 128
+  int slots_a, slots_b;              // pipamd_tape_info.slots of either
+  int staged;                        // 1: both programs are copied to LDS first; 0: both are read from global memory
+  int box;
+  int nvar, nparm;                   // the same for both; nparm: the values of a point
+  int ndual;                         // dual pairs compared behind the unknowns (0: none, or PIPAMD_CMP_DUAL not set)
+  int n_ctx, cus, max_blocks;        // as in TapeSweepLaunch
+  long long n_points;
+  const long long *points;           // device; the list form
+  const long long *ctx;              // device; n_ctx x (nparm + 2)
+  long long *summary;                // device; PIPAMD_CMP_WORDS words, initialised by the launch; or NULL
+  int *cls, *where, *status_a, *status_b;  // device; each may be NULL
+  long long lo[TAPE_MAX_SLOTS - 1];
+  unsigned long long ext[TAPE_MAX_SLOTS - 1];
+};
+
 extern "C" {
+hipError_t pipk_launch_tape_compare(const TapeCompareLaunch *t, hipStream_t stream);
 hipError_t pipk_launch_tape_sweep(const TapeSweepLaunch *t, hipStream_t stream);
 hipError_t pipk_launch_tape_eval(const TapeLaunch *t, hipStream_t stream);
 hipError_t pipk_launch_tape_set_eval(const TapeSetLaunch *t, hipStream_t stream);

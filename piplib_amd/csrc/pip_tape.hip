@@ -212,7 +212,9 @@ struct TapeOut {
 // every step the lanes at the lowest position execute the node there, the others wait.  At the end st and leaf are set
 // and a solution's values written.  nvar and ndual are the lane's tape's.  MARKS: the program may hold the two marks of
 // pip_solve's result edits (pip_tape.h); a program without them is walked by code that does not look for them.
-template <class T, bool MARKS>
+// STOP (pip_tape_compare_kernel): a lane stops AT its leaf -- st PIPAMD_ST_SOLUTION, `leaf` the LEAF's word position --
+// and nothing is evaluated or written there; the caller does that.
+template <class T, bool MARKS, bool STOP = false>
 __device__ __forceinline__ void tape_walk(const i64 *prog, int pc, i64 *S, int tid, int nvar, int ndual, i64 pt,
                                           const TapeOut &o, int &st, int &leaf) {
   typedef Width<T> W;
@@ -243,6 +245,10 @@ __device__ __forceinline__ void tape_walk(const i64 *prog, int pc, i64 *S, int t
       } else {
         pc = f.neg ? aux : cur + 1 + EW * (P + 1);
       }
+    } else if (STOP && op == TAPE_LEAF) {
+      st = PIPAMD_ST_SOLUTION;
+      leaf = cur;
+      pc = END;
     } else if (op == TAPE_LEAF) {
       const bool flip = MARKS && (hdr & TAPE_LEAF_NEGATE) != 0;
       bool good = true;
@@ -388,6 +394,40 @@ __device__ __forceinline__ int sweep_class(int st) {
 }
 __device__ __forceinline__ bool sweep_zero_word(i64 i, i64 L) { return i < PIPAMD_SWEEP_FIRST || (i >= 8 && i < 8 + L); }
 
+// Point k0 + tid of the box (lo, ext), as raw int64 values in slot rows 0 .. cols-1 of S: the decode described above
+// (pip_tape_compare_kernel calls these two; pip_tape_sweep_kernel has the same steps written out, see there)
+__device__ __forceinline__ void box_point(const i64 *lo, const u64 *exts, int cols, i64 k0, int tid, i64 *S) {
+  u64 rem = (u64)k0;
+  unsigned carry = (unsigned)tid;
+  for (int c = cols - 1; c >= 0; c--) {
+    const u64 ext = exts[c];
+    u64 s = carry;
+    if (rem) {  // (wave-uniform; operands of 32 bits, every box below 2^32 points, divide in 32)
+      const u64 q = ((rem | ext) >> 32) ? rem / ext : (u64)((unsigned)rem / (unsigned)ext);
+      s += rem - q * ext;
+      rem = q;
+    }
+    if (ext >> 16) {
+      carry = s >= ext;
+      s -= carry ? ext : 0;
+    } else {
+      const unsigned q = (unsigned)s / (unsigned)ext;
+      s = (unsigned)s - q * (unsigned)ext;
+      carry = q;
+    }
+    S[c * TAPE_BLOCK + tid] = (i64)((u64)lo[c] + s);
+  }
+}
+// `inside`, and the raw int64 point of lane tid meets every row of the context, exactly
+__device__ __forceinline__ bool box_inside(bool inside, const i64 *ctx, int n_ctx, int cols, const i64 *S, int tid) {
+  for (int r = 0; r < n_ctx; r++) {
+    const i64 *row = ctx + (size_t)r * (cols + 2);
+    const FormValue f = form_value(row + 1, cols, S, tid, (i64 *)nullptr);
+    inside = inside && (row[0] == 0 ? f.ok && f.v == 0 : !f.neg);
+  }
+  return inside;
+}
+
 __global__ void pip_tape_sweep_fill_kernel(i64 *sum, i64 L) {
   const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < PIPAMD_SWEEP_WORDS(L)) sum[i] = sweep_zero_word(i, L) ? 0 : -1;
@@ -425,6 +465,8 @@ __global__ __launch_bounds__(TAPE_BLOCK) void pip_tape_sweep_kernel(TapeSweepLau
   for (i64 k0 = (i64)blockIdx.x * TAPE_BLOCK; k0 < n; k0 += (i64)gridDim.x * TAPE_BLOCK) {
     const i64 pt = k0 + tid;
     const bool live = pt < n;
+    // (box_point and box_inside, written out: through the calls the compiler allocates this kernel's scalar registers
+    // differently, and its instantiations are held to their recorded figures)
     u64 rem = (u64)k0;
     unsigned carry = (unsigned)tid;
     for (int c = cols - 1; c >= 0; c--) {
@@ -549,6 +591,172 @@ hipError_t launch_sweep(const TapeSweepLaunch &s, hipStream_t stream) {
   return launch_sweep_as<T, MARKS, true, false>(s, stream);  // (nothing asked for: the walk with nothing to write)
 }
 
+// ------------------------------------------------------------------ pipamd_tape_compare / pipamd_tape_compare_sweep
+// Two programs per lane (TapeCompareLaunch, pip_tape.h), `a` of TA cells and `b` of TB cells, each with slot rows of
+// its own.  Per chunk the point is decoded (BOX: as the sweep does, and tested against the context) or loaded once as
+// raw int64 rows of a's area, copied to b's area in b's width, then widened in place where a is 128-bit.  Tape a is
+// walked to its end node, then tape b, both with STOP: a lane is then at a (leaf of a, leaf of b) pair of word
+// positions, -1 for a side that did not end in a LEAF.  The wave serves its pairs one at a time -- the pair of its
+// first pending lane, read by readlane, and the ballot of the lanes that share it (cheaper than a minimum over the
+// combined key, and the order plays no part) --, so the leaves' words stay one address per wave.  The lanes of a pair
+// evaluate unknown i of both leaves as tape_walk does -- form_value, lowest_terms, negate and unbounded marks -- and
+// compare the pairs handed out in 128 bits; they keep `range` per side and `where`.  Every unknown of both leaves is
+// evaluated, so a side's status is pipamd_tape_eval's whatever the other side does.  The dual pairs are words of the
+// programs, the same for all lanes of a pair.
+// Summary: five counts and five firsts as wave-uniform accumulators, a ballot and a popcount per class and chunk;
+// each wave flushes what it counted, a 64-bit atomicAdd and an unsigned atomicMin per class it met.
+__global__ void pip_tape_compare_fill_kernel(i64 *sum) {
+  const int i = threadIdx.x;
+  if (i < PIPAMD_CMP_WORDS) sum[i] = i < PIPAMD_CMP_WORDS / 2 ? 0 : -1;
+}
+
+// unknown i of the LEAF at word `at` of prog, at lane tid's point: the pair handed out, widened.  false: it leaves T
+template <class T>
+__device__ __forceinline__ bool leaf_pair(const i64 *prog, int at, int i, const i64 *S, int tid, i128 *num, i128 *den) {
+  typedef Width<T> W;
+  constexpr int EW = W::EW;
+  const i64 hdr = prog[at];
+  const int P = (int)((hdr >> 8) & 0xffff);
+  const i64 *u = prog + at + 1 + (size_t)i * EW * (P + 2);
+  const FormValue f = form_value(u + EW, P, S, tid, (T *)nullptr);
+  const T D = W::word(u, 0);
+  const bool unbounded = D < 0;
+  T n = 0, d = 0;
+  const bool good = f.ok && lowest_terms<T>(f.v, (hdr & TAPE_LEAF_NEGATE) != 0, unbounded ? -D : D, &n, &d);
+  *num = (i128)n;
+  *den = unbounded ? (i128)0 : (i128)d;
+  return good;
+}
+
+template <class TA, class TB, bool STAGED, bool BOX>
+__global__ __launch_bounds__(TAPE_BLOCK) void pip_tape_compare_kernel(TapeCompareLaunch a) {
+  typedef Width<TA> WA;
+  typedef Width<TB> WB;
+  constexpr int EA = WA::EW, EB = WB::EW;
+  extern __shared__ __attribute__((aligned(16))) i64 tape_lds[];
+  i64 *SA = tape_lds;                                       // (slots_a - 1) * EA rows of TAPE_BLOCK words
+  i64 *SB = SA + (size_t)(a.slots_a - 1) * EA * TAPE_BLOCK;  // (slots_b - 1) * EB rows
+  const int tid = threadIdx.x, lane = tid & 63, nvar = a.nvar, ndual = a.ndual, cols = a.nparm;
+  const int words_a = (int)a.words_a, words_b = (int)a.words_b;
+  const i64 n = a.n_points;
+  const i64 *pa = a.prog_a, *pb = a.prog_b;
+  if (STAGED) {
+    i64 *LA = SB + (size_t)(a.slots_b - 1) * EB * TAPE_BLOCK, *LB = LA + words_a;
+    for (int i = tid; i < words_a; i += TAPE_BLOCK) LA[i] = a.prog_a[i];
+    for (int i = tid; i < words_b; i += TAPE_BLOCK) LB[i] = a.prog_b[i];
+    pa = LA, pb = LB;
+    __syncthreads();
+  }
+  u64 *sum = (u64 *)a.summary;
+  TapeOut none;  // (STOP: the walk writes nothing)
+  none.status = none.leaf = nullptr;
+  none.x_num = none.x_den = none.dual_num = none.dual_den = nullptr;
+  none.xs = none.ds = 0;
+  u64 cnt[5] = {0, 0, 0, 0, 0}, first[5] = {~(u64)0, ~(u64)0, ~(u64)0, ~(u64)0, ~(u64)0};
+
+  for (i64 k0 = (i64)blockIdx.x * TAPE_BLOCK; k0 < n; k0 += (i64)gridDim.x * TAPE_BLOCK) {
+    const i64 pt = k0 + tid;
+    const bool live = pt < n;
+    bool inside = live;
+    if (BOX) {
+      box_point(a.lo, a.ext, cols, k0, tid, SA);
+      inside = box_inside(live, a.ctx, a.n_ctx, cols, SA, tid);
+    } else if (live) {
+      for (int j = 0; j < cols; j++) SA[j * TAPE_BLOCK + tid] = a.points[pt * cols + j];
+    }
+    // (a lane touches its own column alone; a lane that is not live holds whatever was there and walks nothing)
+    for (int j = 0; j < cols; j++) WB::set_slot(SB, j, tid, (TB)SA[j * TAPE_BLOCK + tid]);
+    if (EA == 2)
+      for (int j = cols - 1; j >= 0; j--) WA::set_slot(SA, j, tid, (TA)SA[j * TAPE_BLOCK + tid]);
+
+    int sa = live && !inside ? PIPAMD_ST_OUTSIDE : PIPAMD_ST_NIL, sb = sa, la = -1, lb = -1;
+    tape_walk<TA, true, true>(pa, inside && words_a ? 0 : END, SA, tid, nvar, 0, pt, none, sa, la);
+    tape_walk<TB, true, true>(pb, inside && words_b ? 0 : END, SB, tid, nvar, 0, pt, none, sb, lb);
+    la = sa == PIPAMD_ST_SOLUTION ? la : -1;
+    lb = sb == PIPAMD_ST_SOLUTION ? lb : -1;
+
+    bool range_a = false, range_b = false;
+    int where = -1;
+    u64 pend = __ballot(la >= 0 || lb >= 0);
+    while (pend) {
+      const int src = __ffsll((unsigned long long)pend) - 1;
+      const int ua = __builtin_amdgcn_readlane(la, src), ub = __builtin_amdgcn_readlane(lb, src);
+      const bool mine = la == ua && lb == ub;  // (not both -1: lane src is pending)
+      if (mine) {
+        for (int i = 0; i < nvar; i++) {
+          i128 na = 0, da = 0, nb = 0, db = 0;
+          if (ua >= 0) range_a = !leaf_pair<TA>(pa, ua, i, SA, tid, &na, &da) || range_a;
+          if (ub >= 0) range_b = !leaf_pair<TB>(pb, ub, i, SB, tid, &nb, &db) || range_b;
+          if (where < 0 && (na != nb || da != db)) where = i;
+        }
+        if (ndual && ua >= 0 && ub >= 0 && where < 0) {
+          const i64 *qa = pa + ua + 1 + (size_t)nvar * EA * ((int)((pa[ua] >> 8) & 0xffff) + 2);
+          const i64 *qb = pb + ub + 1 + (size_t)nvar * EB * ((int)((pb[ub] >> 8) & 0xffff) + 2);
+          for (int i = 0; i < ndual && where < 0; i++)
+            if ((i128)WA::word(qa, 2 * i) != (i128)WB::word(qb, 2 * i) || (i128)WA::word(qa, 2 * i + 1) != (i128)WB::word(qb, 2 * i + 1))
+              where = nvar + i;
+        }
+      }
+      pend &= ~__ballot(mine);
+    }
+    if (range_a) sa = PIPAMD_ST_RANGE;
+    if (range_b) sb = PIPAMD_ST_RANGE;
+    int cls = PIPAMD_CMP_SAME;
+    if (live && !inside) cls = PIPAMD_CMP_OUTSIDE;
+    else if (sa == PIPAMD_ST_RANGE || sb == PIPAMD_ST_RANGE) cls = PIPAMD_CMP_RANGE;
+    else if (sa != sb) cls = PIPAMD_CMP_STATUS;
+    else if (sa == PIPAMD_ST_SOLUTION && where >= 0) cls = PIPAMD_CMP_VALUE;
+    if (live) {
+      if (a.cls) a.cls[pt] = cls;
+      if (a.where) a.where[pt] = cls == PIPAMD_CMP_VALUE ? where : -1;
+      if (a.status_a) a.status_a[pt] = sa;
+      if (a.status_b) a.status_b[pt] = sb;
+    }
+    if (sum) {
+      const u64 wave_k = (u64)(k0 + (tid & ~63));
+#pragma unroll
+      for (int i = 0; i < 5; i++) {
+        const u64 m = __ballot(live && cls == i);
+        if (m) {
+          const u64 k = wave_k + (u64)(__ffsll((unsigned long long)m) - 1);
+          cnt[i] += (u64)__popcll(m);
+          first[i] = k < first[i] ? k : first[i];
+        }
+      }
+    }
+  }
+  if (sum && lane == 0)
+    for (int i = 0; i < 5; i++)
+      if (cnt[i]) {
+        atomicAdd(&sum[i], cnt[i]);
+        atomicMin(&sum[PIPAMD_CMP_WORDS / 2 + i], first[i]);
+      }
+}
+
+template <class TA, class TB>
+hipError_t launch_compare(const TapeCompareLaunch &c, hipStream_t stream) {
+  size_t lds = tape_slot_bytes(c.slots_a, c.bits_a) + tape_slot_bytes(c.slots_b, c.bits_b);
+  if (c.staged) lds += (size_t)(c.words_a + c.words_b) * 8;
+  void (*kernel)(TapeCompareLaunch) =
+      c.box ? (c.staged ? pip_tape_compare_kernel<TA, TB, true, true> : pip_tape_compare_kernel<TA, TB, false, true>)
+            : (c.staged ? pip_tape_compare_kernel<TA, TB, true, false> : pip_tape_compare_kernel<TA, TB, false, false>);
+  const long long chunks = (c.n_points + TAPE_BLOCK - 1) / TAPE_BLOCK;
+  long long blocks = chunks;
+  if (c.box) {  // the sweep's bounded persistent grid (launch_sweep_as)
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, TAPE_BLOCK, lds) != hipSuccess || per_cu < 1) per_cu = 1;
+    const int bound = c.summary ? TAPE_SWEEP_WG_PER_CU_SUM : TAPE_SWEEP_WG_PER_CU;
+    if (per_cu > bound) per_cu = bound;
+    blocks = (long long)(c.cus > 0 ? c.cus : 1) * per_cu;
+    if (c.max_blocks > 0 && c.max_blocks < blocks) blocks = c.max_blocks;
+    if (chunks < blocks) blocks = chunks;
+  } else if (blocks > (1ll << 24)) {
+    blocks = 1ll << 24;  // (a workgroup per chunk up to 2^31 points; beyond, the kernel's loop takes the rest in turn)
+  }
+  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(TAPE_BLOCK), lds, stream, c);
+  return hipGetLastError();
+}
+
 template <class T, bool MARKS>
 hipError_t launch(const TapeLaunch &t, hipStream_t stream) {
   const long long blocks = (t.n_points + TAPE_BLOCK - 1) / TAPE_BLOCK;
@@ -587,6 +795,19 @@ extern "C" hipError_t pipk_launch_tape_sweep(const TapeSweepLaunch *s, hipStream
   }
   if (s->t.marks) return s->t.bits == 128 ? launch_sweep<i128, true>(*s, stream) : launch_sweep<i64, true>(*s, stream);
   return s->t.bits == 128 ? launch_sweep<i128, false>(*s, stream) : launch_sweep<i64, false>(*s, stream);
+}
+
+extern "C" hipError_t pipk_launch_tape_compare(const TapeCompareLaunch *c, hipStream_t stream) {
+  // (the caller checked: 0 <= n_points < 2^38, both slot counts <= TAPE_MAX_SLOTS, the two slot areas -- and the two
+  // programs where staged -- within TAPE_LDS_BYTES)
+  if (c->summary) {
+    hipLaunchKernelGGL(pip_tape_compare_fill_kernel, dim3(1), dim3(64), 0, stream, c->summary);
+    const hipError_t he = hipGetLastError();
+    if (he != hipSuccess) return he;
+  }
+  if (c->n_points <= 0) return hipSuccess;
+  if (c->bits_a == 128) return c->bits_b == 128 ? launch_compare<i128, i128>(*c, stream) : launch_compare<i128, i64>(*c, stream);
+  return c->bits_b == 128 ? launch_compare<i64, i128>(*c, stream) : launch_compare<i64, i64>(*c, stream);
 }
 
 extern "C" hipError_t pipk_launch_tape_set_eval(const TapeSetLaunch *t, hipStream_t stream) {

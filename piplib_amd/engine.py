@@ -1256,6 +1256,79 @@ class Tape:
         n = self.sweep_plan(lo, hi)["n_points"]
         return self.sweep_into(lo, hi, self.outputs(n, names), ctx, True, stream)
 
+    # ---- two tapes compared by value at points (pipamd_tape_compare / pipamd_tape_compare_sweep)
+    CMP_OUTPUTS = ("class", "where", "status_a", "status_b")
+
+    def compare_plan(self, other, lo, hi):
+        """compare_plan() for this tape against `other`: n_points, staged"""
+        return compare_plan(self.info, self.bits, other.info, other.bits, self.point_cols, lo, hi)
+
+    def compare_outputs(self, n, names=CMP_OUTPUTS):
+        """fresh int32 device tensors for `n` points, by the names of CMP_OUTPUTS"""
+        return {k: self.torch.empty((n,), dtype=self.torch.int32, device=self.dev) for k in names}
+
+    def _compare_tail(self, out, summary, stream):
+        t = self.torch
+        if summary is True:
+            summary = t.empty(CMP_WORDS, dtype=t.int64, device=self.dev)
+        if summary is not None:
+            assert summary.dtype == t.int64 and summary.is_contiguous() and summary.numel() >= CMP_WORDS
+        st = C.c_void_p(stream) if stream is not None else C.c_void_p(t.cuda.current_stream(self.dev).cuda_stream)
+        ptrs = [C.c_void_p(out[k].data_ptr()) if out.get(k) is not None else None for k in self.CMP_OUTPUTS]
+        return summary, [C.c_void_p(summary.data_ptr()) if summary is not None else None] + ptrs + [st]
+
+    @staticmethod
+    def _compare_rc(rc):
+        if rc in (-1, -3):
+            raise TapeError(rc, lib().pipamd_last_error().decode())
+        _check(rc)
+
+    def compare_into(self, other, points, out, dual=False, summary=None, stream=None):
+        """pipamd_tape_compare: this tape (a) against `other` (b), a Tape of the same engine, nvar and point_cols and of
+        either cell width, at `points` as eval() takes them, into the int32 tensors of `out`, a dict by the names of
+        CMP_OUTPUTS (a missing name is passed as NULL; `out` may be empty).  dual: compare the dual lists too
+        (PIPAMD_CMP_DUAL).  summary: None, a device int64 tensor of CMP_WORDS, or True to allocate one.  Returns
+        (summary or None, out).  A fill and one launch on `stream` (default: torch's current), no synchronisation."""
+        n, pts = self._points(points)
+        fn = _tape_fn("pipamd_tape_compare", 64)
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int64] + [C.c_void_p] * 7
+        summary, tail = self._compare_tail(out, summary, stream)
+        self._compare_rc(fn(self.e._h, self._h, other._h, CMP_DUAL if dual else 0, n,
+                            C.c_void_p(pts.data_ptr()) if pts is not None else None, *tail))
+        self._cmp_alive = pts  # (the points stay allocated until the next call: the launch is asynchronous)
+        return summary, out
+
+    def compare(self, other, points, dual=False, outputs=CMP_OUTPUTS, stream=None):
+        """this tape against `other` at `points`, with a summary: (summary tensor, dict of the tensors named in
+        `outputs`); outputs=() compares for the summary alone.  See compare_into and compare_summary."""
+        n, pts = self._points(points)
+        return self.compare_into(other, pts if pts is not None else n, self.compare_outputs(n, tuple(outputs)), dual, True, stream)
+
+    def compare_sweep_into(self, other, lo, hi, out, ctx=None, dual=False, summary=None, stream=None):
+        """pipamd_tape_compare_sweep: compare_into at every integer point of the box lo .. hi under the context `ctx`,
+        box, order and rows as sweep_into has them; a point that violates a row is CMP_OUTSIDE."""
+        t = self.torch
+        fn = _tape_fn("pipamd_tape_compare_sweep", 64)
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7
+        clo, chi = self._box(lo, hi)
+        n_ctx, cptr = 0, None
+        if ctx is not None:
+            import numpy as np
+            ctx = (ctx if t.is_tensor(ctx) else t.as_tensor(np.asarray(ctx, dtype=np.int64).reshape(-1, self.point_cols + 2))).to(device=self.dev, dtype=t.int64)
+            ctx = ctx.reshape(-1, self.point_cols + 2).contiguous()
+            n_ctx = int(ctx.shape[0])
+            cptr = C.c_void_p(ctx.data_ptr()) if n_ctx else None
+        summary, tail = self._compare_tail(out, summary, stream)
+        self._compare_rc(fn(self.e._h, self._h, other._h, CMP_DUAL if dual else 0, clo, chi, n_ctx, self.point_cols + 2, cptr, *tail))
+        self._cmp_alive = ctx
+        return summary, out
+
+    def compare_sweep(self, other, lo, hi, ctx=None, dual=False, outputs=CMP_OUTPUTS, stream=None):
+        """this tape against `other` over the box lo .. hi with a summary: (summary tensor, dict of the tensors named in
+        `outputs`); outputs=() compares for the summary alone, whatever the size of the box."""
+        n = self.compare_plan(other, lo, hi)["n_points"]
+        return self.compare_sweep_into(other, lo, hi, self.compare_outputs(n, tuple(outputs)), ctx, dual, True, stream)
+
 
 ST_OUTSIDE = 11  # pipamd_tape_sweep: the point violates a row of the context (PIPAMD_ST_OUTSIDE)
 SWEEP_STATUS = (("solution", ST_SOLUTION), ("nil", ST_NIL), ("range", ST_RANGE), ("outside", ST_OUTSIDE))
@@ -1291,6 +1364,42 @@ def sweep_summary(tensor, leaves):
     return {"counts": {n: w[i] for i, (n, _) in enumerate(SWEEP_STATUS)},
             "first": {n: w[4 + i] for i, (n, _) in enumerate(SWEEP_STATUS)},
             "leaf_count": w[8:8 + L], "leaf_first": w[8 + L:8 + 2 * L]}
+
+
+# pipamd_tape_compare: the class of a point (PIPAMD_CMP_*), the summary's words, the flag
+CMP_SAME, CMP_STATUS, CMP_VALUE, CMP_RANGE, CMP_OUTSIDE = range(5)
+CMP_CLASSES = ("same", "status", "value", "range", "outside")
+CMP_WORDS = 10
+CMP_DUAL = 1
+
+
+class TapeComparePlan(C.Structure):
+    """struct pipamd_tape_compare_plan"""
+    _fields_ = [("n_points", C.c_int64), ("staged", C.c_int32), ("reserved", C.c_int32)]
+
+
+def compare_plan(info_a, bits_a, info_b, bits_b, point_cols, lo, hi):
+    """pipamd_tape_compare_plan: {"n_points", "staged"} for tapes with info_a / info_b (dicts of tape_check, or TapeInfo)
+    of bits_a / bits_b compared over the box lo .. hi, or TapeError where the pair or the box is refused.  Host only."""
+    fn = _tape_fn("pipamd_tape_compare_plan", 64)
+    fn.argtypes = [C.POINTER(TapeInfo), C.c_int, C.POINTER(TapeInfo), C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                   C.POINTER(TapeComparePlan)]
+    infos = [TapeInfo(**{k: int(v) for k, v in i.items()}) if isinstance(i, dict) else i for i in (info_a, info_b)]
+    n = max(1, len(lo))
+    clo, chi = (C.c_int64 * n)(*[int(v) for v in lo]), (C.c_int64 * n)(*[int(v) for v in hi])
+    plan = TapeComparePlan()
+    rc = fn(C.byref(infos[0]), int(bits_a), C.byref(infos[1]), int(bits_b), int(point_cols), clo, chi, C.byref(plan))
+    if rc != 0:
+        raise TapeError(rc, lib().pipamd_last_error().decode())
+    return {"n_points": int(plan.n_points), "staged": int(plan.staged)}
+
+
+def compare_summary(tensor):
+    """a comparison's summary (device or host int64 tensor, or a sequence) as {"counts": {...}, "first": {...}} by class
+    name ("same", "status", "value", "range", "outside"; first: the smallest k, -1 if none)"""
+    w = [int(v) for v in (tensor.cpu().tolist() if hasattr(tensor, "cpu") else tensor)]
+    assert len(w) >= CMP_WORDS
+    return {"counts": {n: w[i] for i, n in enumerate(CMP_CLASSES)}, "first": {n: w[5 + i] for i, n in enumerate(CMP_CLASSES)}}
 
 
 class TapeSetInfo(C.Structure):
