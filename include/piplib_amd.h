@@ -146,6 +146,11 @@ int pipamd_engine_set_lone_batches(pipamd_engine *e, int on);
  * tableau.  0: that replay does all the work, a lane per tableau (the sequence of rounds 3 to 5).  Same statuses, pivot
  * counts and solutions either way; the switch is for measurements. */
 int pipamd_engine_set_spare_replay(pipamd_engine *e, int on);
+/* Waves per tableau in that second lean launch: 4 (default) -- the launch lasts as long as its longest tableau's chain of
+ * pivots, so the rows a pivot rewrites are spread over four waves (csrc/pip_lean.h, NW = 4), where the launch's row
+ * capacity has such a kernel (113 ... 160 row slots, no big parameter), else one wave as before -- or 1, the sequence of
+ * round 6.  Same statuses, pivot counts and solutions either way; the switch is for measurements. */
+int pipamd_engine_set_lean2_waves(pipamd_engine *e, int waves);
 /* 128-bit batches without parameters of 129 ... 256 columns (at least 128 tableaux): 1 = the first launch of
  * pipamd_batch_solve is pip_lean64_kernel (csrc/pip_lean.h, long long rows) -- one wave per tableau, rows held as long longs while every
  * entry fits 63 bits (half the traffic and registers), tableaux with a wider entry handed over to the 128-bit kernel.

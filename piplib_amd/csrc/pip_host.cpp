@@ -53,6 +53,8 @@ extern "C" int pipamd_engine_create(pipamd_engine **out, int device) {
     e->no_lean2 = n2 && n2[0] == '1';
     const char *sr = getenv("PIPAMD_NO_SPARE_REPLAY");  // measurement aid, like pipamd_engine_set_spare_replay(e, 0)
     e->no_spare_replay = sr && sr[0] == '1';
+    const char *lw = getenv("PIPAMD_LEAN2_WAVES");  // measurement aid, like pipamd_engine_set_lean2_waves(e, 1)
+    e->lean2_one_wave = lw && lw[0] == '1';
   }
   pthread_mutex_init(&e->dt_lock, nullptr);
   *out = e;
@@ -188,7 +190,9 @@ extern "C" int pipamd_batch_load(pipamd_engine *e, void *d_ws, const pipamd_batc
 //         tableau is finished, has spent `round_pivots` pivots or has filled the LDS image (sized
 //         for the rows it has plus `round_rows` Gomory cuts, so that 24 tableaux fit a CU).  The
 //         workgroup dispatcher starts the next tableau in its place, so every CU stays busy until
-//         all have had their turn.
+//         all have had their turn.  Where the lean kernel (pip_lean.h) takes the batch, a second lean launch follows
+//         over the list of the tableaux the first one paused: a few hundred, four waves per tableau where the row
+//         capacity has that kernel (pipamd_engine_set_lean2_waves), its blocks beyond the list replaying determinant logs.
 //   tail  : what the bulk launch left unfinished (the few tableaux that need many more pivots or
 //         rows) runs to completion with four waves per tableau and an image for every spare row:
 //         little parallelism is left, so the latency of a pivot is what counts.
@@ -196,7 +200,8 @@ extern "C" int pipamd_batch_load(pipamd_engine *e, void *d_ws, const pipamd_batc
 // hit the per-launch pivot limit `iter_limit` go through further tail launches).
 /* Pivot budget per tableau of the first bulk launch where a second lean launch follows it (begin() takes it for that
  * sequence alone, every other bulk launch has 96; pipamd_engine_set_round_pivots overrides both).  A tableau that has
- * spent it waits for the whole launch to end, is widened, listed and re-packed by the second lean launch; of 256
+ * spent it waits for the whole launch to end, is widened, listed and re-packed by the second lean launch (four waves
+ * per tableau since round 7: the budget was measured with one, and was not measured again); of 256
  * headline tableaux nine spend a budget of 96 and one a budget of 128 (tests/test_gpu_first_launch_budget.py).  Measured
  * against 96, 160 and 256 with 16 batches in flight on 4 and on 16 hardware queues (DESIGN.md section 5 round 6,
  * profiles/r06_ab.txt): 128 is ahead of 96 in every round; 160 and 256 are no better with batches in flight and lose
@@ -499,7 +504,10 @@ struct BatchRun {
           // (a block per tableau of the batch over the list of the paused ones: the blocks beyond the list replay the
           // logs the first launch left behind its finished tableaux, pip_lean.h lean_spare_replay)
           spare_went = replay_pending && !e->no_spare_replay;
-          rc = launch(1, b2, smax2, lay.batch, true, false, spare_went);
+          // (four waves per tableau where that row capacity and flavour have the kernel: the launch is a few hundred
+          // tableaux, each a chain of pivots that lasts as long as the rows of a pivot take one after the other)
+          const int w2 = !e->lean2_one_wave && lay.bigparm < 0 && pipk_lean_waves_class(smax2) ? 4 : 1;
+          rc = launch(w2, b2, smax2, lay.batch, true, false, spare_went);
           replay_pending = true;
         } else {
           rc = launch(1, budget, smax, lay.batch, false, !defer);
@@ -735,6 +743,12 @@ extern "C" int pipamd_engine_set_lone_batches(pipamd_engine *e, int on) {
 extern "C" int pipamd_engine_set_spare_replay(pipamd_engine *e, int on) {
   if (!e) return PIPAMD_E_INVALID;
   e->no_spare_replay = on ? 0 : 1;
+  return PIPAMD_OK;
+}
+
+extern "C" int pipamd_engine_set_lean2_waves(pipamd_engine *e, int waves) {
+  if (!e || (waves != 1 && waves != 4)) return PIPAMD_E_INVALID;
+  e->lean2_one_wave = waves == 1;
   return PIPAMD_OK;
 }
 

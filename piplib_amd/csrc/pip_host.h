@@ -21,6 +21,7 @@ struct pipamd_engine {
   int single_launch; /* debug: stop after one launch */
   int lone_batches;  /* 1: no general one-wave launch between the lean launch and the tail (pipamd_engine_set_lone_batches) */
   int no_spare_replay; /* 1: the second lean launch's spare blocks replay no determinant logs (pipamd_engine_set_spare_replay) */
+  int lean2_one_wave; /* 1: the second lean launch runs one wave per tableau, not four (pipamd_engine_set_lean2_waves) */
   int no_lean;       /* 1: bulk launches without the lean kernel (pip_lean.h) */
   int lean64;        /* 1: 128-bit batches of 129 ... 256 columns start with pip_lean64_kernel (pip_lean.h; pipamd_engine_set_lean64) */
   int lean_big;      /* 1: bulk batches whose one parameter is the big one start with the lean kernel's BIG flavour (pipamd_engine_set_lean_big) */
@@ -73,6 +74,7 @@ extern "C" {
 size_t pipk_advance_lds_bytes(int Lmax, int Smax, int Wmax, int ebits);
 int pipk_static_class(int smax);
 int pipk_lean_class(int smax);
+int pipk_lean_waves_class(int smax);
 hipError_t pipk_launch_advance(PipJob *jobs, long long *arena, int njobs, int Lmax, int Smax, int Wmax, int iter_limit,
                                int waves_per_job, int ebits, unsigned long long *prof, hipStream_t stream);
 size_t pipk_lean64_lds_bytes(int Smax, int Lmax);

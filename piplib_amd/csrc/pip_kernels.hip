@@ -21,6 +21,9 @@ PIP_LEAN_CLASSES(PIP_LEAN_EXTERN)
 #define PIP_LEAN_BIG_EXTERN(SC) extern template hipError_t launch_lean<SC, false, true>(const AdvanceLaunch &);
 PIP_LEAN_BIG_CLASSES(PIP_LEAN_BIG_EXTERN)
 #undef PIP_LEAN_BIG_EXTERN
+#define PIP_LEAN4_EXTERN(SC, FULL) extern template hipError_t launch_lean<SC, FULL, false, 4>(const AdvanceLaunch &);
+PIP_LEAN4_CLASSES(PIP_LEAN4_EXTERN)
+#undef PIP_LEAN4_EXTERN
 
 // ------------------------------------------------------------- determinant replay
 // traiter.c:394-446 for the pivots a launch logged: d = gcd(pivot, dpiv); the limbs lose the
@@ -1172,11 +1175,18 @@ extern "C" int pipk_lean_class(int smax) {
   const int s = (smax + 3) & ~3;
   return s <= 64 ? 64 : (s <= 96 ? 96 : (s <= 112 ? 112 : (s <= 128 ? 128 : (s <= 160 ? 160 : 0))));
 }
+// 1 where the lean kernel's class for `smax` row slots also comes with four waves per tableau (pip_lean.h, NW = 4; the
+// plain flavour only): the classes a second lean launch over paused headline-sized tableaux lands in
+extern "C" int pipk_lean_waves_class(int smax) {
+  const int sc = pipk_lean_class(smax);
+  return sc == 128 || sc == 160;
+}
 // the lean kernel of the 128-bit flavour: pip_lean.h's loop on long long rows, row capacity at run time
 __global__ __launch_bounds__(64, PIP_LEAN64_WAVES) void pip_lean64_kernel(PipJob *jobs, i64 *arena, int njobs, int Smax, int Lmax,
                                                                           int iter_limit, PipQueue q PIP_LEAN_PROF_PARAM) {
   typedef LeanLongRows F;
   constexpr bool FULL = false, BIG = false;
+  constexpr int NW = 1;  // (one wave per tableau)
 #define PIP_LEAN_LOOP
 #include "pip_lean.h"
 #undef PIP_LEAN_LOOP
@@ -1223,6 +1233,13 @@ static hipError_t launch_lean_class(AdvanceLaunch a, bool big) {
       case 112: return launch_lean<112, false, true>(a);
       case 128: return launch_lean<128, false, true>(a);
       case 160: return launch_lean<160, false, true>(a);
+    }
+    return hipErrorInvalidValue;
+  }
+  if (a.waves == 4) {  // (the caller has checked pipk_lean_waves_class)
+    switch (sc) {
+      case 128: return a.full ? launch_lean<128, true, false, 4>(a) : launch_lean<128, false, false, 4>(a);
+      case 160: return a.full ? launch_lean<160, true, false, 4>(a) : launch_lean<160, false, false, 4>(a);
     }
     return hipErrorInvalidValue;
   }
@@ -1283,7 +1300,8 @@ static hipError_t launch_by_shape(const AdvanceLaunch &a, bool one, int wp, int 
 // the wave's column coverage (the caller knows its batch is uniform): see FULL.  Bit 1 (one wave per job, 64-bit entries, at
 // most 128 columns and pipk_lean_class(Smax) != 0, else refused) = the lean kernel of pip_lean.h: it runs the jobs it
 // can (no parameters, entries below 2^15) and leaves the others PIPAMD_ST_RUN on the output list for a launch without
-// this bit.  Bit 2: no determinant replay behind the launch (see pipk_launch_replay_all).  Bit 3 (one wave per job, 128-bit
+// this bit; waves_per_job == 4 with it, where pipk_lean_waves_class(Smax) and not bit 4: the same kernel with four waves per
+// tableau, 256-thread blocks, for a launch over a few paused tableaux.  Bit 2: no determinant replay behind the launch (see pipk_launch_replay_all).  Bit 3 (one wave per job, 128-bit
 // entries, 129 ... 256 columns, pipk_lean64_lds_bytes(Smax, Lmax) within the LDS budget, else refused) = the lean kernel of
 // pip_lean.h on long long rows: it runs the jobs it can (no parameters, entries below 2^63) and leaves the others on the output list.
 // Bit 4 (with bit 1): every job has nparm == 1 and bigparm == nvar + 1 -- the lean kernel's BIG flavour.
@@ -1348,7 +1366,9 @@ extern "C" hipError_t pipk_launch_advance_q(PipJob *jobs, i64 *arena, int njobs,
     // (every workgroup releases its block before it ends), so nothing needs zeroing per launch
   }
   a.stream = stream;
-  const bool one = waves_per_job == 1;
+  // (the lean kernel with four waves per tableau is a bulk launch like the one-wave kernels: same replay behind it)
+  const bool lean4 = (hints & 2) && !(hints & 16) && waves_per_job == 4 && pipk_lean_waves_class(a.Smax);
+  const bool one = waves_per_job == 1 || lean4;
   const int wp = wp_of(Wmax, ebits);
   hipError_t le;
   if (hints & 2) {

@@ -2,7 +2,8 @@
 // batches live in, written once (the text under PIP_LEAN_LOOP at the end of this file) against a "row flavour", compiled
 // for the two flavours below.
 //
-// A lean kernel is one wave per tableau, no parameters (BIG flavour of the int rows: the big parameter alone), rows skipped, plain cuts -- and EVERY entry of
+// A lean kernel is one wave per tableau (pip_lean_kernel also four, NW: for the launch over the few hundred tableaux a first
+// lean launch paused, see the entry points below), no parameters (BIG flavour of the int rows: the big parameter alone), rows skipped, plain cuts -- and EVERY entry of
 // EVERY row stored at HALF the width of the flavour's Entier T (the packed element E).  Under that invariant
 //   * rows live in HBM packed (the first half of the row's slot of W entries of T): half the traffic of the reference's
 //     rows, half the working set, half the registers;
@@ -404,17 +405,19 @@ __device__ __forceinline__ u64 lean_prepare_rows(const Shared<typename F::T> &S,
 }
 
 // rows [0, n) of a block, packed -> the general format, each within its own slot (the loads of a group of rows are back
-// before their slots are overwritten); rows of class 2 or 3 (rcls, LDS) are in the general format already
+// before their slots are overwritten); rows of class 2 or 3 (rcls, LDS) are in the general format already.
+// (first, step: the calling wave's share of the rows -- first, first + step, ... -- where several waves hold a tableau)
 template <class F>
-__device__ __forceinline__ void rows_unpack(typename F::T *vals, int n, int lane, int W, const u8 *rcls) {
+__device__ __forceinline__ void rows_unpack(typename F::T *vals, int n, int lane, int W, const u8 *rcls, int first = 0, int step = 1) {
   constexpr int G = F::UNPACK_GROUP;
-  for (int s0 = 0; s0 < n; s0 += G) {
+  for (int s0 = 0; first + step * s0 < n; s0 += G) {
     typename F::Row rr[G];
     bool packed[G];
 #pragma unroll
     for (int qq = 0; qq < G; qq++) {
-      packed[qq] = s0 + qq < n && rcls[s0 + qq] < 2;
-      if (packed[qq]) F::load(rr[qq], vals + (size_t)(s0 + qq) * W, lane, W);
+      const int s = first + step * (s0 + qq);
+      packed[qq] = s < n && rcls[s] < 2;
+      if (packed[qq]) F::load(rr[qq], vals + (size_t)s * W, lane, W);
     }
 #pragma unroll
     for (int qq = 0; qq < G; qq++)
@@ -422,7 +425,7 @@ __device__ __forceinline__ void rows_unpack(typename F::T *vals, int n, int lane
         typename F::T z[F::NV];
 #pragma unroll
         for (int h = 0; h < F::NV; h++) z[h] = (typename F::T)rr[qq].v[h];
-        F::store_wide(z, vals + (size_t)(s0 + qq) * W, lane, W);
+        F::store_wide(z, vals + (size_t)(first + step * (s0 + qq)) * W, lane, W);
       }
   }
 }
@@ -650,27 +653,46 @@ __device__ __forceinline__ void lean_spare_replay(PipJob *jobs, i64 *arena, int 
 // FULL: 127 unknowns + constant, a row fills the wave's 128 columns (the launcher's promise, as for pip_advance_kernel);
 // else any number of unknowns up to 127 without parameters, rows of W <= 128 columns (W even).
 // BIG (FULL == false only): one parameter, the big one, in column nvar + 1; up to 126 unknowns.
-template <int SC, bool FULL, bool BIG = false>
-__global__ __launch_bounds__(64, PIP_LEAN_WAVES) void pip_lean_kernel(PipJob *jobs, i64 *arena, int njobs, int iter_limit,
-                                                                      PipQueue q PIP_LEAN_PROF_PARAM) {
+// NW: waves per tableau.  1: the kernel of the bulk launches (64 VGPRs, eight waves per SIMD).  4: for a launch over a few
+// hundred paused tableaux (pipamd_batch_solve's second lean launch), where a wave has its SIMD to itself whatever the
+// kernel needs and the launch lasts as long as one tableau's dependent chain: the row-parallel parts of that chain --
+// the entry pass, the row loop of phase B, phase C, the widening of the epilogue -- are spread over the waves the way
+// pip_advance_kernel spreads them (wave v: rows v, v + NW, ...; barriers as there), choisir_piv and the cut stay on
+// wave 0, and every wave holds the pivot row in its own registers.  What decides an exit from the loop is wave-uniform
+// at every point where it is tested: read from LDS behind a barrier (LeanWaves, Scalars) or counted alike by every wave.
+// Same bits as one wave: a row's new value does not depend on which wave computes it.
+struct LeanWaves {
+  int mcw;      // largest magnitude class any wave has published (atomicMax; never lowered)
+  int wide;     // entry pass: some wave met a row beyond the packed elements
+  int verdict;  // integrer(): what wave 0 decided about the cut
+};
+template <int SC, bool FULL, bool BIG = false, int NW = 1>
+__global__ __launch_bounds__(64 * NW, NW == 1 ? PIP_LEAN_WAVES : 2) void pip_lean_kernel(PipJob *jobs, i64 *arena, int njobs,
+                                                                                         int iter_limit,
+                                                                                         PipQueue q PIP_LEAN_PROF_PARAM) {
+  static_assert(NW == 1 || (NW == 4 && !BIG), "four waves per tableau: the plain flavour only");
   typedef LeanIntRows F;
   constexpr int Smax = SC, Lmax = SC + 128;
 #define PIP_LEAN_LOOP
 #include "pip_lean.h"
 #undef PIP_LEAN_LOOP
 }
-template <int SC, bool FULL, bool BIG = false>
+template <int SC, bool FULL, bool BIG = false, int NW = 1>
 hipError_t launch_lean(const AdvanceLaunch &a) {
   const int grid = a.grid > 0 && a.grid < a.njobs ? a.grid : a.njobs;
   const size_t shm = lean_lds_bytes(SC);
 #ifdef PIP_PROFILE
-  hipLaunchKernelGGL((pip_lean_kernel<SC, FULL, BIG>), dim3(grid), dim3(64), shm, a.stream, a.jobs, a.arena, a.njobs, a.iter_limit, a.q,
-                     (u64 *)a.prof);
+  hipLaunchKernelGGL((pip_lean_kernel<SC, FULL, BIG, NW>), dim3(grid), dim3(64 * NW), shm, a.stream, a.jobs, a.arena, a.njobs,
+                     a.iter_limit, a.q, (u64 *)a.prof);
 #else
-  hipLaunchKernelGGL((pip_lean_kernel<SC, FULL, BIG>), dim3(grid), dim3(64), shm, a.stream, a.jobs, a.arena, a.njobs, a.iter_limit, a.q);
+  hipLaunchKernelGGL((pip_lean_kernel<SC, FULL, BIG, NW>), dim3(grid), dim3(64 * NW), shm, a.stream, a.jobs, a.arena, a.njobs,
+                     a.iter_limit, a.q);
 #endif
   return hipGetLastError();
 }
+// the classes that also come with four waves per tableau (pipk_lean_waves_class, pip_kernels.hip)
+#define PIP_LEAN4_CLASSES(X) X(128, true) X(160, true) X(128, false) X(160, false)
+#define PIP_LEAN4_DEFINE(SC, FULL) template hipError_t launch_lean<SC, FULL, false, 4>(const AdvanceLaunch &);
 // the row-capacity classes of launch_static (pip_kernels.hip)
 #define PIP_LEAN_CLASSES(X) \
   X(64, true) X(96, true) X(112, true) X(128, true) X(160, true) X(64, false) X(96, false) X(112, false) X(128, false) X(160, false)
@@ -691,21 +713,27 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
   typedef typename F::Row Row;
   PROF_DECL;
   constexpr int WP = F::WP, NM = F::NM, NV = F::NV;
+  constexpr int NT = 64 * NW;  // (NW: waves per tableau, named by the kernel like F; every wave-index term below folds away at 1)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ Scalars sc;
+  [[maybe_unused]] __shared__ LeanWaves lw;  // (NW > 1 only)
   const int nq = q.in_count ? *q.in_count : njobs;
   if ((int)blockIdx.x >= nq) {
     // a launch sized by the batch over a shorter list: the first blocks beyond the list do the determinant bookkeeping
-    // of the jobs the earlier launch finished, beside this launch's own jobs (PipQueue.replay_spare)
+    // of the jobs the earlier launch finished, beside this launch's own jobs (PipQueue.replay_spare).  (64 jobs a block,
+    // a lane each, whatever the block size: the first wave does it.)
     if constexpr (sizeof(T) == 8)
-      if (q.replay_spare && q.in_list) lean_spare_replay<T>(jobs, arena, njobs, q.in_list, nq, (int)blockIdx.x - nq, smem);
+      if ((NW == 1 || threadIdx.x < 64) && q.replay_spare && q.in_list)
+        lean_spare_replay<T>(jobs, arena, njobs, q.in_list, nq, (int)blockIdx.x - nq, smem);
     return;
   }
   const int jb = q.in_list ? q.in_list[blockIdx.x] : (int)blockIdx.x;
   PipJob *J = &jobs[jb];
-  const int lane = threadIdx.x;
+  const int tid = threadIdx.x;
+  const int lane = NW > 1 ? (tid & 63) : tid;
+  const int wave = NW > 1 ? __builtin_amdgcn_readfirstlane(tid >> 6) : 0;
   if (J->status != PIPAMD_ST_RUN) {
-    if (J->status == PIPAMD_ST_CAPACITY && q.out_count && lane == 0) {
+    if (J->status == PIPAMD_ST_CAPACITY && q.out_count && tid == 0) {
       q.out_list[atomicAdd(q.out_count, 1)] = jb;
       atomicMax(q.out_maxni, PIPAMD_Q_CAPFLAG | J->ni);
       atomicAdd(q.out_maxni + 1, 1);  // (the list's third control word: tableaux out of rows)
@@ -720,7 +748,7 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
   const bool mine = (BIG ? F::shape_big(J, nvar, W) : F::shape(J, nvar, W)) && !(tflags & (PIPAMD_T_NOSKIP | PIPAMD_T_DEEPEST)) && ni <= Smax && nligne <= Lmax &&
                     (!(tflags & PIPAMD_T_STATE) || J->state_nch == F::NCH);
   if (!mine) {
-    if (lane == 0 && q.out_count) {
+    if (tid == 0 && q.out_count) {
       q.out_list[atomicAdd(q.out_count, 1)] = jb;
       atomicMax(q.out_maxni, ni);
     }
@@ -758,11 +786,14 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
   }
 
   // ---- the row tables (the sort keys share storage with the constant terms here: not zeroed)
-  for (int j = lane; j < WP; j += 64) S.urow[j] = NOROW;
-  if (lane == 0) reset_scalars(sc);
-  __builtin_amdgcn_wave_barrier();
-  stage_row_tables<T, 64, false>(S, pip_row_tables<const T>(arena + J->rows_off, J->L), nligne, lane);
-  __builtin_amdgcn_wave_barrier();
+  for (int j = tid; j < WP; j += NT) S.urow[j] = NOROW;
+  if (tid == 0) {
+    reset_scalars(sc);
+    if constexpr (NW > 1) lw = LeanWaves{0, 0, 0};
+  }
+  bsync<NW>();
+  stage_row_tables<T, NT, false>(S, pip_row_tables<const T>(arena + J->rows_off, J->L), nligne, tid);
+  bsync<NW>();
 
   // ---- one pass over the tableau: the rows become packed (int rows of a job loaded with PIPAMD_T_ROWS_STAY come from
   // the caller's array), summaries, sort keys.  A row with an entry of 2^ROW_BITS or more: not a job for this kernel.
@@ -778,14 +809,16 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
     const int pitch = fresh ? nvar + NCOL1 : W;  // the caller's rows are that wide (an even number: pipamd_batch_load), the block's W
     int npacked = 0;
     bool wide = false;
-    for (int s0 = 0; s0 < ni && !wide; s0 += PF0) {
+    // (wave v of NW: rows v, v + NW, ...)
+    for (int s0 = 0; wave + NW * s0 < ni && !wide; s0 += PF0) {
       RowRegs<T, F::NCH> rr[PF0];
 #pragma unroll
       for (int qq = 0; qq < PF0; qq++)
-        if (s0 + qq < ni) row_load<T, F::NCH>(rr[qq], src + (size_t)(s0 + qq) * pitch, (nvar + NCOL1 - 1 + CPL) & ~(CPL - 1), lane);
+        if (wave + NW * (s0 + qq) < ni)
+          row_load<T, F::NCH>(rr[qq], src + (size_t)(wave + NW * (s0 + qq)) * pitch, (nvar + NCOL1 - 1 + CPL) & ~(CPL - 1), lane);
 #pragma unroll
       for (int qq = 0; qq < PF0; qq++) {
-        const int s = s0 + qq;
+        const int s = wave + NW * (s0 + qq);
         if (s >= ni || wide) break;
         typename ET<T>::U mx = 0;
         Row z;
@@ -823,11 +856,21 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
         }
       }
     }
+    if constexpr (NW > 1) {
+      // what the waves found, each in its own rows: known to all of them behind the barrier
+      if (lane == 0) {
+        if (wide) lw.wide = 1;
+        if (mcw) atomicMax(&lw.mcw, mcw);
+      }
+      __syncthreads();
+      wide = lw.wide != 0;
+      mcw = lw.mcw;
+    }
     if (wide) {
       // an entry beyond E: not a job for this kernel.  Its header is untouched (FRESHROWS and SORT still stand); rows
-      // that came from the block itself and were already packed are widened again.
-      if (!fresh) rows_unpack<F>(vals, npacked, lane, W, S.rcls);
-      if (lane == 0 && q.out_count) {
+      // that came from the block itself and were already packed are widened again (by the wave that packed them).
+      if (!fresh) rows_unpack<F>(vals, npacked, lane, W, S.rcls, wave, NW);
+      if (tid == 0 && q.out_count) {
         q.out_list[atomicAdd(q.out_count, 1)] = jb;
         atomicMax(q.out_maxni, ni);
       }
@@ -835,20 +878,21 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
     }
   }
   if constexpr (F::FRESH) tflags &= ~PIPAMD_T_FRESHROWS;
-  __builtin_amdgcn_wave_barrier();
+  if constexpr (NW == 1) __builtin_amdgcn_wave_barrier();  // (NW > 1: the barrier above)
   if (tflags & PIPAMD_T_SORT) {
-    [[clang::always_inline]] sort_rows(S, nvar, nligne, (double)sc.smaxbits);  // (left to the inliner, sort_rows<__int128> stays a call: scratch)
-    __builtin_amdgcn_wave_barrier();
-    for (int i = lane; i < nligne; i += 64)
+    if (NW == 1 || wave == 0)
+      [[clang::always_inline]] sort_rows(S, nvar, nligne, (double)sc.smaxbits);  // (left to the inliner, sort_rows<__int128> stays a call: scratch)
+    bsync<NW>();
+    for (int i = tid; i < nligne; i += NT)
       if (!(S.ref[i] & UNITBIT)) S.srow[S.ref[i]] = (u16)i;
     tflags &= ~PIPAMD_T_SORT;
     // the sort keys overwrote the constant terms: back from the rows (column nvar)
     __threadfence_block();
-    for (int s = lane; s < ni; s += 64) cst[s] = reinterpret_cast<const E *>(vals + (size_t)s * W)[nvar];
-    __builtin_amdgcn_wave_barrier();
+    for (int s = tid; s < ni; s += NT) cst[s] = reinterpret_cast<const E *>(vals + (size_t)s * W)[nvar];
+    bsync<NW>();
   }
-  first_chercher<T, 64>(S, &sc, ni, BIG ? nvar + 1 : -1, lane);
-  __builtin_amdgcn_wave_barrier();
+  first_chercher<T, NT>(S, &sc, ni, BIG ? nvar + 1 : -1, tid);
+  bsync<NW>();
 
   PROF(10);
   int status = PIPAMD_ST_RUN;
@@ -872,8 +916,8 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
         [[clang::always_inline]] pivi = exam_rows<T, 1>(S, &sc, ni);
       } else {
         pivi = sc.pivi2;
-        apply_exam_flags<T, 64>(S, ni, pivi, lane);
-        __builtin_amdgcn_wave_barrier();
+        apply_exam_flags<T, NT>(S, ni, pivi, tid);
+        bsync<NW>();
       }
       if (pivi == BIG_I) {
         // (BIG: the one parameter is the big one, so exam_rows has decided every row -- a negative big coefficient, else a
@@ -884,16 +928,16 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
           break;
         }
         // ------------- integrer(): first non-integral row among the unknowns (integrer.c:305-486, constant cuts)
-        if (lane == 0) sc.tmp = BIG_I;
-        __builtin_amdgcn_wave_barrier();
-        for (int i = lane; i < nvar; i += 64) {
+        if (tid == 0) sc.tmp = BIG_I;
+        bsync<NW>();
+        for (int i = tid; i < nvar; i += NT) {
           const int rf = S.ref[i];
           if (rf & UNITBIT) continue;
           const T D = S.den[rf];
           if (D == 1) continue;
           if (wneg(fmod64(wneg((T)cst[rf]), D)) != 0) atomicMin(&sc.tmp, i);
         }
-        __builtin_amdgcn_wave_barrier();
+        bsync<NW>();
         const int ci = sc.tmp;
         if (ci == BIG_I) {
           status = PIPAMD_ST_SOLUTION;
@@ -904,42 +948,48 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
         why = 3;
         if (DT <= 0 || DT >= ((T)1 << F::CUT_BITS)) break;  // the cut's entries (below D) might not fit E: the general kernel goes on
         const E D = (E)DT;
-        Row &r = pr;  // (PIP_LEAN_KEEPCUT: the cut is the next pivot row)
-        F::load(r, vals + (size_t)cslot * W, lane, W);
-        F::row_mod(r, D, S.rcls[cslot] == 0);
-        bool okv = false;
+        int verdict = PIPAMD_ST_RUN;
+        if (NW == 1 || wave == 0) {  // (several waves: the first builds and appends the cut)
+          Row &r = pr;  // (PIP_LEAN_KEEPCUT: the cut is the next pivot row)
+          F::load(r, vals + (size_t)cslot * W, lane, W);
+          F::row_mod(r, D, S.rcls[cslot] == 0);
+          bool okv = false;
 #pragma unroll
-        for (int h = 0; h < NV; h++) {
-          const E pos = r.v[h];
-          if (F::col(lane, h) < nvar)
-            okv |= pos > 0;
-          else
-            r.v[h] = pos ? pos - D : 0;  // -((-v) mod D) == (v mod D) - D unless D divides v
-          if constexpr (BIG)
-            if (F::col(lane, h) == nvar + 1) r.v[h] = 0;  // the big parameter is divisible by any number (integrer.c:373-377)
-        }
-        const bool any_v = ballot64(okv) != 0;
-        int verdict;
-        if (!any_v)
-          verdict = PIPAMD_ST_NIL;  // integrer.c:482-485 case (b)
-        else if (ni >= cap_ni)
-          verdict = PIPAMD_ST_CAPACITY;
-        else if (ni >= Smax || nligne >= Lmax)
-          verdict = -1;  // no room in this launch's LDS image: pause
-        else {
-          verdict = PIPAMD_ST_RUN;
-          F::store(r, vals + (size_t)ni * W, lane, W);
-          mcw = max(mcw, lean_publish<F, BIG>(r, S, cst, ni, -1, 0, lane, nvar));
+          for (int h = 0; h < NV; h++) {
+            const E pos = r.v[h];
+            if (F::col(lane, h) < nvar)
+              okv |= pos > 0;
+            else
+              r.v[h] = pos ? pos - D : 0;  // -((-v) mod D) == (v mod D) - D unless D divides v
+            if constexpr (BIG)
+              if (F::col(lane, h) == nvar + 1) r.v[h] = 0;  // the big parameter is divisible by any number (integrer.c:373-377)
+          }
+          const bool any_v = ballot64(okv) != 0;
+          if (!any_v)
+            verdict = PIPAMD_ST_NIL;  // integrer.c:482-485 case (b)
+          else if (ni >= cap_ni)
+            verdict = PIPAMD_ST_CAPACITY;
+          else if (ni >= Smax || nligne >= Lmax)
+            verdict = -1;  // no room in this launch's LDS image: pause
+          else {
+            verdict = PIPAMD_ST_RUN;
+            F::store(r, vals + (size_t)ni * W, lane, W);
+            mcw = max(mcw, lean_publish<F, BIG>(r, S, cst, ni, -1, 0, lane, nvar));
+            if (lane == 0) {
+              S.fl[ni] = PIPAMD_F_MINUS;
+              S.nf[ni] = 0;
+              S.den[ni] = DT;
+              S.ref[nligne] = (u16)ni;
+              S.srow[ni] = (u16)nligne;
+            }
+          }
           if (lane == 0) {
-            S.fl[ni] = PIPAMD_F_MINUS;
-            S.nf[ni] = 0;
-            S.den[ni] = DT;
-            S.ref[nligne] = (u16)ni;
-            S.srow[ni] = (u16)nligne;
+            sc.aux = ci;
+            if constexpr (NW > 1) lw.verdict = verdict;
           }
         }
-        if (lane == 0) sc.aux = ci;
-        __builtin_amdgcn_wave_barrier();
+        bsync<NW>();  // (several waves: the cut's row is stored and its tables are written before another wave looks)
+        if constexpr (NW > 1) verdict = lw.verdict;
         why = 5;
         if (verdict != PIPAMD_ST_RUN) {
           status = verdict < 0 ? PIPAMD_ST_RUN : verdict;
@@ -948,7 +998,7 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
         pivi = nligne;
         ni++;
         nligne++;
-        have_pr = PIP_LEAN_KEEPCUT != 0;
+        have_pr = PIP_LEAN_KEEPCUT != 0 && (NW == 1 || wave == 0);
       }
     }
     PROF(0);
@@ -965,23 +1015,45 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
     PROF(1);
-    const int pj = mcw == 0 ? lean_choose_column<F, true>(S, pr, vals, W, nvar, nligne, pivi, &sc)
-                            : lean_choose_column<F, false>(S, pr, vals, W, nvar, nligne, pivi, &sc);
+    int pj = -1;
+    if (NW == 1 || wave == 0)
+      pj = mcw == 0 ? lean_choose_column<F, true>(S, pr, vals, W, nvar, nligne, pivi, &sc)
+                    : lean_choose_column<F, false>(S, pr, vals, W, nvar, nligne, pivi, &sc);
+    if constexpr (NW > 1) {
+      // the first wave chose the column and lists the rows; the others have asked for the pivot row meanwhile (its slot
+      // is rewritten only behind this barrier, their loads are issued ahead of it: the order __syncthreads() keeps
+      // within a workgroup)
+      if (wave == 0) {
+        int nw0 = 0;
+        if (pj != -1) nw0 = pivot_work_list<T, NM>(S, ni, pslot, F::val_of(pj), F::lane_of(pj), false, lane);
+        if (lane == 0) {
+          sc.pivj = pj;
+          sc.nwork = nw0;
+        }
+      }
+      __syncthreads();
+      pj = sc.pivj;
+    }
     if (pj == -1) {  // traiter.c:782-785
       status = PIPAMD_ST_NIL;
       break;
     }
     PROF(2);
     const int pe = F::val_of(pj), pl = F::lane_of(pj);
-    const int nwork = pivot_work_list<T, NM>(S, ni, pslot, pe, pl, false, lane);
-    __builtin_amdgcn_wave_barrier();
-    if (lane == 0) {  // phase C refills them
+    int nwork;
+    if constexpr (NW > 1) {
+      nwork = sc.nwork;
+    } else {
+      nwork = pivot_work_list<T, NM>(S, ni, pslot, pe, pl, false, lane);
+      __builtin_amdgcn_wave_barrier();
+    }
+    if (tid == 0) {  // phase C refills them
       sc.pivi = BIG_I;
       sc.pivi2 = BIG_I;
     }
     const int pivj = pj;
     const E pivot = lean_entry<F>(pr.v, pe, pl);
-    if (lane == 0) {
+    if (tid == 0) {
       g_log[2 * nlog] = (T)pivot;
       g_log[2 * nlog + 1] = dpiv;
     }
@@ -990,7 +1062,9 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
     const int pred = psig_v & SIG_RED;
     PROF(3);
     // ---------------- B: eliminate the pivot column
-    nupd += nwork - 1;
+    nupd += nwork - 1;  // (counted alike by every wave)
+    // wave v of NW takes entries v, v + NW, ... of the work list: entry w of its share is entry wave + NW * w of the list
+    const int nmine = NW == 1 ? nwork : (nwork - wave + NW - 1) / NW;
     {
       // a queue of PF rows on their way from HBM / L2: the row at its head is updated while the loads behind it are in
       // flight
@@ -1007,18 +1081,20 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
       bool pact = false;
       E pf = 0;
       if constexpr (F::PREP) {
-        pk = S.work[lane < nwork ? lane : 0];
-        pact = lane < nwork && pk != pslot;
+        pk = S.work[lane < nmine ? wave + NW * lane : 0];
+        pact = lane < nmine && pk != pslot;
         if (pact) pf = F::gather(vals + (size_t)pk * W, pivj);
       }
 #pragma unroll
       for (int q2 = 0; q2 < PF; q2++) {
-        sq[q2] = S.work[q2 < nwork ? q2 : 0];
-        if (q2 < nwork && sq[q2] != pslot) F::load(rq[q2], vals + (size_t)sq[q2] * W, lane, W);
+        sq[q2] = S.work[q2 < nmine ? wave + NW * q2 : 0];
+        if (q2 < nmine && sq[q2] != pslot) F::load(rq[q2], vals + (size_t)sq[q2] * W, lane, W);
       }
       // while the first rows are on their way: the pivot slot is recycled for the row replacing ku's unit row
-      // (traiter.c:461-465,503-513) -- it needs no load, the pivot row is in registers
-      if (F::fits(dpiv)) {
+      // (traiter.c:461-465,503-513) -- it needs no load, the pivot row is in registers (several waves: the first does it)
+      if (NW > 1 && wave != 0) {
+        // (the first wave's)
+      } else if (F::fits(dpiv)) {
         Row r;
 #pragma unroll
         for (int h = 0; h < NV; h++) r.v[h] = (F::col(lane, h) == pivj) ? (E)dpiv : (E)wneg((i64)pr.v[h]);
@@ -1032,12 +1108,12 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
         mcw = max(mcw, lean_publish_wide<F, BIG>(zw, S, cst, pslot, pivj, pred, lane, nvar));
       }
       PROF(4);
-      for (int w = 0; w < nwork; w++) {
+      for (int w = 0; w < nmine; w++) {
         if constexpr (F::PREP) {
           if ((w & 63) == 0) {
             if (w) {  // (more than 64 work rows: the next 64)
-              pk = S.work[w + lane < nwork ? w + lane : 0];
-              pact = w + lane < nwork && pk != pslot;
+              pk = S.work[w + lane < nmine ? wave + NW * (w + lane) : 0];
+              pact = w + lane < nmine && pk != pslot;
               if (pact) pf = F::gather(vals + (size_t)pk * W, pivj);
             }
             m_small = lean_prepare_rows<F>(S, pk, pact, pf, pivot, dpiv, psmall, m_lp, m_foo, m_g0, m_gs);
@@ -1050,8 +1126,8 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
           rq[q2] = rq[q2 + 1];
           sq[q2] = sq[q2 + 1];
         }
-        if (w + PF < nwork) {
-          sq[PF - 1] = S.work[w + PF];
+        if (w + PF < nmine) {
+          sq[PF - 1] = S.work[wave + NW * (w + PF)];
           if (sq[PF - 1] != pslot) F::load(rq[PF - 1], vals + (size_t)sq[PF - 1] * W, lane, W);
         }
         T *row = vals + (size_t)s * W;
@@ -1119,24 +1195,29 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
         PROF(8);
       }
     }
-    __builtin_amdgcn_wave_barrier();
+    // (several waves: every row of this pivot is stored and summarised behind this barrier -- the ordering of
+    // pip_advance_kernel's row loop -- and the largest class any wave published is every wave's from here on)
+    if constexpr (NW > 1)
+      if (lane == 0 && mcw) atomicMax(&lw.mcw, mcw);
+    bsync<NW>();
+    if constexpr (NW > 1) mcw = lw.mcw;
     PROF(4);
     if (sc.bad) {
       status = PIPAMD_ST_OVERFLOW;
       break;
     }
     // ---------------- C: swap roles, refresh the sign hints, next chercher (traiter.c:503-529)
-    pivot_swap_roles<T, 64>(S, &sc, ni, pivi, pivj, pslot, ku, (T)pivot, BIG ? nvar + 1 : -1, lane);
-    __builtin_amdgcn_wave_barrier();
+    pivot_swap_roles<T, NT>(S, &sc, ni, pivi, pivj, pslot, ku, (T)pivot, BIG ? nvar + 1 : -1, tid);
+    bsync<NW>();
     PROF(9);
   }
 
   // ---- epilogue: the row tables, the header and (if any) the solution
-  __builtin_amdgcn_wave_barrier();
-  publish_row_tables<T, 64>(S, pip_row_tables<T>(arena + J->rows_off, J->L), nligne, lane);
+  bsync<NW>();
+  publish_row_tables<T, NT>(S, pip_row_tables<T>(arena + J->rows_off, J->L), nligne, tid);
   tflags &= ~PIPAMD_T_STATE;
   if (status == PIPAMD_ST_RUN) {
-    save_summaries<T, 64>(S, saved_summaries(arena + J->state_off, J->S, NM), ni, NM, lane);
+    save_summaries<T, NT>(S, saved_summaries(arena + J->state_off, J->S, NM), ni, NM, tid);
     tflags |= PIPAMD_T_STATE;
   }
   if (status == PIPAMD_ST_SOLUTION) {
@@ -1146,7 +1227,7 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
     T *sol_num = (T *)(arena + J->sol_off);
     T *sol_den = sol_num + NN * nvar;
     if constexpr (BIG) __threadfence_block();
-    for (int i = lane; i < nvar; i += 64) {
+    for (int i = tid; i < nvar; i += NT) {
       const int rf = S.ref[i];
       T v = 0, d = 1;
       [[maybe_unused]] T bv = 0;
@@ -1162,10 +1243,11 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
   }
   if (status == PIPAMD_ST_RUN || status == PIPAMD_ST_CAPACITY) {
     // the job goes on elsewhere (pip_advance_kernel, pip_rehouse_kernel): its rows in the general format again
-    rows_unpack<F>(vals, ni, lane, W, S.rcls);
+    rows_unpack<F>(vals, ni, lane, W, S.rcls, wave, NW);
   }
   const int mc = max_row_class(S, ni, lane);
-  if (lane == 0) {
+  if constexpr (NW > 1) __syncthreads();  // (no wave reads the header any more: one lane rewrites it and lists the job)
+  if (tid == 0) {
     // (the header still holds the counts the launch began with: a pivot it counted and did not log is the call of pivoter
     // that found no column and ended the job -- det_unlogged, pip_advance.h)
     const bool nocolumn = status == PIPAMD_ST_NIL && npiv - nlog != J->npiv - J->nlog;

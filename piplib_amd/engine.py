@@ -191,6 +191,12 @@ class Engine:
         lib().pipamd_engine_set_spare_replay.argtypes = [C.c_void_p, C.c_int]
         _check(lib().pipamd_engine_set_spare_replay(self._h, int(bool(on))))
 
+    def set_lean2_waves(self, waves):
+        """waves per tableau of the second lean launch: 4 (default, where its row capacity has that kernel) or 1
+        (pipamd_engine_set_lean2_waves)"""
+        lib().pipamd_engine_set_lean2_waves.argtypes = [C.c_void_p, C.c_int]
+        _check(lib().pipamd_engine_set_lean2_waves(self._h, int(waves)))
+
     def set_lean64(self, on):
         """128-bit batches of 129 ... 256 columns start with pip_lean64_kernel (csrc/pip_lean.h; default off)"""
         lib().pipamd_engine_set_lean64.argtypes = [C.c_void_p, C.c_int]
