@@ -184,31 +184,7 @@ extern "C" int pipamd_batch_load(pipamd_engine *e, void *d_ws, const pipamd_batc
   return pipamd_batch_load_part(e, d_ws, d, d_rows, 0, d->batch, stream);
 }
 
-// traiter() for the whole batch, as a short sequence of launches without a host round trip in
-// between (each launch writes the list of tableaux it left unfinished, the next one reads it):
-//   bulk  (batches of >= `bulk_min` tableaux, default 2048): one wave per tableau; a tableau's workgroup ends when the
-//         tableau is finished, has spent `round_pivots` pivots or has filled the LDS image (sized
-//         for the rows it has plus `round_rows` Gomory cuts, so that 24 tableaux fit a CU).  The
-//         workgroup dispatcher starts the next tableau in its place, so every CU stays busy until
-//         all have had their turn.  Where the lean kernel (pip_lean.h) takes the batch, a second lean launch follows
-//         over the list of the tableaux the first one paused: a few hundred, four waves per tableau where the row
-//         capacity has that kernel (pipamd_engine_set_lean2_waves), its blocks beyond the list replaying determinant logs.
-//   tail  : what the bulk launch left unfinished (the few tableaux that need many more pivots or
-//         rows) runs to completion with four waves per tableau and an image for every spare row:
-//         little parallelism is left, so the latency of a pivot is what counts.
-// Only then the host looks at the number of tableaux still running (normally 0; tableaux that
-// hit the per-launch pivot limit `iter_limit` go through further tail launches).
-/* Pivot budget per tableau of the first bulk launch where a second lean launch follows it (begin() takes it for that
- * sequence alone, every other bulk launch has 96; pipamd_engine_set_round_pivots overrides both).  A tableau that has
- * spent it waits for the whole launch to end, is widened, listed and re-packed by the second lean launch (four waves
- * per tableau since round 7: the budget was measured with one, and was not measured again); of 256
- * headline tableaux nine spend a budget of 96 and one a budget of 128 (tests/test_gpu_first_launch_budget.py).  Measured
- * against 96, 160 and 256 with 16 batches in flight on 4 and on 16 hardware queues (DESIGN.md section 5 round 6,
- * profiles/r06_ab.txt): 128 is ahead of 96 in every round; 160 and 256 are no better with batches in flight and lose
- * 8-11 % for a batch on its own. */
-#ifndef PIPAMD_ROUND_PIVOTS
-#define PIPAMD_ROUND_PIVOTS 128
-#endif
+// The launch sequence of pipamd_batch_solve is decided in pip_plan.h (pip_plan_batch, pip_plan_tail); BatchRun issues it.
 #define Q_CTRL 3 /* control words per launch: out_count, out_maxni, the number of listed jobs that are out of rows */
 // Control words (out_count, out_maxni per launch) must be zero when a launch starts.  They come
 // from a pool of Q_POOL solves x Q_FAST launches that one memset zeroes every Q_POOL solves (a
@@ -228,12 +204,12 @@ struct BatchRun {
   hipStream_t st;
   int *pool, *over, *list[2];
   bool over_zeroed, have_list, active, finishing, replay_pending;
-  bool spare_went;  // the second lean launch's spare blocks replayed the logs of the jobs the first one finished
+  PipPlanIn in;    // what the launch sequence was decided from, and the decision (pip_plan.h)
+  PipPlan plan;
   int stage;       // launches issued
   int curS;        // row capacity of the largest block in play (grows when tableaux are re-housed)
   int grow_round;
   int upper;       // what the host knows about the length of the next input list
-  int tail_waves;
 
   int *ctrl_of(int stg) const { return stg < Q_FAST ? pool + Q_CTRL * stg : over + Q_CTRL * (stg - Q_FAST); }
 
@@ -326,10 +302,10 @@ struct BatchRun {
     return PIPAMD_OK;
   }
 
-  int launch(int waves, int budget, int smax, int grid, bool lean = false, bool replay = true, bool spare = false) {
+  int launch(const PipStep &s) {
     int rcs = next_stage();
     if (rcs) return rcs;
-    if (smax > curS) smax = curS;
+    const int smax = s.smax > curS ? curS : s.smax;
     int *c = ctrl_of(stage);
     void *q5[5] = {nullptr, nullptr, list[stage & 1], c, c + 1};
     if (have_list) {
@@ -345,12 +321,13 @@ struct BatchRun {
       HIPCHK(hipEventRecord(e->ev[2 * e->nlaunch], st));
     }
     void *big[2] = {&e->d_scratch, &e->scratch_bytes};
-    // a uniform batch without parameters whose rows fill a wave's 128 columns exactly: FULL kernels
-    const int hints = ((lay.nparm == 0 && lay.bigparm < 0 && lay.nvar + 1 == 128 && lay.W == 128) ? 1 : 0) |
-                      (lean ? (lay.ebits == 128 ? 8 : (lay.bigparm >= 0 ? 2 | 16 : 2)) : 0) | (replay ? 0 : 4) |
-                      (spare ? 32 : 0);
-    HIPCHK(pipk_launch_advance_q(jobs, arena, lay.batch, lay.nvar + smax, smax, lay.W, budget, waves, lay.ebits, q5, grid,
-                                 big, hints, e->d_prof, st));
+    const int hints = (s.full ? PIPK_HINT_FULL : 0) |
+                      (s.kernel == PIP_K_LEAN64 ? PIPK_HINT_LEAN64
+                       : s.kernel == PIP_K_LEAN_BIG ? PIPK_HINT_LEAN | PIPK_HINT_BIG
+                       : s.kernel == PIP_K_LEAN ? PIPK_HINT_LEAN : 0) |
+                      (s.replay_behind ? 0 : PIPK_HINT_NO_REPLAY) | (s.spare_replay ? PIPK_HINT_SPARE_REPLAY : 0);
+    HIPCHK(pipk_launch_advance_q(jobs, arena, lay.batch, lay.nvar + smax, smax, lay.W, s.budget, s.waves, lay.ebits, q5,
+                                 s.whole_batch ? lay.batch : upper, big, hints, e->d_prof, st));
     if (!e->no_timing) HIPCHK(hipEventRecord(e->ev[2 * e->nlaunch + 1], st));
     e->nlaunch++;
     stage++;
@@ -358,31 +335,19 @@ struct BatchRun {
     return PIPAMD_OK;
   }
 
-  // a tail launch over what is left, and the copy of its control words to the host
-  int tail() {
-    // The determinant logs of the bulk launches are replayed once, behind the first tail launch, for all tableaux
-    // (pipk_launch_replay_all): a replay kernel between two launches is a tiny launch that waits milliseconds for a
-    // turn on a device busy with other batches' bulk launches, and nothing in the pivot launches depends on it -- a
-    // tableau that overflowed goes on pivoting until the replay says so, its status and pivot count are the same (also
-    // where it meanwhile ended in a pivot without a column, counted and not logged: det_unlogged, pip_advance.h).
-    // The bulk launches together log fewer pivots per tableau than the log holds (`defer` in begin()).
-    // Where the second lean launch's spare blocks have replayed the logs of the jobs the first one finished
-    // (spare_went), this replay is the catch-all for what is left -- the few hundred tableaux of the second launch and the
-    // tail, every other log is empty -- and goes out a wave per job, the form with the shortest latency.  It does so
-    // whenever spare blocks went, also where they could reach little or nothing because the list covers most of the
-    // batch (a first-launch budget of a few pivots): correct, since this replay takes every log that is left, but that
-    // case was not measured.
-    // (128-bit entries: a list shorter than the GPU has CUs gets a CU per tableau -- sixteen waves; what is left after the
-    // first tail launch are the few tableaux of hundreds of pivots and rows, each a latency chain of its own)
-    const bool wide16 = lay.ebits == 128 && lay.W <= 256 && upper <= 256 && !e->waves_per_job && !e->tail_waves;
-    int rc = launch(wide16 ? 16 : tail_waves, e->iter_limit, curS, upper, false, !replay_pending);
-    if (rc) return rc;
-    if (replay_pending) {
-      HIPCHK(pipk_launch_replay_all(jobs, arena, lay.batch, lay.ebits, e->lone_batches || spare_went, st));
-      replay_pending = false;
-    }
+  // the one replay of the logs the launches so far left (pip_plan.h), if any, then the copy of the last launch's
+  // control words to the host
+  int replay_and_report(bool replay) {
+    if (replay) HIPCHK(pipk_launch_replay_all(jobs, arena, lay.batch, lay.ebits, plan.catchall_waves, st));
+    replay_pending = false;
     HIPCHK(hipMemcpyAsync(e->h_run, ctrl_of(stage - 1), Q_CTRL * sizeof(int), hipMemcpyDeviceToHost, st));
     return PIPAMD_OK;
+  }
+
+  // a tail launch over what is left (pip_plan_tail), and the copy of its control words to the host
+  int tail() {
+    int rc = launch(pip_plan_tail(in, plan.tail_waves, curS, upper, replay_pending));
+    return rc ? rc : replay_and_report(replay_pending);
   }
 
   int begin(pipamd_engine *e_, void *d_ws, const pipamd_batch_desc *d_, void *stream) {
@@ -418,114 +383,25 @@ struct BatchRun {
     stage = 0;
     have_list = false;
     finishing = false;
-    replay_pending = false;
-    spare_went = false;
     curS = lay.S;
     grow_round = 0;
-    const bool integer = (lay.tflags & PIPAMD_T_INT) != 0;
-    // (the default budget of the first bulk launch is 96; only where a second lean launch takes what the first leaves it
-    // is PIPAMD_ROUND_PIVOTS, chosen below once `lean2` is known -- the general one-wave launches of 128-bit batches and
-    // of batches with parameters, and an engine in lone-batches mode, keep 96)
-    int K1 = e->round_pivots > 0 ? e->round_pivots : 96;
-    const int KA = !integer ? 0 : (e->round_rows > 0 ? e->round_rows : 48);
-    tail_waves = e->waves_per_job ? e->waves_per_job : (e->tail_waves ? e->tail_waves : 4);
     upper = lay.batch;
-    // The 128-bit flavour on rows of 129 ... 256 columns without parameters can start with pip_lean64_kernel (pip_lean.h),
-    // one wave per tableau over the whole batch: it finishes the tableaux whose stored entries stay below 2^63 (two in
-    // three of BASELINE's configs[4]) and leaves the others to the launches below.  Opt-in (pipamd_engine_set_lean64):
-    // measured on that batch it is no faster than pip_advance_kernel's four waves per tableau.
-    // A batch with PIPAMD_T_DUAL takes no lean launch: a tableau the lean kernels finish keeps its rows packed, and
-    // pip_batch_dual_kernel reads logical row 0 in the general format (pipamd_batch_dual, include/piplib_amd.h)
-    const bool dual = (lay.tflags & PIPAMD_T_DUAL) != 0;
-    bool took64 = false;
-    if (!dual && e->lean64 && !e->no_lean && lay.ebits == 128 && lay.nparm == 0 && lay.bigparm < 0 && lay.W > 128 && lay.W <= 256 &&
-        !(lay.tflags & (PIPAMD_T_NOSKIP | PIPAMD_T_DEEPEST)) && lay.batch >= (e->bulk_min > 0 ? e->bulk_min : 128) &&
-        e->waves_per_job != 4 && e->waves_per_job != 8) {
-      int smax = curS < 448 ? curS : 448;  // (448 rows: an image of 30 KB, five tableaux per CU)
-      if (smax >= lay.ni && pipk_lean64_lds_bytes(smax, lay.nvar + smax) <= PIPAMD_LDS_BUDGET) {
-        rc = launch(1, e->iter_limit, smax, lay.batch, true, true);
-        if (rc) return rc;
-        took64 = true;
-        if (e->single_launch) {  // measurement aid: the lean launch on its own (its unfinished tableaux stay PIPAMD_ST_RUN)
-          HIPCHK(hipMemcpyAsync(e->h_run, ctrl_of(stage - 1), Q_CTRL * sizeof(int), hipMemcpyDeviceToHost, st));
-          active = true;
-          return PIPAMD_OK;
-        }
-      }
+    in = PipPlanIn{lay.batch, lay.nvar, lay.nparm, lay.bigparm, lay.ni, lay.S, lay.W, lay.ebits, lay.tflags,
+                   e->round_pivots, e->round_rows, e->bulk_min, e->iter_limit, e->waves_per_job, e->tail_waves,
+                   e->lone_batches, e->no_spare_replay, e->lean2_one_wave, e->no_lean, e->no_lean2, e->lean64, e->lean_big,
+                   e->single_launch, false};
+    if (in.lean64) {
+      const int s64 = pip_plan_lean64_rows(lay.S);
+      in.lean64_fits = pipk_lean64_lds_bytes(s64, lay.nvar + s64) <= PIPAMD_LDS_BUDGET;
     }
-    if (!took64 && lay.batch >= (e->bulk_min > 0 ? e->bulk_min : 2048) && e->waves_per_job != 4 && e->waves_per_job != 8) {
-      int budget, smax;
-      bool lean, lean2;
-      // no parameters, at most 128 columns of 64-bit entries, rows skipped, plain cuts: the lean kernel (pip_lean.h) goes
-      // first -- it finishes the tableaux whose entries stay below 2^15 and leaves the others to the general kernel's launch
-      // ... and its BIG flavour for the batches whose one parameter is the big one (lexicographic maxima, unknowns of either
-      // sign: pipamd_batch_load_shifted), which need no host decision either.  Opt-in (pipamd_engine_set_lean_big):
-      // measured, it is ahead by 13-35 % except for a lone Urs_unknowns batch, where it is 3 % behind
-      const bool plain = lay.nparm == 0 && lay.bigparm < 0;
-      const bool bigone = e->lean_big && lay.nparm == 1 && lay.bigparm == lay.nvar + 1 && lay.nvar + 2 <= lay.W;
-      // The second one-wave launch: the lean kernel again where it can resume its own paused jobs (below), with a budget
-      // of its own; else the general kernel with the first launch's.
-      // The first launch's budget: PIPAMD_ROUND_PIVOTS is tried first and kept only if the two lean launches go out with
-      // it; every other sequence is shaped with 96.
-      for (int k = e->round_pivots > 0 ? K1 : PIPAMD_ROUND_PIVOTS;; k = K1) {
-        budget = e->iter_limit < k ? e->iter_limit : k;
-        smax = lay.ni + (KA < budget ? KA : budget);
-        if (smax > curS) smax = curS;
-        lean = !dual && !e->no_lean && lay.ebits != 128 && (plain || bigone) && lay.W <= 128 && !(lay.W & 1) &&
-               !(lay.tflags & (PIPAMD_T_NOSKIP | PIPAMD_T_DEEPEST)) && pipk_lean_class(smax) != 0;
-        lean2 = lean && !e->lone_batches && !e->no_lean2 && pipk_lean_class(lay.ni + 96 < curS ? lay.ni + 96 : curS) != 0;
-        if (lean2 || k == K1) break;
-      }
-      const int b2 = lean2 ? (e->iter_limit < 160 ? e->iter_limit : 160) : budget;
-      // The bulk launches leave their determinant logs to the replay behind the first tail launch when the two of them
-      // together cannot fill a tableau's log: budget + b2 pivots against the PIPAMD_DETLOG entries it holds.  (A kernel
-      // pauses a tableau whose log is full, so nothing is lost beyond that either: the launch then replays behind itself.)
-      const bool defer = budget + b2 <= PIPAMD_DETLOG;
-      if (lean) {
-        rc = launch(1, budget, smax, lay.batch, true, !defer);
-        if (rc) return rc;
-        replay_pending = defer;
-        if (e->single_launch == 2) {  // measurement aid: the lean launch on its own
-          if (replay_pending) HIPCHK(pipk_launch_replay_all(jobs, arena, lay.batch, lay.ebits, e->lone_batches, st));
-          replay_pending = false;
-          HIPCHK(hipMemcpyAsync(e->h_run, ctrl_of(stage - 1), Q_CTRL * sizeof(int), hipMemcpyDeviceToHost, st));
-          active = true;
-          return PIPAMD_OK;
-        }
-      }
-      // Then what the lean launch left (on the headline: the 6 % of the tableaux that spent its pivot budget) in a second
-      // one-wave launch: the lean kernel again, which resumes its own paused jobs, with the largest row-capacity class and
-      // a budget that covers the longest tableaux -- and leaves what it cannot take (rows beyond ints, more rows than its
-      // image) to the tail.  Where the shape has no lean kernel: the general one-wave kernel.  (Measured with 14 batches
-      // in flight: sending those tableaux straight to the four-wave tail instead costs 10 % of the throughput.)
-      if (!(lean && e->lone_batches)) {  // (pipamd_engine_set_lone_batches: straight to the tail launches)
-        if (lean2) {
-          int smax2 = lay.ni + 96 < curS ? lay.ni + 96 : curS;
-          // (a block per tableau of the batch over the list of the paused ones: the blocks beyond the list replay the
-          // logs the first launch left behind its finished tableaux, pip_lean.h lean_spare_replay)
-          spare_went = replay_pending && !e->no_spare_replay;
-          // (four waves per tableau where that row capacity and flavour have the kernel: the launch is a few hundred
-          // tableaux, each a chain of pivots that lasts as long as the rows of a pivot take one after the other)
-          const int w2 = !e->lean2_one_wave && lay.bigparm < 0 && pipk_lean_waves_class(smax2) ? 4 : 1;
-          rc = launch(w2, b2, smax2, lay.batch, true, false, spare_went);
-          replay_pending = true;
-        } else {
-          rc = launch(1, budget, smax, lay.batch, false, !defer);
-          replay_pending = defer;
-        }
-        if (rc) return rc;
-      }
-      if (e->single_launch) {  // measurement aid: the bulk launch on its own (its tableaux stay PIPAMD_ST_RUN)
-        // (3: without the catch-all replay -- the logs stay as the launches left them, so that a test sees which of them
-        // the second lean launch's spare blocks replayed)
-        if (replay_pending && e->single_launch != 3) HIPCHK(pipk_launch_replay_all(jobs, arena, lay.batch, lay.ebits, e->lone_batches || spare_went, st));
-        replay_pending = false;
-        HIPCHK(hipMemcpyAsync(e->h_run, ctrl_of(stage - 1), Q_CTRL * sizeof(int), hipMemcpyDeviceToHost, st));
-        active = true;
-        return PIPAMD_OK;
-      }
+    plan = pip_plan_batch(in);
+    replay_pending = false;
+    for (int i = 0; i < plan.nsteps; i++) {
+      rc = launch(plan.step[i]);
+      if (rc) return rc;
     }
-    rc = tail();
+    replay_pending = plan.pending;
+    rc = plan.stop ? replay_and_report(plan.stop_replay) : tail();
     if (rc) return rc;
     active = true;
     return PIPAMD_OK;

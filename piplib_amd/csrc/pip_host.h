@@ -5,6 +5,7 @@
 #include <pthread.h>
 
 #include "pip_job.h"
+#include "pip_plan.h"
 #include "pip_tape.h"
 
 #define PIPAMD_MAX_ROUNDS 512
@@ -63,6 +64,16 @@ struct pipamd_engine {
   int last_rehoused; /* tableaux the last pipamd_batch_solve re-housed (all rounds) */
   struct BatchRun *run; /* the batch solve in progress (pipamd_batch_solve_async .. pipamd_batch_wait) */
   int cus;           /* compute units of the device: the bound of pipamd_tape_sweep's persistent grid */
+};
+
+/* pipk_launch_advance_q's `hints`: what the caller knows about the jobs of a launch, and what the launch is to do */
+enum {
+  PIPK_HINT_FULL = 1,      /* every job has no parameters, no big parameter and nvar + 1 == W == the wave's column coverage (the caller knows its batch is uniform): see FULL */
+  PIPK_HINT_LEAN = 2,      /* the lean kernel of pip_lean.h (one wave per job, 64-bit entries, at most 128 columns and pipk_lean_class(Smax) != 0, else refused): it runs the jobs it can (no parameters, entries below 2^15) and leaves the others PIPAMD_ST_RUN on the output list for a launch without this bit; waves_per_job == 4 with it, where pipk_lean_waves_class(Smax) and not PIPK_HINT_BIG: the same kernel with four waves per tableau, 256-thread blocks, for a launch over a few paused tableaux */
+  PIPK_HINT_NO_REPLAY = 4, /* no determinant replay behind the launch (see pipk_launch_replay_all) */
+  PIPK_HINT_LEAN64 = 8,    /* the lean kernel of pip_lean.h on long long rows (one wave per job, 128-bit entries, 129 ... 256 columns, pipk_lean64_lds_bytes(Smax, Lmax) within the LDS budget, else refused): it runs the jobs it can (no parameters, entries below 2^63) and leaves the others on the output list */
+  PIPK_HINT_BIG = 16,      /* with PIPK_HINT_LEAN: every job has nparm == 1 and bigparm == nvar + 1 -- the lean kernel's BIG flavour */
+  PIPK_HINT_SPARE_REPLAY = 32 /* with PIPK_HINT_LEAN and an input list: the launch's workgroups beyond the list replay the determinant logs of the finished jobs that are not on it (PipQueue.replay_spare; `grid` is then the batch, not the list's bound) */
 };
 
 void pipamd_set_error(const char *fmt, ...);

@@ -6,6 +6,7 @@
 // pip_solve's plain system), Compute_dual for the batch layer (pip_batch_dual_kernel),
 // expanser for the batch layer, the helpers of the lock-step scheduler and every launcher.
 #include "pip_lean.h"
+#include "pip_host.h"
 
 // the instantiations of the pivot kernel's launcher live in pip_adv_*.hip
 #define PIP_ADV_EXTERN(...) extern template hipError_t launch_advance_t<__VA_ARGS__>(const AdvanceLaunch &);
@@ -1157,30 +1158,10 @@ static hipError_t launch_static(AdvanceLaunch a, int ebits) {
   a.shm = pipk_advance_lds_bytes(a.Lmax, a.Smax, 128, ebits);
   return a.full ? launch_advance_t<i64, 1, 1, false, SC, true>(a) : launch_advance_t<i64, 1, 1, false, SC, false>(a);
 }
-// Row-capacity class of the one-wave kernels with a compile-time LDS image for a launch of `smax` row slots: the
-// smallest class that holds it if that costs at most an eighth more LDS than its exact size (occupancy is LDS-bound
-// at 24 tableaux per CU); 0 = none.
-extern "C" int pipk_static_class(int smax) {
-  const int s = (smax + 3) & ~3;
-  if (s <= 64) return 64;
-  if (s > 84 && s <= 96) return 96;
-  if (s > 98 && s <= 112) return 112;
-  if (s > 112 && s <= 128) return 128;
-  if (s > 140 && s <= 160) return 160;
-  return 0;
-}
-// Row-capacity class of the lean kernel (pip_lean.h) for `smax` row slots: the smallest that holds them (a class too
-// large costs a little occupancy, no class costs the lean launch); 0 = none.
-extern "C" int pipk_lean_class(int smax) {
-  const int s = (smax + 3) & ~3;
-  return s <= 64 ? 64 : (s <= 96 ? 96 : (s <= 112 ? 112 : (s <= 128 ? 128 : (s <= 160 ? 160 : 0))));
-}
-// 1 where the lean kernel's class for `smax` row slots also comes with four waves per tableau (pip_lean.h, NW = 4; the
-// plain flavour only): the classes a second lean launch over paused headline-sized tableaux lands in
-extern "C" int pipk_lean_waves_class(int smax) {
-  const int sc = pipk_lean_class(smax);
-  return sc == 128 || sc == 160;
-}
+// the row-capacity classes of the one-wave kernels, of the lean kernel, and of its four-wave flavour (pip_plan.h)
+extern "C" int pipk_static_class(int smax) { return pip_static_class(smax); }
+extern "C" int pipk_lean_class(int smax) { return pip_lean_class(smax); }
+extern "C" int pipk_lean_waves_class(int smax) { return pip_lean_waves_class(smax); }
 // the lean kernel of the 128-bit flavour: pip_lean.h's loop on long long rows, row capacity at run time
 __global__ __launch_bounds__(64, PIP_LEAN64_WAVES) void pip_lean64_kernel(PipJob *jobs, i64 *arena, int njobs, int Smax, int Lmax,
                                                                           int iter_limit, PipQueue q PIP_LEAN_PROF_PARAM) {
@@ -1285,6 +1266,25 @@ static hipError_t launch_advance_w(bool one, const AdvanceLaunch &a) {
   return one ? launch_advance_t<T, NCH, 1, false, 0, false>(a) : launch_advance_t<T, NCH, 4, false, 0, false>(a);
 }
 
+// The determinant logs of at most `nrep` jobs replayed (the bound of the list in `q`; without a list: njobs), in either
+// entry width.  A lane per job (jobs with an empty log cost a load): fewest instructions, what counts behind a bulk
+// launch and when other batches keep the device busy.  A wave per job: shortest latency (a lane walks its up to 200 log
+// entries alone for half a millisecond), where few jobs ran and someone is waiting for them.
+static hipError_t launch_det_replay(PipJob *jobs, i64 *arena, int njobs, const PipQueue &q, int nrep, bool wave_per_job, int ebits,
+                                    hipStream_t stream) {
+  const dim3 grid(wave_per_job ? nrep : (nrep + 63) / 64);
+  if (wave_per_job) {
+    if (ebits == 128)
+      hipLaunchKernelGGL(pip_det_replay_kernel<i128>, grid, dim3(64), 0, stream, jobs, arena, njobs, q);
+    else
+      hipLaunchKernelGGL(pip_det_replay_kernel<i64>, grid, dim3(64), 0, stream, jobs, arena, njobs, q);
+  } else if (ebits == 128)
+    hipLaunchKernelGGL(pip_det_replay_lanes_kernel<i128>, grid, dim3(64), 0, stream, jobs, arena, njobs, q);
+  else
+    hipLaunchKernelGGL(pip_det_replay_lanes_kernel<i64>, grid, dim3(64), 0, stream, jobs, arena, njobs, q);
+  return hipGetLastError();
+}
+
 // waves_per_job: 1 = one wave64 per tableau (latency-bound sparse batches: more tableaux in
 // flight per CU), 4 = four waves share a tableau's rows (few, large tableaux).
 // ebits: 64 or 128 -- every job of the launch must have that entry width.
@@ -1296,17 +1296,7 @@ static hipError_t launch_by_shape(const AdvanceLaunch &a, bool one, int wp, int 
 // big: NULL, or {void **buffer, size_t *bytes} of the caller -- a device buffer this function
 // (re)allocates when the row tables of the launch do not fit LDS (64-bit entries only): the launch
 // then keeps them there, `grid` blocks of the image size.  Without it such a launch is refused.
-// hints: bit 0 = every job of the launch has no parameters, no big parameter and nvar + 1 == W ==
-// the wave's column coverage (the caller knows its batch is uniform): see FULL.  Bit 1 (one wave per job, 64-bit entries, at
-// most 128 columns and pipk_lean_class(Smax) != 0, else refused) = the lean kernel of pip_lean.h: it runs the jobs it
-// can (no parameters, entries below 2^15) and leaves the others PIPAMD_ST_RUN on the output list for a launch without
-// this bit; waves_per_job == 4 with it, where pipk_lean_waves_class(Smax) and not bit 4: the same kernel with four waves per
-// tableau, 256-thread blocks, for a launch over a few paused tableaux.  Bit 2: no determinant replay behind the launch (see pipk_launch_replay_all).  Bit 3 (one wave per job, 128-bit
-// entries, 129 ... 256 columns, pipk_lean64_lds_bytes(Smax, Lmax) within the LDS budget, else refused) = the lean kernel of
-// pip_lean.h on long long rows: it runs the jobs it can (no parameters, entries below 2^63) and leaves the others on the output list.
-// Bit 4 (with bit 1): every job has nparm == 1 and bigparm == nvar + 1 -- the lean kernel's BIG flavour.
-// Bit 5 (with bit 1 and an input list): the launch's workgroups beyond the list replay the determinant logs of the finished
-// jobs that are not on it (PipQueue.replay_spare; `grid` is then the batch, not the list's bound).
+// hints: PIPK_HINT_* bits (pip_host.h).
 extern "C" hipError_t pipk_launch_advance_q(PipJob *jobs, i64 *arena, int njobs, int Lmax, int Smax, int Wmax,
                                             int iter_limit, int waves_per_job, int ebits, void *const *q5, int grid,
                                             void **big, int hints, unsigned long long *prof, hipStream_t stream) {
@@ -1328,11 +1318,11 @@ extern "C" hipError_t pipk_launch_advance_q(PipJob *jobs, i64 *arena, int njobs,
   if (q5) {
     a.q = PipQueue{(const int *)q5[0], (const int *)q5[1], (int *)q5[2], (int *)q5[3], (int *)q5[4]};
     a.grid = grid;
-    a.q.replay_spare = (hints & 2) && (hints & 32) ? 1 : 0;
+    a.q.replay_spare = (hints & PIPK_HINT_LEAN) && (hints & PIPK_HINT_SPARE_REPLAY) ? 1 : 0;
   }
   a.prof = prof;
   a.waves = waves_per_job;
-  a.full = (hints & 1) != 0;
+  a.full = (hints & PIPK_HINT_FULL) != 0;
   a.shm = pipk_advance_lds_bytes(Lmax, Smax, Wmax, ebits);
   a.gimg = nullptr;
   a.gslots = 0;
@@ -1367,55 +1357,34 @@ extern "C" hipError_t pipk_launch_advance_q(PipJob *jobs, i64 *arena, int njobs,
   }
   a.stream = stream;
   // (the lean kernel with four waves per tableau is a bulk launch like the one-wave kernels: same replay behind it)
-  const bool lean4 = (hints & 2) && !(hints & 16) && waves_per_job == 4 && pipk_lean_waves_class(a.Smax);
+  const bool lean4 = (hints & PIPK_HINT_LEAN) && !(hints & PIPK_HINT_BIG) && waves_per_job == 4 && pipk_lean_waves_class(a.Smax);
   const bool one = waves_per_job == 1 || lean4;
   const int wp = wp_of(Wmax, ebits);
   hipError_t le;
-  if (hints & 2) {
+  if (hints & PIPK_HINT_LEAN) {
     if (!one || ebits != 64 || wp != 128 || a.gimg || !pipk_lean_class(a.Smax)) return hipErrorInvalidValue;
-    le = launch_lean_class(a, (hints & 16) != 0);
-  } else if (hints & 8) {  // the lean kernel of the 128-bit flavour (pip_lean.h on long long rows): 129 ... 256 columns, one wave per job
+    le = launch_lean_class(a, (hints & PIPK_HINT_BIG) != 0);
+  } else if (hints & PIPK_HINT_LEAN64) {
     if (!one || ebits != 128 || wp != 256 || pipk_lean64_lds_bytes(a.Smax, a.Lmax) > PIPAMD_LDS_BUDGET) return hipErrorInvalidValue;
     le = launch_lean64(a);
   } else {
     le = launch_by_shape(a, one, wp, ebits);
   }
   if (le != hipSuccess) return le;
-  // the determinant bookkeeping of the pivots just logged (hints bit 2: the caller replays later -- pipk_launch_replay_all)
-  if (hints & 4) return hipGetLastError();
-  const int nrep = a.grid > 0 && a.grid < njobs ? a.grid : njobs;
-  if (one) {  // behind a bulk launch: fewest instructions
-    if (ebits == 128)
-      hipLaunchKernelGGL(pip_det_replay_lanes_kernel<i128>, dim3((nrep + 63) / 64), dim3(64), 0, stream, jobs, arena, njobs, a.q);
-    else
-      hipLaunchKernelGGL(pip_det_replay_lanes_kernel<i64>, dim3((nrep + 63) / 64), dim3(64), 0, stream, jobs, arena, njobs, a.q);
-  } else {  // few jobs, someone is waiting for them: shortest latency
-    if (ebits == 128)
-      hipLaunchKernelGGL(pip_det_replay_kernel<i128>, dim3(nrep), dim3(64), 0, stream, jobs, arena, njobs, a.q);
-    else
-      hipLaunchKernelGGL(pip_det_replay_kernel<i64>, dim3(nrep), dim3(64), 0, stream, jobs, arena, njobs, a.q);
-  }
-  return hipGetLastError();
+  // the determinant bookkeeping of the pivots just logged (PIPK_HINT_NO_REPLAY: the caller replays later --
+  // pipk_launch_replay_all): a lane per job behind a bulk launch, a wave per job behind the few jobs of a tail launch
+  if (hints & PIPK_HINT_NO_REPLAY) return hipGetLastError();
+  return launch_det_replay(jobs, arena, njobs, a.q, a.grid > 0 && a.grid < njobs ? a.grid : njobs, !one, ebits, stream);
 }
 
-// The determinant logs of ALL jobs 0..njobs-1 replayed: behind a sequence of launches that ran with hints bit 2.
-// wave_per_job = 0: one lane per job (jobs with an empty log cost a load) -- fewest instructions, what counts when other
-// batches keep the device busy; 1: one wave per job -- shortest latency (a lane walks its up to 200 log entries alone for
-// half a millisecond), for a caller that runs one batch at a time.  The log holds PIPAMD_DETLOG pivots and the pivot
+// The determinant logs of ALL jobs 0..njobs-1 replayed: behind a sequence of launches that ran with
+// PIPK_HINT_NO_REPLAY, a lane (wave_per_job = 0) or a wave per job (launch_det_replay: the second for a caller that runs
+// one batch at a time).  The log holds PIPAMD_DETLOG pivots and the pivot
 // kernels pause a job whose log is full, so a sequence may log at most that many pivots per job between replays.
 extern "C" hipError_t pipk_launch_replay_all(PipJob *jobs, i64 *arena, int njobs, int ebits, int wave_per_job, hipStream_t stream) {
   if (njobs <= 0) return hipSuccess;
-  const PipQueue q{nullptr, nullptr, nullptr, nullptr, nullptr};
-  if (wave_per_job) {
-    if (ebits == 128)
-      hipLaunchKernelGGL(pip_det_replay_kernel<i128>, dim3(njobs), dim3(64), 0, stream, jobs, arena, njobs, q);
-    else
-      hipLaunchKernelGGL(pip_det_replay_kernel<i64>, dim3(njobs), dim3(64), 0, stream, jobs, arena, njobs, q);
-  } else if (ebits == 128)
-    hipLaunchKernelGGL(pip_det_replay_lanes_kernel<i128>, dim3((njobs + 63) / 64), dim3(64), 0, stream, jobs, arena, njobs, q);
-  else
-    hipLaunchKernelGGL(pip_det_replay_lanes_kernel<i64>, dim3((njobs + 63) / 64), dim3(64), 0, stream, jobs, arena, njobs, q);
-  return hipGetLastError();
+  return launch_det_replay(jobs, arena, njobs, PipQueue{nullptr, nullptr, nullptr, nullptr, nullptr}, njobs, wave_per_job != 0, ebits,
+                           stream);
 }
 
 // One of the two replay kernels over a caller's jobs, a block (wave_per_job) or a lane per job of `njobs`, with or
@@ -1424,18 +1393,8 @@ extern "C" hipError_t pipk_launch_replay_all(PipJob *jobs, i64 *arena, int njobs
 extern "C" hipError_t pipk_launch_det_replay(PipJob *jobs, i64 *arena, int njobs, int ebits, int wave_per_job, const int *in_list,
                                              const int *in_count, hipStream_t stream) {
   if (njobs <= 0) return hipSuccess;
-  const PipQueue q{in_list, in_count, nullptr, nullptr, nullptr};
-  const dim3 grid(wave_per_job ? njobs : (njobs + 63) / 64);
-  if (wave_per_job) {
-    if (ebits == 128)
-      hipLaunchKernelGGL(pip_det_replay_kernel<i128>, grid, dim3(64), 0, stream, jobs, arena, njobs, q);
-    else
-      hipLaunchKernelGGL(pip_det_replay_kernel<i64>, grid, dim3(64), 0, stream, jobs, arena, njobs, q);
-  } else if (ebits == 128)
-    hipLaunchKernelGGL(pip_det_replay_lanes_kernel<i128>, grid, dim3(64), 0, stream, jobs, arena, njobs, q);
-  else
-    hipLaunchKernelGGL(pip_det_replay_lanes_kernel<i64>, grid, dim3(64), 0, stream, jobs, arena, njobs, q);
-  return hipGetLastError();
+  return launch_det_replay(jobs, arena, njobs, PipQueue{in_list, in_count, nullptr, nullptr, nullptr}, njobs, wave_per_job != 0, ebits,
+                           stream);
 }
 
 static hipError_t launch_by_shape(const AdvanceLaunch &a, bool one, int wp, int ebits) {
