@@ -14,7 +14,10 @@ parameter), exactly as the reference's fixed-width builds run them:
   choisir_piv     source/traiter.c:297-341   pick_column()
   pivoter         source/traiter.c:345-548   pivot_step(), incl. the multi-limb determinant and its
                                              "Integer overflow" exits (traiter.c:412-446)
-  integrer        source/integrer.c:305-486  gomory() (constant cuts; no deepest cut)
+  integrer        source/integrer.c:305-486  gomory() (constant cuts)
+  deepest cut     source/integrer.c:417-438  deepen(), with `deepest=True` (the reference's -d / Deepest_cut)
+  bezout          source/integrer.c:98-150   bezout(), as the reference computes it: the representative of lambda it
+                                             arrives at decides how often the loop adds D / delta, and so which cut is built
 
 Integers are Python ints, so nothing wraps.  `bits` is the width of the fixed-width build being
 modelled (64 = the reference's `long long` flavour, 128 = the overflow-safe flavour,
@@ -23,7 +26,12 @@ include/piplib/piplib.h:42-88): it enters the algorithm only through the determi
 wrap).  Every other product, difference and row entry the fixed-width code would form is checked
 against that width: `Stats.max_bits` is the largest
 magnitude met, and a result is only comparable with a fixed-width run when
-`max_bits < bits` (no wrap-around happened) -- callers check `Stats.exact`.
+`max_bits < bits` (no wrap-around happened) -- callers check `Stats.exact`.  That holds with the deepest cut on: t,
+delta, tau, d, Bezout's products and differences, lambda after every round, every lambda * coefficient and D - t are
+noted, and `Stats.cut_log` keeps what each deepest cut was made of.
+
+bezout() and deepen() take the callable that is shown every intermediate, so that tests/quast_step_model.py (the device
+tree's steps) runs the same statements under its own width tracker.
 """
 import math
 from dataclasses import dataclass, field
@@ -49,6 +57,9 @@ class Stats:
     nrows: List[int] = field(default_factory=list)          # per pivot: real rows
     det_log: List[tuple] = field(default_factory=list)      # per pivot with a column: (pivot, denominator of the pivot row),
                                                             # what the pivot kernels log for the determinant replay
+    cut_log: List[tuple] = field(default_factory=list)      # per deepest cut: (D, delta, lambda, rounds of the lambda += d
+                                                            # loop, bit length of the largest lambda * coefficient)
+    nil_cut: bool = False      # ended at a fractional constant with no positive coefficient to cut with (integrer.c:482-485)
 
     @property
     def exact(self):
@@ -282,8 +293,54 @@ def pivot_step(rows, det, pivi, nvar, ni, st):
     return 0
 
 
-def gomory(rows, nvar, ni, st):
-    """integrer.c:305-486 for nparm = 0: index of the appended cut row, 0 (all integral), -1 (nil)."""
+def bezout(x, y, delta, need):
+    """integrer.c:98-150: z with z * y == x (mod delta) for coprime y and delta, 0 otherwise.  `need(*vals)` is shown every
+    value the fixed-width code forms and returns the last of them."""
+    a, b, c, d, u, v = 1, 0, 0, 1, y, delta
+    while True:
+        need(u - u % v)
+        q, r = u // v, u % v
+        if r == 0:
+            break
+        u, v = v, r
+        e = need(q * c, a - q * c)
+        f = need(q * d, b - q * d)
+        a, b, c, d = c, d, e, f
+    if v != 1:
+        return 0
+    return need(c * x) % delta
+
+
+def deepen(cut, D, nvar, need, on_round=None):
+    """integrer.c:417-438 on the cut `cut` (unknowns | constant at nvar) under denominator D, in place.  `need` as for
+    bezout(); `on_round(k)` is told the rounds of the lambda += d loop as they are spent (0 once Bezout is back).
+    Returns (lambda, delta, rounds, bit length of the largest lambda * coefficient)."""
+    t = -cut[nvar]
+    delta = math.gcd(t, D)
+    tau, d = t // delta, D // delta
+    lam = bezout(d - 1, tau, d, need)
+    rounds = 0
+    if on_round:
+        on_round(0)
+    while math.gcd(lam, D) != 1:
+        lam = need(lam + d)
+        rounds += 1
+        if on_round:
+            on_round(rounds)
+    big = 0
+    for j in range(nvar):
+        p = need(lam * cut[j])
+        big = max(big, abs(p).bit_length())
+        cut[j] = p % D
+    p = need(cut[nvar] * lam)
+    big = max(big, abs(p).bit_length())
+    cut[nvar] = -(D - p % D)
+    return lam, delta, rounds, big
+
+
+def gomory(rows, nvar, ni, st, deepest=False):
+    """integrer.c:305-486 for nparm = 0: index of the appended cut row, 0 (all integral), -1 (nil).  `deepest`: the cut is
+    scaled as integrer.c:417-438 does under the reference's deepest-cut option."""
     nligne = nvar + ni
     for i in range(nvar):
         r = rows[i]
@@ -297,7 +354,18 @@ def gomory(rows, nvar, ni, st):
         if x == 0:
             continue  # integral row
         if not ok_var:
+            st.nil_cut = True
             return -1
+        if deepest:
+            def need(*vals):
+                _note(st, *vals)
+                return vals[-1]
+            t = -x
+            c = [int(y) for y in cut]
+            lam, delta, rounds, big = deepen(c, D, nvar, need)
+            _note(st, t, delta, t // delta, D // delta, D // delta - 1, D - (x * lam) % D)
+            cut = np.array(c, dtype=object)
+            st.cut_log.append((D, delta, lam, rounds, big))
         rows.append(_Row(MINUS, D, cut))
         assert len(rows) == nligne + 1
         st.cuts += 1
@@ -305,12 +373,13 @@ def gomory(rows, nvar, ni, st):
     return 0
 
 
-def solve(ineq, integer=True, bits=64, det_out=None, stop_inexact=False) -> Result:
+def solve(ineq, integer=True, bits=64, det_out=None, stop_inexact=False, deepest=False) -> Result:
     """ineq: (ni, nvar+1) integers (unknowns | constant).  Returns what traiter() leaves on the
     solution tape for a problem without parameters.  `det_out`: a list that receives the determinant's limbs as the last
     det_update left them (at an Overflow: as it left them when it raised).  `stop_inexact`: give up, with status None,
     before the first pivot that follows an intermediate of `bits` bits or more -- from there on a fixed-width run is
-    not comparable, and a caller that only asks about the comparable part need not pay for the rest."""
+    not comparable, and a caller that only asks about the comparable part need not pay for the rest.  `deepest`: every cut
+    is the deepest cut (gomory())."""
     ineq = np.asarray(ineq, dtype=object)
     ni, ncol = ineq.shape
     nvar = ncol - 1
@@ -341,7 +410,7 @@ def solve(ineq, integer=True, bits=64, det_out=None, stop_inexact=False) -> Resu
                 if not integer:
                     status = ST_SOLUTION
                     break
-                pivi = gomory(rows, nvar, ni, st)
+                pivi = gomory(rows, nvar, ni, st, deepest)
                 if pivi == 0:
                     status = ST_SOLUTION
                     break

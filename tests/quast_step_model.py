@@ -401,38 +401,10 @@ def make_cut(o, i, nvar, ncol, bigparm, width):
     return cut, (1 if ok_var else 0) | (2 if ok_const else 0) | (4 if ok_parm else 0)
 
 
-def bezout(x, y, delta, trk):
-    """integrer.c:98-150"""
-    a, b, c, d, u, v = 1, 0, 0, 1, y, delta
-    while True:
-        trk.need(u - u % v)
-        q, r = u // v, u % v
-        if r == 0:
-            break
-        u, v = v, r
-        e = trk.need(q * c, a - q * c)
-        f = trk.need(q * d, b - q * d)
-        a, b, c, d = c, d, e, f
-    if v != 1:
-        return 0
-    return trk.need(c * x) % delta
-
-
 def deepen(cut, D, nvar, trk):
-    """integrer.c:417-438, in place"""
+    """integrer.c:417-438 with bezout (integrer.c:98-150), in place: bigint_pip.deepen under this run's width tracker"""
     trk.stage = "deepest cut"
-    t = -cut[nvar]
-    delta = math.gcd(t, D)
-    tau, d = t // delta, D // delta
-    lam = bezout(d - 1, tau, d, trk)
-    trk.lambda_steps = 0
-    while math.gcd(lam, D) != 1:
-        lam = trk.need(lam + d)
-        trk.lambda_steps += 1
-    for j in range(nvar):
-        cut[j] = trk.need(lam * cut[j]) % D
-    cut[nvar] = -(D - trk.need(cut[nvar] * lam) % D)
-    return lam
+    return bp.deepen(cut, D, nvar, trk.need, lambda k: setattr(trk, "lambda_steps", k))[0]
 
 
 def find_quotient(o, CW, nc, nparm, trk):

@@ -571,31 +571,59 @@ def test_largest_supported_shape():
 @pytest.mark.parametrize("seed,nvar,ni", [(71, 10, 12), (72, 30, 20), (73, 127, 64)])
 def test_deepest_cut_on_device(seed, nvar, ni):
     """PIPAMD_T_DEEPEST (the reference's -d / Deepest_cut option, integrer.c:417-438) entirely in
-    the kernel, batch API, vs the oracle run with the same option."""
+    the kernel, batch API, vs the oracle run with the same option.  A tableau may end ST_CAPACITY only where the
+    oracle's own cut count (ora_cuts of the oracle library, same option) exceeds the 250 spare rows granted here; at
+    least 28 of the 32 tableaux are compared (on these seeds the oracle cuts 36 times at the most: all 32 are)."""
+    import ctypes as C
+    import os
     import numpy as np
     import torch
     from gpu_common import solution_text
     import pipbatch as pb
     from piplib_amd import engine as eng, synth
+    cap = 250
     rows = synth.lexmin_batch(seed, 32, nvar, ni)
     probs = [synth.Problem(nvar, 0, ni, 0, -1, 1, rows[b], np.zeros((0, 1), np.int64)) for b in range(32)]
     o = pb.run_batch(pb.ORACLEPIP, probs, pb.F_NOSIMPLIFY | pb.F_DEEPEST)
     plain = pb.run_batch(pb.ORACLEPIP, probs, pb.F_NOSIMPLIFY)
+    L = C.CDLL(os.path.join(pb.ROOT, "oracle", "liboracle64.so"))
+    L.ora_new.restype = C.c_void_p
+    L.ora_free.argtypes = [C.c_void_p]
+    L.ora_set_deepest_cut.argtypes = [C.c_void_p, C.c_int]
+    L.ora_solve_tableau.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p, C.c_void_p, C.c_int]
+    for f in (L.ora_pivots, L.ora_cuts):
+        f.argtypes, f.restype = [C.c_void_p], C.c_longlong
+    ocuts = []
+    for k, p in enumerate(probs):
+        h = L.ora_new()
+        try:
+            L.ora_set_deepest_cut(h, 1)
+            a = np.ascontiguousarray(p.ineq, np.int64)
+            assert L.ora_solve_tableau(h, nvar, 0, ni, 0, -1, 1, a.ctypes.data, p.ctx.ctypes.data, 0) == 0
+            assert L.ora_pivots(h) == o.results[k].pivots   # the library and the command-line oracle are one solve
+            ocuts.append(L.ora_cuts(h))
+        finally:
+            L.ora_free(h)
     e = eng.Engine(0)
-    b = eng.Batch(e, rows, nvar, 0, tflags=eng.T_INT | 512, cap_cuts=250)
+    b = eng.Batch(e, rows, nvar, 0, tflags=eng.T_INT | 512, cap_cuts=cap)
     b.load()
     b.solve()
     b.fetch()
     torch.cuda.synchronize()
-    st, pv = b.status.cpu().numpy(), b.pivots.cpu().numpy()
+    st, pv, ct = b.status.cpu().numpy(), b.pivots.cpu().numpy(), b.cuts.cpu().numpy()
     num, den = b.sol_num.cpu().numpy(), b.sol_den.cpu().numpy()
+    compared = 0
     for k, r in enumerate(o.results):
         if st[k] == eng.ST_CAPACITY:
+            assert ocuts[k] > cap, (k, ocuts[k])
             continue
         assert r.status == pb.ST_OK and st[k] in (eng.ST_SOLUTION, eng.ST_NIL)
         assert pv[k] == r.pivots, (k, pv[k], r.pivots)
+        assert ct[k] == ocuts[k], (k, ct[k], ocuts[k])
         got = "()" if st[k] == eng.ST_NIL else pb.squash(solution_text(num[k], den[k]))
         assert got == pb.squash(r.text), k
+        compared += 1
+    assert compared >= 28, compared
     # the option really changes the pivot sequence on this workload
     assert sum(a.pivots != c.pivots for a, c in zip(o.results, plain.results)) > 0
 
