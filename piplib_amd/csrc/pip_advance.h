@@ -42,11 +42,7 @@
 #include <type_traits>
 
 #include "pip_job.h"
-
-typedef long long i64;
-typedef unsigned long long u64;
-typedef __int128 i128;
-typedef unsigned __int128 u128;
+#include "pip_wide.h"
 
 // Entry ("Entier") type traits.  int64: the reference's `long long` build, two columns per
 // lane and chunk (16 B); int128: the overflow-safe variant, one column per lane and chunk.
@@ -109,11 +105,6 @@ __device__ unsigned long long *pf_buf;
 // the wave's ballot as the compare instruction itself (hip's __ballot first materialises the predicate as 0 / 1 in a
 // vector register and compares that: two more VALU instructions per ballot)
 __device__ __forceinline__ u64 ballot64(bool p) { return __builtin_amdgcn_ballot_w64(p); }
-__device__ __forceinline__ u64 uabs64(i64 x) { return x < 0 ? 0ull - (u64)x : (u64)x; }
-__device__ __forceinline__ i64 wmul(i64 a, i64 b) { return (i64)((u64)a * (u64)b); }
-__device__ __forceinline__ i64 wsub(i64 a, i64 b) { return (i64)((u64)a - (u64)b); }
-__device__ __forceinline__ i64 wadd(i64 a, i64 b) { return (i64)((u64)a + (u64)b); }
-__device__ __forceinline__ i64 wneg(i64 a) { return (i64)(0ull - (u64)a); }
 
 // Binary gcd on magnitudes == |Euclid(a,b)| of integrer.c:43-50.
 __device__ __forceinline__ u64 gcd_u64(u64 a, u64 b) {
@@ -157,19 +148,7 @@ __device__ __forceinline__ u64 gcd_mag(u64 a, u64 b) {
   if (((a | b) >> 32) == 0) return gcd_u32((unsigned)a, (unsigned)b);
   return gcd_u64(a, b);
 }
-__device__ __forceinline__ i64 gcd_i64(i64 a, i64 b) { return (i64)gcd_mag(uabs64(a), uabs64(b)); }
-// wave-uniform values: pin them to scalar registers so that the gcd / division / inverse
-// chains that follow run on the scalar unit instead of occupying all 64 vector lanes
-__device__ __forceinline__ i64 uni64(i64 v) {
-  unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)(u64)v);
-  unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)((u64)v >> 32));
-  return (i64)(((u64)hi << 32) | lo);
-}
-__device__ __forceinline__ i64 readlane64(i64 v, int src) {
-  unsigned lo = __builtin_amdgcn_readlane((unsigned)(u64)v, src);
-  unsigned hi = __builtin_amdgcn_readlane((unsigned)((u64)v >> 32), src);
-  return (i64)(((u64)hi << 32) | lo);
-}
+__device__ __forceinline__ i64 gcd_i64(i64 a, i64 b) { return (i64)gcd_mag(uabs(a), uabs(b)); }
 
 // C '/' and '%' made total (the CPU traps on x / 0 and MIN / -1).
 __device__ __forceinline__ i64 cquo(i64 a, i64 b) {
@@ -191,55 +170,18 @@ __device__ __forceinline__ i64 crem(i64 a, i64 b) {
 // integrer.c:69-74 piplib_llmod
 __device__ __forceinline__ i64 fmod64(i64 a, i64 b) {
   i64 m = crem(a, b);
-  if (m < 0) m = wadd(m, (i64)uabs64(b));
+  if (m < 0) m = wadd(m, (i64)uabs(b));
   return m;
 }
 // integrer.c:51-59 piplib_lllog2
 __device__ __forceinline__ int log2_64(i64 x) {
-  u64 u = uabs64(x);
+  u64 u = uabs(x);
   int n = 64 - __builtin_clzll(u | 1ull);
   return u == 0 ? 1 : n;
 }
-__device__ __forceinline__ int bitlen64(u64 u) { return u ? 64 - __builtin_clzll(u) : 0; }
-// inverse of an odd number modulo 2^64 (Newton), for exact division
-__device__ __forceinline__ u64 inv_odd64(u64 m) {
-  u64 x = m;  // 3 correct bits
-  x *= 2 - m * x;
-  x *= 2 - m * x;
-  x *= 2 - m * x;
-  x *= 2 - m * x;
-  x *= 2 - m * x;
-  return x;
-}
 __device__ __forceinline__ int sign_code(i64 x) { return x > 0 ? 1 : (x < 0 ? 2 : 0); }  // 0 zero 1 plus 2 minus
 
-__device__ __forceinline__ i64 shfl64(i64 v, int src) {
-  int lo = __shfl((int)(u64)v, src), hi = __shfl((int)((u64)v >> 32), src);
-  return (i64)(((u64)(unsigned)hi << 32) | (unsigned)lo);
-}
-__device__ __forceinline__ u64 wave_max_u64(u64 v) {
-  for (int o = 32; o; o >>= 1) {
-    u64 t = (u64)shfl64((i64)v, (threadIdx.x & 63) ^ o);
-    v = t > v ? t : v;
-  }
-  return v;
-}
-
 // ---------------------------------------------------------------- 128-bit counterparts
-__device__ __forceinline__ u128 uabs64(i128 x) { return x < 0 ? (u128)0 - (u128)x : (u128)x; }
-__device__ __forceinline__ i128 wmul(i128 a, i128 b) { return (i128)((u128)a * (u128)b); }
-__device__ __forceinline__ i128 wsub(i128 a, i128 b) { return (i128)((u128)a - (u128)b); }
-__device__ __forceinline__ i128 wadd(i128 a, i128 b) { return (i128)((u128)a + (u128)b); }
-__device__ __forceinline__ i128 wneg(i128 a) { return (i128)((u128)0 - (u128)a); }
-__device__ __forceinline__ int ctz128(u128 x) {
-  u64 lo = (u64)x;
-  return lo ? __builtin_ctzll(lo) : 64 + __builtin_ctzll((u64)(x >> 64));
-}
-__device__ __forceinline__ int bitlen64(u128 x) {
-  u64 hi = (u64)(x >> 64);
-  return hi ? 128 - __builtin_clzll(hi) : bitlen64((u64)x);
-}
-__device__ __forceinline__ bool fits64(i128 x) { return (i128)(i64)x == x; }
 // a mod b for a 32-bit b != 0, one 32-bit digit of a at a time: t = r*2^32 + digit < b*2^32,
 // so the quotient of each step is below 2^32 and a double-precision estimate of it is off by
 // at most one.
@@ -264,12 +206,12 @@ __device__ __forceinline__ u128 gcd_mag(u128 a, u128 b) {
   // subtractive binary gcd below needs a 128-bit iteration per bit of the size difference
   if ((b >> 32) == 0) return (u128)gcd_mag((u64)(unsigned)b, (u64)umod128_32(a, (unsigned)b));
   if ((a >> 32) == 0) return (u128)gcd_mag((u64)(unsigned)a, (u64)umod128_32(b, (unsigned)a));
-  int sh = ctz128(a | b);
-  a >>= ctz128(a);
+  int sh = ctz(a | b);
+  a >>= ctz(a);
   CNT(20, 1);
   do {
     CNT(21, 1);
-    b >>= ctz128(b);
+    b >>= ctz(b);
     if (a > b) {
       u128 t = a;
       a = b;
@@ -279,14 +221,7 @@ __device__ __forceinline__ u128 gcd_mag(u128 a, u128 b) {
   } while (b);
   return a << sh;
 }
-__device__ __forceinline__ i128 gcd_i64(i128 a, i128 b) { return (i128)gcd_mag(uabs64(a), uabs64(b)); }
-__device__ __forceinline__ u128 inv_odd64(u128 m) {
-  // the inverse modulo 2^64 on 64-bit registers (five Newton steps from 3 correct bits), one 128-bit step on top:
-  // a 128-bit multiplication is ten 32-bit multiply-adds, a 64-bit one three
-  u128 x = (u128)inv_odd64((u64)m);
-  x *= 2 - m * x;
-  return x;
-}
+__device__ __forceinline__ i128 gcd_i64(i128 a, i128 b) { return (i128)gcd_mag(uabs(a), uabs(b)); }
 // every division on the pivot path is exact (piplib_int_div_exact of a gcd): shift + odd inverse
 // (the divisor is a gcd or a remainder, never negative, at every call site; one pair with a negative one is answered in 64
 // bits: cquo(-2^63, -1) takes the long long shortcut and comes back as -2^63, tests/test_gpu_arith_probe.py)
@@ -295,16 +230,18 @@ __device__ __forceinline__ i128 cquo(i128 a, i128 b) {
   if (b == 0) return 0;
   if (fits64(a) && fits64(b)) return (i128)cquo((i64)a, (i64)b);
   const bool neg = b < 0;
-  u128 ub = uabs64(b);
-  int s = ctz128(ub);
-  i128 q = (i128)((u128)(a >> s) * inv_odd64(ub >> s));
+  u128 ub = uabs(b);
+  int s = ctz(ub);
+  i128 q = (i128)((u128)(a >> s) * inv_odd(ub >> s));
   return neg ? wneg(q) : q;
 }
+// g != 0.  Bit-serial and inline, not pip_wide.h's udivmod: behind that call every 128-bit pivot kernel takes 8 to 32
+// bytes more scratch (pip_advance_kernel<__int128, 4, 1>: 63 -> 93 spilled VGPRs), DESIGN.md (6d)
 __device__ __forceinline__ u128 umod128(u128 a, u128 g) {
   if (((a | g) >> 64) == 0) return (u64)a % (u64)g;
   if (a < g) return a;
   u128 rem = 0;
-  for (int i = bitlen64(a) - 1; i >= 0; i--) {
+  for (int i = bitlen(a) - 1; i >= 0; i--) {
     rem = (rem << 1) | ((a >> i) & 1);
     if (rem >= g) rem -= g;
   }
@@ -313,32 +250,24 @@ __device__ __forceinline__ u128 umod128(u128 a, u128 g) {
 __device__ __forceinline__ i128 crem(i128 a, i128 b) {
   if (b == 0 || b == -1 || b == 1) return 0;
   if (fits64(a) && fits64(b)) return (i128)crem((i64)a, (i64)b);
-  u128 r = umod128(uabs64(a), uabs64(b));
+  u128 r = umod128(uabs(a), uabs(b));
   return a < 0 ? wneg((i128)r) : (i128)r;  // C remainder: sign of the dividend
 }
 __device__ __forceinline__ i128 fmod64(i128 a, i128 b) {
   i128 m = crem(a, b);
-  if (m < 0) m = wadd(m, (i128)uabs64(b));
+  if (m < 0) m = wadd(m, (i128)uabs(b));
   return m;
 }
 __device__ __forceinline__ int log2_64(i128 x) {
-  u128 u = uabs64(x);
-  return u == 0 ? 1 : bitlen64(u);
+  u128 u = uabs(x);
+  return u == 0 ? 1 : bitlen(u);
 }
 __device__ __forceinline__ int sign_code(i128 x) { return x > 0 ? 1 : (x < 0 ? 2 : 0); }
-__device__ __forceinline__ i128 readlane64(i128 v, int src) {
-  u64 lo = (u64)readlane64((i64)(u64)(u128)v, src), hi = (u64)readlane64((i64)(u64)((u128)v >> 64), src);
-  return (i128)(((u128)hi << 64) | lo);
-}
-__device__ __forceinline__ i128 uni64(i128 v) {
-  u64 lo = (u64)uni64((i64)(u64)(u128)v), hi = (u64)uni64((i64)(u64)((u128)v >> 64));
-  return (i128)(((u128)hi << 64) | lo);
-}
 // a / d for d = a positive gcd that divides a: when both fit 32 bits, shift + 32-bit odd inverse
 // (four single multiplies) instead of a division; two quotients by the same d share the inverse.
 template <class T>
 __device__ __forceinline__ T exact_quo(T a, T d) {
-  const auto ua = uabs64(a);
+  const auto ua = uabs(a);
   if (((ua | (decltype(ua))d) >> 32) == 0) {
     unsigned m = (unsigned)d;
     const int sh = __builtin_ctz(m);
@@ -360,12 +289,6 @@ __device__ __forceinline__ u128 umod_small(u128 a, u128 g, bool small32) {
 }
 __device__ __forceinline__ u64 umod_small(u64 a, u64 g, bool small32) {
   return small32 ? (u64)((unsigned)a % (unsigned)g) : a % g;
-}
-__device__ __forceinline__ double to_double(i64 x) { return (double)x; }
-__device__ __forceinline__ double to_double(i128 x) {
-  const u128 m = uabs64(x);  // via the magnitude: hi*2^64 + lo on a negative value would cancel
-  const double d = (double)(u64)(m >> 64) * 18446744073709551616.0 + (double)(u64)m;
-  return x < 0 ? -d : d;
 }
 // workgroup barrier; a single-wave workgroup only needs the compiler to keep LDS order
 template <int NW>
@@ -422,8 +345,6 @@ template <class T>
 __device__ __forceinline__ int colof(int c, int lane, int h) {
   return c * (64 * ET<T>::CPL) + ET<T>::CPL * lane + h;
 }
-__device__ __forceinline__ int ctzU(u64 x) { return __builtin_ctzll(x); }
-__device__ __forceinline__ int ctzU(u128 x) { return ctz128(x); }
 // magnitude classes: every entry of a class-c row is below 2^cls_bits(c)
 template <class T>
 __device__ __forceinline__ int cls_bits(int c) {
@@ -523,7 +444,7 @@ __device__ __forceinline__ T row_entry(const RowRegs<T, NCH> &r, int pc, int ph,
 #pragma unroll
     for (int h = 0; h < ET<T>::CPL; h++)
       if (c == pc && h == ph) mine = r.v[c][h];
-  return readlane64(mine, pl);
+  return readlane(mine, pl);
 }
 
 // Sign summary, non-zero bitmap and magnitude class of a row held in registers
@@ -548,7 +469,7 @@ __device__ __forceinline__ void row_publish(const RowRegs<T, NCH> &r, const Shar
     for (int h = 0; h < ET<T>::CPL; h++) {
       int j = colof<T>(c, lane, h);
       T z = r.v[c][h];
-      mx |= uabs64(z);
+      mx |= uabs(z);
       if (has_parm) {
         if (j == bigparm) bs = sign_code(z);
         if (j > nvar && j < ncol) {
@@ -683,30 +604,9 @@ template <>
 struct WT<i128> {
   typedef u128 U;
 };
-__device__ __forceinline__ int ctzW(unsigned x) { return __builtin_ctz(x); }
-__device__ __forceinline__ int ctzW(u64 x) { return __builtin_ctzll(x); }
-__device__ __forceinline__ int ctzW(u128 x) { return ctz128(x); }
-__device__ __forceinline__ int bitlenW(unsigned x) { return x ? 32 - __builtin_clz(x) : 0; }
-__device__ __forceinline__ int bitlenW(u64 x) { return bitlen64(x); }
-__device__ __forceinline__ int bitlenW(u128 x) { return bitlen64(x); }
-__device__ __forceinline__ unsigned invW(unsigned m) {
-  unsigned x = (3u * m) ^ 2u;  // 5 correct bits, doubled by every step
-  x *= 2u - m * x;
-  x *= 2u - m * x;
-  x *= 2u - m * x;
-  return x;
-}
-__device__ __forceinline__ u64 invW(u64 m) { return inv_odd64(m); }
-__device__ __forceinline__ u128 invW(u128 m) { return inv_odd64(m); }
 __device__ __forceinline__ unsigned gcdW(unsigned a, unsigned b) { return gcd_u32(a, b); }
 __device__ __forceinline__ u64 gcdW(u64 a, u64 b) { return gcd_mag(a, b); }
 __device__ __forceinline__ u128 gcdW(u128 a, u128 b) { return gcd_mag(a, b); }
-__device__ __forceinline__ unsigned uabsW(int x) { return x < 0 ? 0u - (unsigned)x : (unsigned)x; }
-__device__ __forceinline__ u64 uabsW(i64 x) { return uabs64(x); }
-__device__ __forceinline__ u128 uabsW(i128 x) { return uabs64(x); }
-__device__ __forceinline__ int readlaneW(int v, int src) { return __builtin_amdgcn_readlane(v, src); }
-__device__ __forceinline__ i64 readlaneW(i64 v, int src) { return readlane64(v, src); }
-__device__ __forceinline__ i128 readlaneW(i128 v, int src) { return readlane64(v, src); }
 
 // zz (N entries per lane, every |zz| below 2^B, B at most W - 2) is divided by gcd(g, all |zz|) in place; returns that
 // gcd, with its factor 2^s and the inverse of its odd part (the caller divides the denominator with them).  g >= 1.
@@ -721,7 +621,7 @@ __device__ __forceinline__ typename WT<TW>::U reduce_by_inverse(TW (&zz)[N], int
     s = 0;
     inv = 1;
     if (g == 1) return g;
-    s = ctzW(g);
+    s = ctz(g);
     const U m = g >> s;
     if (s) {  // the low s bits of every entry (two's complement: those of z are zero iff those of |z| are)
       const U lowmask = ((U)1 << s) - 1;
@@ -731,7 +631,7 @@ __device__ __forceinline__ typename WT<TW>::U reduce_by_inverse(TW (&zz)[N], int
         if (((U)zz[e] & lowmask) != 0) pick = zz[e];
       const u64 bad = ballot64(pick != 0);
       if (bad) {
-        const U g2 = gcdW(g, uabsW(readlaneW(pick, __ffsll((long long)bad) - 1)));
+        const U g2 = gcdW(g, uabs(readlane(pick, __ffsll((long long)bad) - 1)));
         if (g2 == g) return 0;  // (cannot be: an entry with low bits set is no multiple of 2^s) -- never loop on it
         g = g2;
         continue;
@@ -742,17 +642,17 @@ __device__ __forceinline__ typename WT<TW>::U reduce_by_inverse(TW (&zz)[N], int
       for (int e = 0; e < N; e++) zz[e] >>= s;
       return g;
     }
-    int lim = B - s - bitlenW(m) + 1;
+    int lim = B - s - bitlen(m) + 1;
     lim = lim < 0 ? 0 : lim;
     CNT(13, 1);
-    inv = invW(m);
+    inv = inv_odd(m);
     if constexpr (!INPLACE) {
       TW qq[N], pick = 0;
 #pragma unroll
       for (int e = 0; e < N; e++) {
         const TW q = (TW)((U)(zz[e] >> s) * inv);
         qq[e] = q;
-        if ((uabsW(q) >> lim) != 0) pick = zz[e];  // (a failing entry is not zero: zero's quotient is zero)
+        if ((uabs(q) >> lim) != 0) pick = zz[e];  // (a failing entry is not zero: zero's quotient is zero)
       }
       const u64 bad = ballot64(pick != 0);
       if (!bad) {
@@ -761,7 +661,7 @@ __device__ __forceinline__ typename WT<TW>::U reduce_by_inverse(TW (&zz)[N], int
         return g;
       }
       CNT(14, 1);
-      const U g2 = gcdW(g, uabsW(readlaneW(pick, __ffsll((long long)bad) - 1)));
+      const U g2 = gcdW(g, uabs(readlane(pick, __ffsll((long long)bad) - 1)));
       if (g2 == g) return 0;  // (cannot be, see the proof above: a rejected entry is no multiple of g) -- never loop on it
       g = g2;
     } else {
@@ -770,7 +670,7 @@ __device__ __forceinline__ typename WT<TW>::U reduce_by_inverse(TW (&zz)[N], int
       for (int e = 0; e < N; e++) {
         const TW q = (TW)((U)(zz[e] >> s) * inv);
         zz[e] = q;
-        okl &= (uabsW(q) >> lim) == 0;
+        okl &= (uabs(q) >> lim) == 0;
       }
       const u64 bad = ballot64(!okl);
       if (!bad) return g;
@@ -781,9 +681,9 @@ __device__ __forceinline__ typename WT<TW>::U reduce_by_inverse(TW (&zz)[N], int
         const TW q = zz[e];
         const TW a = (TW)(((U)q * m) << s);
         zz[e] = a;
-        if ((uabsW(q) >> lim) != 0) pick = a;
+        if ((uabs(q) >> lim) != 0) pick = a;
       }
-      const U g2 = gcdW(g, uabsW(readlaneW(pick, __ffsll((long long)bad) - 1)));
+      const U g2 = gcdW(g, uabs(readlane(pick, __ffsll((long long)bad) - 1)));
       if (g2 == g) return 0;
       g = g2;
     }
@@ -799,7 +699,7 @@ __device__ __forceinline__ T reduce_den(T g0, typename WT<TW>::U g, int s, typen
     return (T)((U)(g0 >> s) * (U)inv);
   } else {
     if ((T)(TW)g0 == g0) return (T)(TW)((typename WT<TW>::U)((TW)g0 >> s) * inv);  // the quotient of a narrow g0 is narrow
-    return (T)((U)(g0 >> s) * inv_odd64((U)(g >> s)));
+    return (T)((U)(g0 >> s) * inv_odd((U)(g >> s)));
   }
 }
 
@@ -820,17 +720,17 @@ __device__ __forceinline__ bool row_reduce(T (&z)[N], typename ET<T>::U mx, T g0
   typedef typename ET<T>::U U;
   newden = g0;
   if (g0 == 1) return true;
-  const int B = (int)wave_minmax_u32<true>((unsigned)bitlen64(mx));
+  const int B = (int)wave_minmax_u32<true>((unsigned)bitlen(mx));
   // (g0 == 0 -- the reference would divide by zero unless some entry is not -- and entries of 2^(W-2) and more in magnitude
   // keep the remainder loop)
   if (!PIP_OPT_INV_REDUCE || g0 == 0 || B > ET<T>::BITS - 2) return row_reduce_rem<T, N>(z, mx, g0, lane, newden);
-  U g = (U)uni64((T)uabs64(g0));
+  U g = (U)uni((T)uabs(g0));
   if (gpre != 0)
     g = gpre;
   else if (zfold != 0)
-    g = gcd_mag(g, (U)uni64((T)uabs64(zfold)));
+    g = gcd_mag(g, (U)uni((T)uabs(zfold)));
   if (g == 1) return true;
-  const int gb = bitlen64(g);
+  const int gb = bitlen(g);
   if (TRY32 && B <= 30 && gb <= 32) {
     int zz[N], s;
     unsigned inv;
@@ -887,7 +787,7 @@ __device__ __forceinline__ bool row_reduce_rem_from(T (&z)[N], typename ET<T>::U
   typedef typename ET<T>::U U;
   newden = g0;
   if (gs == 1) return true;  // (g0 = -1 as well: every remainder modulo 1 vanishes)
-  U g = (U)uni64((T)gs);
+  U g = (U)uni((T)gs);
   // 32-bit remainders when everything fits (the common case): one v_rcp-based
   // division instead of the 64-bit software routine
   const bool small = (ballot64((mx >> 32) != 0) == 0) && (g >> 32) == 0;
@@ -895,7 +795,7 @@ __device__ __forceinline__ bool row_reduce_rem_from(T (&z)[N], typename ET<T>::U
     U rr = 0;
 #pragma unroll
     for (int e = 0; e < N; e++) {
-      U a = uabs64(z[e]);
+      U a = uabs(z[e]);
       U m = g == 0 ? a : umod_small(a, g, small);
       rr = rr ? rr : m;
     }
@@ -904,7 +804,7 @@ __device__ __forceinline__ bool row_reduce_rem_from(T (&z)[N], typename ET<T>::U
     u64 nz = ballot64(rr != 0);
     if (!nz) break;
     int src = __ffsll((long long)nz) - 1;
-    U r0 = (U)readlane64((T)rr, src);
+    U r0 = (U)readlane((T)rr, src);
     g = gcd_mag(g, r0);
     if (g == 1) break;
   }
@@ -924,19 +824,19 @@ __device__ __forceinline__ bool row_reduce_rem_from(T (&z)[N], typename ET<T>::U
 #pragma unroll
     for (int e = 0; e < N; e++) {
       const T zz = z[e];
-      const unsigned q = ((unsigned)uabs64(zz) >> s) * inv;
+      const unsigned q = ((unsigned)uabs(zz) >> s) * inv;
       z[e] = zz < 0 ? wneg((T)q) : (T)q;
     }
-    if (FROM && (uabs64(g0) >> 32) != 0) {  // (g began below |g0|: the denominator's quotient need not fit 32 bits)
-      newden = (T)((U)(g0 >> s) * inv_odd64((U)m));
+    if (FROM && (uabs(g0) >> 32) != 0) {  // (g began below |g0|: the denominator's quotient need not fit 32 bits)
+      newden = (T)((U)(g0 >> s) * inv_odd((U)m));
       return true;
     }
-    const unsigned qd = ((unsigned)uabs64(g0) >> s) * inv;
+    const unsigned qd = ((unsigned)uabs(g0) >> s) * inv;
     newden = g0 < 0 ? wneg((T)qd) : (T)qd;
     return true;
   }
-  int s = ctzU(g);
-  U inv = inv_odd64(g >> s);
+  int s = ctz(g);
+  U inv = inv_odd(g >> s);
 #pragma unroll
   for (int e = 0; e < N; e++) z[e] = (T)((U)(z[e] >> s) * inv);
   newden = (T)((U)(g0 >> s) * inv);
@@ -944,7 +844,7 @@ __device__ __forceinline__ bool row_reduce_rem_from(T (&z)[N], typename ET<T>::U
 }
 template <class T, int N>
 __device__ __forceinline__ bool row_reduce_rem(T (&z)[N], typename ET<T>::U mx, T g0, int lane, T &newden) {
-  return row_reduce_rem_from<T, N, false>(z, mx, g0, (typename ET<T>::U)uabs64(g0), lane, newden);
+  return row_reduce_rem_from<T, N, false>(z, mx, g0, (typename ET<T>::U)uabs(g0), lane, newden);
 }
 
 // `narrow64` (128-bit entries only): every entry of the row and of the pivot row and both multipliers fit a long long --
@@ -965,7 +865,7 @@ __device__ __forceinline__ bool update_row(RowRegs<T, NCH> &r, const T *prow, in
         T z = (T)p * (T)lp64 - (T)q * (T)foo64;
         if (j == pivj) z = wmul(dpiv, foo);
         r.v[c][0] = z;
-        mx |= uabs64(z);
+        mx |= uabs(z);
       }
       return row_reduce<T, NCH>(reinterpret_cast<T(&)[NCH]>(r.v), mx, g0, lane, newden, wmul(dpiv, foo), gpre);
     }
@@ -979,7 +879,7 @@ __device__ __forceinline__ bool update_row(RowRegs<T, NCH> &r, const T *prow, in
       T z = wsub(wmul(r.v[c][h], lpiv), wmul(q, foo));
       if (j == pivj) z = wmul(dpiv, foo);
       r.v[c][h] = z;
-      mx |= uabs64(z);
+      mx |= uabs(z);
     }
   if constexpr (LEANREG)
     return row_reduce_rem<T, NCH * ET<T>::CPL>(reinterpret_cast<T(&)[NCH * ET<T>::CPL]>(r.v), mx, g0, lane, newden);
@@ -1003,7 +903,7 @@ __device__ __forceinline__ bool update_row_narrow(RowRegs<i128, NCH> &r, const i
     i64 v = p * lpiv - q * foo;
     if (j == pivj) v = dpiv * foo;
     z[c] = v;
-    mx |= uabs64(v);
+    mx |= uabs(v);
   }
   i64 nd;
   const bool ok = row_reduce<i64, NCH>(z, mx, g0, lane, nd, dpiv * foo, gpre);
@@ -1051,7 +951,7 @@ __device__ __forceinline__ bool small_reduce_from(int (&z)[NCH][2], unsigned mx,
   newden = g0;
   bool ok = true;
   if (gs != 1) {  // (g0 = -1 as well: every remainder modulo 1 vanishes)
-    u64 g64 = (u64)uni64((i64)gs);
+    u64 g64 = (u64)uni((i64)gs);
     if ((g64 >> 32) == 0) {
       unsigned g = (unsigned)g64;
       // every |z| and g below 2^20 (the rule on this path): remainders through a float reciprocal of the wave-uniform
@@ -1102,10 +1002,10 @@ __device__ __forceinline__ bool small_reduce_from(int (&z)[NCH][2], unsigned mx,
             const unsigned qq = ((unsigned)(v < 0 ? -v : v) >> sh) * inv;
             z[c][h] = v < 0 ? -(int)qq : (int)qq;
           }
-        if (FROM && (uabs64(g0) >> 32) != 0) {  // (g began below |g0|: the denominator's quotient need not fit 32 bits)
+        if (FROM && (uabs(g0) >> 32) != 0) {  // (g began below |g0|: the denominator's quotient need not fit 32 bits)
           newden = cquo(g0, (i64)g);
         } else {
-          const unsigned qd = ((unsigned)uabs64(g0) >> sh) * inv;
+          const unsigned qd = ((unsigned)uabs(g0) >> sh) * inv;
           newden = g0 < 0 ? wneg((i64)qd) : (i64)qd;
         }
       }
@@ -1164,7 +1064,7 @@ __device__ __forceinline__ bool small_reduce_from(int (&z)[NCH][2], unsigned mx,
 }
 template <int NCH>
 __device__ __forceinline__ bool small_reduce(int (&z)[NCH][2], unsigned mx, i64 g0, int lane, i64 &newden) {
-  return small_reduce_from<NCH, false>(z, mx, g0, (u64)uabs64(g0), lane, newden);
+  return small_reduce_from<NCH, false>(z, mx, g0, (u64)uabs(g0), lane, newden);
 }
 
 template <int NCH>
@@ -1479,8 +1379,8 @@ __device__ int choose_column(const Shared<T> &S, const RowRegs<T, NCH> &prow, co
                 ab = __builtin_amdgcn_readlane(a[c][h], src);
                 nb = __builtin_amdgcn_readlane((int)n.v[c][h], src);
               } else {
-                ab = readlane64(a[c][h], src);
-                nb = readlane64(n.v[c][h], src);
+                ab = readlane(a[c][h], src);
+                nb = readlane(n.v[c][h], src);
               }
               got = true;
             }
@@ -1575,7 +1475,7 @@ __device__ int choose_column_slow(const Shared<T> &S, const T *vals, int W, int 
       const u64 nz = ballot64(x != 0);
       if (nz) {
         const int src = __ffsll((long long)nz) - 1;
-        less = readlane64(x, src) < 0;
+        less = readlane(x, src) < 0;
         break;
       }
     }
@@ -1660,12 +1560,6 @@ __device__ void sort_rows(const Shared<T> &S, int nvar, int nligne, double smax)
     }
     __builtin_amdgcn_wave_barrier();
   }
-}
-
-// x86 cvttsd2si semantics of the reference's (int)t, traiter.c:583
-__device__ __forceinline__ int trunc_int_x86(double t) {
-  if (!(t > -2147483649.0 && t < 2147483648.0)) return (int)0x80000000;
-  return (int)t;
 }
 
 // ================================================================ main kernel
@@ -2058,7 +1952,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 1 && NCH == 1 && sizeof(T) == 8) ? 
               for (int h = 0; h < ET<T>::CPL; h++) {
                 int j = colof<T>(c, lane, h);
                 if (j < nvar) {
-                  const int q2 = trunc_int_x86(to_double(r.v[c][h]) / d);
+                  const int q2 = trunc_x86(to_double(r.v[c][h]) / d);
                   const int aq = q2 < 0 ? (int)(0u - (unsigned)q2) : q2;
                   sz = sz > aq ? sz : aq;
                 }
@@ -2153,7 +2047,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 1 && NCH == 1 && sizeof(T) == 8) ? 
         // wave 0 builds the cut in its registers (integrer.c:357-386) and appends it
         if (wave == 0) {
           const int cslot = S.ref[ci];
-          const T D = uni64(S.den[cslot]);
+          const T D = uni(S.den[cslot]);
           RowRegs<T, NCH> r;
           bool okv = false, okp = false;
           for (int rep20 = 0; rep20 < PIP_DUP_REPS(20); rep20++) {
@@ -2335,8 +2229,8 @@ __global__ __launch_bounds__(64 * NW, (NW == 1 && NCH == 1 && sizeof(T) == 8) ? 
     }
     // pivot scalars, traiter.c:394-396 (uniform, every thread); the determinant bookkeeping of
     // traiter.c:412-446 only needs them logged
-    const T pivot = uni64(S.prow[pivj]);
-    const T dpiv = uni64(dpiv_v);
+    const T pivot = uni(S.prow[pivj]);
+    const T dpiv = uni(dpiv_v);
     if (tid == 0) {
       g_log[2 * nlog] = pivot;
       g_log[2 * nlog + 1] = dpiv;
@@ -2376,8 +2270,8 @@ __global__ __launch_bounds__(64 * NW, (NW == 1 && NCH == 1 && sizeof(T) == 8) ? 
             m_lp = lpk;
             m_foo = fk;
             const T zf = wmul(dpiv, fk);
-            typename ET<T>::U g = uabs64(g0k);
-            if (g > 1 && zf != 0) g = gcd_mag(g, uabs64(zf));
+            typename ET<T>::U g = uabs(g0k);
+            if (g > 1 && zf != 0) g = gcd_mag(g, uabs(zf));
             m_g = zf != 0 ? g : 0;  // (0: nothing folded in, row_reduce_wide starts from |g0|)
           }
         }
@@ -2399,8 +2293,8 @@ __global__ __launch_bounds__(64 * NW, (NW == 1 && NCH == 1 && sizeof(T) == 8) ? 
             continue;
           }
           row_load<T, NCH>(r, row, ncolp, lane);
-          const T lp = readlane64(m_lp, k), foo = readlane64(m_foo, k);
-          const typename ET<T>::U gpre = (typename ET<T>::U)readlane64((T)m_g, k);
+          const T lp = readlane(m_lp, k), foo = readlane(m_foo, k);
+          const typename ET<T>::U gpre = (typename ET<T>::U)readlane((T)m_g, k);
           PROF(9);
           if (foo == 0 && (S.sig[s] & SIG_RED)) {
             // only reached with PIPAMD_T_NOSKIP: multipliers (1, 0) and gcd 1, the reference rewrites the row with the
@@ -2409,7 +2303,7 @@ __global__ __launch_bounds__(64 * NW, (NW == 1 && NCH == 1 && sizeof(T) == 8) ? 
             if (lane == 0) S.sig[s] &= ~0xC0;
             continue;
           }
-          const T den_s = uni64(S.den[s]);
+          const T den_s = uni(S.den[s]);
           const T g0 = pivot != 1 ? wmul(lp, den_s) : den_s;
           PROF(10);
           T nd;
@@ -2520,13 +2414,13 @@ __global__ __launch_bounds__(64 * NW, (NW == 1 && NCH == 1 && sizeof(T) == 8) ? 
             }
             // pivot > 0 (choisir_piv only takes positive entries): with pivot == 1, or
             // gcd(pivot, foo) == 1, the divisions of traiter.c:472-474 are by 1
-            T den_s = uni64(S.den[s]);
+            T den_s = uni(S.den[s]);
             T d = 1, lp = pivot, g0 = den_s;
             const T foo_in = foo;
             for (int rep16 = 0; rep16 < PIP_DUP_REPS(16); rep16++) {
               if (PIP_DUP == 16) {
                 PIP_OPAQUE_MEM();
-                den_s = uni64(S.den[s]);
+                den_s = uni(S.den[s]);
                 foo = foo_in;
                 if constexpr (sizeof(T) == 8) asm volatile("" : "+s"(foo));
                 d = 1, lp = pivot, g0 = den_s;
@@ -2599,8 +2493,8 @@ __global__ __launch_bounds__(64 * NW, (NW == 1 && NCH == 1 && sizeof(T) == 8) ? 
             PROF_CNT(prof, 2, d != 1);
             PROF_CNT(prof, 3, g0 != 1);
             PROF_CNT(prof, 4, nd != g0);
-            PROF_CNT(prof, 5, uni64(S.den[s]) != 1);
-            PROF_CNT(prof, 6, (u64)uabs64(pivot) >> 16 != 0);
+            PROF_CNT(prof, 5, uni(S.den[s]) != 1);
+            PROF_CNT(prof, 6, (u64)uabs(pivot) >> 16 != 0);
             for (int rep18 = 0; rep18 < PIP_DUP_REPS(18); rep18++) {
               if (PIP_DUP == 18) PIP_OPAQUE_MEM();
               row_store<T, NCH>(r, row, ncolp, lane);

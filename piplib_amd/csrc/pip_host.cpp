@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "pip_host.h"
+#include "pip_wide.h"
 
 static thread_local char g_err[512];
 void pipamd_set_error(const char *fmt, ...) {
@@ -1056,12 +1057,11 @@ extern "C" int pipamd_batch_dual_matrices(pipamd_engine *e, const void *d_ws, co
 // compile: it validates the grammar, counts, applies pip_solve's result edit if there is one (TapeEdit), and -- given a
 // vector -- emits the program.  The walk keeps its own stack of
 // items still to come (an IF pushes its two, a NEW the one behind it), so a deep tape costs heap, not the thread's stack.
-typedef __int128 tape_int;
-static inline tape_int tape_p1(const pipamd_sol_cell &c) { return c.param1; }
-static inline tape_int tape_p2(const pipamd_sol_cell &c) { return c.param2; }
-static inline tape_int tape_wide(int64_t lo, int64_t hi) { return (tape_int)(((unsigned __int128)(uint64_t)hi << 64) | (uint64_t)lo); }
-static inline tape_int tape_p1(const pipamd_sol_cell128 &c) { return tape_wide(c.param1_lo, c.param1_hi); }
-static inline tape_int tape_p2(const pipamd_sol_cell128 &c) { return tape_wide(c.param2_lo, c.param2_hi); }
+static inline i128 tape_p1(const pipamd_sol_cell &c) { return c.param1; }
+static inline i128 tape_p2(const pipamd_sol_cell &c) { return c.param2; }
+static inline i128 tape_wide(int64_t lo, int64_t hi) { return (i128)(((unsigned __int128)(uint64_t)hi << 64) | (uint64_t)lo); }
+static inline i128 tape_p1(const pipamd_sol_cell128 &c) { return tape_wide(c.param1_lo, c.param1_hi); }
+static inline i128 tape_p2(const pipamd_sol_cell128 &c) { return tape_wide(c.param2_lo, c.param2_hi); }
 
 // pip_solve's result edit (sol_vector_edit, sol.c:435-512) as the walk applies it.  Without one: no column is dropped.
 struct TapeEdit {
@@ -1092,7 +1092,7 @@ struct TapeWalk {
     if (prog) prog->push_back(w);
     words++;
   }
-  void emit(tape_int v) {
+  void emit(i128 v) {
     emit_word((long long)(uint64_t)(unsigned __int128)v);
     if (EW == 2) emit_word((long long)(uint64_t)((unsigned __int128)v >> 64));
   }
@@ -1106,20 +1106,20 @@ struct TapeWalk {
   // FORM(len) and its VALs: one positive denominator (1 if `one`); the numerators of the kept columns are emitted, *den
   // gets the denominator.  `unbounded` (a solution list's form): under SOL_SHIFT the big parameter's coefficient becomes
   // n - D before any drop, and *unbounded says whether that is not 0 (sol.c:479-483).
-  bool form(int64_t len, bool one, tape_int *den, const char *w, bool *unbounded = nullptr) {
+  bool form(int64_t len, bool one, i128 *den, const char *w, bool *unbounded = nullptr) {
     const Cell *f = take(PIPAMD_SOL_FORM, w);
     if (!f) return false;
-    if (tape_p1(*f) != (tape_int)len) return fail(w);
-    tape_int d = 1;
+    if (tape_p1(*f) != (i128)len) return fail(w);
+    i128 d = 1;
     if (unbounded) *unbounded = false;
     for (int64_t j = 0; j < len; j++) {
       const Cell *v = take(PIPAMD_SOL_VAL, w);
       if (!v) return false;
       if (j == 0) d = tape_p2(*v);
       if (tape_p2(*v) != d || d <= 0 || (one && d != 1)) return fail(w);
-      tape_int n = tape_p1(*v);
+      i128 n = tape_p1(*v);
       if (unbounded && ed.shift && j == ed.bg) {
-        if (__builtin_sub_overflow(n, d, &n) || (EW == 1 && n != (tape_int)(int64_t)n)) toolarge = true;
+        if (__builtin_sub_overflow(n, d, &n) || (EW == 1 && n != (i128)(int64_t)n)) toolarge = true;
         if (n != 0) *unbounded = true;
       }
       if (j < ed.nparm && ed.dropped(j)) continue;
@@ -1201,10 +1201,10 @@ static int tape_walk(const char *who, const Cell *cells, size_t n_cells, const p
     // (P beyond the limit: the walk goes on to tell an invalid tape from a large one, but emits headers of a fixed P)
     const int hp = P - ndrop < TAPE_MAX_SLOTS ? (int)(P - ndrop) : TAPE_MAX_SLOTS;
     const Cell &c = cells[w.pos++];
-    tape_int den;
+    i128 den;
     switch (c.kind) {
       case PIPAMD_SOL_NEW: {
-        if (tape_p1(c) != (tape_int)P) {
+        if (tape_p1(c) != (i128)P) {
           ok = w.fail("newparm whose number is not the count of parameters in scope");
           break;
         }
@@ -1239,7 +1239,7 @@ static int tape_walk(const char *who, const Cell *cells, size_t n_cells, const p
         break;
       }
       case PIPAMD_SOL_LIST: {
-        if (tape_p1(c) != (tape_int)sh->nvar) {
+        if (tape_p1(c) != (i128)sh->nvar) {
           ok = w.fail("a solution list whose length is not nvar");
           break;
         }
@@ -1260,7 +1260,7 @@ static int tape_walk(const char *who, const Cell *cells, size_t n_cells, const p
         if (!ok) break;
         if (sh->ndual > 0) {
           const Cell *l = w.take(PIPAMD_SOL_LIST, "no dual list behind a solution list");
-          if (!l || tape_p1(*l) != (tape_int)sh->ndual) {
+          if (!l || tape_p1(*l) != (i128)sh->ndual) {
             ok = w.fail("a dual list whose length is not ndual");
             break;
           }
@@ -1271,12 +1271,12 @@ static int tape_walk(const char *who, const Cell *cells, size_t n_cells, const p
               ok = w.fail("dual list: forms of one value over a positive denominator are expected");
               break;
             }
-            const tape_int num = tape_p1(*v), dd = tape_p2(*v);
+            const i128 num = tape_p1(*v), dd = tape_p2(*v);
             const unsigned __int128 mag = num < 0 ? (unsigned __int128)0 - (unsigned __int128)num : (unsigned __int128)num;
             const unsigned __int128 g = tape_gcd(mag, (unsigned __int128)dd);
             const unsigned __int128 q = mag / g;
-            w.emit(num < 0 ? (tape_int)((unsigned __int128)0 - q) : (tape_int)q);
-            w.emit((tape_int)((unsigned __int128)dd / g));
+            w.emit(num < 0 ? (i128)((unsigned __int128)0 - q) : (i128)q);
+            w.emit((i128)((unsigned __int128)dd / g));
           }
           if (!ok) break;
         }

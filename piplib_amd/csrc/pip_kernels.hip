@@ -46,8 +46,8 @@ __global__ __launch_bounds__(64) void pip_det_replay_kernel(PipJob *jobs, i64 *a
   const int nlog = J->nlog;
   if (nlog <= 0 || (J->ebits == 128) != (sizeof(T) == 16)) return;
   const T *lg = (const T *)(arena + J->log_off);
-  T det0 = uni64(det_limb<T>(J, 0)), det1 = uni64(det_limb<T>(J, 1)), det2 = uni64(det_limb<T>(J, 2)),
-    det3 = uni64(det_limb<T>(J, 3));
+  T det0 = uni(det_limb<T>(J, 0)), det1 = uni(det_limb<T>(J, 1)), det2 = uni(det_limb<T>(J, 2)),
+    det3 = uni(det_limb<T>(J, 3));
   int ldet = __builtin_amdgcn_readfirstlane(J->ldet);
   int bad = -1;
   for (int base = 0; base < nlog && bad < 0; base += 64) {
@@ -66,7 +66,7 @@ __global__ __launch_bounds__(64) void pip_det_replay_kernel(PipJob *jobs, i64 *a
     }
     const int n = nlog - base < 64 ? nlog - base : 64;
     for (int j = 0; j < n; j++) {
-      if (!det_step<T>(det0, det1, det2, det3, ldet, readlane64(pp, j), readlane64(dp, j))) {
+      if (!det_step<T>(det0, det1, det2, det3, ldet, readlane(pp, j), readlane(dp, j))) {
         bad = base + j;  // traiter.c:424,442: the reference exits inside this call of pivoter
         break;
       }
@@ -204,31 +204,28 @@ __global__ void pip_batch_load_kernel(PipJob *jobs, i64 *arena, const i64 *rows,
 // does); an equality is followed by its negation in every column.  One WAVE per input row, a lane per column (CPL
 // columns a lane): the row's sum and the gcd of its columns are reductions over the lanes that hold it.
 // pipamd_batch_load_shifted is the launch with no equality, simplify == 0 and nrows == ni.
-__device__ __forceinline__ i64 sys_shfl(i64 v, int src) { return shfl64(v, src); }
-__device__ __forceinline__ i128 sys_shfl(i128 v, int src) {
-  const u64 lo = (u64)shfl64((i64)(u64)(u128)v, src), hi = (u64)shfl64((i64)(u64)((u128)v >> 64), src);
-  return (i128)(((u128)hi << 64) | lo);
-}
+// (pip_wide.h's wave_sum, spelled with the lane the kernel already holds: through xor-shuffles the load kernels are 21 to
+// 25 instructions longer each)
 template <class T>
 __device__ __forceinline__ T sys_wave_sum(T v, int lane) {
-  for (int o = 32; o; o >>= 1) v = wadd(v, sys_shfl(v, lane ^ o));
+  for (int o = 32; o; o >>= 1) v = wadd(v, shfl(v, lane ^ o));
   return v;
 }
 // gcd of the lanes' magnitudes (gcd(0, x) = x); any bit pattern ends the binary gcd
 __device__ __forceinline__ u64 sys_wave_gcd(u64 g, int lane) {
-  for (int o = 32; o; o >>= 1) g = gcd_mag(g, (u64)shfl64((i64)g, lane ^ o));
-  return (u64)uni64((i64)g);
+  for (int o = 32; o; o >>= 1) g = gcd_mag(g, (u64)shfl((i64)g, lane ^ o));
+  return (u64)uni((i64)g);
 }
 // x / g for a g > 1 that divides x; g is a magnitude of up to 64 bits (2^63 for a row of INT64_MINs)
 __device__ __forceinline__ i64 sys_exact(i64 x, u64 g) {
-  const u64 q = uabs64(x) / g;
+  const u64 q = uabs(x) / g;
   return x < 0 ? wneg((i64)q) : (i64)q;
 }
 __device__ __forceinline__ i128 sys_exact(i128 x, u64 g) { return cquo(x, (i128)g); }
 // floor(c / g), g > 1, for a constant of at most 2^63 in magnitude (an input value or its negation)
 template <class T>
 __device__ __forceinline__ T sys_floor(T c, u64 g) {
-  const u64 uc = (u64)uabs64(c);
+  const u64 uc = (u64)uabs(c);
   return c < 0 ? wneg((T)(i64)((uc + (g - 1)) / g)) : (T)(i64)(uc / g);
 }
 
@@ -323,7 +320,7 @@ __device__ __forceinline__ void csr_row_to_lanes(const PipCsrRows &cs, i64 p0, i
     const i64 val = lane < n ? cs.vals[e0 + lane] : 0;
     for (int i = 0; i < n; i++) {
       const int ci = __builtin_amdgcn_readlane(col, i);
-      const i64 vi = readlane64(val, i);
+      const i64 vi = readlane(val, i);
       if (lane == (ci & 63)) {
 #pragma unroll
         for (int c = 0; c < CPL; c++)
@@ -360,11 +357,11 @@ __device__ __forceinline__ bool inst_constant(const i64 *row, const i64 *theta, 
     lo += (u128)(u64)c;
   }
   for (int o = top; o; o >>= 1) {
-    hi = wadd(hi, sys_shfl(hi, lane ^ o));
-    lo = (u128)wadd((i128)lo, sys_shfl((i128)lo, lane ^ o));
+    hi = wadd(hi, shfl(hi, lane ^ o));
+    lo = (u128)wadd((i128)lo, shfl((i128)lo, lane ^ o));
   }
-  hi = uni64(hi);  // lane 0 has the totals
-  lo = (u128)uni64((i128)lo);
+  hi = uni(hi);  // lane 0 has the totals
+  lo = (u128)uni((i128)lo);
   hi += (i128)(u64)(lo >> 64);
   const u64 l0 = (u64)lo;
   if constexpr (sizeof(T) == 8) {
@@ -378,11 +375,11 @@ __device__ __forceinline__ bool inst_constant(const i64 *row, const i64 *theta, 
 // floor(c / g), g > 1, for a constant of PipInstanceRows: any value of the entry type.  Within 2^63 it is sys_floor.
 __device__ __forceinline__ i64 inst_floor(i64 c, u64 g) { return sys_floor(c, g); }
 __device__ __forceinline__ i128 inst_floor(i128 c, u64 g) {
-  const u128 uc = uabs64(c);  // (2^127 for the smallest value)
+  const u128 uc = uabs(c);  // (2^127 for the smallest value)
   if ((uc >> 63) == 0) return sys_floor(c, g);
   const u128 rem = umod128(uc, (u128)g);
   const int s = __builtin_ctzll(g);
-  u128 q = ((uc - rem) >> s) * inv_odd64((u128)(g >> s));  // exact, and below 2^127: g >= 2
+  u128 q = ((uc - rem) >> s) * inv_odd((u128)(g >> s));  // exact, and below 2^127: g >= 2
   if (c < 0 && rem) q += 1;
   return c < 0 ? wneg((i128)q) : (i128)q;
 }
@@ -455,7 +452,7 @@ __global__ __launch_bounds__(256) void pip_batch_load_system_kernel(PipJob *jobs
     i64 sp[CSR ? CPL : 1];  // PipCsrRows: the row's values, each in the lane of its column
     if constexpr (CSR) {
       const i64 *rp = (const i64 *)rs.row_ptr + (size_t)blockIdx.x * nrows + r;
-      csr_row_to_lanes<CPL>(rs, uni64(rp[0]), uni64(rp[1]), lane, sp);
+      csr_row_to_lanes<CPL>(rs, uni(rp[0]), uni(rp[1]), lane, sp);
     }
     T cst = 0;  // PipInstanceRows: the row's constant at the block's point
     if constexpr (INST) {
@@ -481,7 +478,7 @@ __global__ __launch_bounds__(256) void pip_batch_load_system_kernel(PipJob *jobs
         if (j == nvar) v[c] = cst;
       if (j < nvar) {
         sum = wadd(sum, (T)a);
-        if (simplify) g = gcd_mag(g, uabs64(a));
+        if (simplify) g = gcd_mag(g, uabs(a));
         if (shift > 0) v[c] = wneg((T)a);
       }
     }
@@ -497,7 +494,7 @@ __global__ __launch_bounds__(256) void pip_batch_load_system_kernel(PipJob *jobs
     // 2^64 in the 128-bit flavour too: it divides an input value, or every one of them is zero and so is their exact sum
     if (simplify) {
       g = sys_wave_gcd(g, lane);
-      if (shift) g = (u64)gcd_mag((U)g, (U)uni64((T)uabs64(big)));
+      if (shift) g = (u64)gcd_mag((U)g, (U)uni((T)uabs(big)));
     }
     T *out = vals + (size_t)k * W;
 #pragma unroll

@@ -190,7 +190,7 @@ struct LeanIntRows {
       z[0][h] = v;
       mx |= mag(v);
     }
-    const bool ok = small_reduce_from<1>(z, mx, g0, gs ? gs : uabs64(g0), lane, nd);
+    const bool ok = small_reduce_from<1>(z, mx, g0, gs ? gs : uabs(g0), lane, nd);
     r.v[0] = z[0][0];
     r.v[1] = z[0][1];
     return ok;
@@ -206,12 +206,12 @@ struct LeanIntRows {
       i64 v = (i64)r.v[h] * (i64)lp - (i64)pr.v[h] * (i64)foo;
       if (2 * lane + h == pivj) v = wmul(dpiv, (i64)foo);
       zw[h] = v;
-      mx |= uabs64(v);
+      mx |= uabs(v);
     }
 #if PIP_LEAN_MID_INV
     return row_reduce<i64, 2, false>(zw, mx, g0, lane, nd, wmul(dpiv, (i64)foo), gs);
 #else
-    return row_reduce_rem_from<i64, 2>(zw, mx, g0, gs ? gs : uabs64(g0), lane, nd);  // (the remainder loop: reduce_by_inverse costs this kernel 12 bytes of scratch)
+    return row_reduce_rem_from<i64, 2>(zw, mx, g0, gs ? gs : uabs(g0), lane, nd);  // (the remainder loop: reduce_by_inverse costs this kernel 12 bytes of scratch)
 #endif
   }
 };
@@ -232,9 +232,9 @@ struct LeanLongRows {
     return nvar < 256 && nvar >= 1 && J->nparm == 0 && J->bigparm < 0 && W > 128 && W <= 256 && J->ebits == 128;
   }
   static __device__ __forceinline__ bool shape_big(const PipJob *, int, int) { return false; }  // (no BIG flavour of long long rows)
-  static __device__ __forceinline__ u64 mag(i64 v) { return uabs64(v); }
+  static __device__ __forceinline__ u64 mag(i64 v) { return uabs(v); }
   static __device__ __forceinline__ bool fits(i128 x) { return fits64(x); }
-  static __device__ __forceinline__ u64 gcd(i64 a, i64 b) { return gcd_mag((u64)a, uabs64(b)); }
+  static __device__ __forceinline__ u64 gcd(i64 a, i64 b) { return gcd_mag((u64)a, uabs(b)); }
   static __device__ __forceinline__ void load(Row &r, const i128 *slot, int lane, int W) {
     const i64 *p = reinterpret_cast<const i64 *>(slot);
 #pragma unroll
@@ -295,7 +295,7 @@ struct LeanLongRows {
       i64 v = r.v[c] * lp - pr.v[c] * foo;
       if (64 * c + lane == pivj) v = zf;
       r.v[c] = v;
-      mx |= uabs64(v);
+      mx |= uabs(v);
     }
     i64 nd64;
     const bool ok = row_reduce<i64, 4>(r.v, mx, (i64)g0, lane, nd64, zf, (u64)gs);  // (small_den: gs <= |g0| < 2^62)
@@ -314,7 +314,7 @@ struct LeanLongRows {
       i128 v = (i128)r.v[c] * (i128)lp - (i128)pr.v[c] * (i128)foo;
       if (64 * c + lane == pivj) v = zf;
       zw[c] = v;
-      mx |= uabs64(v);
+      mx |= uabs(v);
     }
     return row_reduce<i128, 4>(zw, mx, g0, lane, nd, zf, gs);
   }
@@ -339,7 +339,7 @@ __device__ __forceinline__ X lean_entry(const X (&v)[F::NV], int k, int src) {
   if constexpr (sizeof(X) == 4)
     return __builtin_amdgcn_readlane(mine, src);
   else
-    return readlane64(mine, src);
+    return readlane(mine, src);
 }
 
 // lane k's copy of a value (k uniform)
@@ -348,9 +348,9 @@ __device__ __forceinline__ X lean_lane(X v, int k) {
   if constexpr (sizeof(X) == 4)
     return (X)__builtin_amdgcn_readlane((int)v, k);
   else if constexpr (sizeof(X) == 8)
-    return (X)readlane64((i64)v, k);
+    return (X)readlane((i64)v, k);
   else
-    return (X)readlane64((i128)v, k);
+    return (X)readlane((i128)v, k);
 }
 
 // The part of a row's update that needs no more of the row than its entry `foo` in the pivot column (traiter.c:470-476):
@@ -375,9 +375,9 @@ __device__ __forceinline__ void lean_prep_lane(typename F::E pivot, typename F::
     g0 = wmul((T)lp, den);
   }
   gs = 0;
-  const auto ag = uabs64(g0);
+  const auto ag = uabs(g0);
   const T zf = wmul(dpiv, (T)foo);
-  if (ag > 1 && zf != 0) gs = gcd_mag(ag, uabs64(zf));
+  if (ag > 1 && zf != 0) gs = gcd_mag(ag, uabs(zf));
 }
 
 // Lane k prepares the row of S.work[w0 + k] (k < nwork - w0; the recycled pivot slot is skipped): `fk` is the row's entry
@@ -483,7 +483,7 @@ __device__ __forceinline__ int lean_publish_wide(const typename F::T (&z)[F::NV]
   u64 nz[F::NV];
 #pragma unroll
   for (int h = 0; h < F::NV; h++) {
-    mx |= uabs64(z[h]);
+    mx |= uabs(z[h]);
     nz[h] = ballot64(z[h] != 0);
   }
   int cls = cls_of<T>(mx);
@@ -754,14 +754,14 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
     }
     return;
   }
-  T *vals = (T *)(arena + uni64((i64)J->vals_off));
+  T *vals = (T *)(arena + uni((i64)J->vals_off));
   // (what only the prologue and the epilogue need -- the row tables in HBM, the saved summaries, the counters -- is
   // derived from the job header where it is used, so that it holds no scalar registers across the pivot loop)
   const int ncut0 = J->ncut - ni;  // cuts so far = ncut0 + ni (every row this kernel appends is a cut)
   // (wave-uniform, but loaded through vector memory: pinned to scalar registers, the pivot loop needs the vector ones)
   const int cap_ni = __builtin_amdgcn_readfirstlane(min(J->S, J->L - nvar));  // rows the job's block holds
   int npiv = J->npiv, nupd = J->nupd;
-  T *g_log = (T *)(arena + uni64((i64)J->log_off));
+  T *g_log = (T *)(arena + uni((i64)J->log_off));
   constexpr int LOGCAP = PIPAMD_DETLOG;
   int nlog = J->nlog;
 
@@ -825,7 +825,7 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
 #pragma unroll
         for (int h = 0; h < NV; h++) {
           const T v = rr[qq].v[h / CPL][h % CPL];
-          mx |= uabs64(v);
+          mx |= uabs(v);
           z.v[h] = (E)v;
         }
         if (ballot64((mx >> F::ROW_BITS) != 0)) {  // not below 2^ROW_BITS in magnitude
@@ -844,7 +844,7 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
 #pragma unroll
           for (int h = 0; h < NV; h++) {
             const E v = z.v[h];
-            const int q2 = !den1 ? trunc_int_x86((double)v / d) : (v == (E)(int)v ? (int)v : (int)0x80000000);
+            const int q2 = !den1 ? trunc_x86((double)v / d) : (v == (E)(int)v ? (int)v : (int)0x80000000);
             const int aq = q2 < 0 ? (int)(0u - (unsigned)q2) : q2;
             if (F::col(lane, h) < nvar) sz = sz > aq ? sz : aq;
           }
@@ -944,7 +944,7 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
           break;
         }
         const int cslot = S.ref[ci];
-        const T DT = uni64(S.den[cslot]);
+        const T DT = uni(S.den[cslot]);
         why = 3;
         if (DT <= 0 || DT >= ((T)1 << F::CUT_BITS)) break;  // the cut's entries (below D) might not fit E: the general kernel goes on
         const E D = (E)DT;
@@ -1004,7 +1004,7 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
     PROF(0);
     // ---------------- A: pivot row, choisir_piv, work list
     const int pslot = S.ref[pivi];
-    const T dpiv = uni64(S.den[pslot]);
+    const T dpiv = uni(S.den[pslot]);
     // small path for a row: the row and the pivot row in class 0 and the pivot row's denominator below 2^CLS0_BITS (then
     // the multipliers are below it as well and every product fits E)
     const bool psmall = S.rcls[pslot] == 0 && dpiv > -((T)1 << F::CLS0_BITS) && dpiv < ((T)1 << F::CLS0_BITS);
@@ -1150,7 +1150,7 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
           small = (m_small >> k) & 1;
         } else {
           foo = lean_entry<F>(r.v, pe, pl);
-          const T den_s = uni64(S.den[s]);
+          const T den_s = uni(S.den[s]);
           lp = pivot;
           g0 = den_s;
           if (pivot != 1) {
@@ -1179,7 +1179,7 @@ hipError_t launch_lean(const AdvanceLaunch &a) {
           }
           typename ET<T>::U mx = 0;
 #pragma unroll
-          for (int h = 0; h < NV; h++) mx |= uabs64(zw[h]);
+          for (int h = 0; h < NV; h++) mx |= uabs(zw[h]);
           PROF(7);
           if (ballot64((mx >> F::ROW_BITS) != 0) == 0) {
 #pragma unroll

@@ -12,22 +12,11 @@
 #include <hip/hip_runtime.h>
 
 #include "pip_m2t.h"
+#include "pip_wide.h"
 
 namespace {
-typedef long long w64;
-typedef unsigned long long u64;
-typedef __int128 w128;
-typedef unsigned __int128 u128;
-
-__device__ __forceinline__ w64 wneg(w64 x) { return (w64)(0 - (u64)x); }  // piplib_int_oppose on long long: wraps
-
-__device__ __forceinline__ w128 wave_sum(w128 x) {
-  for (int o = 32; o; o >>= 1) {
-    const u64 lo = (u64)__shfl_xor((w64)(u64)(u128)x, o), hi = (u64)__shfl_xor((w64)(u64)((u128)x >> 64), o);
-    x = (w128)((u128)x + (((u128)hi << 64) | lo));
-  }
-  return x;
-}
+typedef i64 w64;  // an input coefficient: wneg() on it is piplib_int_oppose on long long, which wraps
+typedef i128 w128;
 
 // Output column c of the domain tableau, unknowns | constant | parameters | new big | urs copies: the matrix column it
 // is copied from (-1: none, the new big column) and whether it is negated (tab.c:342-367).

@@ -77,9 +77,9 @@ __global__ __launch_bounds__(64) void pip_probe_arith_kernel(int op, const i64 *
     case P_GCD_MAG128: st2(o, (i128)gcd_mag((u128)ld2(a), (u128)ld2(a + 2))); break;
     case P_GCD_I64: o[0] = gcd_i64(a[0], a[1]); break;
     case P_GCD_I128: st2(o, gcd_i64(ld2(a), ld2(a + 2))); break;
-    case P_INV64: o[0] = (i64)inv_odd64((u64)a[0]); break;
-    case P_INV128: st2(o, (i128)inv_odd64((u128)ld2(a))); break;
-    case P_INVW32: o[0] = (i64)invW((unsigned)a[0]); break;
+    case P_INV64: o[0] = (i64)inv_odd((u64)a[0]); break;
+    case P_INV128: st2(o, (i128)inv_odd((u128)ld2(a))); break;
+    case P_INVW32: o[0] = (i64)inv_odd((unsigned)a[0]); break;
     case P_CQUO64: o[0] = cquo(a[0], a[1]); break;
     case P_CQUO128: st2(o, cquo(ld2(a), ld2(a + 2))); break;
     case P_CREM64: o[0] = crem(a[0], a[1]); break;
@@ -112,9 +112,9 @@ __global__ __launch_bounds__(64) void pip_probe_arith_kernel(int op, const i64 *
     }
     case P_LOG2_64: o[0] = log2_64(a[0]); break;
     case P_LOG2_128: o[0] = log2_64(ld2(a)); break;
-    case P_BITLEN64: o[0] = bitlen64((u64)a[0]); break;
-    case P_BITLEN128: o[0] = bitlen64((u128)ld2(a)); break;
-    case P_CTZ128: o[0] = ctz128((u128)ld2(a)); break;
+    case P_BITLEN64: o[0] = bitlen((u64)a[0]); break;
+    case P_BITLEN128: o[0] = bitlen((u128)ld2(a)); break;
+    case P_CTZ128: o[0] = ctz((u128)ld2(a)); break;
     case P_FITS64: o[0] = fits64(ld2(a)) ? 1 : 0; break;
     case P_BEZOUT64: o[0] = bezout_dev<i64>(a[0], a[1], a[2]); break;
     case P_BEZOUT128: st2(o, bezout_dev<i128>(ld2(a), ld2(a + 2), ld2(a + 4))); break;
@@ -152,7 +152,7 @@ __global__ __launch_bounds__(64) void pip_probe_lean_prep_kernel(const i64 *in, 
   rcls[lane] = (u8)a[5];
   __syncthreads();
   const int pivot = __builtin_amdgcn_readfirstlane((int)a[0]);
-  const i64 dpiv = uni64(a[1]);
+  const i64 dpiv = uni(a[1]);
   const bool psmall = __builtin_amdgcn_readfirstlane((int)(a[2] != 0)) != 0;
   int m_lp, m_foo;
   i64 m_g0;

@@ -23,12 +23,11 @@
 
 #include "pip_job.h"
 #include "pip_quast.h"
+#include "pip_wide.h"
 
 namespace {
-typedef long long w64;            // a raw 64-bit word / an input coefficient (inputs are long longs in either flavour)
-typedef unsigned long long u64;   // ballot masks, bit sets
-typedef __int128 w128;
-typedef unsigned __int128 u128;
+typedef i64 w64;  // a raw 64-bit word / an input coefficient (inputs are long longs in either flavour)
+typedef i128 w128;
 
 // ---- what the kernel needs from its entry type QI (long long: the reference's int64 build; __int128: the overflow-safe
 // flavour, piplib.h:42-88), by overloading.  Everything the compiler would turn into a library call for 128 bits
@@ -36,23 +35,6 @@ typedef unsigned __int128 u128;
 template <class QI> struct QT;
 template <> struct QT<w64> { typedef u64 U; };
 template <> struct QT<w128> { typedef u128 U; };
-__device__ __forceinline__ w64 qshfl(w64 x, int src) { return __shfl(x, src); }
-__device__ __forceinline__ w128 qshfl(w128 x, int src) {
-  const u64 lo = (u64)__shfl((w64)(u64)(u128)x, src), hi = (u64)__shfl((w64)(u64)((u128)x >> 64), src);
-  return (w128)(((u128)hi << 64) | lo);
-}
-__device__ __forceinline__ w64 qrdlane(w64 x, int l) {
-  const unsigned lo = __builtin_amdgcn_readlane((unsigned)(u64)x, l), hi = __builtin_amdgcn_readlane((unsigned)((u64)x >> 32), l);
-  return (w64)(((u64)hi << 32) | lo);
-}
-__device__ __forceinline__ w128 qrdlane(w128 x, int l) {
-  const u64 lo = (u64)qrdlane((w64)(u64)(u128)x, l), hi = (u64)qrdlane((w64)(u64)((u128)x >> 64), l);
-  return (w128)(((u128)hi << 64) | lo);
-}
-__device__ __forceinline__ int qbits(u64 u) { return u ? 64 - __clzll((long long)u) : 0; }
-__device__ __forceinline__ int qbits(u128 u) { return (u64)(u >> 64) ? 128 - __clzll((long long)(u64)(u >> 64)) : qbits((u64)u); }
-__device__ __forceinline__ int qctz(u64 u) { return __builtin_ctzll(u | (1ull << 63)); }
-__device__ __forceinline__ int qctz(u128 u) { return (u64)u ? __builtin_ctzll((u64)u) : 64 + __builtin_ctzll((u64)(u >> 64) | (1ull << 63)); }
 __device__ __forceinline__ bool qaddo(w64 a, w64 b, w64 *r) { return __builtin_add_overflow(a, b, r); }
 __device__ __forceinline__ bool qsubo(w64 a, w64 b, w64 *r) { return __builtin_sub_overflow(a, b, r); }
 __device__ __forceinline__ bool qmulo(w64 a, w64 b, w64 *r) { return __builtin_mul_overflow(a, b, r); }
@@ -64,10 +46,10 @@ __device__ __forceinline__ bool qsubo(w128 a, w128 b, w128 *r) { return __builti
 // only -2^127 itself -- two powers of two under a negative sign -- fits
 __device__ __forceinline__ bool qmulo(w128 a, w128 b, w128 *r) {
   *r = (w128)((u128)a * (u128)b);
-  if ((w128)(w64)a == a && (w128)(w64)b == b) return false;
+  if (fits64(a) && fits64(b)) return false;
   if (a == 0 || b == 0) return false;
-  const u128 ua = a < 0 ? (u128)0 - (u128)a : (u128)a, ub = b < 0 ? (u128)0 - (u128)b : (u128)b;
-  const int n = qbits(ua) + qbits(ub);
+  const u128 ua = uabs(a), ub = uabs(b);
+  const int n = bitlen(ua) + bitlen(ub);
   if (n <= 127) return false;
   if (n >= 130) return true;
   const bool neg = (a < 0) != (b < 0);
@@ -80,53 +62,14 @@ __device__ __noinline__ u64 umod_wide(u64 a, u64 b) { return a % b; }
 __device__ __noinline__ u64 udiv_wide(u64 a, u64 b) { return a / b; }
 __device__ __forceinline__ u64 qumod(u64 a, u64 b) { return ((a | b) >> 32) ? umod_wide(a, b) : (u64)((unsigned)a % (unsigned)b); }
 __device__ __forceinline__ u64 qudiv(u64 a, u64 b) { return ((a | b) >> 32) ? udiv_wide(a, b) : (u64)((unsigned)a / (unsigned)b); }
-// 128 / 128 -> quotient and remainder, shift and subtract over the difference of the bit lengths (operands that fit 64
-// bits take the 64-bit routines)
-__device__ __noinline__ u128 udivmod_wide(u128 a, u128 b, u128 *rem) {
-  u128 q = 0;
-  if (b != 0 && a >= b) {
-    int sh = qbits(a) - qbits(b);
-    u128 d = b << sh;
-    for (; sh >= 0; sh--) {
-      q <<= 1;
-      if (a >= d) {
-        a -= d;
-        q |= 1;
-      }
-      d >>= 1;
-    }
-  }
-  *rem = a;
-  return q;
-}
+// 128 / 128: operands that fit 64 bits take the 64-bit routines, wider ones the shared shift-and-subtract division
 __device__ __forceinline__ u128 qumod(u128 a, u128 b) {
   if (((a | b) >> 64) == 0) return (u128)qumod((u64)a, (u64)b);
-  u128 r;
-  udivmod_wide(a, b, &r);
-  return r;
+  return udivmod<false>(a, b).r;
 }
 __device__ __forceinline__ u128 qudiv(u128 a, u128 b) {
   if (((a | b) >> 64) == 0) return (u128)qudiv((u64)a, (u64)b);
-  u128 r;
-  return udivmod_wide(a, b, &r);
-}
-__device__ __forceinline__ double qdouble(w64 x) { return (double)x; }
-__device__ __forceinline__ double qdouble(w128 x) {
-  const u128 m = x < 0 ? (u128)0 - (u128)x : (u128)x;  // via the magnitude: hi*2^64 + lo on a negative value would cancel
-  const double d = (double)(u64)(m >> 64) * 18446744073709551616.0 + (double)(u64)m;
-  return x < 0 ? -d : d;
-}
-// inverse of an odd number modulo 2^64 / 2^128 (Newton: 3 correct bits, doubled by every step)
-__device__ __forceinline__ u64 qinv(u64 od) {
-  u64 inv = od;
-#pragma unroll
-  for (int q = 0; q < 5; q++) inv *= 2 - od * inv;
-  return inv;
-}
-__device__ __forceinline__ u128 qinv(u128 od) {
-  u128 inv = (u128)qinv((u64)od);
-  inv *= 2 - od * inv;
-  return inv;
+  return udivmod<false>(a, b).q;
 }
 
 enum { F_UNIT = 1, F_PLUS = 2, F_MINUS = 4, F_ZERO = 8, F_CRITIC = 16, F_UNKNOWN = 32 };
@@ -185,7 +128,7 @@ struct Wv {
 
 #define BAD(w) (__any((w).bad) != 0)
 static __device__ __forceinline__ void wsync() { __syncthreads(); }  // one wave per workgroup: orders its LDS traffic
-static __device__ __forceinline__ i64 bcast(i64 x, int src) { return qshfl(x, src); }
+static __device__ __forceinline__ i64 bcast(i64 x, int src) { return shfl(x, src); }
 static __device__ __forceinline__ int popc64(u64 m) { return __popcll(m); }
 static __device__ __forceinline__ int first64(u64 m) { return __ffsll((long long)m) - 1; }
 
@@ -244,12 +187,12 @@ static __device__ __forceinline__ void only_col(u64 (&m)[NB], int j) {
 }
 // lane j < nparm: column nvar + 1 + j (a row's parameter part; nvar + 1 + nparm <= 64 NB)
 static __device__ __forceinline__ i64 parm_part(const i64 (&v)[NB], int nvar, int lane) {
-  if constexpr (NB == 1) return qshfl(v[0], (lane + nvar + 1) & 63);
+  if constexpr (NB == 1) return shfl(v[0], (lane + nvar + 1) & 63);
   const int src = lane + nvar + 1;
   i64 r = 0;
 #pragma unroll
   for (int b = 0; b < NB; b++) {
-    const i64 x = qshfl(v[b], src & 63);
+    const i64 x = shfl(v[b], src & 63);
     if ((src >> 6) == b) r = x;
   }
   return r;
@@ -273,7 +216,7 @@ static __device__ __forceinline__ i64 csub(i64 a, i64 b, int &bad) {
 static __device__ __forceinline__ i64 cneg(i64 a, int &bad) { return csub(0, a, bad); }
 static __device__ __forceinline__ bool fits32(i64 a) { return a == (i64)(int)a; }
 static __device__ __forceinline__ i64 mul32(i64 a, i64 b) { return (i64)((w64)(int)a * (w64)(int)b); }
-static __device__ __forceinline__ uE uabs(i64 a) { return a < 0 ? (uE)0 - (uE)a : (uE)a; }
+static __device__ __forceinline__ uE uabs(i64 a) { return ::uabs(a); }
 static __device__ __forceinline__ uE umod(uE a, uE b) { return qumod(a, b); }
 static __device__ __forceinline__ uE udiv(uE a, uE b) { return qudiv(a, b); }
 // integrer.c:43-50 on true integers: gcd(|a|, |b|)
@@ -311,24 +254,10 @@ static __device__ __forceinline__ i64 floordiv(i64 a, i64 b, int &bad) { return 
 // integrer.c:51-59: bit length of |x|, 1 for 0
 static __device__ __forceinline__ int blen(i64 x) {
   const uE u = uabs(x);
-  return u ? qbits(u) : 1;
+  return u ? bitlen(u) : 1;
 }
 static __device__ __forceinline__ int sgn_flag(i64 x) { return x < 0 ? F_MINUS : (x > 0 ? F_PLUS : F_ZERO); }
 
-static __device__ __forceinline__ int wave_max_i(int x) {
-  for (int o = 32; o; o >>= 1) {
-    const int y = __shfl_xor(x, o);
-    x = x > y ? x : y;
-  }
-  return x;
-}
-static __device__ __forceinline__ int wave_min_i(int x) {
-  for (int o = 32; o; o >>= 1) {
-    const int y = __shfl_xor(x, o);
-    x = x < y ? x : y;
-  }
-  return x;
-}
 static __device__ __forceinline__ float wave_min_f(float x) {
   for (int o = 32; o; o >>= 1) {
     const float y = __shfl_xor(x, o);
@@ -416,9 +345,6 @@ static __device__ __noinline__ int classify_rows(Tab t, int nvar, int ncol, int 
 
 // traiter.c:556-623 tab_sort_rows: selection sort of the real rows nvar..nligne-1 by
 // max |trunc(coefficient / denominator)| over the unknowns (float keys, the reference's types)
-static __device__ __forceinline__ int trunc_x86(double t) {
-  return (!(t > -2147483649.0 && t < 2147483648.0)) ? (int)0x80000000 : (int)t;
-}
 static __device__ __forceinline__ int rdlane(int x, int l) { return __builtin_amdgcn_readlane(x, l); }
 // tab_sort_rows for 65 ... 128 rows to sort (round 4): the same selection sort -- the first row at or after i with the
 // smallest key strictly below the maximum is swapped into place i, traiter.c:591-614 -- with two rows per lane and the rows'
@@ -451,9 +377,9 @@ static __device__ __noinline__ int sort_rows_tall(Tab t, int nvar, int nligne, i
             s = s > a ? s : a;
           }
         } else {
-          const double d = qdouble(dn);
+          const double d = to_double(dn);
           for (int j = 0; j < nvar; j++) {
-            const int q = trunc_x86(qdouble(r[j]) / d);
+            const int q = trunc_x86(to_double(r[j]) / d);
             const int a = q < 0 ? (int)(0u - (unsigned)q) : q;
             s = s > a ? s : a;
           }
@@ -463,7 +389,7 @@ static __device__ __noinline__ int sort_rows_tall(Tab t, int nvar, int nligne, i
     sv[h] = s;
     rl[h] = real;
     realm[h] = __ballot(real);
-    const int m = wave_max_i(real ? s : 0);
+    const int m = wave_max(real ? s : 0);
     smx = m > smx ? m : smx;
     if (r0 < n) skey[r0] = __float_as_int((float)(double)s);  // non-negative floats order like their bit patterns
     if (pos && r0 < n) pos[r0] = (unsigned char)(real ? r0 : 0);
@@ -480,7 +406,7 @@ static __device__ __noinline__ int sort_rows_tall(Tab t, int nvar, int nligne, i
     const u64 c1 = hi == 0 ? below[1] : below[1] & ~((1ull << bi) - 1);
     if (!(c0 | c1)) break;
     const int k0 = ((c0 >> lane) & 1) ? skey[lane] : 0x7fffffff, k1 = ((c1 >> lane) & 1) ? skey[64 + lane] : 0x7fffffff;
-    const int best = wave_min_i(k0 < k1 ? k0 : k1);
+    const int best = wave_min(k0 < k1 ? k0 : k1);
     const u64 m0 = __ballot(k0 == best && ((c0 >> lane) & 1)), m1 = __ballot(k1 == best && ((c1 >> lane) & 1));
     const int p = m0 ? first64(m0) : 64 + first64(m1);
     if (p == i) continue;
@@ -557,9 +483,9 @@ static __device__ __noinline__ int sort_rows(Tab t, int nvar, int nligne, int la
         s = s > a ? s : a;
       }
     } else {
-      const double d = qdouble(dn);
+      const double d = to_double(dn);
       for (int j = 0; j < nvar; j++) {
-        const int q = trunc_x86(qdouble(r[j]) / d);
+        const int q = trunc_x86(to_double(r[j]) / d);
         const int a = q < 0 ? (int)(0u - (unsigned)q) : q;  // abs() incl. INT_MIN
         s = s > a ? s : a;  // (double)INT_MIN never wins against s >= 0
       }
@@ -593,7 +519,7 @@ static __device__ __noinline__ int sort_rows(Tab t, int nvar, int nligne, int la
     {  // rows i and p trade places (traiter.c:604-612)
       const int f_i = rdlane(fl, i), f_p = rdlane(fl, p), r_i = rdlane(rf, i), r_p = rdlane(rf, p);
       const int k_i = rdlane(kb, i), k_p = rdlane(kb, p), o_i = rdlane(oi, i), o_p = rdlane(oi, p);
-      const i64 dn_i = qrdlane(dn, i), dn_p = qrdlane(dn, p);
+      const i64 dn_i = readlane(dn, i), dn_p = readlane(dn, p);
       if (lane == i) {
         fl = f_p;
         rf = r_p;
@@ -806,9 +732,10 @@ static __device__ __noinline__ int pivot_step(Tab t, int pivi, int nvar, int nco
       }
       if (__ballot(act && G != 1)) {
         // exact division by G = 2^tz * odd: shift, then multiply by the inverse of the odd part modulo 2^64
-        const int tz = qctz(G);
+        // (a lane out of the division holds any G, 0 too: the top bit keeps it in ctz's domain and moves no other count)
+        const int tz = ctz(G | (uE)1 << (8 * sizeof(uE) - 1));
         const uE od = G >> tz;
-        const uE inv = qinv(od);
+        const uE inv = inv_odd(od);
         const bool dv = act && G != 1;
 #pragma unroll 4
         for (int j = 0; j < ncol; j++)
@@ -1585,7 +1512,7 @@ __global__ __launch_bounds__(64) void pip_quast_probe_kernel(int fn, const w64 *
     case 4: r = K::floordiv(a[0], a[1], bad); break;
     case 5: r = (QI)qudiv((U)a[0], (U)a[1]); break;
     case 6: r = (QI)qumod((U)a[0], (U)a[1]); break;
-    case 7: r = (QI)qinv((U)a[0]); break;
+    case 7: r = (QI)inv_odd((U)a[0]); break;
     case 8: r = K::blen(a[0]); break;
     case 9: r = K::cmul(a[0], a[1], bad); break;
     case 10: r = K::cadd(a[0], a[1], bad); break;

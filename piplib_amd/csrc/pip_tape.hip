@@ -22,54 +22,16 @@
 
 #include "../../include/piplib_amd.h"
 #include "pip_tape.h"
+#include "pip_wide.h"
 
 namespace {
-typedef long long i64;
-typedef unsigned long long u64;
-typedef __int128 i128;
-typedef unsigned __int128 u128;
-
 enum { END = 0x7fffffff };
 
-__device__ __forceinline__ bool fits64(i128 v) { return (i128)(i64)v == v; }
-__device__ __forceinline__ u128 uabs(i128 v) { return v < 0 ? (u128)0 - (u128)v : (u128)v; }
-__device__ __forceinline__ int ubits(u128 u) {
-  const u64 h = (u64)(u >> 64), l = (u64)u;
-  return h ? 128 - __clzll((i64)h) : (l ? 64 - __clzll((i64)l) : 0);
-}
-// a / b and a % b, b > 0: operands of 64 bits divide natively, wider ones by shift and subtract over the difference of
-// the bit lengths.  64-bit division is a long sequence: one copy, out of line, values in registers both ways.
-struct DivMod {
-  u128 q, r;
-};
-__device__ __noinline__ DivMod udivmod(u128 a, u128 b) {
-  DivMod o;
-  if (((a | b) >> 64) == 0) {
-    const u64 q = (u64)a / (u64)b;
-    o.q = q;
-    o.r = (u64)a - q * (u64)b;
-    return o;
-  }
-  u128 q = 0;
-  if (a >= b) {
-    int sh = ubits(a) - ubits(b);
-    u128 d = b << sh;
-    for (; sh >= 0; sh--) {
-      q <<= 1;
-      if (a >= d) {
-        a -= d;
-        q |= 1;
-      }
-      d >>= 1;
-    }
-  }
-  o.q = q;
-  o.r = a;
-  return o;
-}
+// a / b and a % b, b > 0: the shared division with the native 64-bit path inside (one copy, out of line)
+__device__ __forceinline__ PipDivMod tape_divmod(u128 a, u128 b) { return udivmod<true>(a, b); }
 __device__ __forceinline__ u128 ugcd(u128 x, u128 y) {  // gcd(0, y) = y
   while (y) {
-    const u128 r = udivmod(x, y).r;
+    const u128 r = tape_divmod(x, y).r;
     x = y;
     y = r;
   }
@@ -171,7 +133,7 @@ __device__ __forceinline__ FormValue form_value(const i64 *f, int P, const i64 *
 // floor(v / D), D > 0; false where it does not fit T
 template <class T>
 __device__ __forceinline__ bool floor_div(i128 v, T D, T *q) {
-  const DivMod d = udivmod(uabs(v), (u128)D);
+  const PipDivMod d = tape_divmod(uabs(v), (u128)D);
   const bool neg = v < 0;
   const u128 uq = d.q + (neg && d.r ? 1 : 0);
   if (!Width<T>::fits(uq, neg)) return false;
@@ -183,21 +145,13 @@ __device__ __forceinline__ bool floor_div(i128 v, T D, T *q) {
 template <class T>
 __device__ __forceinline__ bool lowest_terms(i128 N, bool flip, T D, T *num, T *den) {
   const u128 mag = uabs(N), g = ugcd(mag, (u128)D);
-  const u128 qn = udivmod(mag, g).q, qd = udivmod((u128)D, g).q;
+  const u128 qn = tape_divmod(mag, g).q, qd = tape_divmod((u128)D, g).q;
   const bool neg = flip ? N > 0 : N < 0;
   if (flip && mag == ((u128)1 << 127)) return false;
   if (!Width<T>::fits(qn, neg)) return false;
   *num = neg ? (T)((u128)0 - qn) : (T)qn;
   *den = (T)qd;
   return true;
-}
-
-__device__ __forceinline__ int wave_min(int x) {
-  for (int o = 32; o; o >>= 1) {
-    const int y = __shfl_xor(x, o);
-    x = y < x ? y : x;
-  }
-  return __builtin_amdgcn_readfirstlane(x);
 }
 
 // The results of a launch, and where a point's go: unknown i of point pt is value pt * xs + i, dual value i is
@@ -220,7 +174,7 @@ __device__ __forceinline__ void tape_walk(const i64 *prog, int pc, i64 *S, int t
   typedef Width<T> W;
   constexpr int EW = W::EW;
   for (;;) {
-    const int cur = wave_min(pc);
+    const int cur = __builtin_amdgcn_readfirstlane(wave_min(pc));
     if (cur == END) break;
     const i64 hdr = prog[cur];
     const int op = (int)(hdr & 0xff), P = (int)((hdr >> 8) & 0xffff), aux = (int)(hdr >> 32);

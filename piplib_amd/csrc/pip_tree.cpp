@@ -31,6 +31,7 @@
 #include "pip_m2t.h"
 #include "pip_quast.h"
 #include "pip_tree_steps.h"
+#include "pip_wide.h"
 
 using namespace pip_steps;  // the integer helpers, CellT, CtxT and the formulas both trees share
 
@@ -520,7 +521,6 @@ class TreeT {
   // tab_sort_rows' bookkeeping for the dual (traiter.c:556-623): where each inequality of this
   // call's tableau ends up after the sort the kernel is about to do.  Replayed on the host from
   // a snapshot (same keys, same selection sort); rows do not move afterwards.
-  static int trunc_x86(double t) { return (!(t > -2147483649.0 && t < 2147483648.0)) ? (int)0x80000000 : (int)t; }
   std::vector<int> dual_positions(const HostJob &job, int nvar, int ni) {
     Snap s = download(job);
     const int nligne = nvar + ni;

@@ -12,21 +12,23 @@
 #include <vector>
 
 #include "pip_job.h"
+#include "pip_wide.h"
 
 namespace pip_steps {
 
-typedef long long i64;
-typedef unsigned long long u64;
+using ::i64;
+using ::u64;
+using ::i128;
 
 // ---- wrap-around integer helpers (piplib.h:128-169, integrer.c:43-74), host side, for both
 // entry widths: E = long long (the reference's int64 build) or __int128 (the overflow-safe one)
-typedef __int128 i128;
 template <class E> struct UT;
 template <> struct UT<i64> { typedef u64 type; };
-template <> struct UT<i128> { typedef unsigned __int128 type; };
-template <class E> inline E wadd(E a, E b) { return (E)((typename UT<E>::type)a + (typename UT<E>::type)b); }
-template <class E> inline E wsub(E a, E b) { return (E)((typename UT<E>::type)a - (typename UT<E>::type)b); }
-template <class E> inline E wneg(E a) { return (E)((typename UT<E>::type)0 - (typename UT<E>::type)a); }
+template <> struct UT<i128> { typedef u128 type; };
+using ::wadd;  // pip_wide.h's wrap-around overloads for both widths
+using ::wsub;
+using ::wneg;
+using ::wmul;
 template <class E> inline E wabs(E a) { return a < 0 ? wneg(a) : a; }
 template <class E> inline E crem(E a, E b) { return (b == 0 || b == -1) ? (E)0 : a % b; }
 template <class E> inline E cquo(E a, E b) { return b == 0 ? (E)0 : (b == -1 ? wneg(a) : a / b); }
@@ -44,7 +46,6 @@ template <class E> inline E fmod_(E a, E b) {
   return m;
 }
 template <class E> inline E floordiv(E a, E b) { return cquo(wsub(a, fmod_(a, b)), b); }
-template <class E> inline E wmul(E a, E b) { return (E)((typename UT<E>::type)a * (typename UT<E>::type)b); }
 template <class E> E bezout(E x, E y, E delta) {  // integrer.c:98-150
   E a = 1, b = 0, c = 0, d = 1, u = y, v = delta;
   for (;;) {
