@@ -12,7 +12,7 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libpipamd.so")
 SOURCES = ["pip_adv_d.hip", "pip_adv_c.hip", "pip_adv_b.hip", "pip_adv_a.hip", "pip_adv_e.hip", "pip_adv_g.hip", "pip_adv_h.hip", "pip_adv_f.hip", "pip_kernels.hip", "pip_quast.hip", "pip_m2t.hip", "pip_tape.hip", "pip_probe.hip", "pip_host.cpp",
            "pip_tree.cpp"]
-HEADERS = ["pip_job.h", "pip_plan.h", "pip_host.h", "pip_quast.h", "pip_m2t.h", "pip_tape.h", "pip_advance.h", "pip_lean.h", "pip_adv_inst.h", "pip_tree_steps.h", "pip_wide.h", os.path.join("..", "..", "include", "piplib_amd.h")]
+HEADERS = ["pip_job.h", "pip_plan.h", "pip_host.h", "pip_source.h", "pip_quast.h", "pip_m2t.h", "pip_tape.h", "pip_advance.h", "pip_lean.h", "pip_adv_inst.h", "pip_tree_steps.h", "pip_wide.h", os.path.join("..", "..", "include", "piplib_amd.h")]
 
 
 def needs_build():

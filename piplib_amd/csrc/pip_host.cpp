@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "pip_host.h"
+#include "pip_source.h"
 #include "pip_wide.h"
 
 static thread_local char g_err[512];
@@ -147,8 +148,10 @@ struct BatchView {
   long long *arena;
 };
 
-static int batch_view(const char *who, const pipamd_engine *e, const void *d_ws, const pipamd_batch_desc *d, int first, int count,
-                      BatchView *v) {
+// (batch_view without the device: an empty part of a front end is checked like any other, then launches nothing and makes
+// no HIP call)
+static int part_view(const char *who, const pipamd_engine *e, const void *d_ws, const pipamd_batch_desc *d, int first, int count,
+                     BatchView *v) {
   if (!e || !d_ws || !d) {
     pipamd_set_error("%s: null engine, workspace or descriptor", who);
     return PIPAMD_E_INVALID;
@@ -160,10 +163,16 @@ static int batch_view(const char *who, const pipamd_engine *e, const void *d_ws,
     pipamd_set_error("%s_part: tableaux %d..%d outside the batch of %d", who, first, first + count, v->lay.batch);
     return PIPAMD_E_INVALID;
   }
-  if (hipSetDevice(e->device) != hipSuccess) return PIPAMD_E_HIP;  // HIP's current device is per host thread
   v->jobs = (PipJob *)d_ws;
   v->arena = (long long *)((char *)d_ws + jb);
   return PIPAMD_OK;
+}
+
+static int batch_view(const char *who, const pipamd_engine *e, const void *d_ws, const pipamd_batch_desc *d, int first, int count,
+                      BatchView *v) {
+  int rc = part_view(who, e, d_ws, d, first, count, v);
+  if (rc) return rc;
+  return hipSetDevice(e->device) == hipSuccess ? PIPAMD_OK : PIPAMD_E_HIP;  // HIP's current device is per host thread
 }
 
 extern "C" int pipamd_batch_load_part(pipamd_engine *e, void *d_ws, const pipamd_batch_desc *d, const int64_t *d_rows,
@@ -669,48 +678,36 @@ extern "C" int pipamd_batch_results(pipamd_engine *e, const void *d_ws, const pi
   return PIPAMD_OK;
 }
 
-// Maximize / Urs_unknowns for the batch layer (header comment: include/piplib_amd.h).  Everything is checked before the
-// first HIP call; the one launch goes on `stream` and nothing here waits for it.
-static int shifted_check(const char *who, const void *e, const void *d_ws, const pipamd_batch_desc *d, int shift) {
-  if (!e || !d_ws || !d) {
-    pipamd_set_error("%s: null engine, workspace or descriptor", who);
-    return PIPAMD_E_INVALID;
-  }
-  if (shift != PIPAMD_SHIFT_MAX && shift != PIPAMD_SHIFT_URS) {
-    pipamd_set_error("%s: shift must be PIPAMD_SHIFT_MAX (1) or PIPAMD_SHIFT_URS (-1), not %d", who, shift);
-    return PIPAMD_E_INVALID;
-  }
-  if (d->nparm != 1 || d->bigparm != d->nvar + 1) {
-    pipamd_set_error("%s: the descriptor must describe the shifted tableau (nparm == 1, bigparm == nvar + 1)", who);
-    return PIPAMD_E_INVALID;
-  }
-  return PIPAMD_OK;
-}
-
-// the load from a plain system whose description has been checked (`eq`: its equalities as a mask)
-// (`mk` instead: the systems carry their markers and row counts, pipamd_batch_load_matrices)
-static int load_system(const char *who, pipamd_engine *e, void *d_ws, const pipamd_batch_desc *d, const pipamd_system *sys,
-                       const PipEqMask *eq, const PipEqMarkers *mk, const int64_t *d_rows, int first, int count, void *stream) {
+// The batch layer's front ends (header comments: include/piplib_amd.h): the tableau's dual, Maximize / Urs_unknowns, pip_solve's
+// plain system, PolyLib matrices, sparse rows and the instances of one parametric system, each as a load and a dual entry,
+// whole and _part.  An entry runs its form's check (pip_source.h), which fills the PipBatchSource, then load_from or
+// dual_from.  Everything is checked before the first HIP call; the one launch goes on `stream` and nothing here waits for it.
+static int load_from(const char *who, pipamd_engine *e, void *d_ws, const pipamd_batch_desc *d, const PipBatchSource *src,
+                     int first, int count, void *stream) {
   BatchView v;
-  int rc = batch_view(who, e, d_ws, d, first, count, &v);
-  if (rc) return rc;
-  HIPCHK(pipk_launch_batch_load_system(v.jobs, v.arena, (const long long *)d_rows, v.lay, sys->shift, sys->simplify, sys->nrows,
-                                       eq, mk, first, count, (hipStream_t)stream));
+  int rc = (count ? batch_view : part_view)(who, e, d_ws, d, first, count, &v);
+  if (rc || count == 0) return rc;
+  HIPCHK(pipk_launch_batch_load_source(v.jobs, v.arena, v.lay, src, first, count, (hipStream_t)stream));
   return PIPAMD_OK;
 }
 
-// the shifted load is the load of a system without equalities, not simplified
+static int dual_from(const char *who, pipamd_engine *e, const void *d_ws, const pipamd_batch_desc *d, const PipBatchSource *src,
+                     int first, int count, int64_t *d_dual_num, int64_t *d_dual_den, void *stream) {
+  int rc = dual_check(who, d, src, d_dual_num, d_dual_den);
+  if (rc) return rc;
+  BatchView v;
+  rc = (count ? batch_view : part_view)(who, e, d_ws, d, first, count, &v);
+  if (rc || count == 0) return rc;
+  HIPCHK(pipk_launch_batch_dual_source(v.jobs, v.arena, v.lay, src, first, count, (void *)d_dual_num, (void *)d_dual_den,
+                                       (hipStream_t)stream));
+  return PIPAMD_OK;
+}
+
 extern "C" int pipamd_batch_load_shifted_part(pipamd_engine *e, void *d_ws, const pipamd_batch_desc *d, const int64_t *d_rows,
                                               int shift, int first, int count, void *stream) {
-  int rc = shifted_check("batch_load_shifted", e, d_ws, d, shift);
-  if (rc) return rc;
-  if (!d_rows) {
-    pipamd_set_error("batch_load_shifted: null rows pointer");
-    return PIPAMD_E_INVALID;
-  }
-  const pipamd_system sys = {d->ni, 0, nullptr, shift, 0};
-  const PipEqMask eq = {};
-  return load_system("batch_load_shifted", e, d_ws, d, &sys, &eq, nullptr, d_rows, first, count, stream);
+  PipBatchSource src;
+  int rc = shifted_source("batch_load_shifted", e, d_ws, d, d_rows, shift, &src);
+  return rc ? rc : load_from("batch_load_shifted", e, d_ws, d, &src, first, count, stream);
 }
 
 extern "C" int pipamd_batch_load_shifted(pipamd_engine *e, void *d_ws, const pipamd_batch_desc *d, const int64_t *d_rows, int shift,
@@ -731,49 +728,13 @@ extern "C" int pipamd_batch_results_shifted(pipamd_engine *e, const void *d_ws, 
   return PIPAMD_OK;
 }
 
-// Compute_dual for the batch layer (header comment: include/piplib_amd.h).  Everything is checked before the first HIP
-// call; the one launch goes on `stream` and nothing here waits for it.
-// What both dual entries refuse (`d_rows`: the rows the batch was loaded from).
-static int dual_check(const char *who, const pipamd_batch_desc *d, const void *d_rows, const void *d_dual_num,
-                      const void *d_dual_den) {
-  if (!d || !d_rows || !d_dual_num || !d_dual_den) {
-    pipamd_set_error("%s: null descriptor, rows or output array", who);
-    return PIPAMD_E_INVALID;
-  }
-  if (!(d->tflags & PIPAMD_T_DUAL) || (d->tflags & PIPAMD_T_INT)) {
-    pipamd_set_error("%s: the batch must have been solved with PIPAMD_T_DUAL and without PIPAMD_T_INT (the dual needs a "
-                     "rational solve)", who);
-    return PIPAMD_E_INVALID;
-  }
-  if (d->ni > pipk_batch_dual_max_ni()) {
-    pipamd_set_error("%s: %d inequalities per tableau, the dual kernel sorts at most %d", who, d->ni, pipk_batch_dual_max_ni());
-    return PIPAMD_E_TOOLARGE;
-  }
-  return PIPAMD_OK;
-}
-
-// the launch of a dual entry, its arguments checked; eq == nullptr: the plain one (nrows == d->ni, pairs not reduced);
-// `mk` instead: pipamd_batch_dual_matrices
-static int dual_launch(const char *who, pipamd_engine *e, const void *d_ws, const pipamd_batch_desc *d, int nrows,
-                       const PipEqMask *eq, const PipEqMarkers *mk, const int64_t *d_rows, int first, int count,
-                       int64_t *d_dual_num, int64_t *d_dual_den, void *stream) {
-  BatchView v;
-  int rc = batch_view(who, e, d_ws, d, first, count, &v);
-  if (rc) return rc;
-  HIPCHK(pipk_launch_batch_dual(v.jobs, v.arena, (const long long *)d_rows, v.lay, nrows, eq, mk, first, count,
-                                (void *)d_dual_num, (void *)d_dual_den, (hipStream_t)stream));
-  return PIPAMD_OK;
-}
-
+// Compute_dual of a batch loaded by pipamd_batch_load: the tableau rows are the one source without a check of its own
 extern "C" int pipamd_batch_dual_part(pipamd_engine *e, const void *d_ws, const pipamd_batch_desc *d, const int64_t *d_rows,
                                       int first, int count, int64_t *d_dual_num, int64_t *d_dual_den, void *stream) {
-  int rc = dual_check("batch_dual", d, d_rows, d_dual_num, d_dual_den);
-  if (rc) return rc;
-  if (d->nparm != 0 || d->bigparm >= 0) {
-    pipamd_set_error("batch_dual: nparm must be 0 and bigparm -1 (the batch layer finishes only such batches on its own)");
-    return PIPAMD_E_INVALID;
-  }
-  return dual_launch("batch_dual", e, d_ws, d, d->ni, nullptr, nullptr, d_rows, first, count, d_dual_num, d_dual_den, stream);
+  PipBatchSource src;
+  src.kind = PIP_SRC_TABLEAU;
+  src.rows = d_rows;
+  return dual_from("batch_dual", e, d_ws, d, &src, first, count, d_dual_num, d_dual_den, stream);
 }
 
 extern "C" int pipamd_batch_dual(pipamd_engine *e, const void *d_ws, const pipamd_batch_desc *d, const int64_t *d_rows,
@@ -781,79 +742,11 @@ extern "C" int pipamd_batch_dual(pipamd_engine *e, const void *d_ws, const pipam
   return pipamd_batch_dual_part(e, d_ws, d, d_rows, 0, d ? d->batch : 0, d_dual_num, d_dual_den, stream);
 }
 
-// pip_solve's plain system for the batch layer (header comment: include/piplib_amd.h): equalities, tab_simplify and the
-// dual as pip_solve hands it out.  Everything is checked before the first HIP call, the caller's equality list is read
-// into a mask that travels with the launch, and nothing here waits for the stream.
-// What the system and the matrices entries refuse alike: null pointers (`desc`: the system or matrices description), the
-// shift and the descriptor against it ...
-static int plain_check(const char *who, const void *e, const void *d_ws, const pipamd_batch_desc *d, const void *desc,
-                       const void *d_rows, int shift) {
-  if (!e || !d_ws || !d || !desc || !d_rows) {
-    pipamd_set_error("%s: null engine, workspace, descriptor, system or rows pointer", who);
-    return PIPAMD_E_INVALID;
-  }
-  if (shift != 0 && shift != PIPAMD_SHIFT_MAX && shift != PIPAMD_SHIFT_URS) {
-    pipamd_set_error("%s: shift must be 0, PIPAMD_SHIFT_MAX (1) or PIPAMD_SHIFT_URS (-1), not %d", who, shift);
-    return PIPAMD_E_INVALID;
-  }
-  if (shift ? (d->nparm != 1 || d->bigparm != d->nvar + 1) : (d->nparm != 0 || d->bigparm != -1)) {
-    pipamd_set_error("%s: the descriptor must describe the tableau as it is solved (shift 0: nparm == 0, bigparm == -1; "
-                     "otherwise nparm == 1, bigparm == nvar + 1)", who);
-    return PIPAMD_E_INVALID;
-  }
-  return PIPAMD_OK;
-}
-
-// ... and simplify
-static int simplify_check(const char *who, const pipamd_batch_desc *d, int simplify) {
-  if (simplify != 0 && simplify != 1) {
-    pipamd_set_error("%s: simplify must be 0 or 1, not %d", who, simplify);
-    return PIPAMD_E_INVALID;
-  }
-  if (simplify && !(d->tflags & PIPAMD_T_INT)) {
-    pipamd_set_error("%s: simplify without PIPAMD_T_INT (pip_solve simplifies integer problems only)", who);
-    return PIPAMD_E_INVALID;
-  }
-  return PIPAMD_OK;
-}
-
-static int system_check(const char *who, const void *e, const void *d_ws, const pipamd_batch_desc *d, const pipamd_system *sys,
-                        const void *d_rows, PipEqMask *eq) {
-  int rc = plain_check(who, e, d_ws, d, sys, d_rows, sys ? sys->shift : 0);
-  if (rc) return rc;
-  if (sys->nrows < 0 || sys->neq < 0 || sys->neq > sys->nrows || d->ni != sys->nrows + sys->neq) {
-    pipamd_set_error("%s: %d rows with %d equalities do not make the descriptor's %d inequalities", who, sys->nrows, sys->neq,
-                     d->ni);
-    return PIPAMD_E_INVALID;
-  }
-  if (sys->nrows > PIPAMD_SMAX) {
-    pipamd_set_error("%s: %d rows, the engine holds at most %d", who, sys->nrows, PIPAMD_SMAX);
-    return PIPAMD_E_TOOLARGE;
-  }
-  if (sys->neq > 0 && !sys->eq_rows) {
-    pipamd_set_error("%s: %d equalities and no list of them", who, sys->neq);
-    return PIPAMD_E_INVALID;
-  }
-  rc = simplify_check(who, d, sys->simplify);
-  if (rc) return rc;
-  memset(eq, 0, sizeof *eq);
-  for (int i = 0; i < sys->neq; i++) {
-    const int r = sys->eq_rows[i];
-    if (r < 0 || r >= sys->nrows || (i > 0 && r <= sys->eq_rows[i - 1])) {
-      pipamd_set_error("%s: eq_rows[%d] = %d is out of range or not above its predecessor", who, i, r);
-      return PIPAMD_E_INVALID;
-    }
-    eq->w[r >> 6] |= (uint64_t)1 << (r & 63);
-  }
-  return PIPAMD_OK;
-}
-
 extern "C" int pipamd_batch_load_system_part(pipamd_engine *e, void *d_ws, const pipamd_batch_desc *d, const pipamd_system *sys,
                                              const int64_t *d_rows, int first, int count, void *stream) {
-  PipEqMask eq;
-  int rc = system_check("batch_load_system", e, d_ws, d, sys, d_rows, &eq);
-  if (rc) return rc;
-  return load_system("batch_load_system", e, d_ws, d, sys, &eq, nullptr, d_rows, first, count, stream);
+  PipBatchSource src;
+  int rc = system_check("batch_load_system", e, d_ws, d, sys, d_rows, &src);
+  return rc ? rc : load_from("batch_load_system", e, d_ws, d, &src, first, count, stream);
 }
 
 extern "C" int pipamd_batch_load_system(pipamd_engine *e, void *d_ws, const pipamd_batch_desc *d, const pipamd_system *sys,
@@ -864,13 +757,9 @@ extern "C" int pipamd_batch_load_system(pipamd_engine *e, void *d_ws, const pipa
 extern "C" int pipamd_batch_dual_system_part(pipamd_engine *e, const void *d_ws, const pipamd_batch_desc *d,
                                              const pipamd_system *sys, const int64_t *d_rows, int first, int count,
                                              int64_t *d_dual_num, int64_t *d_dual_den, void *stream) {
-  PipEqMask eq;
-  int rc = system_check("batch_dual_system", e, d_ws, d, sys, d_rows, &eq);
-  if (rc) return rc;
-  rc = dual_check("batch_dual_system", d, d_rows, d_dual_num, d_dual_den);
-  if (rc) return rc;
-  return dual_launch("batch_dual_system", e, d_ws, d, sys->nrows, &eq, nullptr, d_rows, first, count, d_dual_num, d_dual_den,
-                     stream);
+  PipBatchSource src;
+  int rc = system_check("batch_dual_system", e, d_ws, d, sys, d_rows, &src);
+  return rc ? rc : dual_from("batch_dual_system", e, d_ws, d, &src, first, count, d_dual_num, d_dual_den, stream);
 }
 
 extern "C" int pipamd_batch_dual_system(pipamd_engine *e, const void *d_ws, const pipamd_batch_desc *d, const pipamd_system *sys,
@@ -878,35 +767,11 @@ extern "C" int pipamd_batch_dual_system(pipamd_engine *e, const void *d_ws, cons
   return pipamd_batch_dual_system_part(e, d_ws, d, sys, d_rows, 0, d ? d->batch : 0, d_dual_num, d_dual_den, stream);
 }
 
-// The plain system as sparse rows (header comment: include/piplib_amd.h): the system entries' checks on `sys` and the
-// descriptor, with the row pointers in the place of the rows; what the arrays hold is checked on the device.
-static int sparse_check(const char *who, const void *e, const void *d_ws, const pipamd_batch_desc *d, const pipamd_sparse *s,
-                        PipEqMask *eq, PipCsrRows *cs) {
-  int rc = system_check(who, e, d_ws, d, s ? &s->sys : nullptr, s ? s->d_row_ptr : nullptr, eq);
-  if (rc) return rc;
-  if (s->nnz < 0 || (s->nnz > 0 && (!s->d_cols || !s->d_vals))) {
-    pipamd_set_error("%s: nnz (%lld) below 0, or entries without a column or a value array", who, (long long)s->nnz);
-    return PIPAMD_E_INVALID;
-  }
-  cs->row_ptr = s->d_row_ptr;
-  cs->cols = s->d_cols;
-  cs->vals = s->d_vals;
-  cs->nnz = s->nnz;
-  return PIPAMD_OK;
-}
-
 extern "C" int pipamd_batch_load_sparse_part(pipamd_engine *e, void *d_ws, const pipamd_batch_desc *d, const pipamd_sparse *s,
                                              int first, int count, void *stream) {
-  PipEqMask eq;
-  PipCsrRows cs;
-  int rc = sparse_check("batch_load_sparse", e, d_ws, d, s, &eq, &cs);
-  if (rc) return rc;
-  BatchView v;
-  rc = batch_view("batch_load_sparse", e, d_ws, d, first, count, &v);
-  if (rc) return rc;
-  HIPCHK(pipk_launch_batch_load_sparse(v.jobs, v.arena, &cs, v.lay, s->sys.shift, s->sys.simplify, s->sys.nrows, &eq, first, count,
-                                       (hipStream_t)stream));
-  return PIPAMD_OK;
+  PipBatchSource src;
+  int rc = sparse_check("batch_load_sparse", e, d_ws, d, s, &src);
+  return rc ? rc : load_from("batch_load_sparse", e, d_ws, d, &src, first, count, stream);
 }
 
 extern "C" int pipamd_batch_load_sparse(pipamd_engine *e, void *d_ws, const pipamd_batch_desc *d, const pipamd_sparse *s,
@@ -916,18 +781,9 @@ extern "C" int pipamd_batch_load_sparse(pipamd_engine *e, void *d_ws, const pipa
 
 extern "C" int pipamd_batch_dual_sparse_part(pipamd_engine *e, const void *d_ws, const pipamd_batch_desc *d, const pipamd_sparse *s,
                                              int first, int count, int64_t *d_dual_num, int64_t *d_dual_den, void *stream) {
-  PipEqMask eq;
-  PipCsrRows cs;
-  int rc = sparse_check("batch_dual_sparse", e, d_ws, d, s, &eq, &cs);
-  if (rc) return rc;
-  rc = dual_check("batch_dual_sparse", d, cs.row_ptr, d_dual_num, d_dual_den);
-  if (rc) return rc;
-  BatchView v;
-  rc = batch_view("batch_dual_sparse", e, d_ws, d, first, count, &v);
-  if (rc) return rc;
-  HIPCHK(pipk_launch_batch_dual_sparse(v.jobs, v.arena, &cs, v.lay, s->sys.nrows, &eq, first, count, (void *)d_dual_num,
-                                       (void *)d_dual_den, (hipStream_t)stream));
-  return PIPAMD_OK;
+  PipBatchSource src;
+  int rc = sparse_check("batch_dual_sparse", e, d_ws, d, s, &src);
+  return rc ? rc : dual_from("batch_dual_sparse", e, d_ws, d, &src, first, count, d_dual_num, d_dual_den, stream);
 }
 
 extern "C" int pipamd_batch_dual_sparse(pipamd_engine *e, const void *d_ws, const pipamd_batch_desc *d, const pipamd_sparse *s,
@@ -935,41 +791,11 @@ extern "C" int pipamd_batch_dual_sparse(pipamd_engine *e, const void *d_ws, cons
   return pipamd_batch_dual_sparse_part(e, d_ws, d, s, 0, d ? d->batch : 0, d_dual_num, d_dual_den, stream);
 }
 
-// The instances of one parametric system (header comment: include/piplib_amd.h): the system entries' checks on `sys` and
-// the descriptor, with the shared matrix in the place of the rows; the substitution, and whether a system's constants
-// fit the entry type, is the device's business.
-static int instances_check(const char *who, const void *e, const void *d_ws, const pipamd_batch_desc *d, const pipamd_instances *in,
-                           PipEqMask *eq, PipInstanceRows *is) {
-  int rc = system_check(who, e, d_ws, d, in ? &in->sys : nullptr, in ? in->d_matrix : nullptr, eq);
-  if (rc) return rc;
-  if (in->nparm < 0 || in->reserved != 0 || (in->nparm > 0 && !in->d_points)) {
-    pipamd_set_error("%s: nparm (%d) below 0, reserved (%d) not 0, or parameters without an array of points", who, in->nparm,
-                     in->reserved);
-    return PIPAMD_E_INVALID;
-  }
-  if ((int64_t)d->nvar + in->nparm + 1 > PIPAMD_MAXCOL) {
-    pipamd_set_error("%s: a matrix row of %d unknowns, %d parameters and the constant, at most %d columns", who, d->nvar,
-                     in->nparm, PIPAMD_MAXCOL);
-    return PIPAMD_E_TOOLARGE;
-  }
-  is->matrix = in->d_matrix;
-  is->points = in->d_points;
-  is->nparm = in->nparm;
-  return PIPAMD_OK;
-}
-
 extern "C" int pipamd_batch_load_instances_part(pipamd_engine *e, void *d_ws, const pipamd_batch_desc *d, const pipamd_instances *in,
                                                 int first, int count, void *stream) {
-  PipEqMask eq;
-  PipInstanceRows is;
-  int rc = instances_check("batch_load_instances", e, d_ws, d, in, &eq, &is);
-  if (rc) return rc;
-  BatchView v;
-  rc = batch_view("batch_load_instances", e, d_ws, d, first, count, &v);
-  if (rc) return rc;
-  HIPCHK(pipk_launch_batch_load_instances(v.jobs, v.arena, &is, v.lay, in->sys.shift, in->sys.simplify, in->sys.nrows, &eq, first,
-                                          count, (hipStream_t)stream));
-  return PIPAMD_OK;
+  PipBatchSource src;
+  int rc = instances_check("batch_load_instances", e, d_ws, d, in, &src);
+  return rc ? rc : load_from("batch_load_instances", e, d_ws, d, &src, first, count, stream);
 }
 
 extern "C" int pipamd_batch_load_instances(pipamd_engine *e, void *d_ws, const pipamd_batch_desc *d, const pipamd_instances *in,
@@ -980,18 +806,9 @@ extern "C" int pipamd_batch_load_instances(pipamd_engine *e, void *d_ws, const p
 extern "C" int pipamd_batch_dual_instances_part(pipamd_engine *e, const void *d_ws, const pipamd_batch_desc *d,
                                                 const pipamd_instances *in, int first, int count, int64_t *d_dual_num,
                                                 int64_t *d_dual_den, void *stream) {
-  PipEqMask eq;
-  PipInstanceRows is;
-  int rc = instances_check("batch_dual_instances", e, d_ws, d, in, &eq, &is);
-  if (rc) return rc;
-  rc = dual_check("batch_dual_instances", d, is.matrix, d_dual_num, d_dual_den);
-  if (rc) return rc;
-  BatchView v;
-  rc = batch_view("batch_dual_instances", e, d_ws, d, first, count, &v);
-  if (rc) return rc;
-  HIPCHK(pipk_launch_batch_dual_instances(v.jobs, v.arena, &is, v.lay, in->sys.nrows, &eq, first, count, (void *)d_dual_num,
-                                          (void *)d_dual_den, (hipStream_t)stream));
-  return PIPAMD_OK;
+  PipBatchSource src;
+  int rc = instances_check("batch_dual_instances", e, d_ws, d, in, &src);
+  return rc ? rc : dual_from("batch_dual_instances", e, d_ws, d, &src, first, count, d_dual_num, d_dual_den, stream);
 }
 
 extern "C" int pipamd_batch_dual_instances(pipamd_engine *e, const void *d_ws, const pipamd_batch_desc *d, const pipamd_instances *in,
@@ -999,35 +816,11 @@ extern "C" int pipamd_batch_dual_instances(pipamd_engine *e, const void *d_ws, c
   return pipamd_batch_dual_instances_part(e, d_ws, d, in, 0, d ? d->batch : 0, d_dual_num, d_dual_den, stream);
 }
 
-// PolyLib matrices with a row count and markers per system (header comment: include/piplib_amd.h).  Which rows are
-// equalities and how many rows a system has is found on the device; what is left to refuse here is the description.
-static int matrices_check(const char *who, const void *e, const void *d_ws, const pipamd_batch_desc *d, const pipamd_matrices *m,
-                          const void *d_rows, PipEqMarkers *mk) {
-  int rc = plain_check(who, e, d_ws, d, m, d_rows, m ? m->shift : 0);
-  if (rc) return rc;
-  if (m->max_rows < 1 || d->ni < 1 || m->reserved != 0) {
-    pipamd_set_error("%s: max_rows (%d) and the descriptor's ni (%d) must be at least 1, reserved (%d) must be 0", who, m->max_rows,
-                     d->ni, m->reserved);
-    return PIPAMD_E_INVALID;
-  }
-  if (m->max_rows > PIPAMD_SMAX) {
-    pipamd_set_error("%s: %d rows of room per system, the engine holds at most %d", who, m->max_rows, PIPAMD_SMAX);
-    return PIPAMD_E_TOOLARGE;
-  }
-  rc = simplify_check(who, d, m->simplify);
-  if (rc) return rc;
-  mk->nrows = m->d_nrows;
-  mk->max_rows = m->max_rows;
-  return PIPAMD_OK;
-}
-
 extern "C" int pipamd_batch_load_matrices_part(pipamd_engine *e, void *d_ws, const pipamd_batch_desc *d, const pipamd_matrices *m,
                                                const int64_t *d_rows, int first, int count, void *stream) {
-  PipEqMarkers mk;
-  int rc = matrices_check("batch_load_matrices", e, d_ws, d, m, d_rows, &mk);
-  if (rc) return rc;
-  const pipamd_system sys = {m->max_rows, 0, nullptr, m->shift, m->simplify};
-  return load_system("batch_load_matrices", e, d_ws, d, &sys, nullptr, &mk, d_rows, first, count, stream);
+  PipBatchSource src;
+  int rc = matrices_check("batch_load_matrices", e, d_ws, d, m, d_rows, &src);
+  return rc ? rc : load_from("batch_load_matrices", e, d_ws, d, &src, first, count, stream);
 }
 
 extern "C" int pipamd_batch_load_matrices(pipamd_engine *e, void *d_ws, const pipamd_batch_desc *d, const pipamd_matrices *m,
@@ -1038,13 +831,9 @@ extern "C" int pipamd_batch_load_matrices(pipamd_engine *e, void *d_ws, const pi
 extern "C" int pipamd_batch_dual_matrices_part(pipamd_engine *e, const void *d_ws, const pipamd_batch_desc *d,
                                                const pipamd_matrices *m, const int64_t *d_rows, int first, int count,
                                                int64_t *d_dual_num, int64_t *d_dual_den, void *stream) {
-  PipEqMarkers mk;
-  int rc = matrices_check("batch_dual_matrices", e, d_ws, d, m, d_rows, &mk);
-  if (rc) return rc;
-  rc = dual_check("batch_dual_matrices", d, d_rows, d_dual_num, d_dual_den);
-  if (rc) return rc;
-  return dual_launch("batch_dual_matrices", e, d_ws, d, m->max_rows, nullptr, &mk, d_rows, first, count, d_dual_num, d_dual_den,
-                     stream);
+  PipBatchSource src;
+  int rc = matrices_check("batch_dual_matrices", e, d_ws, d, m, d_rows, &src);
+  return rc ? rc : dual_from("batch_dual_matrices", e, d_ws, d, &src, first, count, d_dual_num, d_dual_den, stream);
 }
 
 extern "C" int pipamd_batch_dual_matrices(pipamd_engine *e, const void *d_ws, const pipamd_batch_desc *d, const pipamd_matrices *m,

@@ -103,26 +103,11 @@ hipError_t pipk_launch_batch_results(const PipJob *jobs, const long long *arena,
                                      int ebits, int *status, int *pivots, int *cuts, void *sol_num, void *sol_den,
                                      hipStream_t stream);
 int pipk_batch_dual_max_ni(void); /* inequalities per tableau pip_batch_dual_kernel sorts in LDS */
-/* eq == NULL: pipamd_batch_dual (nrows == lay.ni, pairs not reduced); otherwise pipamd_batch_dual_system.  mk != NULL:
- * pipamd_batch_dual_matrices / pipamd_batch_load_matrices (markers and row counts on the device; nrows, eq not looked at) */
-hipError_t pipk_launch_batch_dual(const PipJob *jobs, const long long *arena, const long long *rows, PipBatchLayout lay,
-                                  int nrows, const PipEqMask *eq, const PipEqMarkers *mk, int first, int count, void *dual_num,
-                                  void *dual_den, hipStream_t stream);
-hipError_t pipk_launch_batch_load_system(PipJob *jobs, long long *arena, const long long *rows, PipBatchLayout lay, int shift,
-                                         int simplify, int nrows, const PipEqMask *eq, const PipEqMarkers *mk, int first,
+/* the load and the dual of the batch layer's front ends, from the one source (pip_job.h) the entry's check has filled */
+hipError_t pipk_launch_batch_load_source(PipJob *jobs, long long *arena, PipBatchLayout lay, const PipBatchSource *src, int first,
                                          int count, hipStream_t stream);
-/* pipamd_batch_load_sparse / pipamd_batch_dual_sparse: the system launches with the rows in the CSR arrays of `cs` */
-hipError_t pipk_launch_batch_load_sparse(PipJob *jobs, long long *arena, const PipCsrRows *cs, PipBatchLayout lay, int shift,
-                                         int simplify, int nrows, const PipEqMask *eq, int first, int count, hipStream_t stream);
-hipError_t pipk_launch_batch_dual_sparse(const PipJob *jobs, const long long *arena, const PipCsrRows *cs, PipBatchLayout lay,
-                                         int nrows, const PipEqMask *eq, int first, int count, void *dual_num, void *dual_den,
-                                         hipStream_t stream);
-/* pipamd_batch_load_instances / pipamd_batch_dual_instances: the system launches with the shared matrix and the points of `is` */
-hipError_t pipk_launch_batch_load_instances(PipJob *jobs, long long *arena, const PipInstanceRows *is, PipBatchLayout lay, int shift,
-                                            int simplify, int nrows, const PipEqMask *eq, int first, int count, hipStream_t stream);
-hipError_t pipk_launch_batch_dual_instances(const PipJob *jobs, const long long *arena, const PipInstanceRows *is, PipBatchLayout lay,
-                                            int nrows, const PipEqMask *eq, int first, int count, void *dual_num, void *dual_den,
-                                            hipStream_t stream);
+hipError_t pipk_launch_batch_dual_source(const PipJob *jobs, const long long *arena, PipBatchLayout lay, const PipBatchSource *src,
+                                         int first, int count, void *dual_num, void *dual_den, hipStream_t stream);
 hipError_t pipk_launch_rehouse(PipJob *jobs, long long *arena, void *const *q5, int grid, PipBatchLayout nl, int *side_count,
                                int side_cap, hipStream_t stream);
 hipError_t pipk_launch_rehouse_finish(PipJob *jobs, long long *arena, int njobs, int sol_words, hipStream_t stream);

@@ -99,6 +99,26 @@ typedef struct PipInstanceRows {
   int32_t nparm;
 } PipInstanceRows;
 
+/* What a batch is loaded from, and what its dual is read against: ONE source, of one kind.  The host's check of an entry
+ * fills it in place (the mask is built where the launch reads it), pipk_launch_batch_load_source / _dual_source turn the
+ * kind into the kernels' (EQ, SRC) and hand those members over by value.  Only the members of the kind mean anything:
+ *   kind      | equalities (EQ) | rows (SRC)            | nrows
+ *   TABLEAU   | none            | `rows`, as loaded     | the layout's ni      (dual only: pipamd_batch_dual)
+ *   DENSE     | `mask`          | `rows`                | the system's         (pipamd_system; the shifted load: empty mask)
+ *   MATRICES  | `markers`       | `rows`, marker first  | markers.max_rows     (pipamd_matrices)
+ *   CSR       | `mask`          | `csr`                 | the system's         (pipamd_sparse)
+ *   INSTANCES | `mask`          | `inst`                | the system's         (pipamd_instances) */
+enum PipSourceKind { PIP_SRC_TABLEAU, PIP_SRC_DENSE, PIP_SRC_MATRICES, PIP_SRC_CSR, PIP_SRC_INSTANCES };
+typedef struct PipBatchSource {
+  int32_t kind;
+  int32_t shift, simplify, nrows; /* (the dual looks at nrows alone) */
+  const int64_t *rows;
+  PipEqMask mask;
+  PipEqMarkers markers;
+  PipCsrRows csr;
+  PipInstanceRows inst;
+} PipBatchSource;
+
 #ifdef __HIPCC__
 #define PIP_HD __host__ __device__
 #else

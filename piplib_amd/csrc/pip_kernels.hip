@@ -841,69 +841,54 @@ __global__ __launch_bounds__(64) void pip_batch_dual_kernel(const PipJob *jobs, 
   }
 }
 
-// mk != nullptr: pipamd_batch_dual_matrices (nrows is not looked at: mk->max_rows pairs a system); otherwise
-// eq == nullptr: pipamd_batch_dual (the caller has checked lay.nparm == 0), or pipamd_batch_dual_system.  cs != nullptr
-// (with eq): the rows are the launch's CSR arrays (pipamd_batch_dual_sparse; rows is not looked at); is != nullptr (with
-// eq): they are those of the launch's shared matrix (pipamd_batch_dual_instances; rows is not looked at)
-static hipError_t launch_batch_dual(const PipJob *jobs, const i64 *arena, const i64 *rows, PipBatchLayout lay, int nrows,
-                                    const PipEqMask *eq, const PipEqMarkers *mk, const PipCsrRows *cs, const PipInstanceRows *is,
-                                    int first, int count, void *dual_num, void *dual_den, hipStream_t stream) {
-  if ((cs || is) && (mk || !eq || (cs && is))) return hipErrorInvalidValue;
-  if (mk) nrows = mk->max_rows;
-  if (count <= 0 || lay.ni <= 0 || nrows <= 0) return hipSuccess;
-  if (lay.ni > PIP_DUAL_MAXNI || (!mk && nrows > lay.ni) || (!mk && !eq && (nrows != lay.ni || lay.nparm != 0)))
-    return hipErrorInvalidValue;
-  const size_t shm = pipk_batch_dual_lds_bytes(lay.ni);
-#define PIP_DUAL(T, EQ, MASK, SRC, ROWS)                                                                                    \
-  hipLaunchKernelGGL((pip_batch_dual_kernel<T, EQ, SRC>), dim3(count), dim3(64), shm, stream, jobs, arena, rows, lay, first, \
-                     nrows, MASK, (T *)dual_num, (T *)dual_den, ROWS)
-  if (lay.ebits == 128) {
-    if (is)
-      PIP_DUAL(i128, PipEqMask, *eq, PipInstanceRows, *is);
-    else if (cs)
-      PIP_DUAL(i128, PipEqMask, *eq, PipCsrRows, *cs);
-    else if (mk)
-      PIP_DUAL(i128, PipEqMarkers, *mk, PipDenseRows, PipDenseRows{});
-    else if (eq)
-      PIP_DUAL(i128, PipEqMask, *eq, PipDenseRows, PipDenseRows{});
-    else
-      PIP_DUAL(i128, PipNoEq, PipNoEq{}, PipDenseRows, PipDenseRows{});
-  } else {
-    if (is)
-      PIP_DUAL(i64, PipEqMask, *eq, PipInstanceRows, *is);
-    else if (cs)
-      PIP_DUAL(i64, PipEqMask, *eq, PipCsrRows, *cs);
-    else if (mk)
-      PIP_DUAL(i64, PipEqMarkers, *mk, PipDenseRows, PipDenseRows{});
-    else if (eq)
-      PIP_DUAL(i64, PipEqMask, *eq, PipDenseRows, PipDenseRows{});
-    else
-      PIP_DUAL(i64, PipNoEq, PipNoEq{}, PipDenseRows, PipDenseRows{});
+// The launches from a PipBatchSource (pip_job.h).  visit_source is the one step from the source's kind to the kernels'
+// (EQ, SRC): f(eq, rs) gets the members of the kind.  TABLEAU is the dual's alone and is left out of the load's visit at
+// compile time (no PipNoEq load kernel is instantiated); the kinds are visited in the kernels' order in this file.
+template <bool DUAL, class F>
+static hipError_t visit_source(const PipBatchSource &s, F &&f) {
+  switch (s.kind) {
+    case PIP_SRC_INSTANCES: return f(s.mask, s.inst);
+    case PIP_SRC_CSR: return f(s.mask, s.csr);
+    case PIP_SRC_MATRICES: return f(s.markers, PipDenseRows{});
+    case PIP_SRC_DENSE: return f(s.mask, PipDenseRows{});
+    case PIP_SRC_TABLEAU:
+      if constexpr (DUAL) return f(PipNoEq{}, PipDenseRows{});
   }
-#undef PIP_DUAL
-  return hipGetLastError();
+  return hipErrorInvalidValue;
 }
 
-extern "C" hipError_t pipk_launch_batch_dual(const PipJob *jobs, const i64 *arena, const i64 *rows, PipBatchLayout lay,
-                                             int nrows, const PipEqMask *eq, const PipEqMarkers *mk, int first, int count,
-                                             void *dual_num, void *dual_den, hipStream_t stream) {
-  return launch_batch_dual(jobs, arena, rows, lay, nrows, eq, mk, nullptr, nullptr, first, count, dual_num, dual_den, stream);
+// What the kernels rely on, per kind, and the entries of pip_host.cpp have checked (with a message) before they come here:
+// the row count within the tableau's inequalities -- the layout's own for tableau rows, max_rows of room, within the
+// engine's limit, for matrices --, the layout's parameters against the shift (tableau rows: none), and a matrix row of
+// instances within the PIPAMD_MAXCOL values the load keeps of a point in LDS.
+static bool source_ok(const PipBatchSource &s, const PipBatchLayout &lay, int *nrows) {
+  const bool tableau = s.kind == PIP_SRC_TABLEAU, marked = s.kind == PIP_SRC_MATRICES;
+  *nrows = tableau ? lay.ni : marked ? s.markers.max_rows : s.nrows;
+  if (*nrows < 0 || *nrows > (marked ? PIPAMD_SMAX : lay.ni)) return false;
+  if (tableau) return lay.nparm == 0;
+  if (s.shift < -1 || s.shift > 1 || lay.nparm != (s.shift ? 1 : 0) || (s.shift && lay.bigparm != lay.nvar + 1)) return false;
+  if (s.kind != PIP_SRC_INSTANCES) return true;
+  return s.inst.matrix && s.inst.nparm >= 0 && (s.inst.nparm == 0 || s.inst.points) && lay.nvar + s.inst.nparm + 1 <= PIPAMD_MAXCOL;
 }
 
-// pipamd_batch_dual_sparse: the dual of a batch loaded from the CSR arrays of `cs` (those of the `count` systems)
-extern "C" hipError_t pipk_launch_batch_dual_sparse(const PipJob *jobs, const i64 *arena, const PipCsrRows *cs, PipBatchLayout lay,
-                                                    int nrows, const PipEqMask *eq, int first, int count, void *dual_num,
+extern "C" hipError_t pipk_launch_batch_dual_source(const PipJob *jobs, const i64 *arena, PipBatchLayout lay,
+                                                    const PipBatchSource *s, int first, int count, void *dual_num,
                                                     void *dual_den, hipStream_t stream) {
-  if (!cs) return hipErrorInvalidValue;
-  return launch_batch_dual(jobs, arena, nullptr, lay, nrows, eq, nullptr, cs, nullptr, first, count, dual_num, dual_den, stream);
-}
-
-// pipamd_batch_dual_instances: the dual of a batch loaded from the shared matrix of `is` (the points are not needed)
-extern "C" hipError_t pipk_launch_batch_dual_instances(const PipJob *jobs, const i64 *arena, const PipInstanceRows *is,
-                                                       PipBatchLayout lay, int nrows, const PipEqMask *eq, int first, int count,
-                                                       void *dual_num, void *dual_den, hipStream_t stream) {
-  if (!is || !is->matrix || is->nparm < 0 || lay.nvar + is->nparm + 1 > PIPAMD_MAXCOL) return hipErrorInvalidValue;
-  return launch_batch_dual(jobs, arena, nullptr, lay, nrows, eq, nullptr, nullptr, is, first, count, dual_num, dual_den, stream);
+  int nrows;
+  if (count <= 0) return hipSuccess;
+  if (!source_ok(*s, lay, &nrows) || lay.ni > PIP_DUAL_MAXNI) return hipErrorInvalidValue;
+  if (lay.ni <= 0 || nrows <= 0) return hipSuccess;
+  const size_t shm = pipk_batch_dual_lds_bytes(lay.ni);
+  const auto launch = [&](auto t) {
+    using T = decltype(t);
+    return visit_source<true>(*s, [&](const auto &eq, const auto &rs) {
+      hipLaunchKernelGGL((pip_batch_dual_kernel<T, std::decay_t<decltype(eq)>, std::decay_t<decltype(rs)>>), dim3(count),
+                         dim3(64), shm, stream, jobs, arena, (const i64 *)s->rows, lay, first, nrows, eq, (T *)dual_num,
+                         (T *)dual_den, rs);
+      return hipGetLastError();
+    });
+  };
+  return lay.ebits == 128 ? launch(i128{}) : launch(i64{});
 }
 
 // ---------------------------------------------------------------- expanser for the batch layer
@@ -1431,75 +1416,26 @@ extern "C" hipError_t pipk_launch_batch_load(PipJob *jobs, i64 *arena, const i64
   return hipGetLastError();
 }
 
-// the same from the caller's plain system: equalities expanded, shift 0 / +1 / -1, tab_simplify (the caller has held
-// the layout against the shift and the equality list against lay.ni).  mk != nullptr: the systems carry their markers
-// and row counts (pipamd_batch_load_matrices; nrows and eq are not looked at).  cs != nullptr (with eq): the rows are
-// the launch's CSR arrays (pipamd_batch_load_sparse; rows is not looked at).  is != nullptr (with eq): the systems are the
-// launch's shared matrix at their points (pipamd_batch_load_instances; rows is not looked at)
-static hipError_t launch_batch_load_system(PipJob *jobs, i64 *arena, const i64 *rows, PipBatchLayout lay, int shift, int simplify,
-                                           int nrows, const PipEqMask *eq, const PipEqMarkers *mk, const PipCsrRows *cs,
-                                           const PipInstanceRows *is, int first, int count, hipStream_t stream) {
-  if (count <= 0) return hipSuccess;
-  if ((cs || is) && (mk || !eq || (cs && is))) return hipErrorInvalidValue;
-  if (mk) nrows = mk->max_rows;
-  if (shift < -1 || shift > 1 || lay.nparm != (shift ? 1 : 0) || (shift && lay.bigparm != lay.nvar + 1) ||
-      lay.W < lay.nvar + lay.nparm + 1 || lay.W > 512 || nrows < 0 || (mk ? nrows > PIPAMD_SMAX : nrows > lay.ni))
-    return hipErrorInvalidValue;
-  lay.pad = 0;
-#define PIP_LOAD_SYSTEM(T, CPL)                                                                                              \
-  do {                                                                                                                       \
-    if (is)                                                                                                                  \
-      hipLaunchKernelGGL((pip_batch_load_system_kernel<T, CPL, PipEqMask, PipInstanceRows>), dim3(count), dim3(256), 0, stream, \
-                         jobs, arena, nullptr, lay, first, shift, simplify, nrows, *eq, *is);                                \
-    else if (cs)                                                                                                             \
-      hipLaunchKernelGGL((pip_batch_load_system_kernel<T, CPL, PipEqMask, PipCsrRows>), dim3(count), dim3(256), 0, stream, jobs, \
-                         arena, nullptr, lay, first, shift, simplify, nrows, *eq, *cs);                                      \
-    else if (mk)                                                                                                             \
-      hipLaunchKernelGGL((pip_batch_load_system_kernel<T, CPL, PipEqMarkers, PipDenseRows>), dim3(count), dim3(256), 0, stream, \
-                         jobs, arena, rows, lay, first, shift, simplify, nrows, *mk, PipDenseRows{});                        \
-    else                                                                                                                     \
-      hipLaunchKernelGGL((pip_batch_load_system_kernel<T, CPL, PipEqMask, PipDenseRows>), dim3(count), dim3(256), 0, stream,   \
-                         jobs, arena, rows, lay, first, shift, simplify, nrows, *eq, PipDenseRows{});                        \
-  } while (0)
-  if (lay.ebits == 128) {
-    if (lay.W <= 128)
-      PIP_LOAD_SYSTEM(i128, 2);
-    else
-      PIP_LOAD_SYSTEM(i128, 8);
-  } else {
-    if (lay.W <= 128)
-      PIP_LOAD_SYSTEM(i64, 2);
-    else
-      PIP_LOAD_SYSTEM(i64, 8);
-  }
-#undef PIP_LOAD_SYSTEM
-  return hipGetLastError();
-}
-
-extern "C" hipError_t pipk_launch_batch_load_system(PipJob *jobs, i64 *arena, const i64 *rows, PipBatchLayout lay, int shift,
-                                                    int simplify, int nrows, const PipEqMask *eq, const PipEqMarkers *mk,
+// the load from the caller's system: equalities expanded, shift 0 / +1 / -1, tab_simplify
+extern "C" hipError_t pipk_launch_batch_load_source(PipJob *jobs, i64 *arena, PipBatchLayout lay, const PipBatchSource *s,
                                                     int first, int count, hipStream_t stream) {
-  return launch_batch_load_system(jobs, arena, rows, lay, shift, simplify, nrows, eq, mk, nullptr, nullptr, first, count, stream);
-}
-
-// pipamd_batch_load_sparse: the same load with the rows of the `count` systems in the CSR arrays of `cs`
-extern "C" hipError_t pipk_launch_batch_load_sparse(PipJob *jobs, i64 *arena, const PipCsrRows *cs, PipBatchLayout lay, int shift,
-                                                    int simplify, int nrows, const PipEqMask *eq, int first, int count,
-                                                    hipStream_t stream) {
-  if (!cs) return hipErrorInvalidValue;
-  return launch_batch_load_system(jobs, arena, nullptr, lay, shift, simplify, nrows, eq, nullptr, cs, nullptr, first, count,
-                                  stream);
-}
-
-// pipamd_batch_load_instances: the same load with the `count` systems the shared matrix of `is` at their points (the point
-// array in the block's LDS has room for PIPAMD_MAXCOL values: held against the matrix row here)
-extern "C" hipError_t pipk_launch_batch_load_instances(PipJob *jobs, i64 *arena, const PipInstanceRows *is, PipBatchLayout lay,
-                                                       int shift, int simplify, int nrows, const PipEqMask *eq, int first,
-                                                       int count, hipStream_t stream) {
-  if (!is || !is->matrix || is->nparm < 0 || (is->nparm > 0 && !is->points) || lay.nvar + is->nparm + 1 > PIPAMD_MAXCOL)
-    return hipErrorInvalidValue;
-  return launch_batch_load_system(jobs, arena, nullptr, lay, shift, simplify, nrows, eq, nullptr, nullptr, is, first, count,
-                                  stream);
+  int nrows;
+  if (count <= 0) return hipSuccess;
+  if (!source_ok(*s, lay, &nrows) || lay.W < lay.nvar + lay.nparm + 1 || lay.W > 512) return hipErrorInvalidValue;
+  lay.pad = 0;
+  const auto launch = [&](auto t, auto cpl) {
+    return visit_source<false>(*s, [&](const auto &eq, const auto &rs) {
+      hipLaunchKernelGGL((pip_batch_load_system_kernel<decltype(t), decltype(cpl)::value, std::decay_t<decltype(eq)>,
+                                                       std::decay_t<decltype(rs)>>),
+                         dim3(count), dim3(256), 0, stream, jobs, arena, (const i64 *)s->rows, lay, first, s->shift, s->simplify,
+                         nrows, eq, rs);
+      return hipGetLastError();
+    });
+  };
+  const std::integral_constant<int, 2> narrow;  // columns per lane: the tableau's columns over the 64 lanes
+  const std::integral_constant<int, 8> wide;
+  if (lay.ebits == 128) return lay.W <= 128 ? launch(i128{}, narrow) : launch(i128{}, wide);
+  return lay.W <= 128 ? launch(i64{}, narrow) : launch(i64{}, wide);
 }
 
 extern "C" hipError_t pipk_launch_batch_results_shifted(const PipJob *jobs, const i64 *arena, int njobs, int nvar, int ebits,

@@ -85,6 +85,9 @@ def lib():
         L.pipamd_batch_poll.argtypes = [C.c_void_p]
         L.pipamd_batch_load_part.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BatchDesc), C.c_void_p, C.c_int, C.c_int,
                                              C.c_void_p]
+        if hasattr(L, "pipamd_batch_dual_part"):  # (Batch.dual_part says so where a PIPAMD_LIB build has none)
+            L.pipamd_batch_dual_part.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BatchDesc), C.c_void_p, C.c_int, C.c_int,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p]
         L.pipamd_batch_results.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BatchDesc)] + [C.c_void_p] * 6
         L.pipamd_batch_load_shifted_part.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BatchDesc), C.c_void_p, C.c_int,
                                                      C.c_int, C.c_int, C.c_void_p]
@@ -346,6 +349,9 @@ class Batch:
             ni += len(eq)
         elif not matrices:
             assert not eq_rows and not simplify
+        # the form the batch's systems come in, decided here once: load() and load_part() route on it
+        self.form = ("instances" if instances else "sparse" if sparse else "matrices" if matrices else "system" if system
+                     else "shifted" if self.shift else "tableau")
         if self.shift:
             assert self.shift in (SHIFT_MAX, SHIFT_URS) and nparm == 0 and bigparm == -1
             nparm, bigparm = 1, nvar + 1
@@ -377,17 +383,70 @@ class Batch:
     def _stream(self):
         return C.c_void_p(self.torch.cuda.current_stream(self.dev).cuda_stream)
 
+    def _source(self, form, *a):
+        """The part `a` (its resident arrays, as the public method of `form` takes them) of a batch of that form: the C
+        entry's arguments that describe it -- those between the descriptor and `first` --, its number of systems and
+        the number of dual pairs per system."""
+        t = self.torch
+        if form in ("tableau", "shifted", "system"):
+            rows, = a
+            assert (form != "system" or self.system is not None) and rows.is_cuda and rows.is_contiguous()
+            if form == "system":
+                return [C.byref(self.system), C.c_void_p(rows.data_ptr())], int(rows.shape[0]), self.system.nrows
+            shift = [self.shift] if form == "shifted" else []
+            return [C.c_void_p(rows.data_ptr())] + shift, int(rows.shape[0]), self.desc.ni
+        if form == "matrices":  # the batch's pipamd_matrices, with the part's own row counts
+            rows, nrows = a
+            assert self.matrices is not None and rows.is_cuda and rows.is_contiguous()
+            assert tuple(rows.shape[1:]) == (self.matrices.max_rows, self.desc.nvar + 2)
+            m = Matrices(self.matrices.max_rows, self.matrices.shift, self.matrices.simplify, 0, None)
+            if nrows is not None:
+                assert nrows.is_cuda and nrows.is_contiguous() and nrows.dtype == t.int32 and nrows.shape == (rows.shape[0],)
+                m.d_nrows = nrows.data_ptr()
+            return [C.byref(m), C.c_void_p(rows.data_ptr())], int(rows.shape[0]), self.matrices.max_rows
+        if form == "sparse":  # the batch's system with the part's own arrays
+            row_ptr, cols, vals = a
+            assert self.sparse and all(x.is_cuda and x.is_contiguous() and x.dim() == 1 for x in (row_ptr, cols, vals))
+            assert row_ptr.dtype == t.int64 and cols.dtype == t.int32 and vals.dtype == t.int64 and cols.numel() == vals.numel()
+            count, rest = divmod(row_ptr.numel() - 1, max(1, self.system.nrows))
+            assert rest == 0 and row_ptr.numel() >= 1, "row_ptr holds systems * nrows + 1 offsets"
+            nnz = cols.numel()
+            sp = Sparse(self.system, nnz, row_ptr.data_ptr(), cols.data_ptr() if nnz else None, vals.data_ptr() if nnz else None)
+            return [C.byref(sp)], count, self.system.nrows
+        points, matrix = a  # instances: the batch's system with the part's points and its matrix
+        assert self.instances
+        matrix = self.inst[0] if matrix is None else matrix
+        assert matrix.is_cuda and matrix.is_contiguous() and matrix.dtype == t.int64 and matrix.shape == self.inst[0].shape
+        assert points.is_cuda and points.is_contiguous() and points.dtype == t.int64
+        assert points.dim() == 2 and points.shape[1] == self.inst_nparm
+        ins = Instances(self.system, self.inst_nparm, 0, matrix.data_ptr(), points.data_ptr() if self.inst_nparm else None)
+        return [C.byref(ins)], int(points.shape[0]), self.system.nrows
+
+    def _entry(self, op, form):
+        """pipamd_batch_<op>[_<form>]_part: the tableau entries carry no form in their name"""
+        return getattr(lib(), "pipamd_batch_%s%s_part" % (op, "" if form == "tableau" else "_" + form))
+
+    def _load(self, form, first, stream, *a):
+        args, count, _ = self._source(form, *a)
+        st = C.c_void_p(stream) if stream is not None else self._stream()
+        _check(self._entry("load", form)(self.e._h, C.c_void_p(self.ws.data_ptr()), C.byref(self.desc), *args, int(first), count, st))
+
+    def _dual(self, form, first, stream, out, *a):
+        args, count, pairs = self._source(form, *a)
+        num, den = out if out is not None else self._dual_out(pairs)
+        st = C.c_void_p(stream) if stream is not None else self._stream()
+        _check(self._entry("dual", form)(self.e._h, C.c_void_p(self.ws.data_ptr()), C.byref(self.desc), *args, int(first), count,
+                                         C.c_void_p(num.data_ptr()), C.c_void_p(den.data_ptr()), st))
+        return num, den
+
     def load(self):
-        if self.sparse:
-            return self.load_sparse()
-        if self.instances:
-            return self.load_instances()
-        if self.matrices is not None:
-            return self.load_matrices()
-        if self.shift or self.system is not None:
-            return self.load_part(self.rows, 0)
-        _check(lib().pipamd_batch_load(self.e._h, C.c_void_p(self.ws.data_ptr()), C.byref(self.desc),
-                                       C.c_void_p(self.rows.data_ptr()), self._stream()))
+        if self.form == "tableau":
+            _check(lib().pipamd_batch_load(self.e._h, C.c_void_p(self.ws.data_ptr()), C.byref(self.desc),
+                                           C.c_void_p(self.rows.data_ptr()), self._stream()))
+        elif self.form in ("shifted", "system"):
+            self.load_part(self.rows, 0)
+        else:
+            getattr(self, "load_" + self.form)()
 
     def load_part(self, rows, first, stream=None):
         """tableaux first .. first + len(rows) - 1 of the batch from a resident row array (pipamd_batch_load_part)"""
@@ -395,15 +454,7 @@ class Batch:
         assert self.matrices is None, "a Batch(matrices=True) is loaded with load_matrices_part(rows, nrows, first)"
         assert not self.sparse, "a Batch(sparse=True) is loaded with load_sparse_part(row_ptr, cols, vals, first)"
         assert not self.instances, "a Batch(instances=True) is loaded with load_instances_part(points, first)"
-        st = C.c_void_p(stream) if stream is not None else self._stream()
-        if self.system is not None:
-            return self.load_system_part(rows, first, stream)
-        if self.shift:
-            _check(lib().pipamd_batch_load_shifted_part(self.e._h, C.c_void_p(self.ws.data_ptr()), C.byref(self.desc),
-                                                    C.c_void_p(rows.data_ptr()), self.shift, int(first), int(rows.shape[0]), st))
-            return
-        _check(lib().pipamd_batch_load_part(self.e._h, C.c_void_p(self.ws.data_ptr()), C.byref(self.desc),
-                                            C.c_void_p(rows.data_ptr()), int(first), int(rows.shape[0]), st))
+        self._load(self.form, first, stream, rows)
 
     def load_parts(self, parts, stream=None):
         """the whole batch from a list of resident row arrays (one pipamd_batch_load_part each)"""
@@ -468,17 +519,9 @@ class Batch:
         (as load_part was given it); returns (dual_num, dual_den) of the whole batch's shape, only those tableaux written
         (pass the pair back as `out` to fill it part by part)."""
         assert rows.is_cuda and rows.is_contiguous()
-        L = lib()
-        if not hasattr(L, "pipamd_batch_dual_part"):
+        if not hasattr(lib(), "pipamd_batch_dual_part"):
             raise RuntimeError("libpipamd has no pipamd_batch_dual_part: rebuild the library")
-        L.pipamd_batch_dual_part.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(BatchDesc), C.c_void_p, C.c_int, C.c_int,
-                                             C.c_void_p, C.c_void_p, C.c_void_p]
-        num, den = out if out is not None else self._dual_out(self.desc.ni)
-        st = C.c_void_p(stream) if stream is not None else self._stream()
-        _check(L.pipamd_batch_dual_part(self.e._h, C.c_void_p(self.ws.data_ptr()), C.byref(self.desc),
-                                        C.c_void_p(rows.data_ptr()), int(first), int(rows.shape[0]),
-                                        C.c_void_p(num.data_ptr()), C.c_void_p(den.data_ptr()), st))
-        return num, den
+        return self._dual("tableau", first, stream, out, rows)
 
     def load_system(self, stream=None):
         """pipamd_batch_load_system of a Batch(system=True): the whole batch from its resident plain rows"""
@@ -486,11 +529,7 @@ class Batch:
 
     def load_system_part(self, rows, first, stream=None):
         """pipamd_batch_load_system_part: tableaux first .. first + len(rows) - 1 from the resident plain systems `rows`"""
-        assert self.system is not None and rows.is_cuda and rows.is_contiguous()
-        st = C.c_void_p(stream) if stream is not None else self._stream()
-        _check(lib().pipamd_batch_load_system_part(self.e._h, C.c_void_p(self.ws.data_ptr()), C.byref(self.desc),
-                                                   C.byref(self.system), C.c_void_p(rows.data_ptr()), int(first),
-                                                   int(rows.shape[0]), st))
+        self._load("system", first, stream, rows)
 
     def dual_system(self, stream=None):
         """pipamd_batch_dual_system after a solve with T_DUAL of a Batch(system=True): device tensors (dual_num, dual_den)
@@ -503,23 +542,7 @@ class Batch:
     def dual_system_part(self, rows, first, stream=None, out=None):
         """pipamd_batch_dual_system_part for the tableaux first .. first + len(rows) - 1, loaded from the resident array
         `rows`; returns (dual_num, dual_den) of the whole batch's shape (pass the pair back as `out` to fill it part by part)."""
-        assert self.system is not None and rows.is_cuda and rows.is_contiguous()
-        num, den = out if out is not None else self._dual_out(self.system.nrows)
-        st = C.c_void_p(stream) if stream is not None else self._stream()
-        _check(lib().pipamd_batch_dual_system_part(self.e._h, C.c_void_p(self.ws.data_ptr()), C.byref(self.desc),
-                                                   C.byref(self.system), C.c_void_p(rows.data_ptr()), int(first),
-                                                   int(rows.shape[0]), C.c_void_p(num.data_ptr()), C.c_void_p(den.data_ptr()), st))
-        return num, den
-
-    def _matrices_part(self, rows, nrows):
-        """the pipamd_matrices of a part: the batch's, with the part's own row counts"""
-        assert self.matrices is not None and rows.is_cuda and rows.is_contiguous()
-        assert tuple(rows.shape[1:]) == (self.matrices.max_rows, self.desc.nvar + 2)
-        m = Matrices(self.matrices.max_rows, self.matrices.shift, self.matrices.simplify, 0, None)
-        if nrows is not None:
-            assert nrows.is_cuda and nrows.is_contiguous() and nrows.dtype == self.torch.int32 and nrows.shape == (rows.shape[0],)
-            m.d_nrows = nrows.data_ptr()
-        return m
+        return self._dual("system", first, stream, out, rows)
 
     def load_matrices(self, stream=None):
         """pipamd_batch_load_matrices of a Batch(matrices=True): the whole batch from its resident matrices and row counts"""
@@ -528,10 +551,7 @@ class Batch:
     def load_matrices_part(self, rows, nrows, first, stream=None):
         """pipamd_batch_load_matrices_part: tableaux first .. first + len(rows) - 1 from the resident matrices `rows` and
         their row counts `nrows` (a resident int32 tensor, or None: max_rows each)"""
-        m = self._matrices_part(rows, nrows)
-        st = C.c_void_p(stream) if stream is not None else self._stream()
-        _check(lib().pipamd_batch_load_matrices_part(self.e._h, C.c_void_p(self.ws.data_ptr()), C.byref(self.desc), C.byref(m),
-                                                     C.c_void_p(rows.data_ptr()), int(first), int(rows.shape[0]), st))
+        self._load("matrices", first, stream, rows, nrows)
 
     def dual_matrices(self, stream=None):
         """pipamd_batch_dual_matrices after a solve with T_DUAL of a Batch(matrices=True): device tensors (dual_num,
@@ -544,23 +564,7 @@ class Batch:
     def dual_matrices_part(self, rows, nrows, first, stream=None, out=None):
         """pipamd_batch_dual_matrices_part for the tableaux first .. first + len(rows) - 1, loaded from `rows` and `nrows`;
         returns (dual_num, dual_den) of the whole batch's shape (pass the pair back as `out` to fill it part by part)."""
-        m = self._matrices_part(rows, nrows)
-        num, den = out if out is not None else self._dual_out(self.matrices.max_rows)
-        st = C.c_void_p(stream) if stream is not None else self._stream()
-        _check(lib().pipamd_batch_dual_matrices_part(self.e._h, C.c_void_p(self.ws.data_ptr()), C.byref(self.desc), C.byref(m),
-                                                     C.c_void_p(rows.data_ptr()), int(first), int(rows.shape[0]),
-                                                     C.c_void_p(num.data_ptr()), C.c_void_p(den.data_ptr()), st))
-        return num, den
-
-    def _sparse_part(self, row_ptr, cols, vals):
-        """(the pipamd_sparse of a part: the batch's system with the part's own arrays, the part's systems)"""
-        t = self.torch
-        assert self.sparse and all(x.is_cuda and x.is_contiguous() and x.dim() == 1 for x in (row_ptr, cols, vals))
-        assert row_ptr.dtype == t.int64 and cols.dtype == t.int32 and vals.dtype == t.int64 and cols.numel() == vals.numel()
-        count, rest = divmod(row_ptr.numel() - 1, max(1, self.system.nrows))
-        assert rest == 0 and row_ptr.numel() >= 1, "row_ptr holds systems * nrows + 1 offsets"
-        nnz = cols.numel()
-        return Sparse(self.system, nnz, row_ptr.data_ptr(), cols.data_ptr() if nnz else None, vals.data_ptr() if nnz else None), count
+        return self._dual("matrices", first, stream, out, rows, nrows)
 
     def load_sparse(self, stream=None):
         """pipamd_batch_load_sparse of a Batch(sparse=True): the whole batch from its resident CSR arrays"""
@@ -569,10 +573,7 @@ class Batch:
     def load_sparse_part(self, row_ptr, cols, vals, first, stream=None):
         """pipamd_batch_load_sparse_part: tableaux first .. first + count - 1 from the resident CSR arrays of those systems
         (row_ptr: count * nrows + 1 offsets into cols / vals)"""
-        sp, count = self._sparse_part(row_ptr, cols, vals)
-        st = C.c_void_p(stream) if stream is not None else self._stream()
-        _check(lib().pipamd_batch_load_sparse_part(self.e._h, C.c_void_p(self.ws.data_ptr()), C.byref(self.desc), C.byref(sp),
-                                                   int(first), count, st))
+        self._load("sparse", first, stream, row_ptr, cols, vals)
 
     def dual_sparse(self, stream=None):
         """pipamd_batch_dual_sparse after a solve with T_DUAL of a Batch(sparse=True): device tensors (dual_num, dual_den)
@@ -585,23 +586,7 @@ class Batch:
     def dual_sparse_part(self, row_ptr, cols, vals, first, stream=None, out=None):
         """pipamd_batch_dual_sparse_part for the tableaux first .. first + count - 1, loaded from these CSR arrays; returns
         (dual_num, dual_den) of the whole batch's shape (pass the pair back as `out` to fill it part by part)."""
-        sp, count = self._sparse_part(row_ptr, cols, vals)
-        num, den = out if out is not None else self._dual_out(self.system.nrows)
-        st = C.c_void_p(stream) if stream is not None else self._stream()
-        _check(lib().pipamd_batch_dual_sparse_part(self.e._h, C.c_void_p(self.ws.data_ptr()), C.byref(self.desc), C.byref(sp),
-                                                   int(first), count, C.c_void_p(num.data_ptr()), C.c_void_p(den.data_ptr()), st))
-        return num, den
-
-    def _instances_part(self, points, matrix):
-        """(the pipamd_instances of a part: the batch's system with the part's points and its matrix, the part's systems)"""
-        t = self.torch
-        assert self.instances
-        matrix = self.inst[0] if matrix is None else matrix
-        assert matrix.is_cuda and matrix.is_contiguous() and matrix.dtype == t.int64 and matrix.shape == self.inst[0].shape
-        assert points.is_cuda and points.is_contiguous() and points.dtype == t.int64
-        assert points.dim() == 2 and points.shape[1] == self.inst_nparm
-        return (Instances(self.system, self.inst_nparm, 0, matrix.data_ptr(), points.data_ptr() if self.inst_nparm else None),
-                int(points.shape[0]))
+        return self._dual("sparse", first, stream, out, row_ptr, cols, vals)
 
     def load_instances(self, stream=None):
         """pipamd_batch_load_instances of a Batch(instances=True): the whole batch from its resident matrix and points"""
@@ -610,10 +595,7 @@ class Batch:
     def load_instances_part(self, points, first, stream=None, matrix=None):
         """pipamd_batch_load_instances_part: tableaux first .. first + len(points) - 1, the systems of the resident `points`
         ((count, nparm) int64) under the batch's matrix, or under `matrix`, a resident one of the same shape"""
-        ins, count = self._instances_part(points, matrix)
-        st = C.c_void_p(stream) if stream is not None else self._stream()
-        _check(lib().pipamd_batch_load_instances_part(self.e._h, C.c_void_p(self.ws.data_ptr()), C.byref(self.desc), C.byref(ins),
-                                                      int(first), count, st))
+        self._load("instances", first, stream, points, matrix)
 
     def dual_instances(self, stream=None):
         """pipamd_batch_dual_instances after a solve with T_DUAL of a Batch(instances=True): device tensors (dual_num,
@@ -627,12 +609,7 @@ class Batch:
         """pipamd_batch_dual_instances_part for the tableaux first .. first + len(points) - 1, loaded from these points (and
         `matrix`, if not the batch's); returns (dual_num, dual_den) of the whole batch's shape (pass the pair back as `out`
         to fill it part by part)."""
-        ins, count = self._instances_part(points, matrix)
-        num, den = out if out is not None else self._dual_out(self.system.nrows)
-        st = C.c_void_p(stream) if stream is not None else self._stream()
-        _check(lib().pipamd_batch_dual_instances_part(self.e._h, C.c_void_p(self.ws.data_ptr()), C.byref(self.desc), C.byref(ins),
-                                                      int(first), count, C.c_void_p(num.data_ptr()), C.c_void_p(den.data_ptr()), st))
-        return num, den
+        return self._dual("instances", first, stream, out, points, matrix)
 
     def counters(self):
         """dict of batch totals (pivots, cuts, rows_rewritten, finished) -- synchronises."""
