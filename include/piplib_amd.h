@@ -60,7 +60,9 @@ extern "C" {
  * many parameter points, a lane per point; pipamd_tape_sweep_plan / pipamd_tape_sweep -- a tape swept over a box of
  * points the kernel makes itself, under a context (PIPAMD_ST_OUTSIDE), with a summary reduced on the device;
  * pipamd_tape_compare_plan / pipamd_tape_compare / pipamd_tape_compare_sweep -- two tapes, of either cell width each,
- * compared by value at the points of a list or a box (PIPAMD_CMP_*). */
+ * compared by value at the points of a list or a box (PIPAMD_CMP_*); pipamd_tape_sweep_values_plan /
+ * pipamd_tape_sweep_values -- per unknown the minimum, the maximum, where they are attained and the exact sum over a
+ * box (PIPAMD_VALUES_*). */
 #define PIPAMD_VERSION 500
 
 /* ---- error codes (return values) ---- */
@@ -982,6 +984,65 @@ int pipamd_tape_compare(pipamd_engine *e, const pipamd_tape *a, const pipamd_tap
 int pipamd_tape_compare_sweep(pipamd_engine *e, const pipamd_tape *a, const pipamd_tape *b, int flags, const int64_t *lo,
                               const int64_t *hi, int n_ctx, int ctx_cols, const int64_t *d_ctx, int64_t *d_summary,
                               int32_t *d_class, int32_t *d_where, int32_t *d_status_a, int32_t *d_status_b, void *stream);
+
+/* A sweep's values reduced per unknown on the device (added since interface version 500): over a whole box, what values
+ * does unknown i take -- its smallest, its largest, where they are attained, and the exact total?  The box, the order
+ * of k, the context rows, the statuses, the RANGE rules, the edit marks and the empty tape are exactly
+ * pipamd_tape_sweep's; nothing per point is written, so the box may be far larger than memory for its answers.
+ * The summary: PIPAMD_VALUES_WORDS(nvar) int64 on the device.  Words 0..7 are bit for bit the words 0..7 pipamd_tape_sweep
+ * writes for the same call (counts and firsts by status).  Behind them one record of PIPAMD_VALUES_REC words per unknown,
+ * unknown i at word PIPAMD_VALUES_HEAD + PIPAMD_VALUES_REC * i:
+ *   0 n_int        PIPAMD_ST_SOLUTION points at which unknown i is handed out over denominator 1
+ *   1 n_frac       ... over a denominator > 1
+ *   2 n_unbounded  ... over denominator 0 (an edited tape's unbounded unknown)
+ *   3 0
+ *   4,5 min (low, high: two's complement 128 bits; an int64 tape's value sign-extended)     6 k_min
+ *   7,8 max (low, high)                                                                     9 k_max
+ *   10,11,12 sum: 192 bits two's complement, little-endian limbs
+ *   13..15 0
+ * Only points that end PIPAMD_ST_SOLUTION take part, and RANGE is a status of the point as in pipamd_tape_eval: one
+ * unknown out of range drops the whole point from every record.  For such a point unknown i is the pair
+ * pipamd_tape_eval hands out: over denominator 1 the numerator enters n_int, min, max and sum; over a larger
+ * denominator it is counted in n_frac and nothing else; over 0 in n_unbounded and nothing else.  k_min / k_max: the
+ * smallest k of the box (k counts every point, outside ones included) at which the min / max is attained.  With
+ * n_int == 0, min, max and sum are 0 and both k are -1.  The sum is exact: fewer than 2^38 values below 2^127 in
+ * magnitude cannot leave 192 bits.  Every figure is an order-independent integer, and no record word is ever the target
+ * of an atomic: the summary is bit-identical from run to run and for every grid size.
+ * Two stages in memory the caller gives: the sweep kernel leaves a partial record per wave and unknown in d_work, a
+ * second small kernel on the same stream folds them into d_summary.  The layout of d_work is private; plan.work_bytes
+ * says how much a call needs:
+ *     96 * nvar * 2 * min(ceil(n_points / 128), 2048)  bytes
+ * -- 96 bytes a partial record, two waves a workgroup, a workgroup per chunk of 128 points up to the grid's cap of 2048
+ * workgroups: 24 MiB at most (nvar 64).  d_work is read and written as int64 words: it must be 8-byte aligned, as
+ * whatever hipMalloc returns is (a caller that sub-allocates keeps to it).  Neither d_summary nor d_work needs initialising, two calls do not accumulate,
+ * and calls on several streams with different buffers may run concurrently.
+ * pipamd_tape_sweep_values_plan is host only, as pipamd_tape_sweep_plan; nvar is the tape's shape.nvar.
+ * PIPAMD_E_INVALID: whatever that planner refuses; nvar < 0.  PIPAMD_E_TOOLARGE: what that planner answers so; nvar above
+ * PIPAMD_VALUES_MAX_NVAR (lane i of a wave keeps unknown i's record in registers).  nvar == 0 is legal: eight words.
+ * plan.staged: 1 exactly when info.staged and the program (8 * info.words) fits PIPAMD_TAPE_LDS_BYTES beside the slots
+ * (128 * (info.slots - 1) values of bits / 8 bytes) and beside the LDS of the value reduction -- which is none: its
+ * accumulators are registers, so today the switch is info.staged's; a call reads the plan, not info.  Otherwise the
+ * program is read from global memory.
+ * pipamd_tape_sweep_values: a fill of the head words and two kernels on `stream`, no synchronisation.  PIPAMD_E_INVALID
+ * before any HIP call: what pipamd_tape_sweep refuses; a null d_summary or d_work; a d_work that is not 8-byte aligned;
+ * work_bytes below the plan's.
+ * PIPAMD_E_TOOLARGE as the planner.  pipamd_debug_tape_sweep_blocks bounds this grid too. */
+#define PIPAMD_VALUES_MAX_NVAR 64
+#define PIPAMD_VALUES_HEAD 8 /* the sweep's words 0..7: PIPAMD_SWEEP_COUNT + status, PIPAMD_SWEEP_FIRST + status */
+#define PIPAMD_VALUES_REC 16 /* int64 words per unknown */
+#define PIPAMD_VALUES_WORDS(nvar) (8 + 16 * (nvar))
+struct pipamd_tape_values_plan {
+  int64_t n_points;      /* prod (hi[c] - lo[c] + 1); 1 when point_cols == 0 */
+  int64_t summary_words; /* PIPAMD_VALUES_WORDS(nvar) */
+  int64_t work_bytes;    /* see above */
+  int32_t staged;
+  int32_t reserved;
+}; /* 32 bytes, offsets 0 8 16 24 28 */
+int pipamd_tape_sweep_values_plan(const pipamd_tape_info *info, int bits, int nvar, int point_cols, const int64_t *lo,
+                                  const int64_t *hi, struct pipamd_tape_values_plan *plan);
+int pipamd_tape_sweep_values(pipamd_engine *e, const pipamd_tape *t, const int64_t *lo, const int64_t *hi, int n_ctx,
+                             int ctx_cols, const int64_t *d_ctx, int64_t *d_summary, void *d_work, size_t work_bytes,
+                             void *stream);
 
 #ifdef __cplusplus
 }

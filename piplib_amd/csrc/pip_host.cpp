@@ -1395,6 +1395,76 @@ extern "C" int pipamd_tape_sweep(pipamd_engine *e, const pipamd_tape *t, const i
   return PIPAMD_OK;
 }
 
+// ------------------------------------------------------------------ a sweep's values reduced per unknown
+// The planner's work for `who`: the refusals, the box (its extents into `ext` where that is not NULL) and the plan
+static int tape_values_plan(const char *who, const pipamd_tape_info *info, int bits, int nvar, int point_cols, const int64_t *lo,
+                            const int64_t *hi, unsigned long long *ext, struct pipamd_tape_values_plan *plan) {
+  if (!info || !plan || (bits != 64 && bits != 128) || nvar < 0) {
+    pipamd_set_error("%s: null info or plan, bits other than 64 and 128, or nvar < 0", who);
+    return PIPAMD_E_INVALID;
+  }
+  int64_t n = 0;
+  const int rc = tape_sweep_box(who, point_cols, lo, hi, ext, &n);
+  if (rc) return rc;
+  if (nvar > PIPAMD_VALUES_MAX_NVAR) {
+    pipamd_set_error("%s: %d unknowns, at most %d (a lane of a wave keeps one unknown's record)", who, nvar, PIPAMD_VALUES_MAX_NVAR);
+    return PIPAMD_E_TOOLARGE;
+  }
+  plan->n_points = n;
+  plan->summary_words = PIPAMD_VALUES_WORDS(nvar);
+  plan->work_bytes = (int64_t)tape_values_work_bytes(n, nvar);
+  // (the reduction keeps its accumulators in registers: beside the slots the program alone asks for LDS)
+  const unsigned __int128 lds = (unsigned __int128)tape_slot_bytes(info->slots > 0 ? info->slots : 1, bits) +
+                                (unsigned __int128)8 * (unsigned long long)info->words;
+  plan->staged = info->staged && info->words > 0 && lds <= (unsigned __int128)TAPE_LDS_BYTES;
+  plan->reserved = 0;
+  return PIPAMD_OK;
+}
+
+extern "C" int pipamd_tape_sweep_values_plan(const pipamd_tape_info *info, int bits, int nvar, int point_cols,
+                                             const int64_t *lo, const int64_t *hi, struct pipamd_tape_values_plan *plan) {
+  return tape_values_plan("tape_sweep_values_plan", info, bits, nvar, point_cols, lo, hi, nullptr, plan);
+}
+
+extern "C" int pipamd_tape_sweep_values(pipamd_engine *e, const pipamd_tape *t, const int64_t *lo, const int64_t *hi, int n_ctx,
+                                        int ctx_cols, const int64_t *d_ctx, int64_t *d_summary, void *d_work, size_t work_bytes,
+                                        void *stream) {
+  if (!e || !t || t->device != e->device || !tape_ctx_ok(n_ctx, ctx_cols, d_ctx, t->point_cols) || !d_summary || !d_work ||
+      ((uintptr_t)d_work & 7)) {
+    pipamd_set_error("tape_sweep_values: null engine, tape, summary or work buffer, a work buffer that is not 8-byte aligned, "
+                     "a tape of another device, n_ctx < 0, or context rows without an array of point_cols + 2 columns");
+    return PIPAMD_E_INVALID;
+  }
+  TapeValuesLaunch L;
+  memset(&L, 0, sizeof L);
+  struct pipamd_tape_values_plan plan;
+  const int rc = tape_values_plan("tape_sweep_values", &t->info, t->bits, t->shape.nvar, t->point_cols, lo, hi, L.ext, &plan);
+  if (rc) return rc;
+  if ((unsigned __int128)work_bytes < (unsigned __int128)plan.work_bytes) {
+    pipamd_set_error("tape_sweep_values: a work buffer of %zu bytes, the plan asks for %lld", work_bytes, (long long)plan.work_bytes);
+    return PIPAMD_E_INVALID;
+  }
+  if (hipSetDevice(e->device) != hipSuccess) return PIPAMD_E_HIP;
+  L.t.prog = t->d_prog;
+  L.t.words = t->info.words;
+  L.t.bits = t->bits;
+  L.t.staged = plan.staged;
+  L.t.marks = t->marks;
+  L.t.nvar = t->shape.nvar;
+  L.t.nparm = t->point_cols;
+  L.t.slots = t->info.slots;
+  L.t.n_points = plan.n_points;
+  L.n_ctx = n_ctx;
+  L.ctx = (const long long *)d_ctx;
+  L.summary = (long long *)d_summary;
+  L.work = (long long *)d_work;
+  for (int c = 0; c < t->point_cols; c++) L.lo[c] = lo[c];
+  L.cus = e->cus;
+  L.max_blocks = g_tape_sweep_blocks;
+  HIPCHK(pipk_launch_tape_values(&L, (hipStream_t)stream));
+  return PIPAMD_OK;
+}
+
 // ------------------------------------------------------------------ two tapes compared point by point
 // The LDS of a pair: both slot areas must fit (TOOLARGE otherwise); staged: both programs fit beside them too.
 static int tape_compare_lds(const char *who, const pipamd_tape_info *a, int bits_a, const pipamd_tape_info *b, int bits_b,

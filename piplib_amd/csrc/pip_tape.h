@@ -123,7 +123,42 @@ struct TapeCompareLaunch {
   unsigned long long ext[TAPE_MAX_SLOTS - 1];
 };
 
+// pipamd_tape_sweep_values: the sweep's box, context, grid and head words; per unknown a record of counts, minimum,
+// maximum (each with the smallest k that attains it) and exact sum (piplib_amd.h, PIPAMD_VALUES_*).  Two stages: every
+// wave of the main kernel stores its accumulators as a partial row of `work` -- row 2 * workgroup + wave,
+// nvar x TAPE_VALUES_PART words: n_int, n_frac, n_unbounded, min (low, high), k_min, max (low, high), k_max, sum (three
+// limbs) --, and the fold kernel, a workgroup per unknown, merges the rows into the summary.  LDS: the slot rows and,
+// staged, the program; the reduction itself lives in registers and takes none.
+enum {
+  TAPE_VALUES_PART = 12,           // words of a partial record
+  TAPE_VALUES_MAX_BLOCKS = 2048,   // the grid's cap: 2 rows x 64 unknowns x 96 bytes each is 24 MiB of work at most
+  TAPE_VALUES_FOLD_BLOCK = 1024    // lanes of the fold kernel's workgroup, at most
+};
+// workgroups of the main kernel: no more than chunks of TAPE_BLOCK points, than the cap, and than `bound` (> 0)
+static inline long long tape_values_blocks(long long n_points, long long bound) {
+  long long b = (n_points + TAPE_BLOCK - 1) / TAPE_BLOCK;
+  if (b > TAPE_VALUES_MAX_BLOCKS) b = TAPE_VALUES_MAX_BLOCKS;
+  return b < bound ? b : bound;
+}
+// bytes of `work` a call needs, whatever the device: the rows of tape_values_blocks(n_points, no bound)
+static inline size_t tape_values_work_bytes(long long n_points, int nvar) {
+  return (size_t)tape_values_blocks(n_points, TAPE_VALUES_MAX_BLOCKS) * (TAPE_BLOCK / 64) * (size_t)nvar * TAPE_VALUES_PART * 8;
+}
+struct TapeValuesLaunch {
+  TapeLaunch t;           // the program; t.points and the outputs are not used; t.n_points = prod ext[c]
+  int n_ctx;              // rows of the context
+  int cus;                // compute units of the device
+  int max_blocks;         // testing aid, as in TapeSweepLaunch
+  int pad;
+  const long long *ctx;   // device; n_ctx x (t.nparm + 2)
+  long long *summary;     // device; PIPAMD_VALUES_WORDS(t.nvar) words, written by the launch
+  long long *work;        // device; tape_values_work_bytes(t.n_points, t.nvar) bytes, need not be initialised
+  long long lo[TAPE_MAX_SLOTS - 1];
+  unsigned long long ext[TAPE_MAX_SLOTS - 1];
+};
+
 extern "C" {
+hipError_t pipk_launch_tape_values(const TapeValuesLaunch *t, hipStream_t stream);
 hipError_t pipk_launch_tape_compare(const TapeCompareLaunch *t, hipStream_t stream);
 hipError_t pipk_launch_tape_sweep(const TapeSweepLaunch *t, hipStream_t stream);
 hipError_t pipk_launch_tape_eval(const TapeLaunch *t, hipStream_t stream);

@@ -711,6 +711,290 @@ hipError_t launch_compare(const TapeCompareLaunch &c, hipStream_t stream) {
   return hipGetLastError();
 }
 
+// ------------------------------------------------------------------ pipamd_tape_sweep_values
+// Per unknown the counts, the minimum and the maximum with the smallest k that attains them, and the exact sum of the
+// integer values a box's SOLUTION points hand out (TapeValuesLaunch, pip_tape.h; the record: piplib_amd.h).  The sweep's
+// grid, decode, context test and walk -- with STOP, so a lane is at its leaf's word position.  Then, unknown by unknown
+// in a wave-uniform loop: the wave serves its distinct leaves one at a time as the compare kernel does -- the leaf of
+// the first pending lane by readlane, the ballot of the lanes that share it -- and those lanes evaluate the unknown with
+// leaf_pair; once every lane has its pair, ONE wave reduction per unknown and chunk: the three counts are popcounts of
+// ballots; the minimum and the maximum are butterflies over the values alone, the lane of the smallest k then the
+// lowest set bit of the ballot `value == minimum` (k grows with the lane); the sum is a butterfly over pieces whose 64
+// terms cannot carry out of a register pair.  Lane i of the wave merges unknown i's figures into the ValuesAcc it keeps
+// in registers -- no lane indexes an array --, in the (value, lowest k) order, which is order-independent.
+// RANGE is known only after a point's last unknown, and such a point takes part in nothing.  A chunk is accumulated
+// into a copy of the accumulators with every SOLUTION lane taking part; when the ballot shows a RANGE lane the copy is
+// dropped and the chunk done again without those lanes (a second time is the last: RANGE is a property of the lane).
+// The alternative -- a first pass over the unknowns for RANGE alone, a second that accumulates -- evaluates every leaf
+// twice at every point and measured slower.
+// The head words are the sweep's: wave-uniform counts and firsts, flushed by the sweep's atomics.  The records are not
+// touched by an atomic: every wave stores its 64 accumulators -- the identity where it met nothing -- as row
+// 2 * blockIdx.x + wave of `work` with plain stores, and pip_tape_values_fold_kernel, a workgroup per unknown, merges
+// the rows in the same order-independent way and writes the record.
+struct Sum192 {
+  u64 w0, w1, w2;  // two's complement, little-endian limbs
+};
+__device__ __forceinline__ Sum192 add192(Sum192 a, Sum192 b) {
+  Sum192 r;
+  u128 t = (u128)a.w0 + b.w0;
+  r.w0 = (u64)t;
+  t = (u128)a.w1 + b.w1 + (u64)(t >> 64);
+  r.w1 = (u64)t;
+  r.w2 = a.w2 + b.w2 + (u64)(t >> 64);
+  return r;
+}
+struct ValuesAcc {
+  u64 n_int, n_frac, n_unb;
+  i128 mn, mx;    // meaningful with n_int > 0
+  i64 k_mn, k_mx;
+  Sum192 sum;
+};
+__device__ __forceinline__ ValuesAcc values_identity() {
+  ValuesAcc a;
+  a.n_int = a.n_frac = a.n_unb = 0;
+  a.mn = a.mx = 0;
+  a.k_mn = a.k_mx = -1;
+  a.sum.w0 = a.sum.w1 = a.sum.w2 = 0;
+  return a;
+}
+// a and b merged into a: commutative and associative, a minimum's and a maximum's k the smallest that attains it
+__device__ __forceinline__ void values_merge(ValuesAcc &a, const ValuesAcc &b) {
+  if (b.n_int) {
+    if (!a.n_int || b.mn < a.mn || (b.mn == a.mn && b.k_mn < a.k_mn)) a.mn = b.mn, a.k_mn = b.k_mn;
+    if (!a.n_int || b.mx > a.mx || (b.mx == a.mx && b.k_mx < a.k_mx)) a.mx = b.mx, a.k_mx = b.k_mx;
+  }
+  a.n_int += b.n_int, a.n_frac += b.n_frac, a.n_unb += b.n_unb;
+  a.sum = add192(a.sum, b.sum);
+}
+template <class V>
+__device__ __forceinline__ V wave_min_of(V x) {
+  for (int o = 32; o; o >>= 1) {
+    const V y = shfl_xor(x, o);
+    x = y < x ? y : x;
+  }
+  return x;
+}
+template <class V>
+__device__ __forceinline__ V wave_max_of(V x) {
+  for (int o = 32; o; o >>= 1) {
+    const V y = shfl_xor(x, o);
+    x = y > x ? y : x;
+  }
+  return x;
+}
+__device__ __forceinline__ i64 wave_add64(i64 x) {
+  for (int o = 32; o; o >>= 1) x = (i64)((u64)x + (u64)shfl_xor(x, o));
+  return x;
+}
+// the exact sum of the wave's 64 values.  int64: the low and the signed high 32 bits summed apart, each below 2^38
+__device__ __forceinline__ Sum192 wave_sum192(i64 v) {
+  const i64 lo = wave_add64((i64)(u64)(unsigned)(u64)v), hi = wave_add64(v >> 32);
+  const i128 s = (i128)lo + (i128)hi * ((i128)1 << 32);
+  Sum192 r;
+  r.w0 = (u64)(u128)s, r.w1 = (u64)((u128)s >> 64), r.w2 = (u64)(i64)(s >> 127);
+  return r;
+}
+// 128 bits: pieces of 43, 43 and 42 (signed) bits, each sum below 2^49; joined in 192 bits
+__device__ __forceinline__ Sum192 wave_sum192(i128 v) {
+  const u64 mask = ((u64)1 << 43) - 1;
+  const i64 s0 = wave_add64((i64)((u64)(u128)v & mask)), s1 = wave_add64((i64)((u64)((u128)v >> 43) & mask));
+  const i64 s2 = wave_add64((i64)(v >> 86));
+  const i128 low = (i128)s0 + ((i128)s1 << 43), high = (i128)s2 * ((i128)1 << 22);  // high counts 2^64
+  Sum192 a, b;
+  a.w0 = (u64)(u128)low, a.w1 = (u64)((u128)low >> 64), a.w2 = 0;  // (0 <= low < 2^93)
+  b.w0 = 0, b.w1 = (u64)(u128)high, b.w2 = (u64)((u128)high >> 64);
+  return add192(a, b);
+}
+template <class T>
+struct ValueLimits;
+template <>
+struct ValueLimits<i64> {
+  static __device__ __forceinline__ i64 max() { return (i64)(~(u64)0 >> 1); }
+};
+template <>
+struct ValueLimits<i128> {
+  static __device__ __forceinline__ i128 max() { return (i128)(~(u128)0 >> 1); }
+};
+
+// the wave's figures for one unknown: lanes with `isint` hand out v over 1, `isfrac` over more, `isunb` over 0; lane l
+// is point wave_k + l.  Every lane gets the same ValuesAcc.
+template <class T>
+__device__ __forceinline__ ValuesAcc values_reduce(bool isint, bool isfrac, bool isunb, T v, u64 wave_k) {
+  ValuesAcc r = values_identity();
+  const u64 mi = __ballot(isint);
+  r.n_int = (u64)__popcll(mi);
+  r.n_frac = (u64)__popcll(__ballot(isfrac));
+  r.n_unb = (u64)__popcll(__ballot(isunb));
+  if (mi) {  // (wave-uniform)
+    const T top = ValueLimits<T>::max(), bottom = -top - 1;
+    const T lo = wave_min_of<T>(isint ? v : top), hi = wave_max_of<T>(isint ? v : bottom);
+    r.mn = (i128)lo, r.mx = (i128)hi;
+    r.k_mn = (i64)(wave_k + (u64)(__ffsll((unsigned long long)__ballot(isint && v == lo)) - 1));
+    r.k_mx = (i64)(wave_k + (u64)(__ffsll((unsigned long long)__ballot(isint && v == hi)) - 1));
+    r.sum = wave_sum192(isint ? v : (T)0);
+  }
+  return r;
+}
+
+// One pass of a wave over the unknowns of its lanes' leaves: the lanes with `take` are at the LEAF at word `leaf`.
+// Lane i merges unknown i into acc.  Returns whether the lane's point is RANGE (only a lane with `take` can be).
+template <class T>
+__device__ __forceinline__ bool values_pass(const i64 *prog, const i64 *S, int tid, int nvar, bool take, int leaf, u64 wave_k,
+                                            ValuesAcc &acc) {
+  const int lane = tid & 63;
+  bool range = false;
+  for (int i = 0; i < nvar; i++) {
+    i128 num = 0, den = 0;
+    bool ok = true;
+    u64 pend = __ballot(take);
+    while (pend) {
+      const int src = __ffsll((unsigned long long)pend) - 1;
+      const int l = __builtin_amdgcn_readlane(leaf, src);
+      const bool mine = take && leaf == l;
+      if (mine) ok = leaf_pair<T>(prog, l, i, S, tid, &num, &den);
+      pend &= ~__ballot(mine);
+    }
+    range = range || !ok;
+    const bool good = take && ok;
+    const ValuesAcc r = values_reduce<T>(good && den == 1, good && den > 1, good && den == 0, (T)num, wave_k);
+    if (lane == i) values_merge(acc, r);
+  }
+  return range;
+}
+
+// the partial row of a wave and what the fold reads: TAPE_VALUES_PART words an unknown
+__device__ __forceinline__ void values_store(i64 *p, const ValuesAcc &a) {
+  p[0] = (i64)a.n_int, p[1] = (i64)a.n_frac, p[2] = (i64)a.n_unb;
+  p[3] = (i64)(u64)(u128)a.mn, p[4] = (i64)(u64)((u128)a.mn >> 64), p[5] = a.k_mn;
+  p[6] = (i64)(u64)(u128)a.mx, p[7] = (i64)(u64)((u128)a.mx >> 64), p[8] = a.k_mx;
+  p[9] = (i64)a.sum.w0, p[10] = (i64)a.sum.w1, p[11] = (i64)a.sum.w2;
+}
+__device__ __forceinline__ ValuesAcc values_load(const i64 *p) {
+  ValuesAcc a;
+  a.n_int = (u64)p[0], a.n_frac = (u64)p[1], a.n_unb = (u64)p[2];
+  a.mn = (i128)(((u128)(u64)p[4] << 64) | (u64)p[3]), a.k_mn = p[5];
+  a.mx = (i128)(((u128)(u64)p[7] << 64) | (u64)p[6]), a.k_mx = p[8];
+  a.sum.w0 = (u64)p[9], a.sum.w1 = (u64)p[10], a.sum.w2 = (u64)p[11];
+  return a;
+}
+
+template <class T, bool STAGED, bool MARKS>
+__global__ __launch_bounds__(TAPE_BLOCK) void pip_tape_values_kernel(TapeValuesLaunch a) {
+  typedef Width<T> W;
+  constexpr int EW = W::EW;
+  extern __shared__ __attribute__((aligned(16))) i64 tape_lds[];
+  i64 *S = tape_lds;  // (slots - 1) * EW rows of TAPE_BLOCK words
+  const int tid = threadIdx.x, lane = tid & 63, nvar = a.t.nvar, cols = a.t.nparm;
+  const int words = (int)a.t.words;
+  const i64 n = a.t.n_points;
+  const i64 *prog = a.t.prog;
+  if (STAGED) {
+    i64 *L = tape_lds + (size_t)(a.t.slots - 1) * EW * TAPE_BLOCK;
+    for (int i = tid; i < words; i += TAPE_BLOCK) L[i] = a.t.prog[i];
+    prog = L;
+    __syncthreads();
+  }
+  u64 *sum = (u64 *)a.summary;
+  TapeOut none;  // (STOP: the walk writes nothing)
+  none.status = none.leaf = nullptr;
+  none.x_num = none.x_den = none.dual_num = none.dual_den = nullptr;
+  none.xs = none.ds = 0;
+  u64 cnt[4] = {0, 0, 0, 0}, first[4] = {~(u64)0, ~(u64)0, ~(u64)0, ~(u64)0};
+  ValuesAcc acc = values_identity();  // lane i: unknown i
+
+  for (i64 k0 = (i64)blockIdx.x * TAPE_BLOCK; k0 < n; k0 += (i64)gridDim.x * TAPE_BLOCK) {
+    const i64 pt = k0 + tid;
+    const bool live = pt < n;
+    box_point(a.lo, a.ext, cols, k0, tid, S);
+    const bool inside = box_inside(live, a.ctx, a.n_ctx, cols, S, tid);
+    if (EW == 2)
+      for (int j = cols - 1; j >= 0; j--) W::set_slot(S, j, tid, (T)S[j * TAPE_BLOCK + tid]);
+
+    int st = live && !inside ? PIPAMD_ST_OUTSIDE : PIPAMD_ST_NIL, leaf = -1;
+    tape_walk<T, MARKS, true>(prog, inside && words ? 0 : END, S, tid, nvar, 0, pt, none, st, leaf);
+    const bool sol = st == PIPAMD_ST_SOLUTION;  // (only a live lane inside the context walks)
+    const u64 wave_k = (u64)(k0 + (tid & ~63));
+    bool range = false;
+    for (;;) {  // (twice at most: a chunk without a RANGE lane is done)
+      ValuesAcc trial = acc;
+      const bool r = values_pass<T>(prog, S, tid, nvar, sol && !range, leaf, wave_k, trial);
+      if (!__ballot(r)) {
+        acc = trial;
+        break;
+      }
+      range = range || r;
+    }
+    if (range) st = PIPAMD_ST_RANGE;
+    const int cls = sweep_class(st);
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const u64 m = __ballot(live && cls == i);
+      if (m) {
+        const u64 k = wave_k + (u64)(__ffsll((unsigned long long)m) - 1);
+        cnt[i] += (u64)__popcll(m);
+        first[i] = k < first[i] ? k : first[i];
+      }
+    }
+  }
+
+  if (lane == 0)
+    for (int i = 0; i < 4; i++)
+      if (cnt[i]) {
+        atomicAdd(&sum[PIPAMD_SWEEP_COUNT + i], cnt[i]);
+        atomicMin(&sum[PIPAMD_SWEEP_FIRST + i], first[i]);
+      }
+  // (row 2 * blockIdx.x + wave < 2 * gridDim.x, the rows the host counted in work_bytes)
+  if (lane < nvar) values_store(a.work + (((size_t)blockIdx.x * (TAPE_BLOCK / 64) + (tid >> 6)) * nvar + lane) * TAPE_VALUES_PART, acc);
+}
+
+// Unknown blockIdx.x: the lanes stride over the `rows` partial rows, a wave merges by butterfly, the waves through LDS,
+// and thread 0 writes the record.  blockDim.x is a multiple of 64, at most TAPE_VALUES_FOLD_BLOCK.
+__global__ __launch_bounds__(TAPE_VALUES_FOLD_BLOCK) void pip_tape_values_fold_kernel(const i64 *work, int rows, int nvar, i64 *summary) {
+  __shared__ i64 part[TAPE_VALUES_FOLD_BLOCK / 64][TAPE_VALUES_PART];
+  const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  ValuesAcc acc = values_identity();
+  for (int r = tid; r < rows; r += blockDim.x) values_merge(acc, values_load(work + ((size_t)r * nvar + i) * TAPE_VALUES_PART));
+  for (int o = 32; o; o >>= 1) {
+    ValuesAcc b;
+    b.n_int = (u64)shfl_xor((i64)acc.n_int, o), b.n_frac = (u64)shfl_xor((i64)acc.n_frac, o), b.n_unb = (u64)shfl_xor((i64)acc.n_unb, o);
+    b.mn = shfl_xor(acc.mn, o), b.mx = shfl_xor(acc.mx, o);
+    b.k_mn = shfl_xor(acc.k_mn, o), b.k_mx = shfl_xor(acc.k_mx, o);
+    b.sum.w0 = (u64)shfl_xor((i64)acc.sum.w0, o), b.sum.w1 = (u64)shfl_xor((i64)acc.sum.w1, o), b.sum.w2 = (u64)shfl_xor((i64)acc.sum.w2, o);
+    values_merge(acc, b);
+  }
+  if (lane == 0) values_store(part[wave], acc);
+  __syncthreads();
+  if (tid) return;
+  for (int w = 1; w < (int)(blockDim.x >> 6); w++) values_merge(acc, values_load(part[w]));
+  i64 *rec = summary + PIPAMD_VALUES_HEAD + (size_t)PIPAMD_VALUES_REC * i;
+  const bool any = acc.n_int != 0;
+  rec[0] = (i64)acc.n_int, rec[1] = (i64)acc.n_frac, rec[2] = (i64)acc.n_unb, rec[3] = 0;
+  rec[4] = any ? (i64)(u64)(u128)acc.mn : 0, rec[5] = any ? (i64)(u64)((u128)acc.mn >> 64) : 0, rec[6] = any ? acc.k_mn : -1;
+  rec[7] = any ? (i64)(u64)(u128)acc.mx : 0, rec[8] = any ? (i64)(u64)((u128)acc.mx >> 64) : 0, rec[9] = any ? acc.k_mx : -1;
+  rec[10] = (i64)acc.sum.w0, rec[11] = (i64)acc.sum.w1, rec[12] = (i64)acc.sum.w2;
+  rec[13] = rec[14] = rec[15] = 0;
+}
+
+template <class T, bool MARKS>
+hipError_t launch_values(const TapeValuesLaunch &v, hipStream_t stream) {
+  const size_t lds = tape_slot_bytes(v.t.slots, v.t.bits) + (v.t.staged ? (size_t)v.t.words * 8 : 0);
+  void (*kernel)(TapeValuesLaunch) = v.t.staged ? pip_tape_values_kernel<T, true, MARKS> : pip_tape_values_kernel<T, false, MARKS>;
+  // the sweep's bounded persistent grid with a summary (launch_sweep_as), and no more workgroups than `work` has rows for
+  int per_cu = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, TAPE_BLOCK, lds) != hipSuccess || per_cu < 1) per_cu = 1;
+  if (per_cu > TAPE_SWEEP_WG_PER_CU_SUM) per_cu = TAPE_SWEEP_WG_PER_CU_SUM;
+  long long blocks = (long long)(v.cus > 0 ? v.cus : 1) * per_cu;
+  if (v.max_blocks > 0 && v.max_blocks < blocks) blocks = v.max_blocks;
+  blocks = tape_values_blocks(v.t.n_points, blocks);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(TAPE_BLOCK), lds, stream, v);
+  hipError_t he = hipGetLastError();
+  if (he != hipSuccess || v.t.nvar == 0) return he;
+  const int rows = (int)blocks * (TAPE_BLOCK / 64);
+  const int threads = rows >= TAPE_VALUES_FOLD_BLOCK ? TAPE_VALUES_FOLD_BLOCK : (rows + 63) / 64 * 64;
+  hipLaunchKernelGGL(pip_tape_values_fold_kernel, dim3((unsigned)v.t.nvar), dim3(threads), 0, stream, v.work, rows, v.t.nvar, v.summary);
+  return hipGetLastError();
+}
+
 template <class T, bool MARKS>
 hipError_t launch(const TapeLaunch &t, hipStream_t stream) {
   const long long blocks = (t.n_points + TAPE_BLOCK - 1) / TAPE_BLOCK;
@@ -749,6 +1033,16 @@ extern "C" hipError_t pipk_launch_tape_sweep(const TapeSweepLaunch *s, hipStream
   }
   if (s->t.marks) return s->t.bits == 128 ? launch_sweep<i128, true>(*s, stream) : launch_sweep<i64, true>(*s, stream);
   return s->t.bits == 128 ? launch_sweep<i128, false>(*s, stream) : launch_sweep<i64, false>(*s, stream);
+}
+
+extern "C" hipError_t pipk_launch_tape_values(const TapeValuesLaunch *v, hipStream_t stream) {
+  // (the caller checked: 1 <= n_points < 2^38, nvar <= PIPAMD_VALUES_MAX_NVAR, slots <= TAPE_MAX_SLOTS, a staged program
+  // within TAPE_LDS_BYTES beside the slots, `work` of tape_values_work_bytes)
+  hipLaunchKernelGGL(pip_tape_sweep_fill_kernel, dim3(1), dim3(256), 0, stream, v->summary, 0);  // the eight head words
+  const hipError_t he = hipGetLastError();
+  if (he != hipSuccess) return he;
+  if (v->t.marks) return v->t.bits == 128 ? launch_values<i128, true>(*v, stream) : launch_values<i64, true>(*v, stream);
+  return v->t.bits == 128 ? launch_values<i128, false>(*v, stream) : launch_values<i64, false>(*v, stream);
 }
 
 extern "C" hipError_t pipk_launch_tape_compare(const TapeCompareLaunch *c, hipStream_t stream) {

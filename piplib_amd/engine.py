@@ -1239,6 +1239,49 @@ class Tape:
         n = self.sweep_plan(lo, hi)["n_points"]
         return self.sweep_into(lo, hi, self.outputs(n, names), ctx, True, stream)
 
+    # ---- a sweep's values reduced per unknown (pipamd_tape_sweep_values)
+    def values_plan(self, lo, hi):
+        """values_plan() for this tape: n_points, summary_words, work_bytes, staged"""
+        return values_plan(self.info, self.bits, self.nvar, self.point_cols, lo, hi)
+
+    def sweep_values_into(self, lo, hi, summary, work, ctx=None, stream=None):
+        """pipamd_tape_sweep_values: over the box lo .. hi under the context `ctx` (box, order and rows as sweep_into has
+        them), per unknown the counts, the minimum and the maximum with the smallest k that attains them, and the exact sum
+        of the integer values handed out, into `summary`, a device int64 tensor of values_plan()["summary_words"]; `work`
+        is a device tensor of at least values_plan()["work_bytes"] bytes.  Neither needs initialising.  Returns `summary`
+        (see values_summary).  A fill and two launches on `stream` (default: torch's current), no synchronisation."""
+        t = self.torch
+        fn = _tape_fn("pipamd_tape_sweep_values", 64)
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                       C.c_size_t, C.c_void_p]
+        clo, chi = self._box(lo, hi)
+        n_ctx, cptr = 0, None
+        if ctx is not None:
+            import numpy as np
+            ctx = (ctx if t.is_tensor(ctx) else t.as_tensor(np.asarray(ctx, dtype=np.int64).reshape(-1, self.point_cols + 2))).to(device=self.dev, dtype=t.int64)
+            ctx = ctx.reshape(-1, self.point_cols + 2).contiguous()
+            n_ctx = int(ctx.shape[0])
+            cptr = C.c_void_p(ctx.data_ptr()) if n_ctx else None
+        assert summary.dtype == t.int64 and summary.is_contiguous() and summary.numel() >= 8 + 16 * self.nvar
+        assert work.is_contiguous()
+        st = C.c_void_p(stream) if stream is not None else C.c_void_p(t.cuda.current_stream(self.dev).cuda_stream)
+        rc = fn(self.e._h, self._h, clo, chi, n_ctx, self.point_cols + 2, cptr, C.c_void_p(summary.data_ptr()),
+                C.c_void_p(work.data_ptr()), work.numel() * work.element_size(), st)
+        if rc in (-1, -3):
+            raise TapeError(rc, lib().pipamd_last_error().decode())
+        _check(rc)
+        self._ctx_alive = ctx  # (the rows stay allocated until the next sweep: the launch is asynchronous)
+        return summary
+
+    def sweep_values(self, lo, hi, ctx=None, stream=None):
+        """sweep_values_into with a fresh summary and work tensor: the summary tensor (see values_summary)"""
+        t = self.torch
+        plan = self.values_plan(lo, hi)
+        summary = t.empty(plan["summary_words"], dtype=t.int64, device=self.dev)
+        work = t.empty(max(1, plan["work_bytes"] // 8), dtype=t.int64, device=self.dev)  # (never a null pointer)
+        self._work_alive = work  # (until the next call: the launches are asynchronous)
+        return self.sweep_values_into(lo, hi, summary, work, ctx, stream)
+
     # ---- two tapes compared by value at points (pipamd_tape_compare / pipamd_tape_compare_sweep)
     CMP_OUTPUTS = ("class", "where", "status_a", "status_b")
 
@@ -1347,6 +1390,54 @@ def sweep_summary(tensor, leaves):
     return {"counts": {n: w[i] for i, (n, _) in enumerate(SWEEP_STATUS)},
             "first": {n: w[4 + i] for i, (n, _) in enumerate(SWEEP_STATUS)},
             "leaf_count": w[8:8 + L], "leaf_first": w[8 + L:8 + 2 * L]}
+
+
+VALUES_MAX_NVAR, VALUES_HEAD, VALUES_REC = 64, 8, 16
+
+
+class TapeValuesPlan(C.Structure):
+    """struct pipamd_tape_values_plan"""
+    _fields_ = [("n_points", C.c_int64), ("summary_words", C.c_int64), ("work_bytes", C.c_int64), ("staged", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+def values_plan(info, bits, nvar, point_cols, lo, hi):
+    """pipamd_tape_sweep_values_plan: {"n_points", "summary_words", "work_bytes", "staged"} for a tape with `info` (the
+    dict of tape_check, or a TapeInfo) and `nvar` unknowns swept over the box lo .. hi, or TapeError where it is refused.
+    Host only."""
+    fn = _tape_fn("pipamd_tape_sweep_values_plan", 64)
+    fn.argtypes = [C.POINTER(TapeInfo), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(TapeValuesPlan)]
+    if isinstance(info, dict):
+        info = TapeInfo(**{k: int(v) for k, v in info.items()})
+    n = max(1, len(lo))
+    clo, chi = (C.c_int64 * n)(*[int(v) for v in lo]), (C.c_int64 * n)(*[int(v) for v in hi])
+    plan = TapeValuesPlan()
+    rc = fn(C.byref(info), int(bits), int(nvar), int(point_cols), clo, chi, C.byref(plan))
+    if rc != 0:
+        raise TapeError(rc, lib().pipamd_last_error().decode())
+    return {"n_points": int(plan.n_points), "summary_words": int(plan.summary_words), "work_bytes": int(plan.work_bytes),
+            "staged": int(plan.staged)}
+
+
+def _signed(limbs):
+    """little-endian int64 limbs of a two's complement number as a Python int"""
+    v = sum((int(w) & ((1 << 64) - 1)) << (64 * i) for i, w in enumerate(limbs))
+    return v - (1 << (64 * len(limbs))) if v >> (64 * len(limbs) - 1) else v
+
+
+def values_summary(tensor, nvar):
+    """the summary of sweep_values (device or host int64 tensor, or a sequence) in Python ints: counts and first by status
+    name as sweep_summary has them, and "unknowns": per unknown a dict with n_int, n_frac, n_unbounded, min, k_min, max,
+    k_max, sum"""
+    w = [int(v) for v in (tensor.cpu().tolist() if hasattr(tensor, "cpu") else tensor)]
+    assert len(w) >= VALUES_HEAD + VALUES_REC * int(nvar)
+    out = {"counts": {n: w[i] for i, (n, _) in enumerate(SWEEP_STATUS)},
+           "first": {n: w[4 + i] for i, (n, _) in enumerate(SWEEP_STATUS)}, "unknowns": []}
+    for i in range(int(nvar)):
+        r = w[VALUES_HEAD + VALUES_REC * i:VALUES_HEAD + VALUES_REC * (i + 1)]
+        out["unknowns"].append({"n_int": r[0], "n_frac": r[1], "n_unbounded": r[2], "min": _signed(r[4:6]), "k_min": r[6],
+                                "max": _signed(r[7:9]), "k_max": r[9], "sum": _signed(r[10:13])})
+    return out
 
 
 # pipamd_tape_compare: the class of a point (PIPAMD_CMP_*), the summary's words, the flag
