@@ -1044,6 +1044,64 @@ int pipamd_tape_sweep_values(pipamd_engine *e, const pipamd_tape *t, const int64
                              int ctx_cols, const int64_t *d_ctx, int64_t *d_summary, void *d_work, size_t work_bytes,
                              void *stream);
 
+/* Every tape of a set swept over its own box in one launch (added since interface version 500): the census per answer
+ * of pipamd_pip_solve_many's many small problems -- over this problem's parameter box, under the context it was solved
+ * with, how many points have a solution, how many are NIL, which leaves are reached and where first.  A JOB is a tape of
+ * a set, a box and a context; a launch takes any number of jobs and writes one pipamd_tape_sweep summary per job.
+ * Meaning: with summary_off as below, words summary_off[j] .. summary_off[j + 1] - 1 of the summary are the
+ * PIPAMD_SWEEP_WORDS(L_j) words pipamd_tape_sweep writes for job j's tape, box and context, bit for bit: k counts inside
+ * the job's own box, and the statuses, the RANGE rules, the edit marks, the empty tape (every inside point NIL, leaf -1)
+ * and the exact context test are the single sweep's.  Nothing per point is written: values per point of a set are what
+ * pipamd_tape_set_eval is for.  A tape may appear in several jobs -- a large box cut into tiles, whose summaries merge by
+ * adding the counts and taking the smallest first + offset -- and tapes may be left out.
+ *
+ * pipamd_tape_set_tape_info: what the set keeps of tape i on the host -- its pipamd_tape_info as compiled (leaves sizes
+ * the summary), pipamd_tape_point_cols, nvar and ndual; each output may be NULL.  PIPAMD_E_INVALID: a null set, i outside
+ * 0 .. n - 1.
+ *
+ * pipamd_tape_set_sweep_plan is host only: it needs neither an engine nor a GPU.  leaves[j] and point_cols[j] are those
+ * of job j's tape (the planner does not read jobs[j].tape).  points[j]: the product of the extents of job j's box, 1
+ * for 0 columns.  summary_off[0 .. n_jobs]: the running sums of PIPAMD_SWEEP_WORDS(leaves[j]); summary_off[n_jobs] words
+ * is the summary a run needs.  chunk_off[0 .. n_jobs] (may be NULL): the running sums of ceil(points[j] / 128), the
+ * units of work the kernel deals out.  Products and sums are formed without wrapping.  PIPAMD_E_INVALID, naming the
+ * job: whatever pipamd_tape_sweep_plan refuses of a box (point_cols outside 0 .. PIPAMD_TAPE_MAX_SLOTS - 1, null lo or
+ * hi with point_cols > 0, any lo[c] > hi[c]); n_ctx < 0; a null ctx with n_ctx > 0; leaves[j] outside 0 .. 2^31 - 1;
+ * and n_jobs < 0, a null summary_off, and with n_jobs > 0 a null jobs, leaves, point_cols or points.
+ * PIPAMD_E_TOOLARGE: more than 2^20 jobs (answered before any array is read); a job of 2^38 points or more; all jobs
+ * up to some job together reaching 2^38 points.  Jobs are checked in order and the first refusal is the answer.
+ *
+ * pipamd_tape_set_sweep_create runs the planner's checks with the set's own leaves and point_cols and also refuses,
+ * PIPAMD_E_INVALID: a null engine, set or `out`; a set of another device than the engine's; jobs[j].tape outside
+ * 0 .. n - 1 -- all before any HIP call.  It then copies everything the kernel needs per job -- the tape's table index,
+ * lo and the extents, n_ctx and the context rows (ragged: job j's rows have its own point_cols + 2 columns), the point
+ * count, the summary offset, leaves, the chunk prefix -- into ONE device buffer.  The host arrays may be freed when the
+ * call returns; the object is immutable; the SET MUST OUTLIVE IT.  summary_off (n_jobs + 1 values, may be NULL) is the
+ * planner's.  n_jobs == 0 is legal.  Free with pipamd_tape_set_sweep_free (NULL is allowed), not while a run is still
+ * on a stream.
+ *
+ * pipamd_tape_set_sweep_run: a fill of the summary_off[n_jobs] words of d_summary (counts 0, firsts -1, per job) and one
+ * kernel on `stream`; no synchronisation and no per-call host table, so it may run concurrently on several streams
+ * with different summaries; two calls do not accumulate.  n_jobs == 0: PIPAMD_OK without a launch.  PIPAMD_E_INVALID
+ * before any HIP call: a null engine or sweep, a sweep of another device, a null d_summary with n_jobs > 0.
+ * pipamd_debug_tape_sweep_blocks bounds this grid too.  Every figure is an order-independent integer (64-bit adds and
+ * unsigned minima): the summary is deterministic. */
+typedef struct pipamd_tape_sweep_job {
+  int32_t tape;       /* index into the set */
+  int32_t n_ctx;      /* rows of this job's context */
+  const int64_t *lo;  /* HOST, pipamd_tape_point_cols of that tape values, inclusive; NULL allowed when 0 columns */
+  const int64_t *hi;
+  const int64_t *ctx; /* HOST, n_ctx x (point_cols + 2): marker, coefficients, constant, as ineqpar; NULL when n_ctx == 0 */
+} pipamd_tape_sweep_job; /* 32 bytes, offsets 0 4 8 16 24 */
+typedef struct pipamd_tape_set_sweep pipamd_tape_set_sweep;
+int pipamd_tape_set_tape_info(const pipamd_tape_set *s, int i, pipamd_tape_info *info, int32_t *point_cols, int32_t *nvar,
+                              int32_t *ndual);
+int pipamd_tape_set_sweep_plan(int n_jobs, const pipamd_tape_sweep_job *jobs, const int64_t *leaves, const int32_t *point_cols,
+                               int64_t *points, int64_t *summary_off, int64_t *chunk_off);
+int pipamd_tape_set_sweep_create(pipamd_engine *e, const pipamd_tape_set *s, int n_jobs, const pipamd_tape_sweep_job *jobs,
+                                 pipamd_tape_set_sweep **out, int64_t *summary_off);
+int pipamd_tape_set_sweep_run(pipamd_engine *e, const pipamd_tape_set_sweep *w, int64_t *d_summary, void *stream);
+void pipamd_tape_set_sweep_free(pipamd_tape_set_sweep *w);
+
 #ifdef __cplusplus
 }
 #endif

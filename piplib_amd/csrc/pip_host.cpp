@@ -1595,6 +1595,8 @@ struct pipamd_tape_set {
   pipamd_tape_set_info info;
   long long *d_prog;      // info.words words: the programs one behind the other, else targets relocated
   TapeSetEntry *d_table;  // info.n entries
+  TapeSetEntry *h_table;     // the same entries on the host, and every tape's own counts (pipamd_tape_set_tape_info,
+  pipamd_tape_info *h_info;  // pipamd_tape_set_sweep_create)
 };
 
 extern "C" int pipamd_tape_set_create(pipamd_engine *e, int n, const pipamd_tape *const *tapes, pipamd_tape_set **out,
@@ -1666,6 +1668,16 @@ extern "C" int pipamd_tape_set_create(pipamd_engine *e, int n, const pipamd_tape
   s->device = e->device;
   s->bits = I.bits;
   s->info = I;
+  s->h_table = (TapeSetEntry *)malloc((size_t)n * sizeof(TapeSetEntry));
+  s->h_info = (pipamd_tape_info *)malloc((size_t)n * sizeof(pipamd_tape_info));
+  if (!s->h_table || !s->h_info) {
+    free(s->h_table);
+    free(s->h_info);
+    free(s);
+    return PIPAMD_E_NOMEM;
+  }
+  memcpy(s->h_table, table.data(), (size_t)n * sizeof(TapeSetEntry));
+  for (int i = 0; i < n; i++) s->h_info[i] = tapes[i]->info;
   hipError_t he = hipMalloc((void **)&s->d_table, (size_t)n * sizeof(TapeSetEntry));
   if (he == hipSuccess) he = hipMemcpy(s->d_table, table.data(), (size_t)n * sizeof(TapeSetEntry), hipMemcpyHostToDevice);
   if (he == hipSuccess && I.words) he = hipMalloc((void **)&s->d_prog, (size_t)I.words * 8);
@@ -1674,6 +1686,8 @@ extern "C" int pipamd_tape_set_create(pipamd_engine *e, int n, const pipamd_tape
     pipamd_set_error("tape_set_create: %d tapes, %lld words on the device: %s", n, (long long)I.words, hipGetErrorString(he));
     if (s->d_table) hipFree(s->d_table);
     if (s->d_prog) hipFree(s->d_prog);
+    free(s->h_table);
+    free(s->h_info);
     free(s);
     return PIPAMD_E_HIP;
   }
@@ -1688,6 +1702,8 @@ extern "C" void pipamd_tape_set_free(pipamd_tape_set *s) {
     if (s->d_prog) hipFree(s->d_prog);
     if (s->d_table) hipFree(s->d_table);
   }
+  free(s->h_table);
+  free(s->h_info);
   free(s);
 }
 
@@ -1725,6 +1741,190 @@ extern "C" int pipamd_tape_set_eval(pipamd_engine *e, const pipamd_tape_set *s, 
   L.dual_num = d_dual_num;
   L.dual_den = d_dual_den;
   HIPCHK(pipk_launch_tape_set_eval(&L, (hipStream_t)stream));
+  return PIPAMD_OK;
+}
+
+extern "C" int pipamd_tape_set_tape_info(const pipamd_tape_set *s, int i, pipamd_tape_info *info, int32_t *point_cols,
+                                         int32_t *nvar, int32_t *ndual) {
+  if (!s || i < 0 || i >= s->info.n) {
+    pipamd_set_error("tape_set_tape_info: a null set, or tape %d outside 0 .. n - 1", i);
+    return PIPAMD_E_INVALID;
+  }
+  if (info) *info = s->h_info[i];
+  if (point_cols) *point_cols = s->h_table[i].point_cols;
+  if (nvar) *nvar = s->h_table[i].nvar;
+  if (ndual) *ndual = s->h_table[i].ndual;
+  return PIPAMD_OK;
+}
+
+// ------------------------------------------------------------------ every tape of a set swept over its own box
+enum { TAPE_SET_SWEEP_MAX_JOBS = 1 << 20 };
+// The checks and the arithmetic the planner and pipamd_tape_set_sweep_create share: per job the box (tape_sweep_box)
+// and the context's shape; the running sums of points, summary words and chunks, none of which can wrap: fewer than
+// 2^38 points in all, at most 2^20 jobs, a tape's leaves below 2^31 as its program's words are.  Each output may be NULL.
+static int tape_set_sweep_check(const char *who, int n_jobs, const pipamd_tape_sweep_job *jobs, const int64_t *leaves,
+                                const int32_t *point_cols, int64_t *points, int64_t *summary_off, int64_t *chunk_off) {
+  if (n_jobs < 0 || (n_jobs > 0 && (!jobs || !leaves || !point_cols))) {
+    pipamd_set_error("%s: n_jobs < 0, or jobs without their array, leaves or point_cols", who);
+    return PIPAMD_E_INVALID;
+  }
+  if (n_jobs > TAPE_SET_SWEEP_MAX_JOBS) {
+    pipamd_set_error("%s: %d jobs, at most 2^20 a call", who, n_jobs);
+    return PIPAMD_E_TOOLARGE;
+  }
+  int64_t all = 0, words = 0, chunks = 0;
+  if (summary_off) summary_off[0] = 0;
+  if (chunk_off) chunk_off[0] = 0;
+  for (int j = 0; j < n_jobs; j++) {
+    char job[96];
+    snprintf(job, sizeof job, "%s: job %d", who, j);
+    const pipamd_tape_sweep_job &q = jobs[j];
+    if (q.n_ctx < 0 || (q.n_ctx > 0 && !q.ctx) || leaves[j] < 0 || leaves[j] >= (1ll << 31)) {
+      pipamd_set_error("%s: n_ctx < 0, context rows without an array, or leaves outside 0 .. 2^31 - 1", job);
+      return PIPAMD_E_INVALID;
+    }
+    int64_t n = 0;
+    const int rc = tape_sweep_box(job, point_cols[j], q.lo, q.hi, nullptr, &n);
+    if (rc) return rc;
+    all += n;
+    if (all >= (1ll << 38)) {
+      pipamd_set_error("%s: 2^38 points or more in the jobs up to this one (at most 2^38 - 1 a call)", job);
+      return PIPAMD_E_TOOLARGE;
+    }
+    words += PIPAMD_SWEEP_WORDS(leaves[j]);
+    chunks += (n + TAPE_BLOCK - 1) / TAPE_BLOCK;
+    if (points) points[j] = n;
+    if (summary_off) summary_off[j + 1] = words;
+    if (chunk_off) chunk_off[j + 1] = chunks;
+  }
+  return PIPAMD_OK;
+}
+
+extern "C" int pipamd_tape_set_sweep_plan(int n_jobs, const pipamd_tape_sweep_job *jobs, const int64_t *leaves,
+                                          const int32_t *point_cols, int64_t *points, int64_t *summary_off, int64_t *chunk_off) {
+  if (!summary_off || (n_jobs > 0 && !points)) {
+    pipamd_set_error("tape_set_sweep_plan: null summary_off, or jobs without points");
+    return PIPAMD_E_INVALID;
+  }
+  return tape_set_sweep_check("tape_set_sweep_plan", n_jobs, jobs, leaves, point_cols, points, summary_off, chunk_off);
+}
+
+struct pipamd_tape_set_sweep {
+  const pipamd_tape_set *set;
+  int device, n_jobs, blocks;
+  long long chunks, words;
+  long long *d_buf;  // the buffer pip_tape.h describes (TapeSetSweepLaunch)
+};
+
+extern "C" int pipamd_tape_set_sweep_create(pipamd_engine *e, const pipamd_tape_set *s, int n_jobs,
+                                            const pipamd_tape_sweep_job *jobs, pipamd_tape_set_sweep **out, int64_t *summary_off) {
+  if (out) *out = nullptr;
+  if (!e || !s || !out || s->device != e->device) {
+    pipamd_set_error("tape_set_sweep_create: null engine, set or result pointer, or a set of another device");
+    return PIPAMD_E_INVALID;
+  }
+  if (n_jobs < 0 || (n_jobs > 0 && !jobs)) {
+    pipamd_set_error("tape_set_sweep_create: n_jobs < 0, or jobs without their array");
+    return PIPAMD_E_INVALID;
+  }
+  if (n_jobs > TAPE_SET_SWEEP_MAX_JOBS) {
+    pipamd_set_error("tape_set_sweep_create: %d jobs, at most 2^20 a call", n_jobs);
+    return PIPAMD_E_TOOLARGE;
+  }
+  std::vector<int64_t> leaves((size_t)n_jobs), points((size_t)n_jobs), sum_off((size_t)n_jobs + 1), chunk_off((size_t)n_jobs + 1);
+  std::vector<int32_t> cols((size_t)n_jobs);
+  for (int j = 0; j < n_jobs; j++) {
+    const int t = jobs[j].tape;
+    if (t < 0 || t >= s->info.n) {
+      pipamd_set_error("tape_set_sweep_create: job %d: tape %d outside 0 .. %d", j, t, s->info.n - 1);
+      return PIPAMD_E_INVALID;
+    }
+    leaves[j] = s->h_info[t].leaves;
+    cols[j] = s->h_table[t].point_cols;
+  }
+  const int rc = tape_set_sweep_check("tape_set_sweep_create", n_jobs, jobs, leaves.data(), cols.data(), points.data(),
+                                      sum_off.data(), chunk_off.data());
+  if (rc) return rc;
+  // the buffer: chunk_off, summary_off, the jobs' records, then per job lo, extents and context rows
+  const size_t head = 2 * ((size_t)n_jobs + 1) + (size_t)n_jobs * (sizeof(TapeSetSweepJob) / 8);
+  size_t total = head;
+  for (int j = 0; j < n_jobs; j++) total += 2 * (size_t)cols[j] + (size_t)jobs[j].n_ctx * ((size_t)cols[j] + 2);
+  std::vector<long long> buf(total);
+  TapeSetSweepJob *rec = (TapeSetSweepJob *)(buf.data() + 2 * ((size_t)n_jobs + 1));
+  size_t at = head;
+  for (int j = 0; j <= n_jobs; j++) buf[(size_t)j] = chunk_off[j], buf[(size_t)n_jobs + 1 + j] = sum_off[j];
+  for (int j = 0; j < n_jobs; j++) {
+    const pipamd_tape_sweep_job &q = jobs[j];
+    TapeSetSweepJob &r = rec[j];
+    memset(&r, 0, sizeof r);
+    r.tape = q.tape;
+    r.n_ctx = q.n_ctx;
+    r.box = (long long)at;
+    for (int c = 0; c < cols[j]; c++) {
+      buf[at + c] = q.lo[c];
+      buf[at + cols[j] + c] = (long long)((unsigned long long)q.hi[c] - (unsigned long long)q.lo[c] + 1);  // (below 2^38)
+    }
+    at += 2 * (size_t)cols[j];
+    r.ctx = (long long)at;
+    const size_t ctx_words = (size_t)q.n_ctx * ((size_t)cols[j] + 2);
+    if (ctx_words) memcpy(&buf[at], q.ctx, ctx_words * 8);
+    at += ctx_words;
+    r.n_points = points[j];
+    r.summary_off = sum_off[j];
+    r.leaves = leaves[j];
+    r.chunk_off = chunk_off[j];
+  }
+  if (hipSetDevice(e->device) != hipSuccess) return PIPAMD_E_HIP;
+  pipamd_tape_set_sweep *w = (pipamd_tape_set_sweep *)calloc(1, sizeof *w);
+  if (!w) return PIPAMD_E_NOMEM;
+  w->set = s;
+  w->device = e->device;
+  w->n_jobs = n_jobs;
+  w->chunks = chunk_off[n_jobs];
+  w->words = sum_off[n_jobs];
+  if (n_jobs) {
+    w->blocks = pipk_tape_set_sweep_blocks(s->bits, s->info.slots, e->cus);
+    hipError_t he = hipMalloc((void **)&w->d_buf, total * 8);
+    if (he == hipSuccess) he = hipMemcpy(w->d_buf, buf.data(), total * 8, hipMemcpyHostToDevice);
+    if (he != hipSuccess) {
+      pipamd_set_error("tape_set_sweep_create: %d jobs, %zu words on the device: %s", n_jobs, total, hipGetErrorString(he));
+      if (w->d_buf) hipFree(w->d_buf);
+      free(w);
+      return PIPAMD_E_HIP;
+    }
+  }
+  if (summary_off) memcpy(summary_off, sum_off.data(), ((size_t)n_jobs + 1) * 8);
+  *out = w;
+  return PIPAMD_OK;
+}
+
+extern "C" void pipamd_tape_set_sweep_free(pipamd_tape_set_sweep *w) {
+  if (!w) return;
+  if (w->d_buf && hipSetDevice(w->device) == hipSuccess) hipFree(w->d_buf);
+  free(w);
+}
+
+extern "C" int pipamd_tape_set_sweep_run(pipamd_engine *e, const pipamd_tape_set_sweep *w, int64_t *d_summary, void *stream) {
+  if (!e || !w || w->device != e->device || (w->n_jobs > 0 && !d_summary)) {
+    pipamd_set_error("tape_set_sweep_run: null engine or sweep, a sweep of another device, or jobs without a summary");
+    return PIPAMD_E_INVALID;
+  }
+  if (w->n_jobs == 0) return PIPAMD_OK;
+  if (hipSetDevice(e->device) != hipSuccess) return PIPAMD_E_HIP;
+  TapeSetSweepLaunch L;
+  memset(&L, 0, sizeof L);
+  L.prog = w->set->d_prog;
+  L.table = w->set->d_table;
+  L.buf = w->d_buf;
+  L.n_jobs = w->n_jobs;
+  L.bits = w->set->bits;
+  L.slots = w->set->info.slots;
+  L.blocks = w->blocks;
+  L.max_blocks = g_tape_sweep_blocks;
+  L.chunks = w->chunks;
+  L.words = w->words;
+  L.summary = (long long *)d_summary;
+  HIPCHK(pipk_launch_tape_set_sweep(&L, (hipStream_t)stream));
   return PIPAMD_OK;
 }
 

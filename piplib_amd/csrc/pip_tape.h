@@ -157,7 +157,43 @@ struct TapeValuesLaunch {
   unsigned long long ext[TAPE_MAX_SLOTS - 1];
 };
 
+// pipamd_tape_set_sweep_run: every job -- a tape of a set, a box, a context -- swept in one launch, a summary per job.
+// Everything a job needs lies in ONE device buffer of 8-byte words that pipamd_tape_set_sweep_create fills once:
+//     chunk_off[n_jobs + 1]    the chunks of TAPE_BLOCK consecutive k before job j; the last word is all chunks
+//     summary_off[n_jobs + 1]  the summary words before job j; the last word is all words
+//     n_jobs x TapeSetSweepJob
+//     per job: lo[cols], ext[cols], then its n_ctx context rows of cols + 2 words (cols: the tape's point_cols) -- ragged
+// Offsets inside the buffer count words from its start.  A chunk never spans jobs: chunk c belongs to the job j with
+// chunk_off[j] <= c < chunk_off[j + 1] and holds the k from (c - chunk_off[j]) * TAPE_BLOCK on, inside job j's own box.
+// The sweep's bounded persistent grid (TAPE_SWEEP_WG_PER_CU_SUM) takes the chunks 0 .. chunk_off[n_jobs] - 1 in grid
+// stride; the programs are read from the set's buffer in global memory as pip_tape_set_eval_kernel reads them.
+struct TapeSetSweepJob {
+  int tape, n_ctx;       // index into the set's table; rows of the context
+  long long box;         // word of lo[0]; ext[0] is `cols` words behind
+  long long ctx;         // word of the first context row
+  long long n_points;    // prod ext[c], 1 .. 2^38 - 1
+  long long summary_off; // first word of the job's PIPAMD_SWEEP_WORDS(leaves) in the summary
+  long long leaves;
+  long long chunk_off;   // chunk_off[j]
+  long long pad;
+};  // 64 bytes
+struct TapeSetSweepLaunch {
+  const long long *prog;      // device; the set's programs
+  const TapeSetEntry *table;  // device; the set's table
+  const long long *buf;       // device; the buffer above
+  int n_jobs, bits, slots;    // slots: the set's, the LDS rows
+  int blocks;                 // pipk_tape_set_sweep_blocks of the set: what the device holds at once
+  int max_blocks;             // testing aid, as in TapeSweepLaunch
+  int pad;
+  long long chunks, words;    // chunk_off[n_jobs], summary_off[n_jobs]
+  long long *summary;         // device; `words` words, initialised by the launch
+};
+
 extern "C" {
+// workgroups the device holds at once of pip_tape_set_sweep_kernel for a set of `slots` slots: the occupancy with that
+// LDS, at most TAPE_SWEEP_WG_PER_CU_SUM a compute unit
+int pipk_tape_set_sweep_blocks(int bits, int slots, int cus);
+hipError_t pipk_launch_tape_set_sweep(const TapeSetSweepLaunch *t, hipStream_t stream);
 hipError_t pipk_launch_tape_values(const TapeValuesLaunch *t, hipStream_t stream);
 hipError_t pipk_launch_tape_compare(const TapeCompareLaunch *t, hipStream_t stream);
 hipError_t pipk_launch_tape_sweep(const TapeSweepLaunch *t, hipStream_t stream);

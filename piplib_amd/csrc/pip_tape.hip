@@ -1013,7 +1013,160 @@ hipError_t launch_set(const TapeSetLaunch &t, hipStream_t stream) {
                      tape_slot_bytes(t.slots, t.bits), stream, t);
   return hipGetLastError();
 }
+
+// ------------------------------------------------------------------ pipamd_tape_set_sweep_run
+// The jobs of a set swept in one launch (TapeSetSweepLaunch, pip_tape.h).  gridDim.x persistent workgroups take the
+// chunks of ALL jobs in grid stride.  The job of a chunk is found by bisection of chunk_off: a workgroup's chunk indices
+// only grow, and by gridDim.x a step, so -- every job being a chunk at least -- its job lies between the previous one
+// and gridDim.x jobs further on: at most 12 steps, none while it stays in a job of many chunks.  The index goes through
+// readfirstlane, so the job's record, the tape's table entry, lo, the extents and the context rows are all read at
+// wave-uniform addresses, from the buffer and not from the arguments.
+// Both waves of a workgroup are on one tape: the chunk is decoded, tested and walked as pip_tape_sweep_kernel does it
+// on the global-memory path, the walk starting at the tape's first word as in pip_tape_set_eval_kernel.  A lane touches
+// its own column of the slot rows alone and a tape reads no slot it has not written, so nothing is cleared between jobs.
+// Summary: no LDS bins.  The per-leaf figures go to the job's words by the wave-aggregated atomics of the sweep's
+// unbinned path.  The status figures stay wave-uniform accumulators while the workgroup stays in a job and are flushed
+// -- lanes 0 .. 3, one atomic instruction pair -- when it moves to another and at the end.
+__global__ void pip_tape_set_sweep_fill_kernel(i64 *sum, const i64 *summary_off, const TapeSetSweepJob *jobs, int n_jobs, i64 words) {
+  for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += (i64)gridDim.x * blockDim.x) {
+    int lo = 0, hi = n_jobs - 1;  // the job with summary_off[lo] <= i < summary_off[lo + 1]
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (summary_off[mid] <= i) lo = mid;
+      else hi = mid - 1;
+    }
+    sum[i] = sweep_zero_word(i - summary_off[lo], jobs[lo].leaves) ? 0 : -1;
+  }
+}
+
+// (the figures by value: selected through pointers they would be an indexed array, which lives in scratch)
+__device__ __forceinline__ void sweep_flush_status(u64 *to, u64 c0, u64 c1, u64 c2, u64 c3, u64 f0, u64 f1, u64 f2, u64 f3, int lane) {
+  if (lane < 4) {
+    const u64 c = lane == 0 ? c0 : (lane == 1 ? c1 : (lane == 2 ? c2 : c3));
+    const u64 f = lane == 0 ? f0 : (lane == 1 ? f1 : (lane == 2 ? f2 : f3));
+    if (c) {
+      atomicAdd(&to[PIPAMD_SWEEP_COUNT + lane], c);
+      atomicMin(&to[PIPAMD_SWEEP_FIRST + lane], f);
+    }
+  }
+}
+
+template <class T>
+__global__ __launch_bounds__(TAPE_BLOCK) void pip_tape_set_sweep_kernel(TapeSetSweepLaunch a) {
+  typedef Width<T> W;
+  constexpr int EW = W::EW;
+  extern __shared__ __attribute__((aligned(16))) i64 tape_lds[];
+  i64 *S = tape_lds;  // (a.slots - 1) * EW rows of TAPE_BLOCK words
+  const int tid = threadIdx.x, lane = tid & 63;
+  const i64 *chunk_off = a.buf;
+  const TapeSetSweepJob *jobs = (const TapeSetSweepJob *)(a.buf + 2 * ((i64)a.n_jobs + 1));
+  u64 *sum = (u64 *)a.summary;
+  TapeOut none;  // (a summary alone: the walk writes nothing)
+  none.status = none.leaf = nullptr;
+  none.x_num = none.x_den = none.dual_num = none.dual_den = nullptr;
+  none.xs = none.ds = 0;
+  u64 cnt[4] = {0, 0, 0, 0}, first[4] = {~(u64)0, ~(u64)0, ~(u64)0, ~(u64)0};
+  int j = 0;        // the workgroup's job
+  i64 counted = -1;  // the summary offset of the job cnt and first are of; -1: they are of none
+
+  for (i64 c = blockIdx.x; c < a.chunks; c += gridDim.x) {
+    int lo = j, hi = (int)((i64)j + gridDim.x < (i64)a.n_jobs - 1 ? (i64)j + gridDim.x : (i64)a.n_jobs - 1);
+    if (c < chunk_off[j + 1]) hi = j;  // (still in the job it was in)
+    while (lo < hi) {
+      const int mid = (int)(((i64)lo + hi + 1) >> 1);
+      if (chunk_off[mid] <= c) lo = mid;
+      else hi = mid - 1;
+    }
+    j = __builtin_amdgcn_readfirstlane(lo);
+    const TapeSetSweepJob *J = jobs + j;
+    const TapeSetEntry *e = a.table + J->tape;
+    const i64 off = J->summary_off;
+    if (counted != off) {  // (wave-uniform) another job: what the wave counted belongs to the one it leaves
+      if (counted >= 0) sweep_flush_status(sum + counted, cnt[0], cnt[1], cnt[2], cnt[3], first[0], first[1], first[2], first[3], lane);
+#pragma unroll
+      for (int i = 0; i < 4; i++) cnt[i] = 0, first[i] = ~(u64)0;
+      counted = off;
+    }
+    const int cols = e->point_cols;
+    const i64 *box = a.buf + J->box;
+    const i64 n = J->n_points, L = J->leaves, k0 = (c - J->chunk_off) * TAPE_BLOCK, pt = k0 + tid;
+    const bool live = pt < n;
+    box_point(box, (const u64 *)(box + cols), cols, k0, tid, S);
+    const bool inside = box_inside(live, a.buf + J->ctx, J->n_ctx, cols, S, tid);
+    if (EW == 2)
+      for (int q = cols - 1; q >= 0; q--) W::set_slot(S, q, tid, (T)S[q * TAPE_BLOCK + tid]);
+
+    int st = live && !inside ? PIPAMD_ST_OUTSIDE : PIPAMD_ST_NIL, leaf = -1;
+    tape_walk<T, true>(a.prog, inside && e->words ? e->start : END, S, tid, e->nvar, e->ndual, pt, none, st, leaf);
+
+    const int cls = sweep_class(st);
+    const u64 wave_k = (u64)(k0 + (tid & ~63));
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const u64 m = __ballot(live && cls == i);
+      if (m) {
+        const u64 k = wave_k + (u64)(__ffsll((unsigned long long)m) - 1);
+        cnt[i] += (u64)__popcll(m);
+        first[i] = k < first[i] ? k : first[i];
+      }
+    }
+    // per leaf, as pip_tape_sweep_kernel without bins: the lowest lane of every group adds (size, its k)
+    u64 pend = __ballot(live && leaf >= 0);
+    int group = 0;
+    bool leader = false;
+    while (pend) {
+      const int src = __ffsll((unsigned long long)pend) - 1;
+      const int l = __builtin_amdgcn_readlane(leaf, src);
+      const u64 m = __ballot(live && leaf == l);
+      if (live && leaf == l) {
+        group = __popcll(m);
+        leader = lane == src;
+      }
+      pend &= ~m;
+    }
+    if (leader && (u64)leaf < (u64)L) {  // (a compiled program's ordinals are below L; nothing is written beyond)
+      u64 *to = sum + off;
+      atomicAdd(&to[PIPAMD_SWEEP_LEAF_COUNT(L) + leaf], (u64)group);
+      atomicMin(&to[PIPAMD_SWEEP_LEAF_FIRST(L) + leaf], (u64)pt);
+    }
+  }
+  if (counted >= 0) sweep_flush_status(sum + counted, cnt[0], cnt[1], cnt[2], cnt[3], first[0], first[1], first[2], first[3], lane);
+}
+
+template <class T>
+int set_sweep_blocks(int bits, int slots, int cus) {
+  int per_cu = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, pip_tape_set_sweep_kernel<T>, TAPE_BLOCK, tape_slot_bytes(slots, bits)) != hipSuccess || per_cu < 1)
+    per_cu = 1;
+  if (per_cu > TAPE_SWEEP_WG_PER_CU_SUM) per_cu = TAPE_SWEEP_WG_PER_CU_SUM;
+  return (cus > 0 ? cus : 1) * per_cu;
+}
+template <class T>
+hipError_t launch_set_sweep(const TapeSetSweepLaunch &s, hipStream_t stream) {
+  long long blocks = s.blocks > 0 ? s.blocks : 1;
+  if (s.max_blocks > 0 && s.max_blocks < blocks) blocks = s.max_blocks;
+  if (s.chunks < blocks) blocks = s.chunks;
+  hipLaunchKernelGGL((pip_tape_set_sweep_kernel<T>), dim3((unsigned)blocks), dim3(TAPE_BLOCK), tape_slot_bytes(s.slots, s.bits), stream, s);
+  return hipGetLastError();
+}
 }  // namespace
+
+extern "C" int pipk_tape_set_sweep_blocks(int bits, int slots, int cus) {
+  return bits == 128 ? set_sweep_blocks<i128>(bits, slots, cus) : set_sweep_blocks<i64>(bits, slots, cus);
+}
+
+extern "C" hipError_t pipk_launch_tape_set_sweep(const TapeSetSweepLaunch *s, hipStream_t stream) {
+  // (pipamd_tape_set_sweep_create checked: 1 <= n_jobs <= 2^20, every tape index inside the set's table, every box of
+  // 1 .. 2^38 - 1 points and all together below 2^38, every offset inside the buffer)
+  if (s->n_jobs <= 0 || s->chunks <= 0) return hipSuccess;
+  long long fill = (s->words + 255) / 256;
+  if (fill > 65536) fill = 65536;
+  hipLaunchKernelGGL(pip_tape_set_sweep_fill_kernel, dim3((unsigned)fill), dim3(256), 0, stream, s->summary, s->buf + s->n_jobs + 1,
+                     (const TapeSetSweepJob *)(s->buf + 2 * ((long long)s->n_jobs + 1)), s->n_jobs, s->words);
+  const hipError_t he = hipGetLastError();
+  if (he != hipSuccess) return he;
+  return s->bits == 128 ? launch_set_sweep<i128>(*s, stream) : launch_set_sweep<i64>(*s, stream);
+}
 
 extern "C" hipError_t pipk_launch_tape_eval(const TapeLaunch *t, hipStream_t stream) {
   if (t->n_points <= 0) return hipSuccess;

@@ -1565,3 +1565,128 @@ class TapeSet:
         names = self.OUTPUTS if self.ndual else self.OUTPUTS[:4]
         out = self.eval_into(idx, pts, self.outputs(n, names), stream)
         return tuple(out[k] for k in names)
+
+    def tape_info(self, i):
+        """pipamd_tape_set_tape_info: what the set keeps of tape i -- the dict of its pipamd_tape_info with point_cols,
+        nvar and ndual beside it -- or TapeError for an index outside the set"""
+        fn = _tape_fn("pipamd_tape_set_tape_info", 64)
+        fn.argtypes = [C.c_void_p, C.c_int, C.POINTER(TapeInfo)] + [C.POINTER(C.c_int32)] * 3
+        info, cols, nvar, ndual = TapeInfo(), C.c_int32(), C.c_int32(), C.c_int32()
+        rc = fn(self._h, int(i), C.byref(info), C.byref(cols), C.byref(nvar), C.byref(ndual))
+        if rc != 0:
+            raise TapeError(rc, lib().pipamd_last_error().decode())
+        return dict(info.as_dict(), point_cols=cols.value, nvar=nvar.value, ndual=ndual.value)
+
+    def sweep_jobs(self, jobs):
+        """pipamd_tape_set_sweep_create: jobs is a list of (tape, lo, hi, ctx or None) -- a tape index of the set, the
+        inclusive bounds of a box of that tape's point_cols values, and None or (n_ctx, point_cols + 2) PolyLib rows on
+        the host.  Returns a TapeSetSweep (which keeps this set alive), or TapeError where a job is refused."""
+        return TapeSetSweep(self, jobs)
+
+
+class TapeSweepJob(C.Structure):
+    """pipamd_tape_sweep_job"""
+    _fields_ = [("tape", C.c_int32), ("n_ctx", C.c_int32), ("lo", C.c_void_p), ("hi", C.c_void_p), ("ctx", C.c_void_p)]
+
+
+def _sweep_jobs(jobs, point_cols):
+    """[(tape, lo, hi, ctx or None)] -> (array of TapeSweepJob, the host arrays it points into).  point_cols(j): the
+    columns of job j's tape, or None where it is not known (the rows are then taken as they are shaped)"""
+    import numpy as np
+    arr, keep = (TapeSweepJob * max(1, len(jobs)))(), []
+    for j, (tape, lo, hi, ctx) in enumerate(jobs):
+        lo, hi = [int(v) for v in lo], [int(v) for v in hi]
+        assert len(lo) == len(hi), "a box has as many bounds on either side"
+        cols = point_cols(j)
+        n = max(1, len(lo))
+        clo, chi = (C.c_int64 * n)(*lo), (C.c_int64 * n)(*hi)
+        keep += [clo, chi]
+        arr[j].tape, arr[j].n_ctx = int(tape), 0
+        arr[j].lo, arr[j].hi = C.addressof(clo), C.addressof(chi)
+        if ctx is not None and len(ctx):
+            rows = np.ascontiguousarray(np.asarray(ctx, dtype=np.int64).reshape(-1, (len(lo) if cols is None else cols) + 2))
+            keep.append(rows)
+            arr[j].n_ctx, arr[j].ctx = int(rows.shape[0]), rows.ctypes.data
+    return arr, keep
+
+
+def set_sweep_plan(jobs, leaves, point_cols):
+    """pipamd_tape_set_sweep_plan for jobs [(tape, lo, hi, ctx or None)] whose tapes have leaves[j] leaves and
+    point_cols[j] point columns: {"points": [...], "summary_off": [...], "chunk_off": [...]}, or TapeError where a job is
+    refused.  Host only."""
+    fn = _tape_fn("pipamd_tape_set_sweep_plan", 64)
+    fn.argtypes = [C.c_int] + [C.c_void_p] * 6
+    n = len(jobs)
+    arr, keep = _sweep_jobs(jobs, lambda j: int(point_cols[j]))
+    cl, cc = (C.c_int64 * max(1, n))(*[int(v) for v in leaves]), (C.c_int32 * max(1, n))(*[int(v) for v in point_cols])
+    pts, so, co = (C.c_int64 * max(1, n))(), (C.c_int64 * (n + 1))(), (C.c_int64 * (n + 1))()
+    rc = fn(n, arr, cl, cc, pts, so, co)
+    if rc != 0:
+        raise TapeError(rc, lib().pipamd_last_error().decode())
+    return {"points": list(pts)[:n], "summary_off": list(so), "chunk_off": list(co)}
+
+
+class TapeSetSweep:
+    """The jobs of a TapeSet -- a tape, a box, a context each -- swept in ONE launch with a summary per job
+    (pipamd_tape_set_sweep_create / pipamd_tape_set_sweep_run).  summary_off[j] .. summary_off[j + 1] are job j's words of
+    the summary tensor, laid out as Tape.sweep's; `leaves` has every job's leaf count."""
+
+    def __init__(self, tset, jobs):
+        self.torch = tset.torch
+        self.set = tset  # (the set must outlive the sweep)
+        self.e, self.dev = tset.e, tset.dev
+        fn = _tape_fn("pipamd_tape_set_sweep_create", 64)
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p]
+        jobs = list(jobs)
+        self.n = len(jobs)
+        cols = {}
+
+        def point_cols(j):
+            t = int(jobs[j][0])
+            if t not in cols:
+                cols[t] = tset.tape_info(t)["point_cols"] if 0 <= t < tset.n else None
+            assert cols[t] is None or len(jobs[j][1]) == cols[t], "a box has point_cols bounds on either side"
+            return cols[t]
+
+        arr, keep = _sweep_jobs(jobs, point_cols)
+        so = (C.c_int64 * (self.n + 1))()
+        self._h = C.c_void_p()
+        rc = fn(self.e._h, tset._h, self.n, arr, C.byref(self._h), so)
+        if rc in (-1, -3):
+            raise TapeError(rc, lib().pipamd_last_error().decode())
+        _check(rc)
+        self.summary_off = list(so)
+        self.words = self.summary_off[-1]
+        self.leaves = [(b - a - 8) // 2 for a, b in zip(self.summary_off, self.summary_off[1:])]
+
+    def close(self):
+        if self._h:
+            lib().pipamd_tape_set_sweep_free.argtypes = [C.c_void_p]
+            lib().pipamd_tape_set_sweep_free(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def run_into(self, summary, stream=None):
+        """pipamd_tape_set_sweep_run into `summary`, a contiguous device int64 tensor of at least summary_off[-1] words;
+        it need not be initialised.  A fill and one launch on `stream` (default: torch's current), no synchronisation."""
+        t = self.torch
+        assert summary.dtype == t.int64 and summary.is_contiguous() and summary.numel() >= self.words
+        fn = lib().pipamd_tape_set_sweep_run
+        fn.argtypes = [C.c_void_p] * 4
+        st = C.c_void_p(stream) if stream is not None else C.c_void_p(t.cuda.current_stream(self.dev).cuda_stream)
+        _check(fn(self.e._h, self._h, C.c_void_p(summary.data_ptr()) if self.words else None, st))
+        return summary
+
+    def run(self, stream=None):
+        """run_into a fresh tensor of summary_off[-1] words"""
+        return self.run_into(self.torch.empty(self.words, dtype=self.torch.int64, device=self.dev), stream)
+
+    def summaries(self, tensor):
+        """the summary tensor of a run as a list of what sweep_summary returns, per job (synchronises through the copy)"""
+        w = tensor.cpu().tolist() if hasattr(tensor, "cpu") else list(tensor)
+        return [sweep_summary(w[a:b], L) for a, b, L in zip(self.summary_off, self.summary_off[1:], self.leaves)]

@@ -1,7 +1,7 @@
 """Many small quasts, each at a handful of points: one pipamd_tape_set_eval launch against a pipamd_tape_eval launch per
 tape.
 
-    python tools/tape_set_rate.py [--problems N] [--points K] [--out FILE]
+    python tools/tape_set_rate.py [--problems N] [--points K] [--skip K,K,...] [--out FILE]
 
 Input: N (default 2,000) seeded problems of the `p3` shape of tests/pipsolve_model.py (2-3 unknowns, 1-2 parameters, 3-6
 rows, all option sets), solved once by pipamd_pip_solve_many (not timed); every answer that is not void is compiled with
@@ -29,6 +29,7 @@ def main():
     ap.add_argument("--problems", type=int, default=2000)
     ap.add_argument("--points", type=int, default=64)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--skip", default="", help="comma-separated indices of problems left out of the solve")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     import numpy as np
@@ -38,9 +39,11 @@ def main():
     e = eng.Engine(0)
     rng = np.random.default_rng(a.seed)
     probs = [pm.gen_problem(rng, k, pm.FAMILIES["p3"]) for k in range(a.problems)]
+    left_out = sorted({int(k) for k in a.skip.split(",") if k.strip()})
+    probs = [p for k, p in enumerate(probs) if k not in left_out]  # (drawn all the same: the others stay what they were)
     inputs = [eng.PipInput(np.array(p["inequnk"], dtype=np.int64), np.array(p["ineqpar"], dtype=np.int64), p["bg"], p["options"])
               for p in probs]
-    tapes, skipped = [], {"failed": 0, "void": 0, "refused": 0}
+    tapes, skipped = [], {"failed": 0, "void": 0, "refused": 0, "left_out": left_out}
     for cells, rc, _, _, info in eng.pip_solve_many(e, inputs):
         if rc != 0:
             skipped["failed"] += 1
